@@ -16,7 +16,10 @@ per batch: the roofline's live launch durations; a pair costs the stream about 8
 other timed steps run without them -- `--kernel-events-every-step` keeps them on); the full per-kernel table comes
 from a separate, untimed pass of the same steps.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+`--dump-outputs DIR` writes what the last timed step returned (see dump_outputs) as DIR/<name>.npy; the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -113,6 +116,30 @@ def config_name(N, D, B):
     return "custom (not a BASELINE config)"
 
 
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: all files together, .npy headers included
+
+
+def dump_outputs(path, result, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: what the timed path hands its caller, ctx.fit_cluster's (labels int64[N], sweeps run, labels changed
+    per sweep), as float64 arrays (labels are small integers: exact) in path/labels.npy, sweeps.npy, changed_per_sweep.npy.
+    Labels beyond the budget are written as a fixed, seeded sample of rows in ascending order, whose row numbers go to
+    labels_index.npy.  Returns the names written."""
+    labels, its, changed = result
+    out = {"labels": np.asarray(labels, dtype=np.float64),
+           "sweeps": np.array([its], dtype=np.float64),
+           "changed_per_sweep": np.asarray(changed, dtype=np.float64)}
+    header = 128                                               # an .npy header of a 1-D array
+    room = (budget - 4 * header) // 8 - out["sweeps"].size - out["changed_per_sweep"].size
+    if out["labels"].size > room:
+        idx = np.sort(np.random.default_rng(seed).choice(out["labels"].size, room // 2, replace=False))
+        out["labels"] = out["labels"][idx]
+        out["labels_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(out)
+
+
 def self_launch(n):
     """One rank per GPU as child processes (the driver's own launch line, with a free rendezvous port); this process never
     initialises a GPU and replaces nothing -- it waits, prints rank 0's JSON line and returns the launcher's exit status."""
@@ -186,7 +213,11 @@ def main():
                     help="--gpus N > 1: X reaches the ranks by the library's RCCL broadcast (default) or every rank uploads its own copy")
     ap.add_argument("--launch-check", action="store_true",
                     help="dev / CPU test of the self-launch: the ranks rendezvous over gloo, rank 0 prints one line, no GPU touched")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step (--steps >= 1)")
 
     # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (torch.distributed.run as a CHILD process,
     # before this process has imported torch or touched a GPU), relay rank 0's single JSON line and the children's status
@@ -273,11 +304,11 @@ def main():
     else:
         ctx.set_samples(X)                                    # resident in HBM before timing
 
-    def one_step():
+    def one_step():     # -> (labels, sweeps run, changed per sweep)
         if use_dist and not native:
             return cdist_mod.fit_cluster_distributed(ctx, X, B, initial, perms[:1], m, 1,
-                                                     batch=args.batch, device=xdev)[0]
-        return ctx.fit_cluster(B, initial, perms[:1], m, 1, batch=args.batch)[0]
+                                                     batch=args.batch, device=xdev)
+        return ctx.fit_cluster(B, initial, perms[:1], m, 1, batch=args.batch)
 
     def sync():
         if use_dist:
@@ -285,7 +316,7 @@ def main():
         torch.cuda.synchronize()
 
     for _ in range(args.warmup):
-        labels1 = one_step()
+        labels1 = one_step()[0]
     ctx.profile_reset()
     # (the event pairs around the two dominant kernels -- the roofline's live launch durations -- cost the stream about
     #  8 us per launch, 0.2 ms of a 10 ms step: they are recorded in the LAST timed step only, i.e. around every launch
@@ -297,10 +328,15 @@ def main():
     for i in range(args.steps):
         if 0 < event_steps < args.steps and i == args.steps - event_steps:
             ctx.profile_enable(2)
-        labels1 = one_step()
+        last = one_step()
     sync()
     dt = time.perf_counter() - t0
     ctx.profile_enable(0)
+    if args.steps > 0:
+        labels1 = last[0]
+    if args.dump_outputs is not None and rank == 0:
+        names = dump_outputs(args.dump_outputs, last)
+        print(f"--dump-outputs: {', '.join(n + '.npy' for n in names)} in {args.dump_outputs}", file=sys.stderr)
     if use_dist:
         tt = torch.tensor([dt], dtype=torch.float64, device=xdev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
