@@ -234,8 +234,9 @@ class Context:
         res = (out, iters.value, changed[: iters.value])
         return res + (mind,) if want_min_dist else res
 
-    def fit_cluster_margins(self, B, initial_bins, perms, m, max_iter, batch=0):
-        """fit_cluster plus, per movable contig, runner-up minus winning hull distance at its last visit."""
+    def fit_cluster_margins(self, B, initial_bins, perms, m, max_iter, batch=0, want_min_dist=False):
+        """fit_cluster plus, per movable contig, runner-up minus winning hull distance at its last visit:
+        (labels, sweeps, margin), or with want_min_dist (labels, sweeps, changed, min_dist, margin)."""
         initial = np.ascontiguousarray(initial_bins, dtype=np.int64)
         perms = np.ascontiguousarray(perms, dtype=np.int64).reshape(max_iter, -1)
         out = np.empty(self.N, dtype=np.int64)
@@ -246,6 +247,8 @@ class Context:
         check(self._lib.chb_fit_cluster_ex(self._h, int(B), initial, perms, int(perms.shape[1]), int(m),
                                            int(max_iter), int(batch), out, C.byref(iters), changed,
                                            mind.ctypes.data, margin.ctypes.data))
+        if want_min_dist:
+            return out, iters.value, changed[: iters.value], mind, margin
         return out, iters.value, margin
 
     # stepwise (multi-GPU driver)

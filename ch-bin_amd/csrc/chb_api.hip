@@ -1610,6 +1610,13 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
     int dev_stats[3] = {0, 0, 0};
     const bool dev_stats_on = getenv("CHB_DEV_SKIP_STATS") != nullptr &&
                               sscanf(getenv("CHB_DEV_SKIP_STATS"), "%d,%d,%d", &dev_stats[0], &dev_stats[1], &dev_stats[2]) == 3;
+    // CHB_DEV_ALL_DIST=<file> (tests/test_gpu_bin_distances.py; read per fit): with min_dist_out on one GPU, every hull distance
+    // of each movable contig's last visit -- row perm[t0 + i] of an N x B float64 array (NaN rows for contigs never visited),
+    // written raw to <file> when the fit succeeds.  (min_dist_out keeps the look-ahead off: nothing overwrites a batch's dist
+    // before it is copied.)
+    const char *dev_all_path = (min_dist_out && !xchg_fit) ? getenv("CHB_DEV_ALL_DIST") : nullptr;
+    std::vector<double> dev_all, dev_all_batch;
+    if (dev_all_path) { dev_all.assign((size_t)N * (size_t)h->B, NAN); dev_all_batch.resize((size_t)Kmax * (size_t)h->B); }
 #else
     const bool dev_hook_spec = false, dev_local_verdict = false;
 #endif
@@ -1895,10 +1902,23 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
                 HIPCHK(hipMemcpyAsync(mind_host.data(), h->mind.p, sizeof(double) * K, hipMemcpyDeviceToHost, s));
                 if (margin_out)
                     HIPCHK(hipMemcpyAsync(mind2_host.data(), h->mind2.p, sizeof(double) * K, hipMemcpyDeviceToHost, s));
+#ifdef CHB_DEV_KNOBS
+                if (dev_all_path)
+                    HIPCHK(hipMemcpyAsync(dev_all_batch.data(), h->dist.p, sizeof(double) * K * h->B, hipMemcpyDeviceToHost, s));
+#endif
                 HIPCHK(hipStreamSynchronize(s));
                 for (int i = 0; i < K; ++i) min_dist_out[perm[t0 + i]] = mind_host[(size_t)i];
+                // (runner-up +inf: no other bin has a member -- +inf also when no bin has one, not inf - inf)
                 if (margin_out)
-                    for (int i = 0; i < K; ++i) margin_out[perm[t0 + i]] = mind2_host[(size_t)i] - mind_host[(size_t)i];
+                    for (int i = 0; i < K; ++i) {
+                        const double w = mind_host[(size_t)i], r = mind2_host[(size_t)i];
+                        margin_out[perm[t0 + i]] = r == INFINITY ? INFINITY : r - w;
+                    }
+#ifdef CHB_DEV_KNOBS
+                if (dev_all_path)
+                    for (int i = 0; i < K; ++i)
+                        memcpy(dev_all.data() + (size_t)perm[t0 + i] * h->B, dev_all_batch.data() + (size_t)i * h->B, sizeof(double) * h->B);
+#endif
             }
             if (!inflight) {   // (otherwise the commit went out with the look-ahead)
                 rc = batch_commit_dev(h, h->lab_prev.p);
@@ -1967,6 +1987,14 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
     if (!wrote_out)
         for (int64_t i = 0; i < N; ++i) labels_out[i] = prev[(size_t)i];
     if (iters_run) *iters_run = it;
+#ifdef CHB_DEV_KNOBS
+    if (dev_all_path) {
+        FILE *fp = fopen(dev_all_path, "wb");
+        const bool ok = fp && fwrite(dev_all.data(), sizeof(double), dev_all.size(), fp) == dev_all.size();
+        if (fp) fclose(fp);
+        if (!ok) return fail(CHB_EINVAL, std::string("CHB_DEV_ALL_DIST: cannot write ") + dev_all_path);
+    }
+#endif
     fit_closer.ok = true;
     return CHB_OK;
 }

@@ -1441,7 +1441,9 @@ __global__ __launch_bounds__(64 * kPfW, (ML <= 5 && (KS == 9 || (!UPD && SEG != 
         const unsigned lo32 = __builtin_amdgcn_readfirstlane((unsigned)pool_bins), hi32 = __builtin_amdgcn_readfirstlane((unsigned)(pool_bins >> 32));
         pool_bins = ((unsigned long long)hi32 << 32) | lo32;
     }
-    auto pool_mode_of = [&](int c) -> bool { return POOL && ((pool_bins >> (c - c0)) & 1ull) != 0ull; };
+    // (the mask holds 64 bins: a workgroup of more -- many bins, large batches, or the developer library's CHB_SL_BPW -- has
+    //  none in pool mode, and a shift by 64 or more is undefined)
+    auto pool_mode_of = [&](int c) -> bool { return POOL && c - c0 < 64 && ((pool_bins >> (c - c0)) & 1ull) != 0ull; };
 
     // DMA roles: wavefront w moves the 1-KiB pieces w, w+4, w+8 of a tile (lane l of piece i fills
     // LDS chunk 64 i + l from the global chunk the swizzle maps there: chunk cs of row r sits at

@@ -128,7 +128,8 @@ int chb_fit_cluster(chb_ctx *h, int64_t B, const int64_t *initial_bins, const in
 
 /* Same, additionally margin_out[N] (may be NULL; needs min_dist_out; single GPU): the runner-up bin's hull
  * distance minus the winner's at each movable contig's last visit -- how far the argmin of
- * algorithm.py:57 is from flipping (+inf when no other bin has a member, NaN for seeds). */
+ * algorithm.py:57 is from flipping (0 on a tie; +inf when no other bin has a member, also when no bin
+ * has one and the winning distance is +inf as well; NaN for seeds). */
 int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const int64_t *perms,
                        int64_t n_move, int m, int max_iter, int batch, int64_t *labels_out,
                        int *iters_run, int64_t *changed_per_iter, double *min_dist_out, double *margin_out);
