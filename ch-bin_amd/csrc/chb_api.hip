@@ -187,8 +187,24 @@ struct PackBufs {
     }
 };
 
+// The product's switches (include/chbin_hip.h; read_switches): each selects a slower, independent formulation of the same
+// result for the tests' A/B checks.  (A multi-rank fit may turn speculate, allow_skip, pp_allowed off for itself.)
+struct Switches {
+    bool use_prefilter = true;    // CHB_PREFILTER=0: brute-force fp64 selection instead of the fp16 shortlist stage
+    bool allow_fused = true;      // CHB_FUSED=0: m <= 16 also takes the list-based path (exact rescoring, then the hull kernel)
+    bool fused_ptr64 = false;     // CHB_FUSED_PTR64=1: 64-bit row pointers in the m <= 5 fused kernel whatever the size of X
+    bool speculate = true;        // CHB_SPECULATE=0: never enqueue the next batch ahead of the convergence test
+    bool force_gather = false;    // CHB_FORCE_GATHER=1: run the exchange path even with one rank (tests)
+    bool allow_segments = true;   // CHB_SEGMENTS=0: never (A/B tests)
+    bool fused_stripe = true;     // CHB_FUSED_STRIPE=0: position-major work order in the fused kernels
+    bool pp_allowed = true;       // CHB_PACK_INCR=0: every batch start rebuilds CSR and pack (the form up to round 3; A/B tests)
+    bool pool_allowed = true, pool_force = false;   // CHB_POOL_TAU=0: a bin always streamed twice; =2: pools whatever the size
+    bool allow_skip = true;       // CHB_TILE_SKIP=0: never (A/B tests)
+};
+
 struct chb_ctx {
     int dev = 0;
+    Switches sw;
     hipStream_t stream = nullptr;
     // samples
     DevBuf<double> X;
@@ -210,7 +226,6 @@ struct chb_ctx {
                                 // workgroups of its shortlist launch}: bin sizes and skip statistics ride home with the
                                 // verdict in one 20-byte copy
     hipEvent_t fc_event[2] = {nullptr, nullptr};
-    bool speculate = true;      // CHB_SPECULATE=0: never enqueue the next batch ahead of the convergence test
     bool argmin_in_place = false;   // chb_fit_cluster without exchange: argmin also stores the label to lab_prev
     DevBuf<double> mind, mind2, dist;   // winning hull distance, runner-up (margin report), all distances
     bool want_margin = false;
@@ -231,14 +246,13 @@ struct chb_ctx {
     DevBuf<float> qn;                  // [N][B] float2 exact sample-to-centre norms (per fit)
     DevBuf<double> centers;
     int Dz = 0;
-    bool shadow_ok = false, use_prefilter = true, overflow_total_valid = false;
-    bool pf_base = true, pf_update = true;   // developer switches (CHB_PF_BASE / CHB_PF_UPDATE; -DCHB_DEV_KNOBS builds only)
+    bool shadow_ok = false, overflow_total_valid = false;
     DevBuf<int> cand, cand_cnt, flags64, flaglist, nflag, overflow;
     DevBuf<int> flaglist2, nflag2;   // what the second-chance launch of a pool batch leaves for the brute-force kernel
     DevBuf<int> active, n_active, act_blk;
     // fused selection + hull distance (m <= 16): batch-entry candidates of this / the previous round,
     // the base stage's tau (bound of the m-th nearest distance), the exact path's work list
-    bool fused = false, allow_fused = true;
+    bool fused = false;
     bool pf_fit = false;        // this fit uses the shortlist stage (use_prefilter, D <= 160, m <= 16)
     bool lists_valid = false;   // the open batch was started with need_lists (chb_topm_per_bin)
     DevBuf<int> candu[2], candu_cnt[2], slow, n_slow;
@@ -251,15 +265,10 @@ struct chb_ctx {
     // step" record {flag, my tag, its tag, rank}
     DevBuf<int> xg, xerr;
     int xseq = 0;
-    int dev_inject_batches = 0;   // developer builds: batch starts of this context so far (CHB_SL_INJECT_SHORT)
-#ifdef CHB_DEV_KNOBS
-    chb::ShortlistArgs dev_pa{}; bool dev_pa_valid = false;   // the open batch's base shortlist launch (CHB_DEV_OVERLAP)
-#endif
     // the persistent base pack (prefilter_kernels.hip): the member pack kept across the batches of a fit
     DevBuf<int> pp_start, pp_cap, pp_fill, pp_live, pp_nt, pp_memb, pp_row, pp_ctl, pp_ovf, pp_dest;
     int pp_arena_rows = 0;
     int64_t pp_mark = 0;       // rows handed out from which on the host asks for a rebuild (pack_state_build)
-    bool pp_allowed = true;    // CHB_PACK_INCR=0: every batch start rebuilds CSR and pack (the form up to round 3; A/B tests)
     bool pp_fit = false;       // inside chb_fit_cluster (the stepwise entry points and chb_topm_per_bin always rebuild)
     bool pp_valid = false;     // the pack on the device matches the labels
     bool pp_batch = false;     // the open batch was started on it
@@ -275,8 +284,6 @@ struct chb_ctx {
     DevBuf<unsigned short> pool_Z;
     DevBuf<int> pool_id, pool_hole, pool_ok, pool_stat;
     DevBuf<float> pool_key, pool_sn, pool_tsn;
-    bool pool_force = false;    // CHB_POOL_TAU=2: pools whatever the size of the fit (A/B tests)
-    bool pool_allowed = true;   // CHB_POOL_TAU=0: the base shortlist launch always streams a bin twice (the form up to round 4; A/B tests)
     bool pool_fit = false;      // inside chb_fit_cluster (the stepwise entry points and chb_topm_per_bin never use pools)
     bool pool_valid = false;    // the pools on the device match the labels
     bool pool_holes = true;     // the open batch may hold labelled samples (their pool slots are holes until the commit)
@@ -297,7 +304,6 @@ struct chb_ctx {
     DevBuf<float> seg_lists;
     int seg_gcap = 0;
     int hint_max_tiles = 0, hint_total_tiles = 0;
-    bool allow_segments = true;   // CHB_SEGMENTS=0: never (A/B tests)
     // shells: the CSR of the base members is keyed (bin, shell of the member's distance from the bin's centre), outermost
     // shell first, so that the rows of a 32-row tile have similar norms (tile skipping in the shortlist kernel)
     DevBuf<float> shell_inv;
@@ -311,7 +317,6 @@ struct chb_ctx {
     DevBuf<int4> geo_all;
     PinBuf<int4> pin_geo;
     int *qord_cur = nullptr, *home_cur = nullptr;
-    bool allow_skip = true;       // CHB_TILE_SKIP=0: never (A/B tests)
     int skip_state = 0, skip_batches = 0;
     long long skip_off_key = -1;   // (bins, neighbours, metric) of the fit that found nothing to skip on these samples
     long long last_batch = 0;
@@ -336,9 +341,22 @@ struct chb_ctx {
     chb_allgather_fn hook = nullptr;
     void *hook_user = nullptr;
     std::vector<char> hook_send, hook_recv;
-    bool force_gather = false;   // CHB_FORCE_GATHER=1: run the exchange path even with one rank (tests)
     // work-unit hints for the profile (pairs = queries x members streamed)
     double hint_base_members = 0.0, hint_batch_entries = 0.0;
+#ifdef CHB_DEV_KNOBS
+    // developer builds: the switches of the tests and tools/ (read_switches; the Makefile says what each does), their state
+    struct DevKnobs {
+        bool sl_bounds = false, sl_validate = false;                            // CHB_SL_BOUNDS, CHB_SL_VALIDATE
+        int inject_short = 0, sl_bpw = 0, skip_never = 0;                       // CHB_SL_INJECT_SHORT, CHB_SL_BPW, CHB_SKIP_NEVER
+        std::string sl_dbg;                                                     // CHB_SL_DBG
+        int64_t pack_rebuild_at = -1;                                           // CHB_PACK_REBUILD_AT (-1: unset)
+        bool hook_spec = false, local_verdict = false, skip_stats_on = false;   // CHB_DEV_HOOK_SPEC, CHB_DEV_LOCAL_VERDICT,
+        int skip_stats[3] = {0, 0, 0};                                          // CHB_DEV_SKIP_STATS
+        int batches = 0, launches = 0;   // batch starts (CHB_SL_INJECT_SHORT), base shortlist launches (CHB_SL_DBG) so far
+        DevBuf<int> viol, verr;          // first out-of-range access; validation error + per-position counters
+        DevBuf<unsigned long long> dbg;  // the timeline
+    } dk;
+#endif
 
     Lists L0() { return Lists{l0d.p, l0i.p, l0c.p}; }
     Lists L1() { return Lists{l1d.p, l1i.p, l1c.p}; }
@@ -492,13 +510,13 @@ int fit_begin_impl(chb_ctx *h, int64_t B, const int64_t *initial, int m, bool sy
     h->B = (int)B; h->m = m;
     // the fp16 shortlist stage and the tuned kernels hold lists of up to 16 entries; beyond that the plain
     // one-wavefront-per-problem kernels run (brute-force selection, LDS-resident solver)
-    h->pf_fit = h->use_prefilter && h->shadow_ok && m <= kMaxM;
+    h->pf_fit = h->sw.use_prefilter && h->shadow_ok && m <= kMaxM;
     // (a fit that found nothing to skip settles it for later fits over the same samples with the same bin count,
     //  neighbour count and metric -- the verdict depends on all three)
     // (wide rows, Dz > 160: the plain two-sweep builds only -- no tile skipping, pools or segments)
     h->skip_state = (h->skip_off_key == skip_key(h) || h->Dz > 160) ? -1 : 0;
     h->skip_batches = 0; h->skip_skipped = 0; h->skip_seen = 0; h->skip_unloaded = 0;
-    h->fused = h->allow_fused && h->pf_fit && h->pf_base && h->pf_update && fused_supported(m, h->Dp);
+    h->fused = h->sw.allow_fused && h->pf_fit && fused_supported(m, h->Dp);
     HIPCHK(h->pin_a.ensure((size_t)h->N));
     int *lab = h->pin_a.p;
     std::vector<int64_t> bin_size((size_t)B, 0);
@@ -630,13 +648,13 @@ int pool_build(chb_ctx *h)
     // (m > 8: the 16-lane hull kernel pays for every candidate beyond 16 with extra rows and second tiles -- with the pools'
     //  17.4 instead of 16.8 candidates per pair at m = 15 it ran 34.4 instead of 28.8 ms per sweep, more than the shortlist
     //  kernel saved (5.1 instead of 5.9): those fits keep the two sweeps)
-    if (!h->pool_allowed || !h->fused || !h->pf_fit || !h->pf_base || h->ckey.p == nullptr || B < 2 || h->m > 8 || h->Dz > 160 ||
+    if (!h->sw.pool_allowed || !h->fused || !h->pf_fit || h->ckey.p == nullptr || B < 2 || h->m > 8 || h->Dz > 160 ||
         slots * (size_t)h->Dz * sizeof(unsigned short) > kPoolMaxBytes)
         return CHB_OK;
     // (small fits: a bin of a few tiles has no threshold sweep worth replacing, while the pools' build and upkeep are per
     //  fit and per batch -- BASELINE configs[1], 10k x 32 = 10 tiles per bin, went from 1.45 to 1.85 ms per sweep with them.
     //  From 16 tiles per bin on average; CHB_POOL_TAU=2 keeps them whatever the size)
-    if (!h->pool_force && (size_t)h->N < 512 * B) return CHB_OK;
+    if (!h->sw.pool_force && (size_t)h->N < 512 * B) return CHB_OK;
     if (h->pool_Z.ensure(slots * (size_t)h->Dz) != hipSuccess || h->pool_id.ensure(slots) != hipSuccess ||
         h->pool_hole.ensure(slots) != hipSuccess || h->pool_key.ensure(slots) != hipSuccess || h->pool_sn.ensure(slots) != hipSuccess ||
         h->pool_tsn.ensure(B * B + 64) != hipSuccess || h->pool_ok.ensure(B * B) != hipSuccess) {
@@ -653,6 +671,125 @@ int pool_build(chb_ctx *h)
     return CHB_OK;
 }
 
+// chb_create: the environment switches of the new context (unset: the defaults of Switches and chb_ctx::DevKnobs)
+void read_switches(chb_ctx *h)
+{
+    auto flag = [](const char *name, bool &v) { if (const char *e = getenv(name)) v = atoi(e) != 0; };
+    Switches &w = h->sw;
+    flag("CHB_PREFILTER", w.use_prefilter);
+    flag("CHB_FUSED", w.allow_fused);
+    flag("CHB_FUSED_PTR64", w.fused_ptr64);
+    flag("CHB_SPECULATE", w.speculate);
+    flag("CHB_FORCE_GATHER", w.force_gather);
+    flag("CHB_SEGMENTS", w.allow_segments);
+    flag("CHB_FUSED_STRIPE", w.fused_stripe);
+    flag("CHB_PACK_INCR", w.pp_allowed);
+    flag("CHB_TILE_SKIP", w.allow_skip);
+    if (const char *e = getenv("CHB_POOL_TAU")) { w.pool_allowed = atoi(e) != 0; w.pool_force = atoi(e) == 2; }
+#ifdef CHB_DEV_KNOBS
+    auto &d = h->dk;
+    d.sl_bounds = getenv("CHB_SL_BOUNDS") != nullptr;
+    d.sl_validate = getenv("CHB_SL_VALIDATE") != nullptr;
+    if (const char *e = getenv("CHB_SL_INJECT_SHORT")) d.inject_short = atoi(e);
+    if (const char *e = getenv("CHB_SL_BPW")) d.sl_bpw = atoi(e);
+    if (const char *e = getenv("CHB_SKIP_NEVER")) d.skip_never = atoi(e);
+    if (const char *e = getenv("CHB_SL_DBG")) d.sl_dbg = e;
+    if (const char *e = getenv("CHB_PACK_REBUILD_AT")) d.pack_rebuild_at = atoll(e);
+    flag("CHB_DEV_HOOK_SPEC", d.hook_spec);
+    flag("CHB_DEV_LOCAL_VERDICT", d.local_verdict);
+    if (const char *e = getenv("CHB_DEV_SKIP_STATS"))
+        d.skip_stats_on = sscanf(e, "%d,%d,%d", &d.skip_stats[0], &d.skip_stats[1], &d.skip_stats[2]) == 3;
+#endif
+}
+
+// ---- batch_begin_dev's hooks for the developer builds' checks and records of the shortlist stage (product build: none)
+#ifdef CHB_DEV_KNOBS
+constexpr size_t kDbgWords = (size_t)65536 * 16;   // the timeline: 16 words per workgroup
+int sl_bpw(const chb_ctx *h) { return h->dk.sl_bpw; }
+
+// before the base shortlist launch: CHB_SKIP_NEVER's bits; CHB_SL_DBG=<file>: per-wavefront timeline of the context's 10th
+// launch (tools/sl_timeline.py); CHB_SL_BOUNDS=1: the launch checks its tile DMA sources and member reads against the
+// buffers' extents, skips an access that is out of range and reports the first one (instead of a GPU memory fault)
+int dev_shortlist_args(chb_ctx *h, ShortlistArgs &pa, bool skip_on, bool pp_now)
+{
+    auto &d = h->dk;
+    if (skip_on && d.skip_never) pa.skip = 1 | 2 * d.skip_never;
+    if (!d.sl_dbg.empty() && ++d.launches == 10) {
+        HIPCHK(d.dbg.ensure(kDbgWords));
+        HIPCHK(hipMemsetAsync(d.dbg.p, 0, kDbgWords * 8, h->stream));
+        pa.dbg = d.dbg.p;
+    }
+    if (d.sl_bounds) {
+        HIPCHK(d.viol.ensure(8));
+        HIPCHK(hipMemsetAsync(d.viol.p, 0, 8 * sizeof(int), h->stream));
+        pa.viol = d.viol.p;
+        pa.viol_rows = pp_now ? (long long)h->pp_arena_rows : (long long)h->N + 32LL * h->B + 64;
+        pa.viol_pool_rows = (long long)h->B * h->B * kPoolRows;
+        pa.viol_members = pp_now ? (long long)h->pp_arena_rows : (long long)h->N;
+    }
+    return CHB_OK;
+}
+
+// after it (and its second chance): the bounds report, the timeline's dump
+int dev_shortlist_report(chb_ctx *h, const ShortlistArgs &pa, bool skip_on, bool pool_on, bool pp_now)
+{
+    auto &d = h->dk;
+    if (pa.viol != nullptr) {
+        int hv[8];
+        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(hipMemcpy(hv, d.viol.p, sizeof(hv), hipMemcpyDeviceToHost));
+        if (hv[0] != 0) {
+            fprintf(stderr, "[chb bounds] code %d: %d %d %d %d %d %d (workgroup %d); skip %d pool %d pp %d K %d q %d..%d\n", hv[0], hv[1],
+                    hv[2], hv[3], hv[4], hv[5], hv[6], hv[7], (int)skip_on, (int)pool_on, (int)pp_now, h->K, h->q_lo, h->q_hi);
+            return fail(CHB_ESTATE, "shortlist bounds check failed");
+        }
+    }
+    if (pa.dbg != nullptr) {
+        std::vector<unsigned long long> hostd(kDbgWords);
+        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(hipMemcpy(hostd.data(), d.dbg.p, kDbgWords * 8, hipMemcpyDeviceToHost));
+        if (FILE *fp = fopen(d.sl_dbg.c_str(), "wb")) { fwrite(hostd.data(), 8, kDbgWords, fp); fclose(fp); }
+    }
+    return CHB_OK;
+}
+
+// once a fused batch's base shortlists on a rebuilt CSR are final: CHB_SL_INJECT_SHORT=<n>: the n-th such batch truncates one
+// (the product build's check must turn it into an error); CHB_SL_VALIDATE=1: they and the index arrays behind them are
+// checked on the device before the hull kernels read them
+int dev_shortlist_check(chb_ctx *h, bool skip_on, const int *qord)
+{
+    auto &d = h->dk;
+    const int q_lo = h->q_lo, q_hi = h->q_hi;
+    if (d.inject_short > 0 && ++d.batches == d.inject_short)
+        launch_inject_short(h->cand_cnt.p, h->B, h->Kcap, q_lo, h->bin_ptr.p, h->m, h->stream);
+    if (!d.sl_validate) return CHB_OK;
+    HIPCHK(d.verr.ensure(4 + 65536));
+    HIPCHK(hipMemsetAsync(d.verr.p, 0, sizeof(int) * (4 + 65536), h->stream));
+    launch_validate_batch(h->cand.p, h->cand_cnt.p, h->B, h->Kcap, q_lo, q_hi, kCandCap, (int)h->N, h->bin_ptr.p,
+                          h->memb_id.p, skip_on ? qord : nullptr, h->m, d.verr.p, h->stream);
+    int herr[4];
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(herr, d.verr.p, sizeof(herr), hipMemcpyDeviceToHost));
+    if (herr[0] != 0) {
+        fprintf(stderr, "[chb validate] code %d bin %d position %d value %d (batch positions %d..%d, skip %d)\n", herr[0],
+                herr[1], herr[2], herr[3], q_lo, q_hi, (int)skip_on);
+        if (herr[0] >= 5 && skip_on && q_hi - q_lo <= 256) {
+            const int nq = q_hi - q_lo;
+            std::vector<int> qo(nq);
+            HIPCHK(hipMemcpy(qo.data(), h->qord.p, 4 * (size_t)nq, hipMemcpyDeviceToHost));
+            for (int i = 0; i < nq; ++i) fprintf(stderr, "  i %d qord %d\n", i, qo[i]);
+        }
+        return fail(CHB_ESTATE, "shortlist validation failed");
+    }
+    return CHB_OK;
+}
+#else
+int sl_bpw(const chb_ctx *) { return 0; }
+int dev_shortlist_args(chb_ctx *, ShortlistArgs &, bool, bool) { return CHB_OK; }
+int dev_shortlist_report(chb_ctx *, const ShortlistArgs &, bool, bool, bool) { return CHB_OK; }
+int dev_shortlist_check(chb_ctx *, bool, const int *) { return CHB_OK; }
+#endif
+
 // bq already holds the K sample indices (device).  need_lists: the caller wants the exact base lists
 // L0 (chb_topm_per_bin); the fit loop of the fused path (m <= 16) works on the shortlists directly.
 int batch_begin_dev(chb_ctx *h, int K, int q_lo, int q_hi, bool need_lists)
@@ -666,14 +803,14 @@ int batch_begin_dev(chb_ctx *h, int K, int q_lo, int q_hi, bool need_lists)
     // segment launches -- which it does when the bin sizes it saw last (one or two batches old) say that a bin may
     // have more than kSegMinTiles tiles and four times the average
     SegPlan sp{};
-    const bool pf_base_path = h->pf_fit && h->pf_base && h->cand.p;
+    const bool pf_base_path = h->pf_fit && h->cand.p;
     // tile skipping: on until the fit's first batches have shown that it skips (next to) nothing
-    const bool skip_on = pf_base_path && h->allow_skip && h->nsh > 1 && h->skip_state >= 0 && h->ckey.p != nullptr;
+    const bool skip_on = pf_base_path && h->sw.allow_skip && h->nsh > 1 && h->skip_state >= 0 && h->ckey.p != nullptr;
     if (pf_base_path && h->seg_gflag.p) {
         sp.nseg = h->seg_nseg.p; sp.items = h->seg_items.p; sp.gflag = h->seg_gflag.p; sp.lists = h->seg_lists.p;
         sp.cap = 16 * h->seg_gcap; sp.gcap = h->seg_gcap;
         const long long est = (long long)h->hint_max_tiles * 3 / 2 + 8;
-        sp.launch = h->allow_segments && h->Dz <= 160 && est > kSegMinTiles && est * h->B > 3LL * std::max(1, h->hint_total_tiles);
+        sp.launch = h->sw.allow_segments && h->Dz <= 160 && est > kSegMinTiles && est * h->B > 3LL * std::max(1, h->hint_total_tiles);
         if (sp.launch) {
             HIPCHK(h->seg_lists.ensure((size_t)h->seg_gcap * 16 * (size_t)h->Kcap * (size_t)shortlist_list_len(h->m)));
             sp.lists = h->seg_lists.p;
@@ -682,7 +819,7 @@ int batch_begin_dev(chb_ctx *h, int K, int q_lo, int q_hi, bool need_lists)
     // the persistent base pack serves the fit loop's batches whenever the shortlist launch does not skip tiles (whose
     // shell order needs the rebuild); built / rebuilt only outside a look-ahead window
     bool pp_now = false;
-    if (h->pp_fit && h->pp_allowed && fusedp && pf_base_path && !skip_on) {
+    if (h->pp_fit && h->sw.pp_allowed && fusedp && pf_base_path && !skip_on) {
         if ((!h->pp_valid || h->pp_rebuild) && g_gate.flag == nullptr) { const int r_ = pack_state_build(h); if (r_) return r_; }
         pp_now = h->pp_valid;
     }
@@ -720,11 +857,10 @@ int batch_begin_dev(chb_ctx *h, int K, int q_lo, int q_hi, bool need_lists)
     a.B = h->B; a.m = h->m; a.Kcap = h->Kcap;
     a.in = Lists{nullptr, nullptr, nullptr};
     a.out = h->L0();
-    if (h->pf_fit && h->pf_base && h->cand.p) {
+    if (pf_base_path) {
         // two-stage exact selection: fp16 matrix-core shortlist, exact fp64 on the shortlist,
         // brute force only for (query tile, bin) pairs whose shortlist overflowed
-        const int nq64 = (q_hi - q_lo + kQTile - 1) / kQTile;
-        (void)nq64;   // (flags64 is all zero here: launch_topm_flagged clears what it serves)
+        // (flags64 is all zero here: launch_topm_flagged clears what it serves)
         if (!h->overflow_total_valid) { launch_fill_i32(h->overflow.p, 0, 1, s); h->overflow_total_valid = true; }
         if (!pp_now) {
             // the members' shadow rows (relative to their bin's centre) gathered into padded CSR order, and the per-bin
@@ -758,38 +894,11 @@ int batch_begin_dev(chb_ctx *h, int K, int q_lo, int q_hi, bool need_lists)
             pa.qord = qord_p; pa.home = home_p; pa.ckey = h->ckey.p; pa.pool = h->pool_view(); pa.pool_stat = h->fc_cur + 7;
             h->stats_pool_batches += 1;
         }
-#ifdef CHB_DEV_KNOBS
-        if (skip_on) { if (const char *ev = getenv("CHB_SKIP_NEVER")) if (atoi(ev)) pa.skip = 1 | 2 * atoi(ev); }
-#endif
-#ifdef CHB_DEV_KNOBS
-        // CHB_SL_DBG=<file>: per-wavefront timeline of the 10th base shortlist launch of the process (tools/sl_timeline.py)
-        static int dbg_launch = 0;
-        static unsigned long long *dbg_dev = nullptr;
-        const char *dbg_path = getenv("CHB_SL_DBG");
-        const size_t dbg_words = (size_t)65536 * 16;
-        if (dbg_path != nullptr && ++dbg_launch == 10) {
-            HIPCHK(hipMalloc(&dbg_dev, dbg_words * 8));
-            HIPCHK(hipMemsetAsync(dbg_dev, 0, dbg_words * 8, s));
-            pa.dbg = dbg_dev;
-        }
-#endif
-#ifdef CHB_DEV_KNOBS
-        // CHB_SL_BOUNDS=1: the base shortlist launch checks its tile DMA sources and member reads against the buffers' extents,
-        // skips an access that is out of range and reports the first one (instead of a GPU memory fault)
-        static int *viol_dev = nullptr;
-        if (getenv("CHB_SL_BOUNDS") != nullptr) {
-            if (viol_dev == nullptr) HIPCHK(hipMalloc(&viol_dev, 8 * sizeof(int)));
-            HIPCHK(hipMemsetAsync(viol_dev, 0, 8 * sizeof(int), s));
-            pa.viol = viol_dev;
-            pa.viol_rows = pp_now ? (long long)h->pp_arena_rows : (long long)h->N + 32LL * h->B + 64;
-            pa.viol_pool_rows = (long long)h->B * h->B * kPoolRows;
-            pa.viol_members = pp_now ? (long long)h->pp_arena_rows : (long long)h->N;
-        }
-#endif
+        { const int r_ = dev_shortlist_args(h, pa, skip_on, pp_now); if (r_) return r_; }
         {
             Timed t(h, "prefilter", (double)(q_hi - q_lo) * h->hint_base_members);
             pa.flaglist = h->flaglist.p; pa.nflag = h->nflag.p;   // (counter reset by the CSR scan / the batch CSR kernel)
-            launch_shortlist(pa, h->flags64.p, s);
+            launch_shortlist(pa, h->flags64.p, sl_bpw(h), s);
         }
         const int *fb_list = h->flaglist.p, *fb_n = h->nflag.p;   // the brute-force kernel's work list
         if (pool_on) {
@@ -801,28 +910,7 @@ int batch_begin_dev(chb_ctx *h, int K, int q_lo, int q_hi, bool need_lists)
             launch_shortlist_worklist(pb, h->flags64.p, s);
             fb_list = h->flaglist2.p; fb_n = h->nflag2.p;
         }
-#ifdef CHB_DEV_KNOBS
-        if (pa.viol != nullptr) {
-            int hv[8];
-            HIPCHK(hipStreamSynchronize(s));
-            HIPCHK(hipMemcpy(hv, viol_dev, sizeof(hv), hipMemcpyDeviceToHost));
-            if (hv[0] != 0) {
-                fprintf(stderr, "[chb bounds] code %d: %d %d %d %d %d %d (workgroup %d); skip %d pool %d pp %d K %d q %d..%d\n", hv[0], hv[1], hv[2], hv[3],
-                        hv[4], hv[5], hv[6], hv[7], (int)skip_on, (int)pool_on, (int)pp_now, K, q_lo, q_hi);
-                return fail(CHB_ESTATE, "shortlist bounds check failed");
-            }
-        }
-        h->dev_pa = pa; h->dev_pa_valid = true;   // (CHB_DEV_OVERLAP)
-#endif
-#ifdef CHB_DEV_KNOBS
-        if (pa.dbg != nullptr) {
-            std::vector<unsigned long long> hostd(dbg_words);
-            HIPCHK(hipStreamSynchronize(s));
-            HIPCHK(hipMemcpy(hostd.data(), dbg_dev, dbg_words * 8, hipMemcpyDeviceToHost));
-            if (FILE *fp = fopen(dbg_path, "wb")) { fwrite(hostd.data(), 8, dbg_words, fp); fclose(fp); }
-            HIPCHK(hipFree(dbg_dev)); dbg_dev = nullptr;
-        }
-#endif
+        { const int r_ = dev_shortlist_report(h, pa, skip_on, pool_on, pp_now); if (r_) return r_; }
         if (!fusedp) {
             RescoreArgs ra{};
             ra.X = h->X.p; ra.Dp = h->Dp; ra.bq = h->bq_cur; ra.pos_begin = q_lo; ra.pos_end = q_hi;
@@ -840,36 +928,7 @@ int batch_begin_dev(chb_ctx *h, int K, int q_lo, int q_hi, bool need_lists)
             Timed t(h, "topm_fallback", 0.0);
             launch_topm_flagged(a, h->flags64.p, fb_list, fb_n, s);
         }
-#ifdef CHB_DEV_KNOBS
-        // CHB_SL_INJECT_SHORT=<n>: the n-th batch start of a context hands the hull kernels one truncated shortlist
-        // (tests: the product build's check must turn it into an error)
-        if (fusedp && !pp_now) if (const char *ev = getenv("CHB_SL_INJECT_SHORT")) {
-            if (++h->dev_inject_batches == atoi(ev)) launch_inject_short(h->cand_cnt.p, h->B, h->Kcap, q_lo, h->bin_ptr.p, h->m, s);
-        }
-#endif
-#ifdef CHB_DEV_KNOBS
-        if (fusedp && !pp_now && getenv("CHB_SL_VALIDATE") != nullptr) {   // (the validation kernel reads the rebuilt CSR)
-            static int *verr = nullptr;
-            if (verr == nullptr) HIPCHK(hipMalloc(&verr, 16 + 4 * 65536));
-            HIPCHK(hipMemsetAsync(verr, 0, 16 + 4 * 65536, s));
-            launch_validate_batch(h->cand.p, h->cand_cnt.p, h->B, h->Kcap, q_lo, q_hi, kCandCap, (int)h->N, h->bin_ptr.p,
-                                  h->memb_id.p, skip_on ? qord_p : nullptr, h->m, verr, s);
-            int herr[4];
-            HIPCHK(hipStreamSynchronize(s));
-            HIPCHK(hipMemcpy(herr, verr, 16, hipMemcpyDeviceToHost));
-            if (herr[0] != 0) {
-                fprintf(stderr, "[chb validate] code %d bin %d position %d value %d (batch positions %d..%d, skip %d)\n", herr[0],
-                        herr[1], herr[2], herr[3], q_lo, q_hi, (int)skip_on);
-                if (herr[0] >= 5 && skip_on && q_hi - q_lo <= 256) {
-                    const int nq = q_hi - q_lo;
-                    std::vector<int> qo(nq);
-                    HIPCHK(hipMemcpy(qo.data(), h->qord.p, 4 * (size_t)nq, hipMemcpyDeviceToHost));
-                    for (int i = 0; i < nq; ++i) fprintf(stderr, "  i %d qord %d\n", i, qo[i]);
-                }
-                return fail(CHB_ESTATE, "shortlist validation failed");
-            }
-        }
-#endif
+        if (fusedp && !pp_now) { const int r_ = dev_shortlist_check(h, skip_on, qord_p); if (r_) return r_; }
     } else {
         Timed t(h, "topm_base", (double)(q_hi - q_lo) * h->hint_base_members);
         if (h->m > kMaxM) launch_topm_generic(a, s); else launch_topm(a, s);
@@ -918,7 +977,7 @@ int batch_round_dev(chb_ctx *h, int active)
             {
                 Timed t(h, "prefilter_update", (double)(hi - lo) * h->hint_batch_entries);
                 pa.flaglist = h->flaglist.p; pa.nflag = h->nflag.p;   // (counter reset by the CSR scan / the batch CSR kernel)
-            launch_shortlist(pa, h->flags64.p, s);
+            launch_shortlist(pa, h->flags64.p, sl_bpw(h), s);
             }
             {
                 // overflowed pairs: exact top-m among the (eligible) batch entries as their shortlist
@@ -937,41 +996,10 @@ int batch_round_dev(chb_ctx *h, int active)
             f.dist = h->dist.p; f.metric = h->metric; f.slow = h->slow.p; f.n_slow = h->n_slow.p;
             f.bin_ptr = h->bin_ptr.p; f.short_cnt = h->short_cnt.p;
             if (h->pp_batch) f.bin_size = h->pp_live.p;
-#ifdef CHB_DEV_KNOBS
-            // CHB_DEV_OVERLAP=1: how much would the base shortlist launch of the NEXT batch gain from running beside this
-            // batch's hull kernel?  The batch's own base shortlist launch is repeated into scratch buffers on a second
-            // stream while the hull kernel runs (2: the same repeat in line on the main stream -- the additive baseline).
-            static const int dev_overlap = getenv("CHB_DEV_OVERLAP") ? atoi(getenv("CHB_DEV_OVERLAP")) : 0;
-            static hipStream_t dev_s2 = nullptr; static hipEvent_t dev_e1 = nullptr, dev_e2 = nullptr;
-            static int *dev_scratch = nullptr; static size_t dev_scratch_n = 0;
-            bool dev_side = false;
-            if (dev_overlap && h->round_in_batch == 0 && h->dev_pa_valid) {
-                const size_t KB = (size_t)h->Kcap * h->B;
-                const size_t need = KB * kCandCap + 4 * KB + 64;
-                if (dev_scratch_n < need) { if (dev_scratch) (void)hipFree(dev_scratch); HIPCHK(hipMalloc(&dev_scratch, need * sizeof(int))); dev_scratch_n = need; HIPCHK(hipMemset(dev_scratch, 0, need * sizeof(int))); }
-                if (!dev_s2) { HIPCHK(hipStreamCreateWithFlags(&dev_s2, hipStreamNonBlocking)); HIPCHK(hipEventCreateWithFlags(&dev_e1, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&dev_e2, hipEventDisableTiming)); }
-                ShortlistArgs pb = h->dev_pa;
-                pb.cand = dev_scratch; pb.cand_cnt = dev_scratch + KB * kCandCap; pb.tau_out = reinterpret_cast<float *>(dev_scratch + KB * kCandCap + KB);
-                pb.overflow = dev_scratch + KB * kCandCap + 2 * KB; pb.nflag = pb.overflow + 1; pb.flaglist = pb.overflow + 8;
-                pb.skip_stat = nullptr;
-                int *fl = dev_scratch + KB * kCandCap + 3 * KB;
-                if (dev_overlap == 1) {
-                    HIPCHK(hipEventRecord(dev_e1, s)); HIPCHK(hipStreamWaitEvent(dev_s2, dev_e1, 0));
-                    launch_shortlist(pb, fl, dev_s2);
-                    HIPCHK(hipEventRecord(dev_e2, dev_s2));
-                    dev_side = true;
-                } else {
-                    launch_shortlist(pb, fl, s);
-                }
-            }
-#endif
             {
                 Timed t(h, "hull_qp", (double)(hi - lo) * h->B);
-                launch_hull_select_qp(f, s);
+                launch_hull_select_qp(f, h->sw.fused_stripe, h->sw.fused_ptr64, s);
             }
-#ifdef CHB_DEV_KNOBS
-            if (dev_side) HIPCHK(hipStreamWaitEvent(s, dev_e2, 0));
-#endif
             {
                 // the exact path for what the fused kernel left: cdist-rounded distances on both shortlists,
                 // (distance, index) order, then the list-based hull kernel
@@ -993,7 +1021,7 @@ int batch_round_dev(chb_ctx *h, int active)
                 launch_hull_qp(q, s);
             }
         } else {
-        if (h->pf_fit && h->pf_update && h->cand.p) {
+        if (h->pf_fit && h->cand.p) {
             // batch members that can displace an entry of the base list: fp16 shortlist against
             // the exact m-th distance, exact rescoring seeded with the base list
             // (fit rounds only produce the "earlier" / "later" eligibility codes, which have the affine
@@ -1012,7 +1040,7 @@ int batch_round_dev(chb_ctx *h, int active)
             {
                 Timed t(h, "prefilter_update", (double)(hi - lo) * h->hint_batch_entries);
                 pa.flaglist = h->flaglist.p; pa.nflag = h->nflag.p;   // (counter reset by the CSR scan / the batch CSR kernel)
-            launch_shortlist(pa, h->flags64.p, s);
+            launch_shortlist(pa, h->flags64.p, sl_bpw(h), s);
                 // the (position, bin) pairs with a non-empty shortlist, for rescore_kernel
                 launch_compact_active(h->cand_cnt.p, lo, hi, h->B, h->Kcap, h->act_blk.p, h->active.p,
                                       h->n_active.p, s);
@@ -1181,23 +1209,10 @@ int chb_create(int device_id, chb_ctx **out)
     HIPCHK(hipSetDevice(device_id));
     chb_ctx *h = new chb_ctx();
     h->dev = device_id;
-    if (const char *e = getenv("CHB_PREFILTER")) h->use_prefilter = atoi(e) != 0;
-    if (const char *e = getenv("CHB_FORCE_GATHER")) h->force_gather = atoi(e) != 0;
-    // CHB_FUSED=0: m <= 16 also takes the list-based path (exact rescoring of every shortlist, then the hull
-    // kernel); like CHB_PREFILTER=0 a switch to the slower, independent formulation for the tests' A/B checks
-    if (const char *e = getenv("CHB_FUSED")) h->allow_fused = atoi(e) != 0;
-#ifdef CHB_DEV_KNOBS   // developer builds only (tools/): the product library reads no tuning knob
-    if (const char *e = getenv("CHB_PF_BASE")) h->pf_base = atoi(e) != 0;
-    if (const char *e = getenv("CHB_PF_UPDATE")) h->pf_update = atoi(e) != 0;
-#endif
+    read_switches(h);
     hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipHostMalloc((void **)&h->fc_host, 128, hipHostMallocDefault);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&h->fc_event[i], hipEventDisableTiming);
-    if (const char *ev = getenv("CHB_SPECULATE")) h->speculate = atoi(ev) != 0;
-    if (const char *ev = getenv("CHB_SEGMENTS")) h->allow_segments = atoi(ev) != 0;
-    if (const char *ev = getenv("CHB_TILE_SKIP")) h->allow_skip = atoi(ev) != 0;
-    if (const char *ev = getenv("CHB_PACK_INCR")) h->pp_allowed = atoi(ev) != 0;
-    if (const char *ev = getenv("CHB_POOL_TAU")) { h->pool_allowed = atoi(ev) != 0; h->pool_force = atoi(ev) == 2; }
     if (e != hipSuccess) { delete h; return fail(CHB_EHIP, hipGetErrorString(e)); }
     *out = h;
     return CHB_OK;
@@ -1274,7 +1289,7 @@ static int samples_finish(chb_ctx *h)
     // D <= 573 as two to four 144-column slices in the wide ones (shadow_row_elems)
     h->shadow_ok = false;
     const int Dz = shadow_row_elems((int)D);
-    if (h->use_prefilter && Dz > 0) {
+    if (h->sw.use_prefilter && Dz > 0) {
         // global mean, the power-of-two scale that puts every centred feature inside +-2^11, and the
         // query-side shadow row of every sample: functions of X alone
         const int part_blocks = 1024;
@@ -1579,11 +1594,11 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
     h->stats_lookahead = 0; h->stats_lookahead_failed = 0;
 
     // ---- more than one rank: agree on the fit before its first collective (fit_agree above)
-    const bool xchg_fit = (h->comm != nullptr || h->hook != nullptr) && (h->world > 1 || h->force_gather);
+    const bool xchg_fit = (h->comm != nullptr || h->hook != nullptr) && (h->world > 1 || h->sw.force_gather);
     struct SwitchRestore {   // (the agreed switches hold for this fit only)
         chb_ctx *h; bool skip, pack, spec;
-        ~SwitchRestore() { h->allow_skip = skip; h->pp_allowed = pack; h->speculate = spec; }
-    } switch_restore{h, h->allow_skip, h->pp_allowed, h->speculate};
+        ~SwitchRestore() { h->sw.allow_skip = skip; h->sw.pp_allowed = pack; h->sw.speculate = spec; }
+    } switch_restore{h, h->sw.allow_skip, h->sw.pp_allowed, h->sw.speculate};
     h->xseq = 0;
     if (xchg_fit) {
         FitAgree fa{};
@@ -1593,30 +1608,24 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
                                        (int)(hp & 0x7fffffff), (int)((hp >> 32) & 0x7fffffff), (int)(hi_ & 0x7fffffff),
                                        (int)((hi_ >> 32) & 0x7fffffff)};
         memcpy(fa.v, eq, sizeof(eq));
-        fa.v[16] = h->skip_state; fa.v[17] = h->speculate ? 1 : 0; fa.v[18] = h->allow_skip ? 1 : 0; fa.v[19] = h->pp_allowed ? 1 : 0;
+        fa.v[16] = h->skip_state; fa.v[17] = h->sw.speculate ? 1 : 0; fa.v[18] = h->sw.allow_skip ? 1 : 0; fa.v[19] = h->sw.pp_allowed ? 1 : 0;
         fa.v[20] = h->pool_valid ? h->pool_state : -1;
         rc = fit_agree(h, &fa);
         if (rc) return rc;
-        h->skip_state = fa.v[16]; h->speculate = fa.v[17] != 0; h->allow_skip = fa.v[18] != 0; h->pp_allowed = fa.v[19] != 0;
+        h->skip_state = fa.v[16]; h->sw.speculate = fa.v[17] != 0; h->sw.allow_skip = fa.v[18] != 0; h->sw.pp_allowed = fa.v[19] != 0;
         if (fa.v[20] < 0) { h->pool_state = -1; h->pool_valid = false; }
     }
 #ifdef CHB_DEV_KNOBS
-    // developer builds, tests of the exchange schedule (tests/test_gpu_world2.py): CHB_DEV_HOOK_SPEC=1 lets the look-ahead run
-    // over the host-staged hook (its exchanges synchronise the stream, so nothing is gained -- but the ORDER of the exchanges
-    // is the RCCL path's); CHB_DEV_SKIP_STATS=<skipped>,<seen>,<unloaded> replaces this rank's tile-skipping statistics of
-    // every batch; CHB_DEV_LOCAL_VERDICT=1 restores the behaviour before round 5 (every rank decides from its OWN statistics)
-    const bool dev_hook_spec = getenv("CHB_DEV_HOOK_SPEC") != nullptr && atoi(getenv("CHB_DEV_HOOK_SPEC")) != 0;
-    const bool dev_local_verdict = getenv("CHB_DEV_LOCAL_VERDICT") != nullptr && atoi(getenv("CHB_DEV_LOCAL_VERDICT")) != 0;
-    int dev_stats[3] = {0, 0, 0};
-    const bool dev_stats_on = getenv("CHB_DEV_SKIP_STATS") != nullptr &&
-                              sscanf(getenv("CHB_DEV_SKIP_STATS"), "%d,%d,%d", &dev_stats[0], &dev_stats[1], &dev_stats[2]) == 3;
+    // developer builds, tests of the exchange schedule (tests/test_gpu_world2.py): CHB_DEV_HOOK_SPEC=1 runs the look-ahead over
+    // the host-staged hook (no gain, but the RCCL path's ORDER of exchanges); CHB_DEV_SKIP_STATS=<skipped>,<seen>,<unloaded>
+    // replaces this rank's tile-skipping statistics of every batch; CHB_DEV_LOCAL_VERDICT=1: each rank decides from its OWN ones
+    const bool dev_hook_spec = h->dk.hook_spec, dev_local_verdict = h->dk.local_verdict;
     // CHB_DEV_ALL_DIST=<file> (tests/test_gpu_bin_distances.py; read per fit): with min_dist_out on one GPU, every hull distance
     // of each movable contig's last visit -- row perm[t0 + i] of an N x B float64 array (NaN rows for contigs never visited),
     // written raw to <file> when the fit succeeds.  (min_dist_out keeps the look-ahead off: nothing overwrites a batch's dist
     // before it is copied.)
     const char *dev_all_path = (min_dist_out && !xchg_fit) ? getenv("CHB_DEV_ALL_DIST") : nullptr;
-    std::vector<double> dev_all, dev_all_batch;
-    if (dev_all_path) { dev_all.assign((size_t)N * (size_t)h->B, NAN); dev_all_batch.resize((size_t)Kmax * (size_t)h->B); }
+    std::vector<double> dev_all(dev_all_path ? (size_t)N * (size_t)h->B : 0, NAN);
 #else
     const bool dev_hook_spec = false, dev_local_verdict = false;
 #endif
@@ -1671,12 +1680,12 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
         // The stream never drains while rounds converge at once -- the common case after sweep 1's start;
         // a failed guess switches the look-ahead off until a batch converges in one round again.
         const int world = h->world;
-        const bool xchg = (h->comm != nullptr || h->hook != nullptr) && (world > 1 || h->force_gather);
+        const bool xchg = (h->comm != nullptr || h->hook != nullptr) && (world > 1 || h->sw.force_gather);
         // (look-ahead under an exchange: the RCCL all-gather sits on the context's stream, so the first-changed position of
         //  a round is computed on the device right behind it and feeds the same gate as on one GPU; every rank sees the same
         //  labels, hence the same verdict, and the all-gathers of a gated-off batch move identical bytes between the ranks'
         //  identical buffers.  The hook transport needs the host between rounds anyway.)
-        const bool can_spec = h->speculate && h->fused && (!xchg || (h->hook == nullptr && h->comm != nullptr) || dev_hook_spec) &&
+        const bool can_spec = h->sw.speculate && h->fused && (!xchg || (h->hook == nullptr && h->comm != nullptr) || dev_hook_spec) &&
                               min_dist_out == nullptr;
         // the tag of the fit's next exchange (kind 1: a batch's label guess, 2: a round's labels)
         auto next_tag = [&](int kind) { const int t = ((h->xseq & 0x7ffffff) << 4) | kind; h->xseq += 1; return t; };
@@ -1685,10 +1694,6 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
             // sweep 1 starts from few labelled members: do not let a batch outnumber them by much
             // (measured: a batch of up to 1.5x the labelled members costs no extra rounds and saves a batch)
             int64_t members = (it == 0) ? (assigned0 + t0) * 3 / 2 : N;
-#ifdef CHB_DEV_KNOBS
-            { static double r = -1.0; if (r < 0.0) { const char *e = getenv("CHB_EARLY_RATIO"); r = e ? atof(e) : 1.5; }
-              if (it == 0) members = (int64_t)((assigned0 + t0) * r); }
-#endif
             int K = (int)std::min<int64_t>(Kmax, n_move - t0);
             if (members < K) K = (int)std::max<int64_t>(std::min<int64_t>(64, n_move - t0), members);
             K = std::min(K, Kmax);   // (the floor of 64 above must not exceed a caller's smaller batch: buffers hold Kmax)
@@ -1702,7 +1707,7 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
         // function of the sweep alone.  (Not for sweeps of thousands of tiny batches: those order theirs one by one.)
         h->qord_cur = nullptr; h->home_cur = nullptr;
         std::vector<int64_t> batch_t0;
-        if (h->pf_fit && h->fused && h->ckey.p != nullptr && n_move > 0 && (h->pool_valid || (h->allow_skip && h->skip_state >= 0))) {
+        if (h->pf_fit && h->fused && h->ckey.p != nullptr && n_move > 0 && (h->pool_valid || (h->sw.allow_skip && h->skip_state >= 0))) {
             std::vector<int4> geo;
             for (int64_t t = 0; t < n_move && geo.size() <= 4096;) {
                 const Geom g = geom_at(t);
@@ -1736,7 +1741,7 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
                 const int tag = next_tag(2);
                 const bool first = active == 0;
 #ifdef CHB_DEV_KNOBS
-                if (first && dev_stats_on) for (int k = 0; k < 3; ++k) launch_fill_i32(h->fc_cur + 3 + k, dev_stats[k], 1, s);
+                if (first && h->dk.skip_stats_on) for (int k = 0; k < 3; ++k) launch_fill_i32(h->fc_cur + 3 + k, h->dk.skip_stats[k], 1, s);
 #endif
                 launch_xchg_pack(h->xg.p, h->rank, g.C, h->lab_new.p, tag, h->fc_cur, first, first && h->pp_batch, true, g.K, s);
                 { const int r_ = exchange_all_gather(h, h->xg.p, (size_t)(g.C + kXchgHdr), sizeof(int), ncclInt32); if (r_) return r_; }
@@ -1757,7 +1762,7 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
             {
                 int64_t mark_at = h->pp_mark;
 #ifdef CHB_DEV_KNOBS   // CHB_PACK_REBUILD_AT=<rows>: rebuild (compact) the pack from that fill mark on -- tests of the rebuild path
-                { static const char *e = getenv("CHB_PACK_REBUILD_AT"); if (e) mark_at = atoll(e); }
+                if (h->dk.pack_rebuild_at >= 0) mark_at = h->dk.pack_rebuild_at;
 #endif
                 if (h->pp_valid && h->fc_host[kSlotInts * slot + 6] > mark_at) h->pp_rebuild = true;
             }
@@ -1859,8 +1864,8 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
             if (!inflight) { rc = open_batch(g, slot); if (rc) return rc; }
             const int64_t t1 = t0 + K;
             // (a batch start that has to build or rebuild the persistent pack stays outside the look-ahead window)
-            const bool skip_would = h->allow_skip && h->nsh > 1 && h->skip_state >= 0 && h->ckey.p != nullptr;
-            const bool pack_sync = h->pp_fit && h->pp_allowed && h->fused && h->pf_base && h->cand.p && !skip_would &&
+            const bool skip_would = h->sw.allow_skip && h->nsh > 1 && h->skip_state >= 0 && h->ckey.p != nullptr;
+            const bool pack_sync = h->pp_fit && h->sw.pp_allowed && h->fused && h->cand.p && !skip_would &&
                                    (!h->pp_valid || h->pp_rebuild);
             const bool spec = spec_ok && t1 < n_move && !pack_sync;
             Snap snap{};
@@ -1902,10 +1907,6 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
                 HIPCHK(hipMemcpyAsync(mind_host.data(), h->mind.p, sizeof(double) * K, hipMemcpyDeviceToHost, s));
                 if (margin_out)
                     HIPCHK(hipMemcpyAsync(mind2_host.data(), h->mind2.p, sizeof(double) * K, hipMemcpyDeviceToHost, s));
-#ifdef CHB_DEV_KNOBS
-                if (dev_all_path)
-                    HIPCHK(hipMemcpyAsync(dev_all_batch.data(), h->dist.p, sizeof(double) * K * h->B, hipMemcpyDeviceToHost, s));
-#endif
                 HIPCHK(hipStreamSynchronize(s));
                 for (int i = 0; i < K; ++i) min_dist_out[perm[t0 + i]] = mind_host[(size_t)i];
                 // (runner-up +inf: no other bin has a member -- +inf also when no bin has one, not inf - inf)
@@ -1915,9 +1916,12 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
                         margin_out[perm[t0 + i]] = r == INFINITY ? INFINITY : r - w;
                     }
 #ifdef CHB_DEV_KNOBS
-                if (dev_all_path)
+                if (dev_all_path) {   // (the batch's K x B distances, each row to its contig's)
+                    std::vector<double> rows((size_t)K * h->B);
+                    HIPCHK(hipMemcpy(rows.data(), h->dist.p, sizeof(double) * rows.size(), hipMemcpyDeviceToHost));
                     for (int i = 0; i < K; ++i)
-                        memcpy(dev_all.data() + (size_t)perm[t0 + i] * h->B, dev_all_batch.data() + (size_t)i * h->B, sizeof(double) * h->B);
+                        memcpy(dev_all.data() + (size_t)perm[t0 + i] * h->B, rows.data() + (size_t)i * h->B, sizeof(double) * h->B);
+                }
 #endif
             }
             if (!inflight) {   // (otherwise the commit went out with the look-ahead)
@@ -1926,11 +1930,6 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
             } else {
                 slot ^= 1;
             }
-#ifdef CHB_DEV_KNOBS
-            { static const bool tr = getenv("CHB_DEV_TRACE_BATCHES") != nullptr;
-              if (tr) fprintf(stderr, "[chb batch] sweep %d t0 %lld K %d rounds so far %lld pool %d/%d skip %d spec %d\n", it, (long long)t0, K,
-                              (long long)h->stats[1], (int)h->pool_valid, h->pool_state, h->skip_state, (int)inflight); }
-#endif
             h->stats[0] += 1;
             t0 = t1;
         }
@@ -2417,7 +2416,7 @@ int chb_counter(chb_ctx *h, const char *name, int64_t *out)
     if (!strcmp(name, "tile_seen")) { *out = h->skip_seen; return CHB_OK; }
     if (!strcmp(name, "tile_unloaded")) { *out = h->skip_unloaded; return CHB_OK; }
     if (!strcmp(name, "last_batch_k")) { *out = h->K; return CHB_OK; }
-    if (!strcmp(name, "prefilter_enabled")) { *out = (h->use_prefilter && h->shadow_ok) ? 1 : 0; return CHB_OK; }
+    if (!strcmp(name, "prefilter_enabled")) { *out = (h->sw.use_prefilter && h->shadow_ok) ? 1 : 0; return CHB_OK; }
     return fail(CHB_EINVAL, "unknown counter");
 }
 

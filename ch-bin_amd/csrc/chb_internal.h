@@ -246,8 +246,9 @@ void launch_pool_commit(const PoolState &ps, const unsigned short *Zs, const voi
                         hipStream_t s);
 
 // flags64[bin][ceil(nq/64)] (pre-zeroed): set for (query tile of 64, bin) pairs whose shortlist overflowed
-// (and listed once in a.flaglist)
-void launch_shortlist(const ShortlistArgs &a, int *flags64, hipStream_t s);
+// (and listed once in a.flaglist); bpw_force > 0: bins per workgroup (the developer library's CHB_SL_BPW; not for the
+// tile-skipping and wide-row builds), else the launcher's choice
+void launch_shortlist(const ShortlistArgs &a, int *flags64, int bpw_force, hipStream_t s);
 // the exact two-sweep selection for the listed work items only (a.worklist / a.nwork = the overflow list of a launch that
 // took its thresholds from the pools); what overflows here as well goes on a.flaglist / a.nflag for the brute-force kernel
 void launch_shortlist_worklist(const ShortlistArgs &a, int *flags64, hipStream_t s);
@@ -323,7 +324,9 @@ struct FusedArgs {
 // kFusedMaxDp doubles (the 16-lane kernel stages the query row in LDS)
 constexpr int kFusedMaxDp = 288;
 bool fused_supported(int m, int Dp);
-void launch_hull_select_qp(const FusedArgs &a, hipStream_t s);
+// stripe: the work striped over the XCDs by bin (from 16 bins on; CHB_FUSED_STRIPE=0: position-major); ptr64: the m <= 5
+// kernel's 64-bit-pointer instantiation whatever the size of X (CHB_FUSED_PTR64=1)
+void launch_hull_select_qp(const FusedArgs &a, bool stripe, bool ptr64, hipStream_t s);
 
 // explicit problems: query sample q[p], hull_idx[p][m_max] compacted, hull_cnt[p] vertices
 // 16 < m <= kMaxMGeneric: one wavefront per problem, Gram and the solver's inverse in LDS (slow, see

@@ -1023,7 +1023,7 @@ __global__ __launch_bounds__(256) void pack_state_fix_kernel(PackState ps, Membe
 // smallest upper bound over the bin's members) and the admission sweep.  But ANY m base members of c bound the m-th nearest
 // distance from above, and which members are near a query is mostly decided by where the query's own bin lies: with
 // x_j = mu_h + e_j and x_p = mu_c + e_p the part of d^2(j, p) that varies over p is dominated by -2 <mu_h - mu_c, e_p>
-// (86 % of its variance on the benchmark generator, tools/pool_tau_probe.py).  So for every ordered pair (bin c, home bin
+// (86 % of its variance on the benchmark generator, DESIGN.md's numpy sizing).  So for every ordered pair (bin c, home bin
 // h) the 32 base members of c NEAREST TO THE CENTRE OF h are kept as one tile of shadow rows; a query whose nearest centre
 // is h learns tau(j, c) from that one tile (5.0-5.1 candidates per pair where the exact threshold gives 5.0; benchmark
 // configs[2] / [3] / [4]), and the bin itself is streamed once.  The query's own bin (h == c) keeps the two sweeps: a
@@ -2426,7 +2426,7 @@ static size_t shortlist_lds_bytes(int ks, int ml, bool four = false)
 }
 
 template <int ML, bool UPD>
-static void launch_sl(const ShortlistArgs &a, int *flags64, hipStream_t s)
+static void launch_sl(const ShortlistArgs &a, int *flags64, int bpw_force, hipStream_t s)
 {
     const int nq = a.pos_end - a.pos_begin;
     const int nqt = (nq + kPfQ - 1) / kPfQ;
@@ -2438,20 +2438,13 @@ static void launch_sl(const ShortlistArgs &a, int *flags64, hipStream_t s)
     bool skip_build = false;
     if constexpr (!UPD) skip_build = a.skip != 0;
     int bpw = skip_build ? 1 : (int)std::max<long long>(1, units / ((UPD ? 1024 : 2048) * 4 / kPfW));
-#ifdef CHB_DEV_KNOBS
-    static int env_bpw = -2;
-    if (env_bpw == -2) { const char *e = getenv("CHB_SL_BPW"); env_bpw = e ? atoi(e) : 0; }
-    if (env_bpw > 0) bpw = env_bpw;
-#endif
     bool pool_build = false;
     if constexpr (!UPD) pool_build = a.pool.Z != nullptr && a.qord != nullptr && a.ckey != nullptr;
     // (a pool-mode bin is ntile + a few tiles instead of 2 ntile: twice the bins per workgroup keep the streams as long)
     if (pool_build && !skip_build) bpw = (int)std::max<long long>(1, units / 1024);
-#ifdef CHB_DEV_KNOBS
-    if (env_bpw > 0) bpw = env_bpw;
-#endif
+    if (bpw_force > 0) bpw = bpw_force;
     // (the tile-skipping builds are one bin per workgroup by construction -- their early run ends and, with the pools, the
-    //  order of a bin's runs have only ever been exercised that way; the developer knob above does not reach them:
+    //  order of a bin's runs have only ever been exercised that way; the forced count above does not reach them:
     //  experiment 29 of round 5 saw short shortlists from the skipping pool build with two and more bins per workgroup)
     if (skip_build) bpw = 1;
     bpw = std::min(bpw, a.B);
@@ -2742,21 +2735,12 @@ void launch_shortlist_worklist(const ShortlistArgs &a_, int *flags64, hipStream_
     else launch_sl_work<16>(a, flags64, grid, s);
 }
 
-void launch_shortlist(const ShortlistArgs &a_, int *flags64, hipStream_t s)
+void launch_shortlist(const ShortlistArgs &a_, int *flags64, int bpw_force, hipStream_t s)
 {
     ShortlistArgs a = a_;
     // The accumulation-error factor is part of the proof that the shortlist contains the exact
-    // top-m: the product library takes it from the constant only.
+    // top-m: it is taken from the constant only.
     a.gamma = kGamma; a.tile_best_min = 16; a.tile_k2 = 3;
-#ifdef CHB_DEV_KNOBS   // developer builds (tools/): never below kGamma
-    {
-        static float g = -1.f; static int tb = -1;
-        if (g < 0.f) { const char *e = getenv("CHB_SL_GAMMA"); g = e ? std::max((float)atof(e), kGamma) : kGamma; }
-        if (tb < 0) { const char *e = getenv("CHB_SL_TILEBEST"); tb = e ? atoi(e) : 16; }
-        a.gamma = g; a.tile_best_min = tb;
-        { static int tk = -1; if (tk < 0) { const char *e = getenv("CHB_SL_TILEK"); tk = e ? std::max(1, atoi(e)) : 3; } a.tile_k2 = tk; }
-    }
-#endif
     const int nq = a.pos_end - a.pos_begin;
     if (nq <= 0 || a.B <= 0) return;
     if (a.Dz > 160) {
@@ -2771,14 +2755,14 @@ void launch_shortlist(const ShortlistArgs &a_, int *flags64, hipStream_t s)
         return;
     }
     if (a.update) {
-        if (a.m <= 8) launch_sl<1, true>(a, flags64, s);
-        else launch_sl<2, true>(a, flags64, s);   // (ML is unused in update mode: 2 marks the m > 8 build)
+        if (a.m <= 8) launch_sl<1, true>(a, flags64, bpw_force, s);
+        else launch_sl<2, true>(a, flags64, bpw_force, s);   // (ML is unused in update mode: 2 marks the m > 8 build)
     } else if (a.m <= 5) {
-        launch_sl<5, false>(a, flags64, s);
+        launch_sl<5, false>(a, flags64, bpw_force, s);
     } else if (a.m <= 8) {
-        launch_sl<8, false>(a, flags64, s);
+        launch_sl<8, false>(a, flags64, bpw_force, s);
     } else {
-        launch_sl<16, false>(a, flags64, s);
+        launch_sl<16, false>(a, flags64, bpw_force, s);
     }
 }
 

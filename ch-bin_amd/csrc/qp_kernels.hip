@@ -2108,14 +2108,13 @@ void launch_hull_qp(const QpArgs &a, hipStream_t s)
 //  windows of kFusedMaxDp columns)
 bool fused_supported(int m, int Dp) { (void)Dp; return m >= 1 && m <= 16; }
 
-void launch_hull_select_qp(const FusedArgs &a, hipStream_t s)
+void launch_hull_select_qp(const FusedArgs &a, bool stripe, bool ptr64, hipStream_t s)
 {
     const int nprob = (a.pos_end - a.pos_begin) * a.B;
     if (nprob <= 0) return;
     constexpr int WV = 4;
     FusedArgs as = a;
-    static const bool stripe_off = getenv("CHB_FUSED_STRIPE") != nullptr && atoi(getenv("CHB_FUSED_STRIPE")) == 0;
-    as.stripe = (!stripe_off && a.B >= 16) ? 1 : 0;
+    as.stripe = (stripe && a.B >= 16) ? 1 : 0;
     if (a.m > 5) {   // 16 lanes per pair, four pairs per wavefront
         int np16 = nprob, grid16 = (nprob + 4 * WV - 1) / (4 * WV);
         if (as.stripe) {
@@ -2134,9 +2133,8 @@ void launch_hull_select_qp(const FusedArgs &a, hipStream_t s)
         np5 = (a.pos_end - a.pos_begin) * ((a.B + 7) / 8);
         grid = 8 * ((np5 + 64 * WV - 1) / (64 * WV));
     }
-    // (rows as 32-bit byte offsets while the sample matrix is smaller than 4 GiB: see gram_rows; CHB_FUSED_PTR64=1
+    // (rows as 32-bit byte offsets while the sample matrix is smaller than 4 GiB: see gram_rows; ptr64 -- CHB_FUSED_PTR64=1 --
     //  selects the 64-bit-pointer instantiation regardless, for the tests)
-    static const bool ptr64 = getenv("CHB_FUSED_PTR64") != nullptr && atoi(getenv("CHB_FUSED_PTR64")) != 0;
     if (!ptr64 && (unsigned long long)a.n_samples * (unsigned long long)a.Dp * 8ull < (1ull << 32))
         hipLaunchKernelGGL((hull_select_qp_kernel<5, CHB_FUSED_C, WV, true>), dim3(grid), dim3(64 * WV), 0, s, as, np5, g_gate);
     else

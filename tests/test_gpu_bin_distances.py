@@ -8,8 +8,8 @@ replayed by the oracle with all B distances of every visit (oracle.sweep(..., wa
       row minimum as min_dist and second-smallest minus smallest as margin;
   (b) the developer library (child process) dumps the whole n_move x B matrix of the fit (CHB_DEV_ALL_DIST) with the
       shortlist stage's checks on (CHB_SL_BOUNDS, CHB_SL_VALIDATE): every entry must match the oracle's;
-  (c) the same with the bins per workgroup of the shortlist launches forced (CHB_SL_BPW, read once per process: one child
-      per value), above 64 once;
+  (c) the same with the bins per workgroup of the shortlist launches forced (CHB_SL_BPW, read when a context is created:
+      one child per value), above 64 once;
   (d) the ABI edges of margin_out.
 
 The cases cover the shortlist builds the product uses (threshold pools, tile skipping, the persistent member pack, several
@@ -287,7 +287,7 @@ def _run_child(data, tag, names, env):
 @pytest.fixture(scope="module")
 def dev_runs(data):
     """The developer children, one after another: the main one over every case except the pack case; the pack case with
-    its rebuild mark (read once per process); then the bins-per-workgroup children."""
+    its rebuild mark (read when a context is created); then the bins-per-workgroup children."""
     runs = {}
     main = [n for n in NAMES if "dev_env" not in CASES[n]]
     runs["dev"] = _run_child(data, "dev", main, {})

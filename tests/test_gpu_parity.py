@@ -1020,7 +1020,7 @@ def test_fused_16_lane_kernel_vs_oracle_and_lists(O, N, D, B, m, n_seed, batch, 
 def test_fused_kernel_64bit_row_pointers(O):
     """The m <= 5 fused kernel addresses the rows of X by 32-bit byte offsets below 4 GiB; the 64-bit-pointer
     instantiation (what a larger sample matrix gets) is selected here by CHB_FUSED_PTR64=1 in a child process (the
-    switch is read once per process) and must give the same fit."""
+    switch is read when a context is created) and must give the same fit."""
     import subprocess
     import sys
     code = (
