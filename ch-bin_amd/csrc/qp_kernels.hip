@@ -897,18 +897,13 @@ __device__ __forceinline__ void group_argmin16(double key, int lane, double &kmi
 // scratch is a 16-step dependent chain.  The pivot of the update is the Schur complement delta, the
 // same quantity whose collapse marks an affinely dependent support in solve_affine<M>.
 // developer variants (tools/m15_probe.py; tools/build_variant.sh <name> "-DCHB_DEV_QP16_STAT" or "-DCHB_DEV_CLK"):
-// CHB_DEV_QP16_STAT = iteration statistics of the 16-lane solver (its atomics distort timings), CHB_DEV_CLK = cycle
+// CHB_DEV_QP16_STAT = iteration statistics of the 16-lane solver (Group16::stat; its atomics distort timings), CHB_DEV_CLK = cycle
 // stamps of the fused 16-lane kernel's phases only
 #if defined(CHB_DEV_QP16_STAT) || defined(CHB_DEV_CLK)
 __device__ unsigned long long g_qp16_stats[16];
 #endif
 #ifdef CHB_DEV_CLK
 __device__ unsigned long long g_qp16_clk[131072][8];   // per-wavefront cycle stamps of the last launch (no atomics)
-#endif
-#ifdef CHB_DEV_QP16_STAT
-#define QP16_STAT(i, v) do { if (l16 == 0) atomicAdd(&g_qp16_stats[i], (unsigned long long)(v)); } while (0)
-#else
-#define QP16_STAT(i, v) do { } while (0)
 #endif
 #ifdef CHB_DEV_CLK
 #define QP16_CLK(t) const unsigned long long t = __builtin_readcyclecounter()
@@ -960,7 +955,7 @@ constexpr int kQ16Ld = 18;   // row stride of the 16 x 16 Gram tile in LDS (16-b
 // Qt = the group's LIFTED Gram tile in LDS (Q + s, row stride kQ16Ld), sv = its 16-double exchange row.
 // Rows and columns of H outside the support are zero, so the products below need no support mask.
 // small (out): the accepted pivot was below kSmallPivot x the vertex's own lifted norm -- the support is ill-conditioned
-// (cond ~ 1 / that ratio), see solve16's rebuild.  reject: the pivot below which the vertex counts as dependent.
+// (cond ~ 1 / that ratio), see active_set_distance2's rebuild.  reject: the pivot below which the vertex counts as dependent.
 constexpr double kSmallPivot = 1e-4;
 __device__ __forceinline__ bool inv16_insert(Inv16 &I, const double *Qt, double *sv, unsigned &S, int v, int l16, bool &small,
                                              double reject = 1e-13)
@@ -1010,12 +1005,6 @@ __device__ __forceinline__ bool inv16_insert(Inv16 &I, const double *Qt, double 
     return true;
 }
 
-__device__ __forceinline__ bool inv16_insert(Inv16 &I, const double *Qt, double *sv, unsigned &S, int v, int l16)
-{
-    bool small;
-    return inv16_insert(I, Qt, sv, S, v, l16, small);
-}
-
 // vertex r (in S) leaves
 __device__ __forceinline__ void inv16_remove(Inv16 &I, double *sv, unsigned &S, int r, int l16)
 {
@@ -1044,24 +1033,178 @@ __device__ __forceinline__ bool inv16_beta(const Inv16 &I, double &beta)
     return sum > 0.0;
 }
 
-// phase 2 of the 16-lane kernels: the hull (metric 0) or affine-hull distance SQUARED of the group's problem.
+// ---------------------------------------------------------------------------------------------
+// The Wolfe active-set iteration of the 16-lane kernels (solve16) and of hull_generic_kernel, written once: the hull
+// (metric 0) or affine-hull distance SQUARED of one problem with n > 0 vertices whose largest squared distance is
+// `scale`.  Every lane owns one vertex (`me`; `mine`: it exists; `diag`: its squared distance) and returns its weight in
+// `alpha`.  Where the Gram and the inverse H of the lifted support Gram live, and how the lanes of a problem talk to each
+// other, is the backend G (Group16 below, Wave64 further down), handed over reset (H = 0, support S = 0).  value(alpha, gi)
+// publishes the weights: gi = my entry of the gradient Q alpha, the result is alpha^T Q alpha.  cap() bounds the minor
+// cycle and rebuild's scan of S: 16 or n, the same scan, since S never has a bit at or above n.
+// `dirty` / rebuild: the explicit inverse is only as good as the supports it has been through.  A vertex that enters
+// with a pivot of 1e-7 of its norm (four nearly coplanar points in three dimensions: a near-duplicate contig among the
+// neighbours) leaves H with entries of 1e7 and a relative error of eps * cond; the Schur update that takes a vertex out
+// again cancels all but 1 / cond of that magnitude, so H -- and with it every later weight vector -- is off by
+// eps * cond^2 (6e-2 in the case tools/solve16_cases.py found: a distance 1.2 % too large, a corral of eight
+// "independent" vertices in three dimensions).  Hence: once a small pivot has been accepted (`dirty`), every removal
+// REBUILDS H from the Gram's rows for the vertices that remain -- |S| borderings, error eps * cond of the CURRENT
+// support, no history.  Well-conditioned problems (every benchmark configuration) never take that path.
+template <class G>
+__device__ __forceinline__ double active_set_distance2(G &g, int n, int metric, double scale, double &alpha)
+{
+    using Mask = typename G::Mask;
+    const Mask one = 1;
+    double val, gi;
+    bool sm;
+    if (!(scale > 0.0)) {   // every vertex coincides with the query (or NaN input)
+        alpha = g.me == 0 ? 1.0 : 0.0;
+        val = scale == 0.0 ? 0.0 : scale;
+    } else if (metric == 0) {
+        double best;
+        int i0;
+        g.argmin(g.mine ? g.diag : kInf, best, i0);
+        Mask banned = 0;
+        (void)g.insert(i0, sm);   // a single vertex is always independent
+        alpha = g.me == i0 ? 1.0 : 0.0;
+        bool dirty = false;
+        // H for the vertices in S from scratch; a vertex whose pivot comes out non-positive now (it was accepted on a
+        // corrupted H) is dropped and its weight shared out.  false: nothing usable was left, the solver has been set back
+        // to the nearest vertex alone (the caller leaves its minor cycle).
+        auto rebuild = [&]() __attribute__((always_inline)) -> bool {
+            const Mask S2 = g.S;
+            Mask lost = 0;
+            g.reset(); dirty = false;
+            for (int v = 0; v < g.cap(); ++v) {
+                if (!((S2 >> v) & one)) continue;
+                bool smv;
+                if (g.insert(v, smv, 0.0)) dirty = dirty || smv;
+                else lost |= one << v;
+            }
+            if (lost == 0) return true;
+            alpha = ((lost >> g.me) & one) ? 0.0 : alpha;
+            const double s1 = g.sum(alpha);
+            if (g.S != 0 && s1 > 0.0) { alpha = g.renormalise(alpha, s1); return true; }
+            g.reset();
+            (void)g.insert(i0, sm);
+            alpha = g.me == i0 ? 1.0 : 0.0;
+            return false;
+        };
+        const double tol = 1.4210854715202004e-14 * scale;  // 64 eps * scale
+        g.stat(0, 1);
+        for (int it = 0; it < G::kMajorCap; ++it) {
+            g.stat(1, 1);
+            val = g.value(alpha, gi);
+            double gmin;
+            int jb;
+            g.argmin((g.mine && !(((g.S | banned) >> g.me) & one)) ? gi : kInf, gmin, jb);
+            if (jb < 0 || !(gmin < val - tol)) break;
+            if (!g.insert(jb, sm)) {
+                banned |= one << jb;
+                continue;
+            }
+            dirty = dirty || sm;
+            for (int mi = 0; mi <= g.cap(); ++mi) {
+                double beta;
+                if (!g.beta(beta)) {   // (degenerate weights: give the vertex up)
+                    if ((g.S >> jb) & one) {
+                        g.remove(jb);
+                        if (dirty) (void)rebuild();
+                    }
+                    banned |= one << jb;
+                    break;
+                }
+                const bool in = (g.S >> g.me) & one;
+                const bool bad = in && !(beta > 0.0);
+                if (!g.any(bad)) {
+                    alpha = in ? beta : 0.0;
+                    break;
+                }
+                g.stat(2, 1);
+                const double den = alpha - beta;
+                double theta;
+                int kr;
+                g.argmin(bad ? (den > 0.0 ? alpha / den : 0.0) : kInf, theta, kr);
+                const double vnew = alpha + theta * (beta - alpha);
+                alpha = (in && g.me != kr) ? vnew : 0.0;
+                g.remove(kr);
+                if (kr == jb) banned |= one << jb;
+                if (dirty && !rebuild()) break;
+            }
+        }
+        g.stat(3, __popcll(g.S));
+        val = g.value(alpha, gi);
+    } else {
+        // distance to the AFFINE hull: greedy maximal affinely independent subset (affine_min_norm)
+        for (int k = 0; k < n; ++k) (void)g.insert(k, sm);
+        double beta = 0.0;
+        const bool okb = g.S != 0 && g.beta(beta);
+        alpha = (okb && ((g.S >> g.me) & one)) ? beta : 0.0;
+        if (!okb) alpha = g.me == 0 ? 1.0 : 0.0;
+        val = g.value(alpha, gi);
+    }
+    return val;
+}
+
+// The 16-lane backend: lane l16 of the group owns vertex l16, i.e. row l16 of the plain Gram (Qr) and of H (I), both in
+// registers.  Qt = the group's LIFTED Gram tile in LDS (what inv16_insert reads), sv = its exchange row.
+struct Group16 {
+    using Mask = unsigned;
+    static constexpr int kMajorCap = 3 * 16 + 8;
+    Inv16 I;
+    const double *Qt;
+    double *sv;
+    double Qr[16], diag;
+    int me, lane;   // (me = l16)
+    bool mine;
+    Mask S;
+    __device__ __forceinline__ int cap() const { return 16; }
+    __device__ __forceinline__ void reset()
+    {
+        S = 0u;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) I.H[j] = 0.0;
+    }
+    __device__ __forceinline__ bool insert(int v, bool &small, double reject = 1e-13) { return inv16_insert(I, Qt, sv, S, v, me, small, reject); }
+    __device__ __forceinline__ void remove(int r) { inv16_remove(I, sv, S, r, me); }
+    __device__ __forceinline__ bool beta(double &b) const { return inv16_beta(I, b); }
+    __device__ __forceinline__ double value(double alpha, double &gi)
+    {
+        double ag[16];   // gathered weights
+        group_allgather16(sv, me, alpha, ag);
+        gi = 0.0;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) gi = fma(Qr[j], ag[j], gi);
+        return group_sum16(alpha * gi);
+    }
+    __device__ __forceinline__ double sum(double v) const { return group_sum16(v); }
+    __device__ __forceinline__ void argmin(double key, double &kmin, int &idx) const { group_argmin16(key, lane, kmin, idx); }
+    __device__ __forceinline__ bool any(bool p) const { return ((__ballot(p) >> (lane & 48)) & 0xFFFFull) != 0ull; }
+    __device__ __forceinline__ double renormalise(double alpha, double s1) const { return alpha * fast_rcp(s1); }   // (s1 is O(1))
+    __device__ __forceinline__ void stat(int i, unsigned long long v) const
+    {
+#ifdef CHB_DEV_QP16_STAT
+        if (me == 0) atomicAdd(&g_qp16_stats[i], v);
+#endif
+    }
+};
+
+// phase 2 of the 16-lane kernels: the hull (metric 0) or affine-hull distance SQUARED of the group's problem, by
+// active_set_distance2 on a Group16.
 // Qt = the group's plain shifted Gram tile in LDS (rows / columns >= n finite, e.g. zero), sv = its exchange row;
 // lane l16 owns vertex l16 (n <= 16 vertices, n > 0) and returns its weight in `alpha`.
 __device__ __forceinline__ double solve16(double *Qt, double *sv, int n, int metric, int lane, double &alpha)
 {
     const int l16 = lane & 15;
-    double Qr[16];
+    Group16 g;
+    g.Qt = Qt; g.sv = sv; g.me = l16; g.lane = lane; g.mine = l16 < n;
 #pragma unroll
     for (int j = 0; j < 16; j += 2) {
         const double2 t = *reinterpret_cast<const double2 *>(Qt + l16 * kQ16Ld + j);
-        Qr[j] = t.x; Qr[j + 1] = t.y;
+        g.Qr[j] = t.x; g.Qr[j + 1] = t.y;
     }
-    double ag[16];   // gathered weights
-    const bool mine = l16 < n;
-    double val = 0.0;
     alpha = 0.0;
     const double diag = Qt[l16 * kQ16Ld + l16];
-    const double scale0 = group_max16(mine ? diag : 0.0);
+    const double scale0 = group_max16(g.mine ? diag : 0.0);
     // The problem is normalised by a power of two (exact): the largest squared distance becomes `scale` in
     // [0.5, 1), so thresholds and reciprocals see O(1) numbers whatever the units of the data.
     int ex = 0;
@@ -1069,134 +1212,16 @@ __device__ __forceinline__ double solve16(double *Qt, double *sv, int n, int met
     ex = ex < -1000 ? -1000 : (ex > 1000 ? 1000 : ex);
     const double dn = ldexp(1.0, -ex);
     const double scale = scale0 * dn;
+    g.diag = diag * dn;
 #pragma unroll
-    for (int j = 0; j < 16; ++j) Qr[j] *= dn;
+    for (int j = 0; j < 16; ++j) g.Qr[j] *= dn;
     // the tile in LDS becomes the lifted Gram Q + scale (what inv16_insert reads); Qr keeps the plain rows
 #pragma unroll
     for (int j = 0; j < 16; j += 2)
-        *reinterpret_cast<double2 *>(Qt + l16 * kQ16Ld + j) = double2{Qr[j] + scale, Qr[j + 1] + scale};
+        *reinterpret_cast<double2 *>(Qt + l16 * kQ16Ld + j) = double2{g.Qr[j] + scale, g.Qr[j + 1] + scale};
     __builtin_amdgcn_wave_barrier();
-    if (!(scale > 0.0)) {   // every vertex coincides with the query (or NaN input)
-        alpha = l16 == 0 ? 1.0 : 0.0;
-        val = scale == 0.0 ? 0.0 : scale;
-    } else if (metric == 0) {
-        double best;
-        int i0;
-        group_argmin16(mine ? diag * dn : kInf, lane, best, i0);
-        unsigned S = 0u, banned = 0u;
-        Inv16 I;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) I.H[j] = 0.0;
-        (void)inv16_insert(I, Qt, sv, S, i0, l16);   // a single vertex is always independent
-        alpha = l16 == i0 ? 1.0 : 0.0;
-        // Round 5: the explicit inverse is only as good as the supports it has been through.  A vertex that enters with a
-        // pivot of 1e-7 of its norm (four nearly coplanar points in three dimensions: a near-duplicate contig among the
-        // neighbours) leaves H with entries of 1e7 and a relative error of eps * cond; the Schur update that takes a vertex
-        // out again cancels all but 1 / cond of that magnitude, so H -- and with it every later weight vector -- is off by
-        // eps * cond^2 (6e-2 in the case tools/solve16_cases.py found: a distance 1.2 % too large, a corral of eight
-        // "independent" vertices in three dimensions).  Hence: once a small pivot has been accepted (`dirty`), every removal
-        // REBUILDS H from the tile's rows for the vertices that remain -- |S| borderings, error eps * cond of the CURRENT
-        // support, no history.  Well-conditioned problems (every benchmark configuration) never take that path.
-        bool dirty = false;
-        // H for the vertices in S from scratch; a vertex whose pivot comes out non-positive now (it was accepted on a
-        // corrupted H) is dropped and its weight shared out.  false: nothing usable was left, the solver has been set back
-        // to the nearest vertex alone (the caller leaves its minor cycle).
-        auto rebuild = [&]() __attribute__((always_inline)) -> bool {
-            const unsigned S2 = S;
-            unsigned lost = 0u;
-            S = 0u; dirty = false;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) I.H[j] = 0.0;
-            for (int v = 0; v < 16; ++v) {
-                if (!((S2 >> v) & 1u)) continue;
-                bool sm;
-                if (inv16_insert(I, Qt, sv, S, v, l16, sm, 0.0)) dirty = dirty || sm;
-                else lost |= 1u << v;
-            }
-            if (lost == 0u) return true;
-            alpha = ((lost >> l16) & 1u) ? 0.0 : alpha;
-            const double s1 = group_sum16(alpha);
-            if (S != 0u && s1 > 0.0) { alpha *= fast_rcp(s1); return true; }
-            S = 0u;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) I.H[j] = 0.0;
-            (void)inv16_insert(I, Qt, sv, S, i0, l16);
-            alpha = l16 == i0 ? 1.0 : 0.0;
-            return false;
-        };
-        const double tol = 1.4210854715202004e-14 * scale;  // 64 eps * scale
-        QP16_STAT(0, 1);
-        for (int it = 0; it < 3 * 16 + 8; ++it) {
-            double gi = 0.0;
-            QP16_STAT(1, 1);
-            group_allgather16(sv, l16, alpha, ag);
-#pragma unroll
-            for (int j = 0; j < 16; ++j) gi = fma(Qr[j], ag[j], gi);
-            val = group_sum16(alpha * gi);
-            double gmin;
-            int jb;
-            group_argmin16((mine && !(((S | banned) >> l16) & 1u)) ? gi : kInf, lane, gmin, jb);
-            if (jb < 0 || !(gmin < val - tol)) break;
-            {
-                bool sm;
-                if (!inv16_insert(I, Qt, sv, S, jb, l16, sm)) {
-                    banned |= 1u << jb;
-                    continue;
-                }
-                dirty = dirty || sm;
-            }
-            for (int mi = 0; mi <= 16; ++mi) {
-                double beta;
-                if (!inv16_beta(I, beta)) {   // (degenerate weights: give the vertex up)
-                    if ((S >> jb) & 1u) {
-                        inv16_remove(I, sv, S, jb, l16);
-                        if (dirty) (void)rebuild();
-                    }
-                    banned |= 1u << jb;
-                    break;
-                }
-                const bool in = (S >> l16) & 1u;
-                const bool bad = in && !(beta > 0.0);
-                if (((__ballot(bad) >> (lane & 48)) & 0xFFFFull) == 0ull) {
-                    alpha = in ? beta : 0.0;
-                    break;
-                }
-                QP16_STAT(2, 1);
-                const double den = alpha - beta;
-                double theta;
-                int kr;
-                group_argmin16(bad ? (den > 0.0 ? alpha / den : 0.0) : kInf, lane, theta, kr);
-                const double vnew = alpha + theta * (beta - alpha);
-                alpha = (in && l16 != kr) ? vnew : 0.0;
-                inv16_remove(I, sv, S, kr, l16);
-                if (kr == jb) banned |= 1u << jb;
-                if (dirty && !rebuild()) break;
-            }
-        }
-        QP16_STAT(3, __popc(S));
-        double gi = 0.0;
-        group_allgather16(sv, l16, alpha, ag);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) gi = fma(Qr[j], ag[j], gi);
-        val = group_sum16(alpha * gi);
-    } else {
-        // distance to the AFFINE hull: greedy maximal affinely independent subset (affine_min_norm)
-        unsigned S = 0u;
-        Inv16 I;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) I.H[j] = 0.0;
-        for (int k = 0; k < n; ++k) (void)inv16_insert(I, Qt, sv, S, k, l16);
-        double beta = 0.0;
-        const bool okb = S != 0u && inv16_beta(I, beta);
-        alpha = (okb && ((S >> l16) & 1u)) ? beta : 0.0;
-        if (!okb) alpha = l16 == 0 ? 1.0 : 0.0;
-        double gi = 0.0;
-        group_allgather16(sv, l16, alpha, ag);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) gi = fma(Qr[j], ag[j], gi);
-        val = group_sum16(alpha * gi);
-    }
-    return ldexp(val, ex);   // back to the data's units (exact)
+    g.reset();
+    return ldexp(active_set_distance2(g, n, metric, scale, alpha), ex);   // back to the data's units (exact)
 }
 
 // One k-sweep of the matrix core over the 16 rows `idv` (lane (row, kq): row = lane & 15 supplies the row,
@@ -1770,9 +1795,10 @@ __global__ __launch_bounds__(64 * WAVES, CHB_QP16_OCC) void hull_select_qp16_ker
 // ---------------------------------------------------------------------------------------------
 // num_neighbors > 16 (no cap in the reference: algorithm.py:17, cli/clustering.py:118-120): the plain form,
 // ONE wavefront per problem, up to 64 vertices.  Lane i owns vertex i: row i of the shifted Gram Q and of the
-// inverse H of the lifted support Gram (both in LDS, [64][65] doubles) and its weight alpha_i.  The same Wolfe
-// iteration and the same bordering / Schur updates as hull_qp16_kernel, with loops over the vertex count and
-// LDS rows where that kernel has 16-entry register arrays and shuffles.  Slow by design.
+// inverse H of the lifted support Gram (both in LDS, [64][65] doubles) and its weight alpha_i.  The iteration is
+// active_set_distance2 (above, shared with the 16-lane kernels) on the Wave64 backend: the same bordering / Schur
+// updates as Inv16, with loops over the vertex count and LDS rows where that has 16-entry register arrays and DPP
+// reductions.  Slow by design.
 constexpr int kGenN = 64, kGenLd = 65;
 
 struct GenLds {
@@ -1857,12 +1883,6 @@ __device__ __forceinline__ bool gen_insert(GenLds &L, int n, double s, unsigned 
     return true;
 }
 
-__device__ __forceinline__ bool gen_insert(GenLds &L, int n, double s, unsigned long long &S, int v, int lane)
-{
-    bool small;
-    return gen_insert(L, n, s, S, v, lane, small);
-}
-
 // vertex r (in the support) leaves
 __device__ __forceinline__ void gen_remove(GenLds &L, int n, unsigned long long &S, int r, int lane)
 {
@@ -1891,6 +1911,46 @@ __device__ __forceinline__ bool gen_beta(GenLds &L, int n, unsigned long long S,
     beta = b / sum;
     return sum > 0.0;
 }
+
+// The wavefront backend of active_set_distance2: lane i owns vertex i, i.e. row i of L.Q and of L.H.  It works on the
+// un-normalised Gram (the lift is s = scale).  gen_sync() stands between a write of L.va and its reads, and after the
+// reads before the next write (after the final evaluation that second one has nothing left to order).
+struct Wave64 {
+    using Mask = unsigned long long;
+    static constexpr int kMajorCap = 3 * kGenN + 8;
+    GenLds &L;
+    int n;
+    double scale, diag;
+    int me;   // (= lane)
+    bool mine;
+    Mask S;
+    __device__ __forceinline__ int cap() const { return n; }
+    __device__ __forceinline__ void reset()
+    {
+        S = 0ull;
+        for (int j = 0; j < kGenN; ++j) L.H[me][j] = 0.0;
+        gen_sync();
+    }
+    __device__ __forceinline__ bool insert(int v, bool &small, double reject = 1e-13) { return gen_insert(L, n, scale, S, v, me, small, reject); }
+    __device__ __forceinline__ void remove(int r) { gen_remove(L, n, S, r, me); }
+    __device__ __forceinline__ bool beta(double &b) const { return gen_beta(L, n, S, me, b); }
+    __device__ __forceinline__ double value(double alpha, double &gi)
+    {
+        L.va[me] = alpha;
+        gen_sync();
+        gi = 0.0;
+        if (mine)
+            for (int j = 0; j < n; ++j) gi = fma(L.Q[me][j], L.va[j], gi);
+        const double val = wave_sum64(alpha * gi);
+        gen_sync();
+        return val;
+    }
+    __device__ __forceinline__ double sum(double v) const { return wave_sum64(v); }
+    __device__ __forceinline__ void argmin(double key, double &kmin, int &idx) const { wave_argmin64(key, me, kmin, idx); }
+    __device__ __forceinline__ bool any(bool p) const { return __ballot(p) != 0ull; }
+    __device__ __forceinline__ double renormalise(double alpha, double s1) const { return alpha / s1; }
+    __device__ __forceinline__ void stat(int, unsigned long long) const { }
+};
 
 template <bool INDEXED>
 __global__ __launch_bounds__(64) void hull_generic_kernel(QpArgs a, int nprob, const int *xq, const int *xhull,
@@ -1941,109 +2001,8 @@ __global__ __launch_bounds__(64) void hull_generic_kernel(QpArgs a, int nprob, c
         double scale = diag;
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) scale = fmax(scale, __shfl_xor(scale, off, 64));
-        unsigned long long S = 0ull, banned = 0ull;
-        if (!(scale > 0.0)) {   // every vertex coincides with the query (or NaN input)
-            alpha = lane == 0 ? 1.0 : 0.0;
-            val = scale == 0.0 ? 0.0 : scale;
-        } else if (a.metric == 0) {
-            double best;
-            int i0;
-            wave_argmin64(mine ? diag : kInf, lane, best, i0);
-            (void)gen_insert(L, n, scale, S, i0, lane);   // a single vertex is always independent
-            alpha = lane == i0 ? 1.0 : 0.0;
-            // (as solve16: once a small pivot has been accepted, every removal rebuilds the inverse for what remains)
-            bool dirty = false;
-            auto rebuild = [&]() -> bool {
-                const unsigned long long S2 = S;
-                unsigned long long lost = 0ull;
-                S = 0ull; dirty = false;
-                for (int j = 0; j < kGenN; ++j) L.H[lane][j] = 0.0;
-                gen_sync();
-                for (int v = 0; v < n; ++v) {
-                    if (!((S2 >> v) & 1ull)) continue;
-                    bool sm;
-                    if (gen_insert(L, n, scale, S, v, lane, sm, 0.0)) dirty = dirty || sm;
-                    else lost |= 1ull << v;
-                }
-                if (lost == 0ull) return true;
-                alpha = ((lost >> lane) & 1ull) ? 0.0 : alpha;
-                const double s1 = wave_sum64(alpha);
-                if (S != 0ull && s1 > 0.0) { alpha /= s1; return true; }
-                S = 0ull;
-                for (int j = 0; j < kGenN; ++j) L.H[lane][j] = 0.0;
-                gen_sync();
-                (void)gen_insert(L, n, scale, S, i0, lane);
-                alpha = lane == i0 ? 1.0 : 0.0;
-                return false;
-            };
-            const double tol = 1.4210854715202004e-14 * scale;  // 64 eps * scale
-            for (int it = 0; it < 3 * kGenN + 8; ++it) {
-                L.va[lane] = alpha;
-                gen_sync();
-                double gi = 0.0;
-                if (mine)
-                    for (int j = 0; j < n; ++j) gi = fma(L.Q[lane][j], L.va[j], gi);
-                val = wave_sum64(alpha * gi);
-                gen_sync();
-                double gmin;
-                int jb;
-                wave_argmin64((mine && !(((S | banned) >> lane) & 1ull)) ? gi : kInf, lane, gmin, jb);
-                if (jb < 0 || !(gmin < val - tol)) break;
-                {
-                    bool sm;
-                    if (!gen_insert(L, n, scale, S, jb, lane, sm)) {
-                        banned |= 1ull << jb;
-                        continue;
-                    }
-                    dirty = dirty || sm;
-                }
-                for (int mi = 0; mi <= n; ++mi) {
-                    double beta;
-                    if (!gen_beta(L, n, S, lane, beta)) {   // (degenerate weights: give the vertex up)
-                        if ((S >> jb) & 1ull) {
-                            gen_remove(L, n, S, jb, lane);
-                            if (dirty) (void)rebuild();
-                        }
-                        banned |= 1ull << jb;
-                        break;
-                    }
-                    const bool in = (S >> lane) & 1ull;
-                    const bool bad = in && !(beta > 0.0);
-                    if (__ballot(bad) == 0ull) {
-                        alpha = in ? beta : 0.0;
-                        break;
-                    }
-                    const double den = alpha - beta;
-                    double theta;
-                    int kr;
-                    wave_argmin64(bad ? (den > 0.0 ? alpha / den : 0.0) : kInf, lane, theta, kr);
-                    const double vnew = alpha + theta * (beta - alpha);
-                    alpha = (in && lane != kr) ? vnew : 0.0;
-                    gen_remove(L, n, S, kr, lane);
-                    if (kr == jb) banned |= 1ull << jb;
-                    if (dirty && !rebuild()) break;
-                }
-            }
-            L.va[lane] = alpha;
-            gen_sync();
-            double gi = 0.0;
-            if (mine)
-                for (int j = 0; j < n; ++j) gi = fma(L.Q[lane][j], L.va[j], gi);
-            val = wave_sum64(alpha * gi);
-        } else {
-            // distance to the AFFINE hull: greedy maximal affinely independent subset (affine_min_norm)
-            for (int k = 0; k < n; ++k) (void)gen_insert(L, n, scale, S, k, lane);
-            double beta = 0.0;
-            const bool okb = S != 0ull && gen_beta(L, n, S, lane, beta);
-            alpha = (okb && ((S >> lane) & 1ull)) ? beta : 0.0;
-            if (!okb) alpha = lane == 0 ? 1.0 : 0.0;
-            L.va[lane] = alpha;
-            gen_sync();
-            double gi = 0.0;
-            if (mine)
-                for (int j = 0; j < n; ++j) gi = fma(L.Q[lane][j], L.va[j], gi);
-            val = wave_sum64(alpha * gi);
-        }
+        Wave64 g{L, n, scale, diag, lane, mine, 0ull};   // (handed over reset: H was zeroed above)
+        val = active_set_distance2(g, n, a.metric, scale, alpha);
     }
     const double dist = n <= 0 ? kInf : sqrt(fmax(val, 0.0));
     if (INDEXED) {
