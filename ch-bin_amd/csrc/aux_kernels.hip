@@ -382,14 +382,14 @@ __global__ void copy_i32_kernel(int *dst, const int *src, int n, Gate gate)
 }
 
 // ---- framed exchange of the sharded loop (chb_api.hip: open_batch / finish_round).  What a rank sends in a round's
-// all-gather is a FRAME: kXchgHdr header words -- {tag = exchange number of the fit << 4 | kind, wave-tiles skipped / seen /
-// never loaded by its base shortlist launch, fill mark of its persistent pack's arena, 0, 0, 0} -- followed by the C labels
-// of its slice.  Everything that steers the host loop (and with it the ORDER of the collectives) is then derived from what
-// ALL ranks sent: the statistics are summed / maximised over the frames before they travel home with the verdict, so every
-// rank takes the same decisions in the same batch; and a rank that is out of step (its tag differs) is noticed on the
-// device and fails the fit at the sweep's end instead of silently mixing label buffers.
-// (preset: slot[0] = K, the start value of the unpack kernel's first-change minimum -- this launch is ordered before the
-//  all-gather and the unpack launch on the stream)
+// all-gather is a FRAME: kXchgHdr header words -- FrameWord in chb_internal.h: the tag, then the statistics and the arena
+// mark of the batch's verdict slot (SlotWord) -- followed by the C labels of its slice.  Everything that steers the host
+// loop (and with it the ORDER of the collectives) is then derived from what ALL ranks sent: the statistics are summed /
+// maximised over the frames before they travel home with the verdict, so every rank takes the same decisions in the same
+// batch; and a rank that is out of step (its tag differs) is noticed on the device and fails the fit at the sweep's end
+// instead of silently mixing label buffers.
+// (preset: slot[kSlotFirstChange] = K, the start value of the unpack kernel's first-change minimum -- this launch is
+//  ordered before the all-gather and the unpack launch on the stream)
 __global__ void xchg_pack_kernel(int *frames, int rank, int C, const int *src, int tag, int *slot, int with_stats,
                                  int with_mark, int preset, int K, Gate gate)
 {
@@ -398,17 +398,20 @@ __global__ void xchg_pack_kernel(int *frames, int rank, int C, const int *src, i
     int *f = frames + (size_t)rank * (C + kXchgHdr);
     if (i < C) f[kXchgHdr + i] = src[(size_t)rank * C + i];
     if (i == 0) {
-        f[0] = tag;
-        f[1] = with_stats ? slot[3] : 0; f[2] = with_stats ? slot[4] : 0; f[3] = with_stats ? slot[5] : 0;
-        f[4] = with_mark ? slot[6] : 0;
-        f[5] = with_stats ? slot[7] : 0; f[6] = with_stats ? slot[8] : 0; f[7] = 0;
-        if (preset) slot[0] = K;
+        f[kFrameTag] = tag;
+        f[kFrameSkipped] = with_stats ? slot[kSlotSkipped] : 0; f[kFrameSeen] = with_stats ? slot[kSlotSeen] : 0;
+        f[kFrameUnloaded] = with_stats ? slot[kSlotUnloaded] : 0;
+        f[kFrameMark] = with_mark ? slot[kSlotMark] : 0;
+        f[kFramePoolCand] = with_stats ? slot[kSlotPoolCand] : 0; f[kFramePoolPairs] = with_stats ? slot[kSlotPoolPairs] : 0;
+        f[kFrameSpare] = 0;
+        if (preset) slot[kSlotFirstChange] = K;
     }
 }
 
 // labels of every rank's frame -> dst[pos]; round kind (lab_prev != nullptr): positions >= active are compared with
-// lab_prev (first change -> slot[0], preset to K by the pack launch) and then written to it; thread r < world checks rank
-// r's tag; with_stats: slot[3..5] = sums over the ranks, slot[6] = largest fill mark
+// lab_prev (first change -> slot[kSlotFirstChange], preset to K by the pack launch) and then written to it; thread
+// r < world checks rank r's tag; with_stats: the slot's skip and pool statistics = sums over the ranks, slot[kSlotMark] =
+// largest fill mark
 __global__ void xchg_unpack_kernel(const int *frames, int world, int C, int K, int tag, int *dst, int *lab_prev, int active,
                                    int *slot, int with_stats, int *xerr, Gate gate)
 {
@@ -428,7 +431,7 @@ __global__ void xchg_unpack_kernel(const int *frames, int world, int C, int K, i
         }
     }
     if (idx < world) {
-        const int theirs = frames[(size_t)idx * F];
+        const int theirs = frames[(size_t)idx * F + kFrameTag];
         if (theirs != tag && atomicCAS(&xerr[0], 0, 1) == 0) { xerr[1] = tag; xerr[2] = theirs; xerr[3] = idx; }
     }
     if (idx == 0 && with_stats) {
@@ -436,11 +439,13 @@ __global__ void xchg_unpack_kernel(const int *frames, int world, int C, int K, i
         for (int r = 0; r < world; ++r) {
             const int *f = frames + (size_t)r * F;
             // (saturating: the sums only feed ratio tests)
-            a = (int)min(0x7fffffffll, (long long)a + f[1]); b = (int)min(0x7fffffffll, (long long)b + f[2]);
-            c = (int)min(0x7fffffffll, (long long)c + f[3]); mk = max(mk, f[4]);
-            pc = (int)min(0x7fffffffll, (long long)pc + f[5]); pp = (int)min(0x7fffffffll, (long long)pp + f[6]);
+            a = (int)min(0x7fffffffll, (long long)a + f[kFrameSkipped]); b = (int)min(0x7fffffffll, (long long)b + f[kFrameSeen]);
+            c = (int)min(0x7fffffffll, (long long)c + f[kFrameUnloaded]); mk = max(mk, f[kFrameMark]);
+            pc = (int)min(0x7fffffffll, (long long)pc + f[kFramePoolCand]);
+            pp = (int)min(0x7fffffffll, (long long)pp + f[kFramePoolPairs]);
         }
-        slot[3] = a; slot[4] = b; slot[5] = c; slot[6] = mk; slot[7] = pc; slot[8] = pp;
+        slot[kSlotSkipped] = a; slot[kSlotSeen] = b; slot[kSlotUnloaded] = c; slot[kSlotMark] = mk;
+        slot[kSlotPoolCand] = pc; slot[kSlotPoolPairs] = pp;
     }
 }
 

@@ -36,11 +36,6 @@ namespace {
 
 thread_local std::string g_err;
 
-// a batch's verdict slot: [0] first changed position of the round, [1] tiles of the largest bin, [2] tiles of all bins,
-// [3..5] wave-tiles skipped / seen / never loaded (tile skipping), [6] fill mark of the persistent pack's arena,
-// [7..8] candidates admitted / pairs (threshold pools), sampled by the batch's base shortlist launch; the rest spare
-constexpr int kSlotInts = 16;
-
 int fail(int code, const std::string &msg)
 {
     g_err = msg;
@@ -221,10 +216,9 @@ struct chb_ctx {
     DevBuf<int> bq, lab_old, lab_prev, lab_new, first_change;
     int *bq_cur = nullptr;      // the open batch's sample indices: bq.p, or a window of perm (no copy)
     int *fc_host = nullptr;     // pinned landing places of the two verdict slots (kSlotInts ints each, as on the device)
-    int *fc_cur = nullptr;      // slot of the open batch (first_change.p + 0 / kSlotInts): {first changed position, tiles of the
-                                // batch's largest bin, tiles of all bins, wave-tiles skipped / seen by the first
-                                // workgroups of its shortlist launch}: bin sizes and skip statistics ride home with the
-                                // verdict in one 20-byte copy
+    int *fc_cur = nullptr;      // slot of the open batch (first_change.p + 0 / kSlotInts), words as SlotWord names them: bin
+                                // sizes, skip / pool statistics and the pack's fill mark ride home with the verdict in
+                                // one copy of kSlotHome ints
     hipEvent_t fc_event[2] = {nullptr, nullptr};
     bool argmin_in_place = false;   // chb_fit_cluster without exchange: argmin also stores the label to lab_prev
     DevBuf<double> mind, mind2, dist;   // winning hull distance, runner-up (margin report), all distances
@@ -363,6 +357,45 @@ struct chb_ctx {
     Lists L2() { return Lists{l2d.p, l2i.p, l2c.p}; }
     Lists Lcur() { return (round_in_batch & 1) ? L2() : L1(); }
     Lists Lprev() { return (round_in_batch & 1) ? L1() : L2(); }
+
+    // The kernels' argument blocks for the positions [lo, hi) of the open batch, with the fields that every launch of a
+    // kind shares; a call site adds only what makes it different, and what nobody sets stays zero.
+    TopmArgs topm_args(int lo, int hi)
+    {
+        TopmArgs a{};
+        a.X = X.p; a.Dp = Dp; a.bq = bq_cur; a.pos_begin = lo; a.pos_end = hi; a.B = B; a.m = m; a.Kcap = Kcap;
+        return a;
+    }
+    // (query side, geometry, scale, overflow counter, the brute-force kernel's work list -- its counter reset by the CSR kernels)
+    ShortlistArgs shortlist_args(int lo, int hi)
+    {
+        ShortlistArgs a{};
+        a.Gs = Gs.p; a.gq = reinterpret_cast<const float2 *>(gq.p); a.qn = reinterpret_cast<const float2 *>(qn.p);
+        a.Dz = Dz; a.S = shadow_scale; a.bq = bq_cur; a.pos_begin = lo; a.pos_end = hi; a.B = B; a.m = m; a.Kcap = Kcap;
+        a.overflow = overflow.p; a.flaglist = flaglist.p; a.nflag = nflag.p;
+        return a;
+    }
+    RescoreArgs rescore_args(int lo, int hi)   // (candidates: the base shortlists)
+    {
+        RescoreArgs a{};
+        a.X = X.p; a.Dp = Dp; a.bq = bq_cur; a.pos_begin = lo; a.pos_end = hi; a.B = B; a.m = m; a.Kcap = Kcap;
+        a.cand = cand.p; a.cand_cnt = cand_cnt.p; a.cand_cap = kCandCap;
+        return a;
+    }
+    QpArgs qp_args(int lo, int hi)
+    {
+        QpArgs a{};
+        a.X = X.p; a.D = D; a.Dp = Dp; a.bq = bq_cur; a.pos_begin = lo; a.pos_end = hi; a.B = B; a.m = m; a.Kcap = Kcap;
+        a.dist = dist.p; a.metric = metric;
+        return a;
+    }
+    FusedArgs fused_args(int lo, int hi)
+    {
+        FusedArgs a{};
+        a.X = X.p; a.n_samples = N; a.D = D; a.Dp = Dp; a.bq = bq_cur; a.pos_begin = lo; a.pos_end = hi;
+        a.B = B; a.m = m; a.Kcap = Kcap; a.dist = dist.p; a.metric = metric;
+        return a;
+    }
 };
 
 // In-place all-gather of `count` elements per rank inside the device buffer `buf` (rank r's slice sits at
@@ -834,14 +867,14 @@ int batch_begin_dev(chb_ctx *h, int K, int q_lo, int q_hi, bool need_lists)
         // one launch instead of count + scan + fill + gather
         Timed t(h, "bucket", (double)K);
         launch_pack_state_start(h->pack_state(), h->pk.view(), h->D, h->Dz, h->labels.p, h->inb.p, h->bq_cur, K, h->lab_old.p,
-                                h->B, sp.gflag ? &sp : nullptr, h->fc_cur + 1, h->nflag.p, s);
+                                h->B, sp.gflag ? &sp : nullptr, h->fc_cur + kSlotMaxTiles, h->nflag.p, s);
         h->stats_pp_batches += 1;
     } else {
         // (the batch is opened -- labels remembered, members marked -- inside the CSR count's launch)
         Timed t(h, "bucket", (double)h->N);
         launch_bucket_base(h->labels.p, h->inb.p, (int)h->N, h->B, h->cnt.p, h->bin_ptr.p,
                            h->cursor.p, h->memb_id.p, h->pk.pad_ptr.p, h->nflag.p, s, h->bq_cur, K, h->lab_old.p,
-                           sp.gflag ? &sp : nullptr, h->fc_cur + 1, pf_base_path ? h->ms.p : nullptr,
+                           sp.gflag ? &sp : nullptr, h->fc_cur + kSlotMaxTiles, pf_base_path ? h->ms.p : nullptr,
                            skip_on ? h->shell_inv.p : nullptr, skip_on ? h->nsh : 1);
     }
     if (h->pool_valid) {
@@ -850,13 +883,9 @@ int batch_begin_dev(chb_ctx *h, int K, int q_lo, int q_hi, bool need_lists)
         launch_pool_open(h->pool_view(), h->inb.p, h->D, h->Dz, h->B, h->nflag2.p, s);
     }
     h->pool_holes = true;
-    TopmArgs a{};
-    a.X = h->X.p; a.Dp = h->Dp; a.bq = h->bq_cur; a.pos_begin = q_lo; a.pos_end = q_hi;
-    a.bin_ptr = h->bin_ptr.p; a.memb_id = h->memb_id.p; a.memb_code = nullptr;
+    TopmArgs a = h->topm_args(q_lo, q_hi);
+    a.bin_ptr = h->bin_ptr.p; a.memb_id = h->memb_id.p; a.out = h->L0();
     if (pp_now) { a.bin_ptr = h->pp_start.p; a.bin_cnt = h->pp_fill.p; a.memb_id = h->pp_memb.p; }
-    a.B = h->B; a.m = h->m; a.Kcap = h->Kcap;
-    a.in = Lists{nullptr, nullptr, nullptr};
-    a.out = h->L0();
     if (pf_base_path) {
         // two-stage exact selection: fp16 matrix-core shortlist, exact fp64 on the shortlist,
         // brute force only for (query tile, bin) pairs whose shortlist overflowed
@@ -874,30 +903,24 @@ int batch_begin_dev(chb_ctx *h, int K, int q_lo, int q_hi, bool need_lists)
             Timed t(h, "bucket", 0.0);
             launch_query_order(h->ckey.p, h->bq_cur, q_lo, q_hi, h->B, h->qord.p, h->home.p, s);
         }
-        ShortlistArgs pa{};
-        pa.Gs = h->Gs.p; pa.gq = reinterpret_cast<const float2 *>(h->gq.p);
-        pa.qn = reinterpret_cast<const float2 *>(h->qn.p);
-        pa.P = h->pk.view(); pa.Dz = h->Dz; pa.S = h->shadow_scale;
-        pa.bq = h->bq_cur; pa.pos_begin = q_lo; pa.pos_end = q_hi;
-        pa.bin_ptr = h->bin_ptr.p; pa.memb_id = h->memb_id.p; pa.update = false;
+        ShortlistArgs pa = h->shortlist_args(q_lo, q_hi);
+        pa.P = h->pk.view(); pa.bin_ptr = h->bin_ptr.p; pa.memb_id = h->memb_id.p;
         if (pp_now) {   // (a bin = its region: first row, tiles in use; a row's sample, -1 for a hole)
             pa.P.pad_ptr = h->pp_start.p; pa.P.nt = h->pp_nt.p;
             pa.bin_ptr = h->pp_start.p; pa.memb_id = h->pp_memb.p;
         }
-        pa.B = h->B; pa.m = h->m; pa.Kcap = h->Kcap;
-        pa.cand = h->cand.p; pa.cand_cnt = h->cand_cnt.p; pa.cand_cap = kCandCap; pa.overflow = h->overflow.p;
+        pa.cand = h->cand.p; pa.cand_cnt = h->cand_cnt.p; pa.cand_cap = kCandCap; pa.seg = sp;
         if (fusedp) pa.tau_out = h->tau.p;
-        pa.seg = sp;
         if (sp.launch) h->stats_seg_batches += 1;
-        if (skip_on) { pa.qord = qord_p; pa.home = home_p; pa.skip = 1; pa.skip_stat = h->fc_cur + 3; }
+        if (skip_on) { pa.qord = qord_p; pa.home = home_p; pa.skip = 1; pa.skip_stat = h->fc_cur + kSlotSkipped; }
         if (pool_on) {
-            pa.qord = qord_p; pa.home = home_p; pa.ckey = h->ckey.p; pa.pool = h->pool_view(); pa.pool_stat = h->fc_cur + 7;
+            pa.qord = qord_p; pa.home = home_p; pa.ckey = h->ckey.p; pa.pool = h->pool_view();
+            pa.pool_stat = h->fc_cur + kSlotPoolCand;
             h->stats_pool_batches += 1;
         }
         { const int r_ = dev_shortlist_args(h, pa, skip_on, pp_now); if (r_) return r_; }
         {
             Timed t(h, "prefilter", (double)(q_hi - q_lo) * h->hint_base_members);
-            pa.flaglist = h->flaglist.p; pa.nflag = h->nflag.p;   // (counter reset by the CSR scan / the batch CSR kernel)
             launch_shortlist(pa, h->flags64.p, sl_bpw(h), s);
         }
         const int *fb_list = h->flaglist.p, *fb_n = h->nflag.p;   // the brute-force kernel's work list
@@ -912,10 +935,8 @@ int batch_begin_dev(chb_ctx *h, int K, int q_lo, int q_hi, bool need_lists)
         }
         { const int r_ = dev_shortlist_report(h, pa, skip_on, pool_on, pp_now); if (r_) return r_; }
         if (!fusedp) {
-            RescoreArgs ra{};
-            ra.X = h->X.p; ra.Dp = h->Dp; ra.bq = h->bq_cur; ra.pos_begin = q_lo; ra.pos_end = q_hi;
-            ra.B = h->B; ra.m = h->m; ra.Kcap = h->Kcap;
-            ra.cand = h->cand.p; ra.cand_cnt = h->cand_cnt.p; ra.cand_cap = kCandCap; ra.out = h->L0();
+            RescoreArgs ra = h->rescore_args(q_lo, q_hi);
+            ra.out = h->L0();
             Timed t(h, "rescore", (double)(q_hi - q_lo) * h->B);
             launch_rescore(ra, s);
         } else {
@@ -938,154 +959,131 @@ int batch_begin_dev(chb_ctx *h, int K, int q_lo, int q_hi, bool need_lists)
     return CHB_OK;
 }
 
+// ---- a round's three formulations (batch_round_dev picks one; a = its exact selection over the batch's own entries)
+// the batch's own entries as a padded pack, and the update-mode shortlist launch over it, less its thresholds and candidates
+ShortlistArgs batch_entry_shortlist(chb_ctx *h, int lo, int hi)
+{
+    launch_pack_centered(h->X.p, h->D, h->Dp, h->memb2_id.p, h->memb2_code.p, h->bin_ptr2.p, h->B, 2 * h->K,
+                         h->centers.p, h->mu_g.p, h->shadow_scale, h->Dz, h->pk2.view(), h->stream);
+    ShortlistArgs pa = h->shortlist_args(lo, hi);
+    pa.P = h->pk2.view(); pa.bin_ptr = h->bin_ptr2.p; pa.memb_id = h->memb2_id.p; pa.update = true;
+    return pa;
+}
+
+// fused (m <= 16, no lists wanted): shortlist of the batch's own entries against the base stage's tau, then selection +
+// hull distance straight from the two shortlists
+void round_fused(chb_ctx *h, int lo, int hi, TopmArgs a)
+{
+    hipStream_t s = h->stream;
+    const int cur = h->round_in_batch & 1;
+    ShortlistArgs pa = batch_entry_shortlist(h, lo, hi);
+    pa.tau_in = h->tau.p; pa.cand = h->candu[cur].p; pa.cand_cnt = h->candu_cnt[cur].p; pa.cand_cap = kCandCapU;
+    {
+        Timed t(h, "prefilter_update", (double)(hi - lo) * h->hint_batch_entries);
+        launch_shortlist(pa, h->flags64.p, sl_bpw(h), s);
+    }
+    {
+        // overflowed pairs: exact top-m among the (eligible) batch entries as their shortlist
+        a.in = a.out = Lists{nullptr, nullptr, nullptr};
+        a.cand_out = h->candu[cur].p; a.cand_cnt_out = h->candu_cnt[cur].p; a.cand_cap = kCandCapU;
+        Timed t(h, "topm_fallback", 0.0);
+        launch_topm_flagged(a, h->flags64.p, h->flaglist.p, h->nflag.p, s);
+    }
+    FusedArgs f = h->fused_args(lo, hi);
+    f.cand = h->cand.p; f.cand_cnt = h->cand_cnt.p; f.candu = h->candu[cur].p; f.candu_cnt = h->candu_cnt[cur].p;
+    if (h->round_in_batch > 0) { f.candp = h->candu[cur ^ 1].p; f.candp_cnt = h->candu_cnt[cur ^ 1].p; }
+    f.slow = h->slow.p; f.n_slow = h->n_slow.p; f.bin_ptr = h->bin_ptr.p; f.short_cnt = h->short_cnt.p;
+    if (h->pp_batch) f.bin_size = h->pp_live.p;
+    {
+        Timed t(h, "hull_qp", (double)(hi - lo) * h->B);
+        launch_hull_select_qp(f, h->sw.fused_stripe, h->sw.fused_ptr64, s);
+    }
+    {
+        // the exact path for what the fused kernel left: cdist-rounded distances on both shortlists,
+        // (distance, index) order, then the list-based hull kernel
+        Timed t(h, "slow_path", 0.0);
+        RescoreArgs ra = h->rescore_args(lo, hi);
+        ra.cand2 = h->candu[cur].p; ra.cand2_cnt = h->candu_cnt[cur].p; ra.cand2_cap = kCandCapU;
+        ra.active = h->slow.p; ra.n_active = h->n_slow.p; ra.out = h->L1();
+        launch_rescore(ra, s);
+        QpArgs q = h->qp_args(lo, hi);
+        q.lists = h->L1(); q.active = h->slow.p; q.n_active = h->n_slow.p;
+        launch_hull_qp(q, s);
+    }
+}
+
+// list-based with the shortlist stage: the batch members that can displace an entry of the base list -- fp16 shortlist
+// against the exact m-th distance, exact rescoring seeded with the base list
+// (fit rounds only produce the "earlier" / "later" eligibility codes, which have the affine form the shortlist kernel
+// evaluates; chb_topm_per_bin's "not equal" code stays on launch_topm)
+int round_lists_shortlist(chb_ctx *h, int lo, int hi, const TopmArgs &a)
+{
+    hipStream_t s = h->stream;
+    ShortlistArgs pa = batch_entry_shortlist(h, lo, hi);
+    pa.seed = h->L0(); pa.cand = h->cand.p; pa.cand_cnt = h->cand_cnt.p; pa.cand_cap = kCandCap;
+    {
+        Timed t(h, "prefilter_update", (double)(hi - lo) * h->hint_batch_entries);
+        launch_shortlist(pa, h->flags64.p, sl_bpw(h), s);
+        // the (position, bin) pairs with a non-empty shortlist, for rescore_kernel
+        launch_compact_active(h->cand_cnt.p, lo, hi, h->B, h->Kcap, h->act_blk.p, h->active.p, h->n_active.p, s);
+    }
+    RescoreArgs ra = h->rescore_args(lo, hi);
+    ra.active = h->active.p; ra.n_active = h->n_active.p; ra.in = h->L0(); ra.out = h->Lcur();
+    // pairs without any candidate keep the base list
+    const size_t nl = (size_t)h->Kcap * h->B;
+    HIPCHK(hipMemcpyAsync(ra.out.d, h->l0d.p, sizeof(double) * nl * h->m, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(ra.out.idx, h->l0i.p, sizeof(int) * nl * h->m, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(ra.out.cnt, h->l0c.p, sizeof(int) * nl, hipMemcpyDeviceToDevice, s));
+    {
+        Timed t(h, "rescore_update", (double)(hi - lo) * h->B);
+        launch_rescore(ra, s);
+    }
+    {
+        Timed t(h, "topm_fallback", 0.0);
+        launch_topm_flagged(a, h->flags64.p, h->flaglist.p, h->nflag.p, s);
+    }
+    return CHB_OK;
+}
+
+// list-based, brute force: the exact selection over all of the batch's entries
+void round_lists_plain(chb_ctx *h, int lo, int hi, const TopmArgs &a)
+{
+    Timed t(h, "topm_update", (double)(hi - lo) * h->hint_batch_entries);
+    if (h->m > kMaxM) launch_topm_generic(a, h->stream); else launch_topm(a, h->stream);
+}
+
 // lab_prev (device) holds the labels of the previous round.  Evaluates [max(active,q_lo), q_hi).
 int batch_round_dev(chb_ctx *h, int active)
 {
     hipStream_t s = h->stream;
     const int lo = std::max(active, h->q_lo), hi = h->q_hi;
-    if (hi <= lo) launch_fill_i32(h->fc_cur, h->K, 1, s);
+    if (hi <= lo) launch_fill_i32(h->fc_cur + kSlotFirstChange, h->K, 1, s);
     const bool fusedp = h->fused && h->lists_valid == false;
     if (hi > lo) {
         {
             Timed t(h, "bucket", (double)h->K);
-            launch_bucket_batch(h->lab_prev.p, h->lab_old.p, h->bq_cur, h->K, h->B, h->cnt2.p,
-                                h->bin_ptr2.p, h->cursor2.p, h->memb2_id.p, h->memb2_code.p, h->pk2.pad_ptr.p,
-                                h->fc_cur, fusedp ? h->n_slow.p : nullptr, h->nflag.p, s,
-                                (h->pf_fit && h->pk2.bb.p) ? h->pk2.bb.p : nullptr);
+            launch_bucket_batch(h->lab_prev.p, h->lab_old.p, h->bq_cur, h->K, h->B, h->cnt2.p, h->bin_ptr2.p, h->cursor2.p,
+                                h->memb2_id.p, h->memb2_code.p, h->pk2.pad_ptr.p, h->fc_cur + kSlotFirstChange,
+                                fusedp ? h->n_slow.p : nullptr, h->nflag.p, s, (h->pf_fit && h->pk2.bb.p) ? h->pk2.bb.p : nullptr);
         }
-        TopmArgs a{};
-        a.X = h->X.p; a.Dp = h->Dp; a.bq = h->bq_cur; a.pos_begin = lo; a.pos_end = hi;
+        TopmArgs a = h->topm_args(lo, hi);
         a.bin_ptr = h->bin_ptr2.p; a.memb_id = h->memb2_id.p; a.memb_code = h->memb2_code.p;
-        a.B = h->B; a.m = h->m; a.Kcap = h->Kcap;
         a.in = h->L0(); a.out = h->Lcur();
-        if (fusedp) {
-            // ---- fused path: shortlist of the batch's own entries against the base stage's tau, then
-            // selection + hull distance straight from the two shortlists
-            const int cur = h->round_in_batch & 1;
-            launch_pack_centered(h->X.p, h->D, h->Dp, h->memb2_id.p, h->memb2_code.p, h->bin_ptr2.p, h->B, 2 * h->K,
-                                 h->centers.p, h->mu_g.p, h->shadow_scale, h->Dz, h->pk2.view(), s);
-            ShortlistArgs pa{};
-            pa.Gs = h->Gs.p; pa.gq = reinterpret_cast<const float2 *>(h->gq.p);
-            pa.qn = reinterpret_cast<const float2 *>(h->qn.p);   // (the fit's table)
-            pa.P = h->pk2.view(); pa.Dz = h->Dz; pa.S = h->shadow_scale;
-            pa.bq = h->bq_cur; pa.pos_begin = lo; pa.pos_end = hi;
-            pa.bin_ptr = h->bin_ptr2.p; pa.memb_id = h->memb2_id.p; pa.update = true;
-            pa.tau_in = h->tau.p;
-            pa.B = h->B; pa.m = h->m; pa.Kcap = h->Kcap;
-            pa.cand = h->candu[cur].p; pa.cand_cnt = h->candu_cnt[cur].p; pa.cand_cap = kCandCapU;
-            pa.overflow = h->overflow.p;
-            {
-                Timed t(h, "prefilter_update", (double)(hi - lo) * h->hint_batch_entries);
-                pa.flaglist = h->flaglist.p; pa.nflag = h->nflag.p;   // (counter reset by the CSR scan / the batch CSR kernel)
-            launch_shortlist(pa, h->flags64.p, sl_bpw(h), s);
-            }
-            {
-                // overflowed pairs: exact top-m among the (eligible) batch entries as their shortlist
-                a.in = Lists{nullptr, nullptr, nullptr};
-                a.out = Lists{nullptr, nullptr, nullptr};
-                a.cand_out = h->candu[cur].p; a.cand_cnt_out = h->candu_cnt[cur].p; a.cand_cap = kCandCapU;
-                Timed t(h, "topm_fallback", 0.0);
-                launch_topm_flagged(a, h->flags64.p, h->flaglist.p, h->nflag.p, s);
-            }
-            FusedArgs f{};
-            f.X = h->X.p; f.n_samples = h->N; f.D = h->D; f.Dp = h->Dp; f.bq = h->bq_cur; f.pos_begin = lo; f.pos_end = hi;
-            f.B = h->B; f.m = h->m; f.Kcap = h->Kcap;
-            f.cand = h->cand.p; f.cand_cnt = h->cand_cnt.p;
-            f.candu = h->candu[cur].p; f.candu_cnt = h->candu_cnt[cur].p;
-            if (h->round_in_batch > 0) { f.candp = h->candu[cur ^ 1].p; f.candp_cnt = h->candu_cnt[cur ^ 1].p; }
-            f.dist = h->dist.p; f.metric = h->metric; f.slow = h->slow.p; f.n_slow = h->n_slow.p;
-            f.bin_ptr = h->bin_ptr.p; f.short_cnt = h->short_cnt.p;
-            if (h->pp_batch) f.bin_size = h->pp_live.p;
-            {
-                Timed t(h, "hull_qp", (double)(hi - lo) * h->B);
-                launch_hull_select_qp(f, h->sw.fused_stripe, h->sw.fused_ptr64, s);
-            }
-            {
-                // the exact path for what the fused kernel left: cdist-rounded distances on both shortlists,
-                // (distance, index) order, then the list-based hull kernel
-                Timed t(h, "slow_path", 0.0);
-                RescoreArgs ra{};
-                ra.X = h->X.p; ra.Dp = h->Dp; ra.bq = h->bq_cur; ra.pos_begin = lo; ra.pos_end = hi;
-                ra.B = h->B; ra.m = h->m; ra.Kcap = h->Kcap;
-                ra.cand = h->cand.p; ra.cand_cnt = h->cand_cnt.p; ra.cand_cap = kCandCap;
-                ra.cand2 = h->candu[cur].p; ra.cand2_cnt = h->candu_cnt[cur].p; ra.cand2_cap = kCandCapU;
-                ra.active = h->slow.p; ra.n_active = h->n_slow.p;
-                ra.out = h->L1();
-                launch_rescore(ra, s);
-                QpArgs q{};
-                q.X = h->X.p; q.D = h->D; q.Dp = h->Dp; q.bq = h->bq_cur; q.pos_begin = lo; q.pos_end = hi;
-                q.B = h->B; q.m = h->m; q.Kcap = h->Kcap; q.lists = h->L1(); q.dist = h->dist.p;
-                q.prev = Lists{nullptr, nullptr, nullptr};
-                q.metric = h->metric;
-                q.active = h->slow.p; q.n_active = h->n_slow.p;
-                launch_hull_qp(q, s);
-            }
-        } else {
-        if (h->pf_fit && h->cand.p) {
-            // batch members that can displace an entry of the base list: fp16 shortlist against
-            // the exact m-th distance, exact rescoring seeded with the base list
-            // (fit rounds only produce the "earlier" / "later" eligibility codes, which have the affine
-            // form the shortlist kernel evaluates; chb_topm_per_bin's "not equal" code stays on launch_topm)
-            launch_pack_centered(h->X.p, h->D, h->Dp, h->memb2_id.p, h->memb2_code.p, h->bin_ptr2.p, h->B, 2 * h->K,
-                                 h->centers.p, h->mu_g.p, h->shadow_scale, h->Dz, h->pk2.view(), s);
-            ShortlistArgs pa{};
-            pa.Gs = h->Gs.p; pa.gq = reinterpret_cast<const float2 *>(h->gq.p);
-            pa.qn = reinterpret_cast<const float2 *>(h->qn.p);   // (the fit's table)
-            pa.P = h->pk2.view(); pa.Dz = h->Dz; pa.S = h->shadow_scale;
-            pa.bq = h->bq_cur; pa.pos_begin = lo; pa.pos_end = hi;
-            pa.bin_ptr = h->bin_ptr2.p; pa.memb_id = h->memb2_id.p; pa.update = true;
-            pa.seed = h->L0();
-            pa.B = h->B; pa.m = h->m; pa.Kcap = h->Kcap;
-            pa.cand = h->cand.p; pa.cand_cnt = h->cand_cnt.p; pa.cand_cap = kCandCap; pa.overflow = h->overflow.p;
-            {
-                Timed t(h, "prefilter_update", (double)(hi - lo) * h->hint_batch_entries);
-                pa.flaglist = h->flaglist.p; pa.nflag = h->nflag.p;   // (counter reset by the CSR scan / the batch CSR kernel)
-            launch_shortlist(pa, h->flags64.p, sl_bpw(h), s);
-                // the (position, bin) pairs with a non-empty shortlist, for rescore_kernel
-                launch_compact_active(h->cand_cnt.p, lo, hi, h->B, h->Kcap, h->act_blk.p, h->active.p,
-                                      h->n_active.p, s);
-            }
-            RescoreArgs ra{};
-            ra.X = h->X.p; ra.Dp = h->Dp; ra.bq = h->bq_cur; ra.pos_begin = lo; ra.pos_end = hi;
-            ra.B = h->B; ra.m = h->m; ra.Kcap = h->Kcap;
-            ra.cand = h->cand.p; ra.cand_cnt = h->cand_cnt.p; ra.cand_cap = kCandCap;
-            ra.active = h->active.p; ra.n_active = h->n_active.p;
-            ra.in = h->L0(); ra.out = h->Lcur();
-            // pairs without any candidate keep the base list
-            {
-                const size_t nl = (size_t)h->Kcap * h->B;
-                const Lists dst = h->Lcur();
-                HIPCHK(hipMemcpyAsync(dst.d, h->l0d.p, sizeof(double) * nl * h->m, hipMemcpyDeviceToDevice, s));
-                HIPCHK(hipMemcpyAsync(dst.idx, h->l0i.p, sizeof(int) * nl * h->m, hipMemcpyDeviceToDevice, s));
-                HIPCHK(hipMemcpyAsync(dst.cnt, h->l0c.p, sizeof(int) * nl, hipMemcpyDeviceToDevice, s));
-            }
-            {
-                Timed t(h, "rescore_update", (double)(hi - lo) * h->B);
-                launch_rescore(ra, s);
-            }
-            {
-                Timed t(h, "topm_fallback", 0.0);
-                launch_topm_flagged(a, h->flags64.p, h->flaglist.p, h->nflag.p, s);
-            }
-        } else {
-            Timed t(h, "topm_update", (double)(hi - lo) * h->hint_batch_entries);
-            if (h->m > kMaxM) launch_topm_generic(a, s); else launch_topm(a, s);
-        }
-        QpArgs q{};
-        q.X = h->X.p; q.D = h->D; q.Dp = h->Dp; q.bq = h->bq_cur; q.pos_begin = lo; q.pos_end = hi;
-        q.B = h->B; q.m = h->m; q.Kcap = h->Kcap; q.lists = h->Lcur(); q.dist = h->dist.p;
-        // a (position, bin) whose vertex list is the one of the previous round keeps its distance
-        q.prev = h->round_in_batch > 0 ? h->Lprev() : Lists{nullptr, nullptr, nullptr};
-        q.metric = h->metric;
-        {
+        if (fusedp) round_fused(h, lo, hi, a);
+        else {
+            if (h->pf_fit && h->cand.p) { const int r_ = round_lists_shortlist(h, lo, hi, a); if (r_) return r_; }
+            else round_lists_plain(h, lo, hi, a);
+            QpArgs q = h->qp_args(lo, hi);
+            q.lists = h->Lcur();
+            // a (position, bin) whose vertex list is the one of the previous round keeps its distance
+            q.prev = h->round_in_batch > 0 ? h->Lprev() : Lists{nullptr, nullptr, nullptr};
             Timed t(h, "hull_qp", (double)(hi - lo) * h->B);
             if (h->m > kMaxM) launch_hull_generic(q, s); else launch_hull_qp(q, s);
         }
-        }   // list-based paths
         {
             Timed t(h, "argmin", (double)(hi - lo));
-            launch_argmin(h->dist.p, h->lab_old.p, h->lab_prev.p, lo, hi, h->B, h->lab_new.p,
-                          h->mind.p, h->want_margin ? h->mind2.p : nullptr, h->fc_cur, h->argmin_in_place, s);
+            launch_argmin(h->dist.p, h->lab_old.p, h->lab_prev.p, lo, hi, h->B, h->lab_new.p, h->mind.p,
+                          h->want_margin ? h->mind2.p : nullptr, h->fc_cur + kSlotFirstChange, h->argmin_in_place, s);
         }
         h->stats[2] += (int64_t)(hi - lo) * h->B;
     }
@@ -1741,36 +1739,36 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
                 const int tag = next_tag(2);
                 const bool first = active == 0;
 #ifdef CHB_DEV_KNOBS
-                if (first && h->dk.skip_stats_on) for (int k = 0; k < 3; ++k) launch_fill_i32(h->fc_cur + 3 + k, h->dk.skip_stats[k], 1, s);
+                if (first && h->dk.skip_stats_on) for (int k = 0; k < 3; ++k) launch_fill_i32(h->fc_cur + kSlotSkipped + k, h->dk.skip_stats[k], 1, s);
 #endif
                 launch_xchg_pack(h->xg.p, h->rank, g.C, h->lab_new.p, tag, h->fc_cur, first, first && h->pp_batch, true, g.K, s);
                 { const int r_ = exchange_all_gather(h, h->xg.p, (size_t)(g.C + kXchgHdr), sizeof(int), ncclInt32); if (r_) return r_; }
                 launch_xchg_unpack(h->xg.p, world, g.C, g.K, tag, h->lab_new.p, h->lab_prev.p, active, h->fc_cur,
                                    first && !dev_local_verdict, h->xerr.p, s);
             }
-            HIPCHK(hipMemcpyAsync(h->fc_host + kSlotInts * slot, h->fc_cur, 9 * sizeof(int), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(h->fc_host + kSlotInts * slot, h->fc_cur, kSlotHome * sizeof(int), hipMemcpyDeviceToHost, s));
             HIPCHK(hipEventRecord(h->fc_event[slot], s));
             return CHB_OK;
         };
         auto wait_round = [&](const Geom &g, int active, int slot, int *f) -> int {
             HIPCHK(hipEventSynchronize(h->fc_event[slot]));
-            *f = h->fc_host[kSlotInts * slot];
+            const int *v = h->fc_host + kSlotInts * slot;   // (the verdict as it came home: SlotWord)
+            *f = v[kSlotFirstChange];
             // (bin sizes of that batch, for the segment decision of the batches still to be enqueued; and what the tile
             //  skipping of its shortlist launch achieved: a fit whose first batches skip next to nothing turns it off)
-            h->hint_max_tiles = h->fc_host[kSlotInts * slot + 1]; h->hint_total_tiles = h->fc_host[kSlotInts * slot + 2];
+            h->hint_max_tiles = v[kSlotMaxTiles]; h->hint_total_tiles = v[kSlotTotalTiles];
             // (the persistent pack's arena: rows handed out so far, as of that batch's start)
             {
                 int64_t mark_at = h->pp_mark;
 #ifdef CHB_DEV_KNOBS   // CHB_PACK_REBUILD_AT=<rows>: rebuild (compact) the pack from that fill mark on -- tests of the rebuild path
                 if (h->dk.pack_rebuild_at >= 0) mark_at = h->dk.pack_rebuild_at;
 #endif
-                if (h->pp_valid && h->fc_host[kSlotInts * slot + 6] > mark_at) h->pp_rebuild = true;
+                if (h->pp_valid && v[kSlotMark] > mark_at) h->pp_rebuild = true;
             }
             // (the slot's statistics are written by the batch's one base shortlist launch: counted with the batch's first
             //  round only -- later rounds of the same batch bring the same three numbers home again)
-            if (active == 0 && h->fc_host[kSlotInts * slot + 4] > 0) {
-                h->skip_skipped += h->fc_host[kSlotInts * slot + 3]; h->skip_seen += h->fc_host[kSlotInts * slot + 4];
-                h->skip_unloaded += h->fc_host[kSlotInts * slot + 5];
+            if (active == 0 && v[kSlotSeen] > 0) {
+                h->skip_skipped += v[kSlotSkipped]; h->skip_seen += v[kSlotSeen]; h->skip_unloaded += v[kSlotUnloaded];
                 if (h->skip_state == 0 && ++h->skip_batches >= 3)
                 {
                     // (it pays from a few per cent of the wave-tiles)
@@ -1783,15 +1781,15 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
                     // (checked per batch below: sweep 1's first batches stream bins of a few tiles, nothing to go by)
                 }
             }
-            if (active == 0 && h->skip_state == 1 && h->pool_state >= 0 && h->fc_host[kSlotInts * slot + 4] > 0) {
-                const long long un = h->fc_host[kSlotInts * slot + 5], sn = h->fc_host[kSlotInts * slot + 4];
+            if (active == 0 && h->skip_state == 1 && h->pool_state >= 0 && v[kSlotSeen] > 0) {
+                const long long un = v[kSlotUnloaded], sn = v[kSlotSeen];
                 if (un * 10 > 3 * (sn + un)) { h->pool_state = -1; h->pool_off_key = skip_key(h); }
             }
             // (threshold pools: candidates per pair of that batch's base shortlist launch, as sampled; a fit whose first
             //  batches admit far more than the exact threshold would -- overlapping bins -- goes back to the two sweeps)
             //  -- checked for EVERY batch: the pools of sweep 1's first batches hold whole bins and say nothing yet)
-            if (active == 0 && h->pool_state >= 0 && h->fc_host[kSlotInts * slot + 8] > 0) {
-                const long long pc = h->fc_host[kSlotInts * slot + 7], pp = h->fc_host[kSlotInts * slot + 8];
+            if (active == 0 && h->pool_state >= 0 && v[kSlotPoolPairs] > 0) {
+                const long long pc = v[kSlotPoolCand], pp = v[kSlotPoolPairs];
                 h->pool_cand += pc; h->pool_pairs += pp;
                 if (++h->pool_batches >= 3 && h->pool_state == 0) h->pool_state = 1;
                 // (the benchmark configurations admit m + 0.1 .. m + 0.4 per pair; from m + 3 on the loose thresholds cost the
@@ -1936,11 +1934,11 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
         h->stats[3] += n_move * (int64_t)h->B;
         HIPCHK(h->pin_b.ensure((size_t)N));
         HIPCHK(hipMemcpyAsync(h->pin_b.p, h->labels.p, sizeof(int) * N, hipMemcpyDeviceToHost, s));
-        if (h->fused && h->short_cnt.p)   // (fc_host[12]: a spare word of the first verdict slot)
-            HIPCHK(hipMemcpyAsync(h->fc_host + 12, h->short_cnt.p, sizeof(int), hipMemcpyDeviceToHost, s));
-        h->fc_host[13] = 0;
-        if (h->pp_ctl.p)   // (fc_host[13]: another spare word -- the persistent pack's error flag)
-            HIPCHK(hipMemcpyAsync(h->fc_host + 13, h->pp_ctl.p + 2, sizeof(int), hipMemcpyDeviceToHost, s));
+        if (h->fused && h->short_cnt.p)   // (spare words of the first verdict slot)
+            HIPCHK(hipMemcpyAsync(h->fc_host + kSlotShortCnt, h->short_cnt.p, sizeof(int), hipMemcpyDeviceToHost, s));
+        h->fc_host[kSlotPackErr] = 0;
+        if (h->pp_ctl.p)
+            HIPCHK(hipMemcpyAsync(h->fc_host + kSlotPackErr, h->pp_ctl.p + 2, sizeof(int), hipMemcpyDeviceToHost, s));
         std::vector<int> xend;
         if (xchg) {
             // every rank's "a rank was out of step" record: all ranks then leave the sweep with the same status
@@ -1959,11 +1957,11 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
                                         " sent exchange " + std::to_string(e[2] >> 4) + " kind " + std::to_string(e[2] & 15) +
                                         "); labels not returned");
             }
-        if (h->fc_host[13] != 0)
+        if (h->fc_host[kSlotPackErr] != 0)
             return fail(CHB_ESTATE, "internal error: the persistent member pack ran out of rows; labels not returned");
-        if (h->fused && h->short_cnt.p && h->fc_host[12] != 0) {
-            h->short_seen = h->fc_host[12];
-            return fail(CHB_ESTATE, "internal error: " + std::to_string(h->fc_host[12]) + " (position, bin) shortlists of this sweep came "
+        if (h->fused && h->short_cnt.p && h->fc_host[kSlotShortCnt] != 0) {
+            h->short_seen = h->fc_host[kSlotShortCnt];
+            return fail(CHB_ESTATE, "internal error: " + std::to_string(h->fc_host[kSlotShortCnt]) + " (position, bin) shortlists of this sweep came "
                         "out short of min(num_neighbors, bin size) candidates or held a wild index; labels not returned");
         }
         int64_t diff = 0;  // algorithm.py:63
@@ -2030,10 +2028,8 @@ int chb_topm_per_bin(chb_ctx *h, const int64_t *labels, int64_t B, int m, const 
         // every other query of the chunk is an ordinary member: code "pos != i"
         launch_bucket_batch(h->lab_old.p, nullptr, h->bq_cur, K, h->B, h->cnt2.p, h->bin_ptr2.p,
                             h->cursor2.p, h->memb2_id.p, h->memb2_code.p, nullptr, nullptr, nullptr, nullptr, s);
-        TopmArgs a{};
-        a.X = h->X.p; a.Dp = h->Dp; a.bq = h->bq_cur; a.pos_begin = 0; a.pos_end = K;
+        TopmArgs a = h->topm_args(0, K);
         a.bin_ptr = h->bin_ptr2.p; a.memb_id = h->memb2_id.p; a.memb_code = h->memb2_code.p;
-        a.B = h->B; a.m = h->m; a.Kcap = h->Kcap;
         a.in = h->L0(); a.out = h->L1();
         {
             Timed t(h, "topm_update", (double)K);

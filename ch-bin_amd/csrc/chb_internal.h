@@ -384,15 +384,45 @@ void launch_guess(const double *list_d, const int *list_cnt, const int *lab_old,
 // members): the bin with the smallest one
 void launch_guess_near(const float *tau, const int *lab_old, int p0, int p1, int B, int Kcap, int *lab_prev,
                        hipStream_t s);
+// ---- a batch's verdict slot (chb_api.hip: chb_ctx::fc_cur on the device, fc_host in pinned memory): kSlotInts ints, of
+// which a round's verdict brings the first kSlotHome home in one copy
+enum SlotWord {
+    kSlotFirstChange = 0,   // first changed position of the round (K: none)
+    kSlotMaxTiles = 1,      // tiles of the batch's largest bin ...
+    kSlotTotalTiles = 2,    // ... and of all bins (the `stats` of launch_bucket_base / launch_pack_state_start start here)
+    kSlotSkipped = 3,       // wave-tiles skipped / seen / never loaded (ShortlistArgs::skip_stat: tile skipping), ...
+    kSlotSeen = 4,
+    kSlotUnloaded = 5,
+    kSlotMark = 6,          // fill mark of the persistent pack's arena as of the batch's start
+    kSlotPoolCand = 7,      // candidates admitted / (query, bin) pairs (ShortlistArgs::pool_stat: threshold pools), ...
+    kSlotPoolPairs = 8,     // ... all sampled by the batch's base shortlist launch
+    kSlotHome = 9,          // words copied home with every round's verdict
+    // host only, spare words of fc_host's first slot, read back at a sweep's end:
+    kSlotShortCnt = 12,     // short shortlists of the fit so far (FusedArgs::short_cnt)
+    kSlotPackErr = 13,      // the persistent pack's error flag (PackState::ctl[2])
+};
+constexpr int kSlotInts = 16;
 // ---- framed exchange of the sharded loop (aux_kernels.hip): a rank's slice of a round's all-gather = kXchgHdr header
-// words {tag, skipped, seen, unloaded, arena mark, 0, 0, 0} + the C labels of its positions
+// words (FrameWord) + the C labels of its positions
+enum FrameWord {
+    kFrameTag = 0,          // exchange number of the fit << 4 | kind
+    kFrameSkipped = 1,      // the sender's kSlotSkipped / kSlotSeen / kSlotUnloaded, ...
+    kFrameSeen = 2,
+    kFrameUnloaded = 3,
+    kFrameMark = 4,         // ... kSlotMark, ...
+    kFramePoolCand = 5,     // ... kSlotPoolCand / kSlotPoolPairs (each 0 where the exchange carries none)
+    kFramePoolPairs = 6,
+    kFrameSpare = 7,        // 0
+};
 constexpr int kXchgHdr = 8;
-// frames[rank] <- header + src[rank * C .. + C); slot = the batch's verdict slot (statistics in slot[3..6]); preset: slot[0] = K
+// frames[rank] <- header + src[rank * C .. + C); slot = the batch's verdict slot (the header's statistics and mark are its
+// words of the same names); preset: slot[kSlotFirstChange] = K
 void launch_xchg_pack(int *frames, int rank, int C, const int *src, int tag, int *slot, bool with_stats, bool with_mark,
                       bool preset, int K, hipStream_t s);
 // dst[pos] <- every frame's labels (pos < K); lab_prev != nullptr: round form -- positions >= active compared with lab_prev
-// (first change -> slot[0]) and written to it; tags checked against `tag` (xerr[0..3] = {1, mine, theirs, rank} on the first
-// mismatch); with_stats: slot[3..5] = sums over the ranks' headers, slot[6] = their largest mark
+// (first change -> slot[kSlotFirstChange]) and written to it; tags checked against `tag` (xerr[0..3] = {1, mine, theirs,
+// rank} on the first mismatch); with_stats: the slot's skip and pool statistics = sums over the ranks' headers,
+// slot[kSlotMark] = their largest mark
 void launch_xchg_unpack(const int *frames, int world, int C, int K, int tag, int *dst, int *lab_prev, int active, int *slot,
                         bool with_stats, int *xerr, hipStream_t s);
 // active[] = the pairs (pos - pos_begin) * B + bin whose cand_cnt is positive, *n_active their number
