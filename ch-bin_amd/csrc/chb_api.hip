@@ -226,6 +226,7 @@ struct chb_ctx {
     DevBuf<double> l0d, l1d, l2d;
     DevBuf<int> l0i, l1i, l0c, l1c, l2i, l2c;
     int round_in_batch = 0;   // rounds alternate between the list sets 1 and 2 (the other = previous)
+    int64_t round_active = 0; // `active` of the open batch's last chb_batch_round: may not decrease (include/chbin_hip.h)
     DevBuf<int> cnt, bin_ptr, cursor, memb_id;
     DevBuf<int> cnt2, bin_ptr2, cursor2, memb2_id, memb2_code;
     DevBuf<int> perm;
@@ -831,6 +832,7 @@ int batch_begin_dev(chb_ctx *h, int K, int q_lo, int q_hi, bool need_lists)
     h->lists_valid = !fusedp;
     h->K = K; h->q_lo = q_lo; h->q_hi = q_hi;
     h->round_in_batch = 0;
+    h->round_active = 0;
     hipStream_t s = h->stream;
     // segmented bins: the plan is made by the CSR scan on the device, but only if the host will also enqueue the two
     // segment launches -- which it does when the bin sizes it saw last (one or two batches old) say that a bin may
@@ -1454,13 +1456,30 @@ int chb_batch_begin(chb_ctx *h, const int64_t *perm_slice, int64_t K, int64_t q_
     return batch_begin_dev(h, (int)K, (int)q_lo, (int)q_hi, false);
 }
 
+// the labels a caller hands a round or a commit index the per-bin arrays on the device: -1 (unassigned) or a bin
+static int check_label_range(const int64_t *lab, int K, int B, const char *what)
+{
+    for (int i = 0; i < K; ++i)
+        if (lab[i] < -1 || lab[i] >= B)
+            return fail(CHB_EINVAL, std::string(what) + "[" + std::to_string(i) + "] = " + std::to_string(lab[i]) +
+                                    " is outside [-1, num_clusters)");
+    return CHB_OK;
+}
+
 int chb_batch_round(chb_ctx *h, const int64_t *lab_prev, int64_t active, int64_t *lab_new,
                     double *min_dist)
 {
     if (!h || !lab_prev || !lab_new) return fail(CHB_EINVAL, "null argument");
     if (!h->batch_open) return fail(CHB_ESTATE, "no open batch");
-    HIPCHK(hipSetDevice(h->dev));
     const int K = h->K;
+    // (host checks before anything is enqueued: a refused call leaves the batch open and as it was)
+    if (active < 0 || active > K) return fail(CHB_EINVAL, "active must be in [0, K]");
+    // the rounds keep the distance of a (position, bin) pair whose candidates are those of the previous round: that round
+    // must have evaluated the position
+    if (active < h->round_active) return fail(CHB_EINVAL, "active must not decrease within a batch");
+    { const int rc = check_label_range(lab_prev, K, h->B, "lab_prev"); if (rc) return rc; }
+    HIPCHK(hipSetDevice(h->dev));
+    h->round_active = active;
     std::vector<int> v = to_i32(lab_prev, (size_t)K);
     HIPCHK(hipMemcpyAsync(h->lab_prev.p, v.data(), sizeof(int) * K, hipMemcpyHostToDevice, h->stream));
     h->argmin_in_place = false;
@@ -1501,6 +1520,7 @@ int chb_batch_commit(chb_ctx *h, const int64_t *final_labels)
 {
     if (!h || !final_labels) return fail(CHB_EINVAL, "null argument");
     if (!h->batch_open) return fail(CHB_ESTATE, "no open batch");
+    { const int rc = check_label_range(final_labels, h->K, h->B, "final_labels"); if (rc) return rc; }
     HIPCHK(hipSetDevice(h->dev));
     std::vector<int> v = to_i32(final_labels, (size_t)h->K);
     HIPCHK(hipMemcpyAsync(h->lab_prev.p, v.data(), sizeof(int) * h->K, hipMemcpyHostToDevice, h->stream));

@@ -12,7 +12,7 @@
  *   - every function returns 0 on success, a negative CHB_E* code on failure; chb_last_error()
  *     returns a thread-local human-readable message.  No exceptions cross the ABI.
  *   - pointers are caller-owned HOST pointers unless the name says `_device`; C-contiguous;
- *     nothing is retained after return except by chb_set_samples_device (borrowed, see below).
+ *     nothing is retained after return (chb_set_samples_device copies its matrix as well, see below).
  *   - labels / indices are int64 at the ABI (numpy's default, what pandas hands the reference:
  *     cli/clustering.py:52); -1 = unassigned.  Features are float64 (cli/clustering.py:53).
  *   - calls are blocking; a context is not thread-safe (the reference caller is single-threaded).
@@ -79,7 +79,10 @@ int chb_set_metric(chb_ctx *h, int metric);
 
 /* Feature matrix `samples` of fit_cluster (algorithm.py:13): copied to HBM once and kept resident. */
 int chb_set_samples(chb_ctx *h, const double *X, int64_t N, int64_t D);
-/* same, from a device buffer (e.g. a torch tensor's data_ptr); copied device-to-device */
+/* same, from a device buffer (e.g. a torch tensor's data_ptr): copied device-to-device into the context's own resident
+ * matrix, nothing is borrowed -- the caller may overwrite or free X_device once the call has returned.  The copy runs on
+ * the context's own stream, which knows nothing of the caller's: the caller's writes to X_device must be complete (its
+ * stream or device synchronised) before the call. */
 int chb_set_samples_device(chb_ctx *h, const double *X_device, int64_t N, int64_t D);
 
 /* distance_matrix.py:33-44 create_in_mem_distance_matrix / :12-30 create_distance_matrix:
@@ -140,15 +143,25 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
 int chb_fit_begin(chb_ctx *h, int64_t B, const int64_t *initial_bins, int m);
 /* open a batch: perm_slice[K] are the contigs visited, in order */
 int chb_batch_begin(chb_ctx *h, const int64_t *perm_slice, int64_t K, int64_t q_lo, int64_t q_hi);
-/* optional: starting labels for the rounds of this batch, positions [q_lo,q_hi) of guess[K] --
- * the contig's current label, or for a still unlabelled contig the bin of its nearest member
- * outside the batch.  Any start gives the same final labels; a good one saves rounds. */
+/* optional: starting labels for the rounds of this batch, positions [q_lo,q_hi) of guess[K] (other entries untouched).
+ * A contig that has a label keeps it.  A still unlabelled one gets a bin by one of two rules, whichever the fit's
+ * kernels have the data for: on the list-based paths (CHB_FUSED=0, more than 16 neighbours, rows too wide for the
+ * shortlist stage) the bin of its nearest member outside the batch, ties to the lower bin; on the fused path the bin
+ * whose num_neighbors-th nearest member outside the batch is nearest by the shortlist stage's single-precision bound.
+ * Guaranteed are only: a labelled contig keeps its label, and every value lies in [-1, num_clusters) -- -1 where no bin
+ * has a member outside the batch.  Any start gives the same final labels; a good one saves rounds. */
 int chb_batch_guess(chb_ctx *h, int64_t *guess);
 /* one speculative round: lab_prev[K] in; for positions [max(active,q_lo), q_hi) writes
- * lab_new[pos] and min_dist[pos] (arrays of length K, other entries untouched) */
+ * lab_new[pos] and min_dist[pos] (arrays of length K, other entries untouched; min_dist may be NULL).
+ *   - every lab_prev[i], i in [0,K), must lie in [-1, num_clusters): CHB_EINVAL otherwise;
+ *   - active must lie in [0, K] and must not be smaller than the `active` of the previous round of the same batch
+ *     (positions below it are final: a round keeps what the round before it found for a position whose candidates did
+ *     not change, so that round must have evaluated the position): CHB_EINVAL otherwise.
+ * Both are checked on the host before anything is enqueued; a refused call leaves the batch open and usable. */
 int chb_batch_round(chb_ctx *h, const int64_t *lab_prev, int64_t active, int64_t *lab_new,
                     double *min_dist);
-/* close the batch: labels[perm_slice[i]] = final[i] */
+/* close the batch: labels[perm_slice[i]] = final[i].  Every final_labels[i] must lie in [-1, num_clusters): CHB_EINVAL
+ * otherwise, checked on the host before anything is enqueued, and the batch stays open. */
 int chb_batch_commit(chb_ctx *h, const int64_t *final_labels);
 int chb_fit_labels(chb_ctx *h, int64_t *labels_out);
 

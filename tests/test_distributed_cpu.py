@@ -98,3 +98,36 @@ def test_bench_self_launch_prints_one_line():
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=dict(env, WORLD_SIZE="1", RANK="0"),
                        timeout=300)
     assert p.returncode != 0 and p.stdout == ""
+
+
+def test_round_script_with_the_oracle_backend():
+    """The round script of tests/test_gpu_stepwise.py driven with the oracle alone, on the `fused5` data at K = 40: the
+    script's own invariants hold (it asserts the sentinels outside the evaluated range itself), the oracle backend is
+    a fixed point of its own definition, and the rounds converge to what O.sweep gives for the same permutation slice:
+    the positions from round 4's `active` on, visited in order with the positions before it at the labels the script
+    froze them at."""
+    import stepwise_script as S
+    N, Dm, B, m = 600, 136, 5, 5
+    X, initial, is_seed = S.make_case(N, Dm, B, seed=11)
+    assert 0.15 < (initial[~is_seed] < 0).mean() < 0.45 and np.all(initial[is_seed] >= 0)
+    rng = np.random.default_rng(5)
+    sl = S.draw_batches(is_seed, rng, sizes=(40,))[0]
+    assert (initial[sl] < 0).any() and (initial[sl] >= 0).any()      # labelled and unlabelled entries mix
+    for name, (lo, hi) in S.slices(len(sl)).items():
+        be = OracleBackend(want_all=True)
+        be.set_samples(X)
+        be.fit_begin(B, initial, m)
+        res = S.run_batch([be], sl, lo, hi, B, np.random.default_rng(6), tag=name)
+        assert res["rounds"] >= 5 and res["active0"] == 20
+        got = be.fit_labels()
+        rest = np.setdiff1d(np.arange(N), sl)
+        assert np.array_equal(got[rest], initial[rest])
+        assert np.array_equal(got[sl], res["final"])
+        if name == "full":
+            a0 = res["active0"]
+            start = initial.copy()
+            start[sl[:a0]] = res["frozen"]
+            want, _ = O.sweep(X, B, start, sl[a0:], m)
+            assert np.array_equal(got, want)
+        elif name == "empty":
+            assert res["rounds"] == 5      # nothing to evaluate: round 4 reproduces its input at once
