@@ -63,21 +63,11 @@ using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-#ifndef CHB_SL_DEFER
-#define CHB_SL_DEFER 0   // 1: a tile's selection code runs one tile late, under the next tile's LDS reads (round 4 experiment:
-                         // no gain at 100k x 136 x 64, +21 % / +45 % on the tile-skipping builds, whose registers it spills)
-#endif
-#ifndef CHB_SL_DMAREP
-#define CHB_SL_DMAREP 1   // developer experiment: issue every tile's DMA this many times
-#endif
 constexpr int kBiasCols = 3;         // spare shadow columns that carry -bias / 2 of a base member
 constexpr int kBiasExp = 14;         // ... as (h1 + h2 + h3) 2^kBiasExp; the query rows hold 2^kBiasExp there
 constexpr float kGamma = 2.5e-5f;
 constexpr float kSlack = 1e-6f;
-#ifndef CHB_SL_WAVES
-#define CHB_SL_WAVES 4   // wavefronts per workgroup of the shortlist kernel (developer experiment: 8)
-#endif
-constexpr int kPfW = CHB_SL_WAVES;
+constexpr int kPfW = 4;    // wavefronts per workgroup of the shortlist kernels
 constexpr int kPfQ = 32 * kPfW;  // batch positions per workgroup (32 per wavefront)
 constexpr int kPfP = 32;   // members per tile
 constexpr int kWideMaxSlices = 4;   // wide rows: at most this many 144-column slices (shortlist_wide_kernel)
@@ -1206,6 +1196,11 @@ __global__ __launch_bounds__(256) void pool_open_kernel(PoolState ps, const int 
 // four workgroups per CU; lists for m > 8 are longer and get 1024 (three per CU).
 __host__ __device__ constexpr int shortlist_pool_entries(int ml) { return ml <= 8 ? 512 : 1024; }
 
+// The 160-column base builds for m <= 5 drop what they do not use -- the bias / norm columns' slots, the segment flush's
+// bases -- and read their fragments in two halves through the same registers: 4 instead of 3 workgroups per CU.  ONE rule
+// for the kernel's LDS layout (kFour) and for the size the host launches it with.
+__host__ __device__ constexpr bool sl_four(int KS, bool UPD, int ML, int SEG) { return KS == 10 && !UPD && ML <= 5 && SEG != 2; }
+
 __device__ __forceinline__ void wait_vmcnt(int n)   // n: wave-uniform
 {
     if (n <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1324,12 +1319,7 @@ __global__ __launch_bounds__(64 * kPfW, (ML <= 5 && (KS == 9 || (!UPD && SEG != 
     constexpr int ROWB = 32 * KS;            // bytes per shadow row
     constexpr int TILEB = kPfP * ROWB;       // one member tile
     constexpr int METAB = 512;               // floats [0,32) bias | [32,64) ||zh|| (base) or s | [64,96) b | [96,128) ||zh|| (update)
-    // (kFour: the 160-column base builds for m <= 5 drop what they do not use -- the bias / norm columns' slots, the
-    //  segment flush's bases -- and read their fragments in two halves through the same registers: 4 instead of 3
-    //  workgroups per CU)
-    constexpr bool kFour = KS == 10 && !UPD && ML <= 5 && SEG != 2;
-    constexpr bool kDefer = CHB_SL_DEFER != 0 && !UPD;   // base mode: a tile's selection code runs under the next tile's LDS reads
-    constexpr bool kHalf9 = kDefer && KS == 9 && ML <= 5;   // ... and the 144-column builds read their fragments in two halves too
+    constexpr bool kFour = sl_four(KS, UPD, ML, SEG);
     constexpr int BUFB = kFour ? TILEB : TILEB + METAB;
     constexpr int NBUF = 3;
     constexpr int kPoolW = shortlist_pool_entries(ML);
@@ -1460,7 +1450,7 @@ __global__ __launch_bounds__(64 * kPfW, (ML <= 5 && (KS == 9 || (!UPD && SEG != 
     }
     int n_w = 0;
 #pragma unroll
-    for (int j = 0; j < 3; ++j) n_w += (w + kPfW * j < KS) ? CHB_SL_DMAREP : 0;
+    for (int j = 0; j < 3; ++j) n_w += (w + kPfW * j < KS) ? 1 : 0;
     n_w += (UPD && w == 3) ? 1 : 0;   // (base mode moves no bias / norm columns: -bias / 2 rides in the rows)
     n_w += (UPD && w == 2) ? 1 : 0;
     const unsigned char *zall = reinterpret_cast<const unsigned char *>(a.P.Z);
@@ -1519,7 +1509,6 @@ __global__ __launch_bounds__(64 * kPfW, (ML <= 5 && (KS == 9 || (!UPD && SEG != 
         const size_t row_ = (size_t)irow0 + (size_t)it * kPfP;                                     \
         const unsigned char *src_ = POOL ? zall + (ioff + (long long)it * (kPfP * ROWB)) : zall + row_ * ROWB; \
         CHB_SL_BOUNDS_DMA()                                                                        \
-        _Pragma("unroll") for (int rep_ = 0; rep_ < CHB_SL_DMAREP; ++rep_)                         \
         _Pragma("unroll") for (int j = 0; j < 3; ++j)                                              \
             if (w + kPfW * j < KS)                                                                 \
                 __builtin_amdgcn_global_load_lds(src_ + src_off[j],                                \
@@ -1748,16 +1737,9 @@ __global__ __launch_bounds__(64 * kPfW, (ML <= 5 && (KS == 9 || (!UPD && SEG != 
             // every iteration (the loop header merges the pre-loop state) -- which drains the two member tiles kept in
             // flight once per tile (round 3's builds did, in the selection code of sweep 1).  Once per run costs nothing.
             __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
-            // The selection code of a tile ("epilogue").  kDefer (base mode): it runs one tile LATE -- between the issue of the
-            // next tile's fragment reads and their wait -- so that a wavefront's matrix-core chain runs under its own trip
-            // round the barrier, the DMA issue and the next reads instead of being waited for right behind its last
-            // instruction, and the selection's vector work hides the LDS latency (MI355X_MICROARCH.md, "Two waves that run
-            // the SAME program ...": a deferred epilogue; here for every wavefront, the accumulators are simply left alone
-            // until the next tile's products are about to overwrite them -- no second set of registers).
+            // The selection code of a tile ("epilogue"), run right behind the tile's matrix-core chain.  (Running it one tile late,
+            // under the next tile's LDS reads, was tried in round 4: no gain, and +21 % / +45 % on the tile-skipping builds.)
             f32x16 acc;
-            bool pend = false;
-            float dlt_p = 0.f;
-            int ct_p = 0;
             auto epilogue = [&](const float dlt, const int ctp) __attribute__((always_inline)) {
                 if (!UPD && sweep == 0) {
                     // acc = -t/2: UB is monotone in t, so the m LARGEST accumulators are kept (pushed down by the
@@ -1883,7 +1865,6 @@ __global__ __launch_bounds__(64 * kPfW, (ML <= 5 && (KS == 9 || (!UPD && SEG != 
                 }
                 if (POOL && psweep && (h_lo + ct < hw_lo || h_lo + ct > hw_hi)) do_tile = false;   // none of my lanes' home
                 if (!do_tile) {
-                    if (kDefer && pend) { epilogue(dlt_p, ct_p); pend = false; }
                     ++n_consumed;
                     if (++cbuf == NBUF) cbuf = 0;
                     continue;
@@ -1934,7 +1915,6 @@ __global__ __launch_bounds__(64 * kPfW, (ML <= 5 && (KS == 9 || (!UPD && SEG != 
                     const unsigned fa0 = tb + (unsigned)fbase0, fa1 = tb + (unsigned)fbase1;
                     f16x8 h0 = lds_read_frag<0>(fa0), h1 = lds_read_frag<0>(fa1), h2 = lds_read_frag<64>(fa0),
                           h3 = lds_read_frag<64>(fa1), h4 = lds_read_frag<128>(fa0);
-                    if (kDefer && pend) epilogue(dlt_p, ct_p);   // (the previous tile's, under this tile's LDS reads)
                     if (SKIP && !POOL)
                         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(h0), "+v"(h1), "+v"(h2), "+v"(h3), "+v"(h4) : : "memory");
                     else
@@ -1955,28 +1935,6 @@ __global__ __launch_bounds__(64 * kPfW, (ML <= 5 && (KS == 9 || (!UPD && SEG != 
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(h2, qreg[7], acc, 0, 0, 0);
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(h3, qreg[8], acc, 0, 0, 0);
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(h4, qreg[9], acc, 0, 0, 0);
-                } else if constexpr (kHalf9) {
-                    // nine fragments through five registers (as kFour): the deferred selection code of the previous tile runs
-                    // while the first five are on their way -- with all nine in flight it would not fit 128 registers
-                    const unsigned fa0 = tb + (unsigned)fbase0;
-                    f16x8 h0 = lds_read_frag<0>(fa0), h1 = lds_read_frag<32>(fa0), h2 = lds_read_frag<64>(fa0),
-                          h3 = lds_read_frag<96>(fa0), h4 = lds_read_frag<128>(fa0);
-                    if (pend) epilogue(dlt_p, ct_p);   // (the previous tile's, under this tile's LDS reads)
-                    if (SKIP && !POOL)
-                        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(h0), "+v"(h1), "+v"(h2), "+v"(h3), "+v"(h4) : : "memory");
-                    else
-                        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(h0), "+v"(h1), "+v"(h2), "+v"(h3), "+v"(h4), "+s"(tsn_t) : : "memory");
-                    _Pragma("unroll") for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(h0, qreg[0], acc, 0, 0, 0); h0 = lds_read_frag<160>(fa0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(h1, qreg[1], acc, 0, 0, 0); h1 = lds_read_frag<192>(fa0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(h2, qreg[2], acc, 0, 0, 0); h2 = lds_read_frag<224>(fa0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(h3, qreg[3], acc, 0, 0, 0); h3 = lds_read_frag<256>(fa0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(h4, qreg[4], acc, 0, 0, 0);
-                    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(h0), "+v"(h1), "+v"(h2), "+v"(h3) : : "memory");
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(h0, qreg[5], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(h1, qreg[6], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(h2, qreg[7], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(h3, qreg[8], acc, 0, 0, 0);
                 } else {
                 f16x8 af[KS == 9 ? 9 : 10];
                 {
@@ -1992,7 +1950,6 @@ __global__ __launch_bounds__(64 * kPfW, (ML <= 5 && (KS == 9 || (!UPD && SEG != 
                         af[9] = lds_read_frag<256>(fa1);
                     }
                 }
-                if (kDefer && pend) epilogue(dlt_p, ct_p);   // (the previous tile's, under this tile's LDS reads)
                 if (SKIP && !POOL)
                     asm volatile("s_waitcnt lgkmcnt(0)"
                                  : "+v"(af[0]), "+v"(af[1]), "+v"(af[2]), "+v"(af[3]), "+v"(af[4]), "+v"(af[5]),
@@ -2018,12 +1975,10 @@ __global__ __launch_bounds__(64 * kPfW, (ML <= 5 && (KS == 9 || (!UPD && SEG != 
 
                 // base mode: this tile's query-rounding term (a wave-uniform table read)
                 const float dlt = UPD ? 0.f : rgq * tsn_t;
-                if (kDefer) { dlt_p = dlt; ct_p = ct; pend = true; }
-                else epilogue(dlt, ct);
+                epilogue(dlt, ct);
                 ++n_consumed;
                 if (++cbuf == NBUF) cbuf = 0;
             }
-            if (kDefer && pend) { epilogue(dlt_p, ct_p); pend = false; }   // the run's last tile
             if (skp) wt_unloaded += ntile - nt_run;
         }
 
@@ -2418,19 +2373,52 @@ __global__ __launch_bounds__(64 * kPfW, 2) void shortlist_wide_kernel(ShortlistA
     }
 }
 
-// (four: the layout of the kFour builds -- no bias / norm column slots, the seat table in the segment bases' place)
-static size_t shortlist_lds_bytes(int ks, int ml, bool four = false)
+// (four: the layout of the sl_four builds -- no bias / norm column slots, the seat table in the segment bases' place)
+static size_t shortlist_lds_bytes(int ks, int ml, bool four)
 {
     if (four) return (size_t)3 * (kPfP * 32 * ks) + (size_t)kPfW * shortlist_pool_entries(ml) * 4 + 3 * kPfQ * 4 + 16 + 8 * kPfW;
     return (size_t)3 * (kPfP * 32 * ks + 512) + (size_t)kPfW * shortlist_pool_entries(ml) * 4 + 4 * kPfQ * 4 + 16 + 8 * kPfW;
 }
 
+// launch geometry of a shortlist kernel: workgroups, query tiles of 128 / of 64 positions, work items along the bins and
+// bins per item
+struct SlGrid { int grid, nqt, nqt64, nchunk, bpw; };
+
+static SlGrid sl_grid(const ShortlistArgs &a, int bpw)
+{
+    const int nq = a.pos_end - a.pos_begin;
+    SlGrid g;
+    g.nqt = (nq + kPfQ - 1) / kPfQ;
+    g.nqt64 = (nq + kQTile - 1) / kQTile;
+    g.bpw = std::min(bpw, a.B);
+    g.nchunk = (a.B + g.bpw - 1) / g.bpw;
+    g.grid = ((g.nqt * g.nchunk + 7) / 8) * 8;
+    return g;
+}
+
+using ShortlistKernel = void (*)(ShortlistArgs, int, int, int, int *, int, Gate);
+static void sl_launch_kernel(ShortlistKernel k, size_t lds, const ShortlistArgs &a, const SlGrid &g, int *flags64, hipStream_t s)
+{
+    hipLaunchKernelGGL(k, dim3(g.grid), dim3(64 * kPfW), lds, s, a, g.nqt, g.nchunk, g.bpw, flags64, g.nqt64, g_gate);
+}
+
+// the narrow builds (144 or 160 columns): the LDS size follows from the template arguments of the kernel launched, by the
+// rule (sl_four) the kernel itself lays its LDS out with
+template <int ML, bool UPD, int SEG = 0, bool SKIP = false, bool POOL = false, bool WORK = false>
+static void sl_launch(const ShortlistArgs &a, const SlGrid &g, int *flags64, hipStream_t s)
+{
+    if (a.Dz == 144)
+        sl_launch_kernel(shortlist_kernel<ML, UPD, 9, SEG, SKIP, POOL, WORK>, shortlist_lds_bytes(9, ML, sl_four(9, UPD, ML, SEG)),
+                         a, g, flags64, s);
+    else
+        sl_launch_kernel(shortlist_kernel<ML, UPD, 10, SEG, SKIP, POOL, WORK>, shortlist_lds_bytes(10, ML, sl_four(10, UPD, ML, SEG)),
+                         a, g, flags64, s);
+}
+
 template <int ML, bool UPD>
 static void launch_sl(const ShortlistArgs &a, int *flags64, int bpw_force, hipStream_t s)
 {
-    const int nq = a.pos_end - a.pos_begin;
-    const int nqt = (nq + kPfQ - 1) / kPfQ;
-    const int nqt64 = (nq + kQTile - 1) / kQTile;
+    const int nqt = (a.pos_end - a.pos_begin + kPfQ - 1) / kPfQ;
     // bins per workgroup: long tile streams per workgroup, but enough workgroups for the 256 CUs x 4
     const long long units = (long long)nqt * a.B;
     // (tile skipping: the workgroups' run lengths differ by what they could skip -- one bin each, for an even finish:
@@ -2447,99 +2435,44 @@ static void launch_sl(const ShortlistArgs &a, int *flags64, int bpw_force, hipSt
     //  order of a bin's runs have only ever been exercised that way; the forced count above does not reach them:
     //  experiment 29 of round 5 saw short shortlists from the skipping pool build with two and more bins per workgroup)
     if (skip_build) bpw = 1;
-    bpw = std::min(bpw, a.B);
-    const int nchunk = (a.B + bpw - 1) / bpw;
-    const int total = nqt * nchunk;
-    const int grid = ((total + 7) / 8) * 8;
-    if (pool_build) {
-        if constexpr (!UPD) {
-            if (skip_build) {
-                if (a.Dz == 144)
-                    hipLaunchKernelGGL((shortlist_kernel<ML, false, 9, 0, true, true>), dim3(grid), dim3(64 * kPfW),
-                                       shortlist_lds_bytes(9, ML), s, a, nqt, nchunk, bpw, flags64, nqt64, g_gate);
-                else
-                    hipLaunchKernelGGL((shortlist_kernel<ML, false, 10, 0, true, true>), dim3(grid), dim3(64 * kPfW),
-                                       shortlist_lds_bytes(10, ML, ML <= 5), s, a, nqt, nchunk, bpw, flags64, nqt64, g_gate);
-            } else if (a.Dz == 144)
-                hipLaunchKernelGGL((shortlist_kernel<ML, false, 9, 0, false, true>), dim3(grid), dim3(64 * kPfW),
-                                   shortlist_lds_bytes(9, ML), s, a, nqt, nchunk, bpw, flags64, nqt64, g_gate);
-            else
-                hipLaunchKernelGGL((shortlist_kernel<ML, false, 10, 0, false, true>), dim3(grid), dim3(64 * kPfW),
-                                   shortlist_lds_bytes(10, ML, ML <= 5), s, a, nqt, nchunk, bpw, flags64, nqt64, g_gate);
-        }
-    } else if (skip_build) {
-        if constexpr (!UPD) {
-            if (a.Dz == 144)
-                hipLaunchKernelGGL((shortlist_kernel<ML, false, 9, 0, true>), dim3(grid), dim3(64 * kPfW),
-                                   shortlist_lds_bytes(9, ML), s, a, nqt, nchunk, bpw, flags64, nqt64, g_gate);
-            else
-                hipLaunchKernelGGL((shortlist_kernel<ML, false, 10, 0, true>), dim3(grid), dim3(64 * kPfW),
-                                   shortlist_lds_bytes(10, ML, ML <= 5), s, a, nqt, nchunk, bpw, flags64, nqt64, g_gate);
-        }
-    } else if (a.Dz == 144)
-        hipLaunchKernelGGL((shortlist_kernel<ML, UPD, 9>), dim3(grid), dim3(64 * kPfW), shortlist_lds_bytes(9, ML), s, a,
-                           nqt, nchunk, bpw, flags64, nqt64, g_gate);
-    else
-        hipLaunchKernelGGL((shortlist_kernel<ML, UPD, 10>), dim3(grid), dim3(64 * kPfW), shortlist_lds_bytes(10, ML, !UPD && ML <= 5), s, a,
-                           nqt, nchunk, bpw, flags64, nqt64, g_gate);
+    const SlGrid g = sl_grid(a, bpw);
     if constexpr (!UPD) {
+        if (pool_build && skip_build) sl_launch<ML, false, 0, true, true>(a, g, flags64, s);
+        else if (pool_build) sl_launch<ML, false, 0, false, true>(a, g, flags64, s);
+        else if (skip_build) sl_launch<ML, false, 0, true>(a, g, flags64, s);
+        else sl_launch<ML, false>(a, g, flags64, s);
         // the segmented bins of this batch (usually none: the host only asks for these launches when the last batches'
         // bin sizes say a bin may qualify): phase 1 (m best accumulators per segment), phase 2 (shortlists)
         if (a.seg.gflag != nullptr && a.seg.launch) {
-            const int gseg = ((nqt * a.seg.cap + 7) / 8) * 8;
-            if (a.Dz == 144) {
-                hipLaunchKernelGGL((shortlist_kernel<ML, false, 9, 1>), dim3(gseg), dim3(64 * kPfW), shortlist_lds_bytes(9, ML), s,
-                                   a, nqt, 0, 1, flags64, nqt64, g_gate);
-                hipLaunchKernelGGL((shortlist_kernel<ML, false, 9, 2>), dim3(gseg), dim3(64 * kPfW), shortlist_lds_bytes(9, ML), s,
-                                   a, nqt, 0, 1, flags64, nqt64, g_gate);
-            } else {
-                hipLaunchKernelGGL((shortlist_kernel<ML, false, 10, 1>), dim3(gseg), dim3(64 * kPfW), shortlist_lds_bytes(10, ML, ML <= 5), s,
-                                   a, nqt, 0, 1, flags64, nqt64, g_gate);
-                hipLaunchKernelGGL((shortlist_kernel<ML, false, 10, 2>), dim3(gseg), dim3(64 * kPfW), shortlist_lds_bytes(10, ML), s,
-                                   a, nqt, 0, 1, flags64, nqt64, g_gate);
-            }
+            const SlGrid gs{((nqt * a.seg.cap + 7) / 8) * 8, g.nqt, g.nqt64, 0, 1};
+            sl_launch<ML, false, 1>(a, gs, flags64, s);
+            sl_launch<ML, false, 2>(a, gs, flags64, s);
         }
-    }
+    } else
+        sl_launch<ML, true>(a, g, flags64, s);
 }
 
 // the wide-row builds (Dz = 144 NS, NS = 2 .. 4): plain two-sweep base launch / one-sweep update launch
 template <int ML, bool UPD>
 static void launch_sl_wide(const ShortlistArgs &a, int *flags64, hipStream_t s)
 {
-    const int nq = a.pos_end - a.pos_begin;
-    const int nqt = (nq + kPfQ - 1) / kPfQ;
-    const int nqt64 = (nq + kQTile - 1) / kQTile;
-    const long long units = (long long)nqt * a.B;
-    int bpw = (int)std::max<long long>(1, units / (UPD ? 1024 : 2048));
-    bpw = std::min(bpw, a.B);
-    const int nchunk = (a.B + bpw - 1) / bpw;
-    const int total = nqt * nchunk;
-    const int grid = ((total + 7) / 8) * 8;
-    const size_t lds = shortlist_lds_bytes(9, ML);
+    const int nqt = (a.pos_end - a.pos_begin + kPfQ - 1) / kPfQ;
+    const SlGrid g = sl_grid(a, (int)std::max<long long>(1, (long long)nqt * a.B / (UPD ? 1024 : 2048)));
+    const size_t lds = shortlist_lds_bytes(9, ML, false);
     switch (a.Dz / 144) {
-    case 2:
-        hipLaunchKernelGGL((shortlist_wide_kernel<ML, UPD, 2>), dim3(grid), dim3(64 * kPfW), lds, s, a, nqt, nchunk, bpw, flags64, nqt64, g_gate);
-        break;
-    case 3:
-        hipLaunchKernelGGL((shortlist_wide_kernel<ML, UPD, 3>), dim3(grid), dim3(64 * kPfW), lds, s, a, nqt, nchunk, bpw, flags64, nqt64, g_gate);
-        break;
-    default:
-        hipLaunchKernelGGL((shortlist_wide_kernel<ML, UPD, 4>), dim3(grid), dim3(64 * kPfW), lds, s, a, nqt, nchunk, bpw, flags64, nqt64, g_gate);
-        break;
+    case 2: sl_launch_kernel(shortlist_wide_kernel<ML, UPD, 2>, lds, a, g, flags64, s); break;
+    case 3: sl_launch_kernel(shortlist_wide_kernel<ML, UPD, 3>, lds, a, g, flags64, s); break;
+    default: sl_launch_kernel(shortlist_wide_kernel<ML, UPD, 4>, lds, a, g, flags64, s); break;
     }
 }
 
+// the work-list form: one workgroup per listed item, every item one bin
 template <int ML>
 static void launch_sl_work(const ShortlistArgs &a, int *flags64, int grid, hipStream_t s)
 {
     const int nq = a.pos_end - a.pos_begin;
-    const int nqt = (nq + kPfQ - 1) / kPfQ, nqt64 = (nq + kQTile - 1) / kQTile;
-    if (a.Dz == 144)
-        hipLaunchKernelGGL((shortlist_kernel<ML, false, 9, 0, false, false, true>), dim3(grid), dim3(64 * kPfW),
-                           shortlist_lds_bytes(9, ML), s, a, nqt, a.B, 1, flags64, nqt64, g_gate);
-    else
-        hipLaunchKernelGGL((shortlist_kernel<ML, false, 10, 0, false, false, true>), dim3(grid), dim3(64 * kPfW),
-                           shortlist_lds_bytes(10, ML, ML <= 5), s, a, nqt, a.B, 1, flags64, nqt64, g_gate);
+    const SlGrid g{grid, (nq + kPfQ - 1) / kPfQ, (nq + kQTile - 1) / kQTile, a.B, 1};
+    sl_launch<ML, false, 0, false, false, true>(a, g, flags64, s);
 }
 
 }  // namespace
