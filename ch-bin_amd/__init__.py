@@ -7,4 +7,12 @@ HIP library or a GPU is missing.
 """
 from . import synth  # noqa: F401
 
-__all__ = ["synth"]
+__all__ = ["synth", "recruit"]
+
+
+def __getattr__(name):
+    # chbin_amd.recruit = clustering.recruit, resolved on first use (importing the package stays free of ctypes work)
+    if name == "recruit":
+        from .clustering import recruit
+        return recruit
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -40,6 +40,8 @@ SIGNATURES = {
     "chb_pairwise_distance": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _f64p]),
     "chb_topm_per_bin": (C.c_int, [C.c_void_p, _i64p, C.c_int64, C.c_int, _i64p, C.c_int64, _i64p,
                                    C.c_void_p, _i32p]),
+    "chb_recruit_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "chb_find_nearest_from_row": (C.c_int, [C.c_void_p, C.c_int64, _i64p, _f64p, C.c_int64, C.c_int,
                                             _i64p, C.POINTER(C.c_int32)]),
     "chb_hull_distance_batch": (C.c_int, [C.c_void_p, _i64p, C.c_int64, _i64p, C.c_int, _f64p,
@@ -186,6 +188,25 @@ class Context:
         check(self._lib.chb_topm_per_bin(self._h, labels, int(B), int(m), q, Q, idx,
                                          dist.ctypes.data, cnt))
         return idx, dist, cnt
+
+    def recruit_rows(self, labels, B, m, Y, want_dist=True):
+        """chb_recruit_rows: hull distance of the NEW rows Y (not samples) to every bin of the frozen `labels`.
+        Returns (bins [Q], dist [Q, B] or None, min_dist [Q], margin [Q])."""
+        labels = np.ascontiguousarray(labels, dtype=np.int64)
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim != 2:
+            raise ValueError("rows must be a 2-D array")
+        if labels.shape != (self.N,):
+            raise ValueError("labels must have one entry per resident sample")
+        Q, D = Y.shape
+        bins = np.empty(Q, dtype=np.int64)
+        dist = np.empty((Q, int(B)), dtype=np.float64) if want_dist else None
+        mind = np.empty(Q, dtype=np.float64)
+        margin = np.empty(Q, dtype=np.float64)
+        check(self._lib.chb_recruit_rows(self._h, labels.ctypes.data, int(B), int(m), Y.ctypes.data, Q, D,
+                                         bins.ctypes.data, None if dist is None else dist.ctypes.data,
+                                         mind.ctypes.data, margin.ctypes.data))
+        return bins, dist, mind, margin
 
     def find_nearest_from_row(self, c, labels, row, m):
         labels = np.ascontiguousarray(labels, dtype=np.int64)

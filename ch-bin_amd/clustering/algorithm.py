@@ -63,3 +63,33 @@ def fit_cluster(
     else:
         logger.info("Exit due to max iteration limit.")                  # algorithm.py:74-75
     return labels
+
+
+def recruit(
+    samples: np.ndarray,
+    labels: np.ndarray,
+    rows: np.ndarray,
+    num_clusters: int,
+    num_neighbors: int = 15,
+    metric: str = "convex",
+    qp_solver: str = "quadprog",
+    return_distances: bool = False,
+):
+    """Bins for `rows` that were NOT part of the fit (no counterpart in the reference, which drops the contigs under
+    ContigLengthFilterBp before the fit: cli/features.py:60-64): for every row the step of algorithm.py:49-58 against
+    the finished, frozen `labels` of `samples` -- per bin the `num_neighbors` nearest members, the distance to their
+    hull, the strict-'>' argmin over the bins (-1 where no bin has a member).  Neither `samples` nor `labels` change.
+
+    Returns `bins` [len(rows)] or, with return_distances, (bins, distances [len(rows), num_clusters])."""
+    if metric not in ("convex", "affine", "affine-qp"):
+        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
+    check_solver(qp_solver)                                              # solve_qp.py:132
+
+    samples = np.ascontiguousarray(samples, dtype=np.float64)
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    ctx = default_context()
+    ctx.set_samples_cached(samples)
+    with ctx.using_metric(metric):
+        bins, dist, _, _ = ctx.recruit_rows(labels, int(num_clusters), int(num_neighbors), rows,
+                                            want_dist=return_distances)
+    return (bins, dist) if return_distances else bins

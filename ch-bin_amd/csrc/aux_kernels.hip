@@ -6,8 +6,6 @@ namespace chb {
 thread_local Gate g_gate;
 namespace {
 
-constexpr double kInf = __builtin_huge_val();
-
 __global__ void fill_i32_kernel(int *p, int v, int n, Gate gate)
 {
     CHB_GATE(gate);

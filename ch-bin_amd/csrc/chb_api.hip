@@ -209,6 +209,7 @@ struct chb_ctx {
     int B = 0, m = 0;
     int metric = 0;   // CHB_METRIC_CONVEX / CHB_METRIC_AFFINE
     bool fit_open = false;
+    bool stepwise = false;   // the open fit was begun by chb_fit_begin (the caller drives its batches): chb_recruit_rows refuses
     DevBuf<int> labels, inb;
     // batch state
     int K = 0, Kcap = 0, q_lo = 0, q_hi = 0;
@@ -317,6 +318,16 @@ struct chb_ctx {
     long long last_batch = 0;
     long long skip_skipped = 0, skip_seen = 0, skip_unloaded = 0;
     DevBuf<float> tau;
+    // chb_recruit_rows: a chunk of the new rows (padded like X), its distances and row reductions, the call's CSR over the
+    // labels -- the call's own buffers, nothing of a fit.  Two of each per-chunk buffer, on the device and pinned on the
+    // host: while the kernels of chunk k run on the context's stream, rc_copy brings chunk k + 1 up and chunk k - 1 down
+    // (rc_up / rc_done / rc_down: upload, kernels, download of the chunk in that half are through)
+    DevBuf<double> rc_Y[2], rc_dist[2], rc_min[2], rc_margin[2];
+    DevBuf<int> rc_bin[2], rc_ptr, rc_memb;
+    PinBuf<double> rc_hY[2], rc_hdist[2], rc_hmin[2], rc_hmargin[2];
+    PinBuf<int> rc_hbin[2], rc_hptr, rc_hmemb;
+    hipStream_t rc_copy = nullptr;
+    hipEvent_t rc_up[2] = {nullptr, nullptr}, rc_done[2] = {nullptr, nullptr}, rc_down[2] = {nullptr, nullptr};
     // scratch for the indexed / explicit-point entry points
     DevBuf<int> xq, xhull, xcnt;
     DevBuf<double> xdist, xalpha, xpts;
@@ -1246,6 +1257,14 @@ int chb_destroy(chb_ctx *h)
     h->seg_nseg.release(); h->seg_gflag.release(); h->seg_items.release(); h->seg_lists.release();
     h->shell_inv.release(); h->ckey.release(); h->qord.release(); h->home.release();
     h->qord_all.release(); h->home_all.release(); h->geo_all.release();
+    if (h->rc_copy) { (void)hipStreamSynchronize(h->rc_copy); (void)hipStreamDestroy(h->rc_copy); }
+    for (int i = 0; i < 2; ++i) {
+        h->rc_Y[i].release(); h->rc_dist[i].release(); h->rc_min[i].release(); h->rc_margin[i].release(); h->rc_bin[i].release();
+        h->rc_hY[i].release(); h->rc_hdist[i].release(); h->rc_hmin[i].release(); h->rc_hmargin[i].release(); h->rc_hbin[i].release();
+        hipEvent_t ev[] = {h->rc_up[i], h->rc_done[i], h->rc_down[i]};
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    }
+    h->rc_ptr.release(); h->rc_memb.release(); h->rc_hptr.release(); h->rc_hmemb.release();
     (void)hipStreamDestroy(h->stream);
     if (h->fc_host) (void)hipHostFree(h->fc_host);
     for (int i = 0; i < 2; ++i) if (h->fc_event[i]) (void)hipEventDestroy(h->fc_event[i]);
@@ -1275,7 +1294,7 @@ static int samples_upload(chb_ctx *h, const double *X, int64_t N, int64_t D, boo
                                 h->stream));
     }
     h->N = N; h->D = (int)D; h->Dp = Dp;
-    h->fit_open = false; h->batch_open = false;
+    h->fit_open = false; h->batch_open = false; h->stepwise = false;
     return CHB_OK;
 }
 
@@ -1422,6 +1441,7 @@ int chb_fit_begin(chb_ctx *h, int64_t B, const int64_t *initial_bins, int m)
     if (!h || !initial_bins) return fail(CHB_EINVAL, "null argument");
     HIPCHK(hipSetDevice(h->dev));
     const int rc = fit_begin_impl(h, B, initial_bins, m);
+    if (rc == CHB_OK) h->stepwise = true;
     // (the stepwise batches have no loop that reads the skip statistics and could turn the tile-skipping builds off
     //  where they do not pay: they run the ordinary builds)
     if (rc == CHB_OK) h->skip_state = -1;
@@ -1575,6 +1595,7 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
     }
     int rc = fit_begin_impl(h, B, initial_bins, m, /*sync=*/false);
     if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }   // (an upload from pin_a may be in flight: the next call rewrites it)
+    h->stepwise = false;
     struct FitCloser {   // an error return must not leave an open fit / batch behind
         chb_ctx *h; bool ok = false;
         ~FitCloser() { if (!ok) { (void)hipStreamSynchronize(h->stream); h->fit_open = false; h->batch_open = false; } }
@@ -2026,6 +2047,7 @@ int chb_topm_per_bin(chb_ctx *h, const int64_t *labels, int64_t B, int m, const 
     for (int64_t i = 0; i < h->N; ++i) lab[(size_t)i] = (labels[i] >= 0 && labels[i] < B) ? labels[i] : -1;
     int rc = fit_begin_impl(h, B, lab.data(), m);
     if (rc) return rc;
+    h->stepwise = false;
     for (int64_t i = 0; i < Q; ++i)
         if (query_idx[i] < 0 || query_idx[i] >= h->N) return fail(CHB_EINVAL, "query index out of range");
     const int Kmax = (int)std::min<int64_t>(std::max<int64_t>(Q, 1), 4096);
@@ -2169,6 +2191,155 @@ int chb_hull_distance_points(chb_ctx *h, const double *x, const double *pts, int
     std::vector<int64_t> idx((size_t)m);
     for (int a = 0; a < m; ++a) idx[(size_t)a] = a + 1;
     return hull_indexed(h, h->xpts.p, (int)D, Dp, m + 1, &q, 1, idx.data(), m, dist, alpha);
+}
+
+namespace {
+
+constexpr int kRecruitPiece = 2048;   // rows per host-to-device copy of a chunk
+
+// The chunks of one chb_recruit_rows call, pipelined: the rows of chunk k are packed (zero-padded to Dp) into pinned
+// memory and copied up on rc_copy piece by piece, so the copy of a piece runs under the packing of the next; the kernels
+// run on the context's stream; the results come down on rc_copy into pinned memory and are unpacked by the host.  The
+// order of a step -- kernels of k, upload of k + 1, download of k, unpack of k - 1 -- keeps rc_copy from queueing an
+// upload behind a download that waits for kernels.  Everything asynchronous reads and writes context-owned memory.
+hipError_t recruit_chunks(chb_ctx *h, RecruitArgs a, const double *Y, int64_t Q, int64_t chunk, int64_t *bin_out,
+                          double *dist_out, double *min_dist_out, double *margin_out)
+{
+#define RCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
+    hipStream_t s = h->stream, c = h->rc_copy;
+    const int64_t D = a.D, Dp = a.Dp, B = a.B;
+    const int64_t n = (Q + chunk - 1) / chunk;
+    auto rows = [&](int64_t k) { return (int)std::min<int64_t>(chunk, Q - k * chunk); };
+    auto upload = [&](int64_t k) -> hipError_t {
+        const int b = (int)(k & 1), nq = rows(k);
+        RCHK(hipEventSynchronize(h->rc_up[b]));          // the pinned half: its last upload (chunk k - 2) has left it
+        RCHK(hipStreamWaitEvent(c, h->rc_done[b], 0));   // the device half: the kernels of chunk k - 2 have read it
+        for (int r0 = 0; r0 < nq; r0 += kRecruitPiece) {
+            const int nr = std::min(kRecruitPiece, nq - r0);
+            double *dst = h->rc_hY[b].p + (size_t)r0 * Dp;
+            const double *src = Y + (k * chunk + r0) * D;
+            for (int r = 0; r < nr; ++r, dst += Dp, src += D) {
+                memcpy(dst, src, sizeof(double) * D);
+                for (int64_t j = D; j < Dp; ++j) dst[j] = 0.0;
+            }
+            RCHK(hipMemcpyAsync(h->rc_Y[b].p + (size_t)r0 * Dp, h->rc_hY[b].p + (size_t)r0 * Dp, sizeof(double) * (size_t)nr * Dp,
+                                hipMemcpyHostToDevice, c));
+        }
+        return hipEventRecord(h->rc_up[b], c);
+    };
+    auto download = [&](int64_t k) -> hipError_t {
+        const int b = (int)(k & 1), nq = rows(k);
+        RCHK(hipStreamWaitEvent(c, h->rc_done[b], 0));
+        if (dist_out)
+            RCHK(hipMemcpyAsync(h->rc_hdist[b].p, h->rc_dist[b].p, sizeof(double) * (size_t)nq * (size_t)B, hipMemcpyDeviceToHost, c));
+        if (min_dist_out) RCHK(hipMemcpyAsync(h->rc_hmin[b].p, h->rc_min[b].p, sizeof(double) * nq, hipMemcpyDeviceToHost, c));
+        if (margin_out) RCHK(hipMemcpyAsync(h->rc_hmargin[b].p, h->rc_margin[b].p, sizeof(double) * nq, hipMemcpyDeviceToHost, c));
+        if (bin_out) RCHK(hipMemcpyAsync(h->rc_hbin[b].p, h->rc_bin[b].p, sizeof(int) * nq, hipMemcpyDeviceToHost, c));
+        return hipEventRecord(h->rc_down[b], c);
+    };
+    auto unpack = [&](int64_t k) -> hipError_t {
+        const int b = (int)(k & 1), nq = rows(k);
+        const int64_t t0 = k * chunk;
+        RCHK(hipEventSynchronize(h->rc_down[b]));
+        if (dist_out) memcpy(dist_out + t0 * B, h->rc_hdist[b].p, sizeof(double) * (size_t)nq * (size_t)B);
+        if (min_dist_out) memcpy(min_dist_out + t0, h->rc_hmin[b].p, sizeof(double) * nq);
+        if (margin_out) memcpy(margin_out + t0, h->rc_hmargin[b].p, sizeof(double) * nq);
+        if (bin_out)
+            for (int i = 0; i < nq; ++i) bin_out[t0 + i] = h->rc_hbin[b].p[i];
+        return hipSuccess;
+    };
+    RCHK(upload(0));
+    for (int64_t k = 0; k < n; ++k) {
+        const int b = (int)(k & 1), nq = rows(k);
+        RCHK(hipStreamWaitEvent(s, h->rc_up[b], 0));
+        RCHK(hipStreamWaitEvent(s, h->rc_down[b], 0));   // (chunk k - 2 has been copied out of this half's results)
+        a.Y = h->rc_Y[b].p; a.dist = h->rc_dist[b].p; a.nq = nq;
+        {
+            Timed t(h, "recruit", (double)nq * (double)B);
+            launch_recruit(a, s);
+            launch_recruit_reduce(h->rc_dist[b].p, nq, (int)B, h->rc_bin[b].p, h->rc_min[b].p, h->rc_margin[b].p, s);
+        }
+        RCHK(hipGetLastError());
+        RCHK(hipEventRecord(h->rc_done[b], s));
+        if (k + 1 < n) RCHK(upload(k + 1));
+        RCHK(download(k));
+        if (k > 0) RCHK(unpack(k - 1));
+    }
+    return unpack(n - 1);
+#undef RCHK
+}
+
+}  // namespace
+
+int chb_recruit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
+                     int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
+{
+    if (!h) return fail(CHB_EINVAL, "null context");
+    if (Q < 0 || B < 1 || m < 1) return fail(CHB_EINVAL, "Q < 0, B < 1 or m < 1");
+    if (Q > 0 && (!labels || !Y)) return fail(CHB_EINVAL, "null argument");
+    if (!bin_out && !dist_out) return fail(CHB_EINVAL, "bin_out and dist_out are both null");
+    if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
+    if (D != h->D) return fail(CHB_EINVAL, "the rows must have the resident samples' number of columns");
+    if (m > kMaxM) return fail(CHB_EUNSUPPORTED, "chb_recruit_rows supports at most 16 neighbours");
+    if (B > kRecruitMaxBins) return fail(CHB_EUNSUPPORTED, "chb_recruit_rows supports at most 8192 bins");
+    if (h->batch_open || (h->fit_open && h->stepwise))
+        return fail(CHB_ESTATE, "a stepwise fit is open on this context (chb_fit_begin): chb_set_samples ends it");
+    if (Q == 0) return CHB_OK;
+    HIPCHK(hipSetDevice(h->dev));
+    hipStream_t s = h->stream;
+    const int64_t N = h->N;
+    const int Dp = h->Dp;
+    if (!h->rc_copy) {
+        HIPCHK(hipStreamCreateWithFlags(&h->rc_copy, hipStreamNonBlocking));
+        for (int i = 0; i < 2; ++i) {
+            HIPCHK(hipEventCreateWithFlags(&h->rc_up[i], hipEventDisableTiming));
+            HIPCHK(hipEventCreateWithFlags(&h->rc_done[i], hipEventDisableTiming));
+            HIPCHK(hipEventCreateWithFlags(&h->rc_down[i], hipEventDisableTiming));
+        }
+    }
+    // CSR over the labels (host counting sort into pinned memory; members of a bin in index order -- the selection does
+    // not depend on it)
+    HIPCHK(h->rc_hptr.ensure((size_t)B + 1));
+    int *ptr = h->rc_hptr.p;
+    std::fill(ptr, ptr + B + 1, 0);
+    for (int64_t i = 0; i < N; ++i)
+        if (labels[i] >= 0 && labels[i] < B) ++ptr[labels[i] + 1];
+    for (int64_t c = 0; c < B; ++c) ptr[c + 1] += ptr[c];
+    const size_t n_memb = (size_t)std::max(ptr[B], 1);
+    HIPCHK(h->rc_hmemb.ensure(n_memb));
+    {
+        std::vector<int> cur(ptr, ptr + B);
+        for (int64_t i = 0; i < N; ++i)
+            if (labels[i] >= 0 && labels[i] < B) h->rc_hmemb.p[cur[(size_t)labels[i]]++] = (int)i;
+    }
+    const int64_t chunk = std::min<int64_t>(Q, kRecruitChunk);
+    const int halves = Q > chunk ? 2 : 1;
+    HIPCHK(h->rc_ptr.ensure((size_t)B + 1));
+    HIPCHK(h->rc_memb.ensure(n_memb));
+    for (int i = 0; i < halves; ++i) {
+        HIPCHK(h->rc_Y[i].ensure((size_t)chunk * Dp));
+        HIPCHK(h->rc_hY[i].ensure((size_t)chunk * Dp));
+        HIPCHK(h->rc_dist[i].ensure((size_t)chunk * (size_t)B));
+        if (dist_out) HIPCHK(h->rc_hdist[i].ensure((size_t)chunk * (size_t)B));
+        HIPCHK(h->rc_bin[i].ensure((size_t)chunk));
+        HIPCHK(h->rc_hbin[i].ensure((size_t)chunk));
+        HIPCHK(h->rc_min[i].ensure((size_t)chunk));
+        HIPCHK(h->rc_hmin[i].ensure((size_t)chunk));
+        HIPCHK(h->rc_margin[i].ensure((size_t)chunk));
+        HIPCHK(h->rc_hmargin[i].ensure((size_t)chunk));
+    }
+    HIPCHK(hipMemcpyAsync(h->rc_ptr.p, ptr, sizeof(int) * ((size_t)B + 1), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->rc_memb.p, h->rc_hmemb.p, sizeof(int) * n_memb, hipMemcpyHostToDevice, s));
+    RecruitArgs a{};
+    a.X = h->X.p; a.D = h->D; a.Dp = Dp; a.bin_ptr = h->rc_ptr.p; a.memb_id = h->rc_memb.p;
+    a.B = (int)B; a.m = m; a.metric = h->metric;
+    const hipError_t e = recruit_chunks(h, a, Y, Q, chunk, bin_out, dist_out, min_dist_out, margin_out);
+    if (e != hipSuccess) {   // nothing of this call stays in flight behind the error
+        (void)hipStreamSynchronize(h->rc_copy);
+        (void)hipStreamSynchronize(s);
+        return fail(CHB_EHIP, hipGetErrorString(e));
+    }
+    return CHB_OK;
 }
 
 int chb_find_nearest_from_row(chb_ctx *h, int64_t c, const int64_t *labels, const double *row,
@@ -2431,6 +2602,7 @@ int chb_counter(chb_ctx *h, const char *name, int64_t *out)
     if (!strcmp(name, "tile_skipped")) { *out = h->skip_skipped; return CHB_OK; }
     if (!strcmp(name, "tile_seen")) { *out = h->skip_seen; return CHB_OK; }
     if (!strcmp(name, "tile_unloaded")) { *out = h->skip_unloaded; return CHB_OK; }
+    if (!strcmp(name, "recruit_chunk")) { *out = kRecruitChunk; return CHB_OK; }   // rows per launch of chb_recruit_rows
     if (!strcmp(name, "last_batch_k")) { *out = h->K; return CHB_OK; }
     if (!strcmp(name, "prefilter_enabled")) { *out = (h->sw.use_prefilter && h->shadow_ok) ? 1 : 0; return CHB_OK; }
     return fail(CHB_EINVAL, "unknown counter");

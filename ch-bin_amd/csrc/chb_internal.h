@@ -17,6 +17,7 @@ struct Gate {
 extern thread_local Gate g_gate;   // what every launch_* helper passes to its kernels
 #define CHB_GATE(g) do { if ((g).flag != nullptr && *(g).flag < (g).need) return; } while (0)
 
+constexpr double kInf = __builtin_huge_val();
 constexpr int kMaxM = 16;       // largest num_neighbors of the tuned kernels
 constexpr int kMaxMGeneric = 64; // CHB_MAX_NEIGHBORS: beyond kMaxM the plain one-wavefront-per-problem kernels run
 constexpr int kQTile = 64;      // queries per workgroup tile
@@ -340,6 +341,24 @@ void launch_hull_generic_indexed(const double *X, int D, int Dp, const int *q, c
 void launch_hull_qp_indexed(const double *X, int D, int Dp, const int *q, const int *hull_idx,
                             const int *hull_cnt, int P, int m_max, int metric, double *dist,
                             double *alpha, hipStream_t s);
+
+// ---- recruit (recruit_kernels.hip): hull distance of NEW rows Y (not samples) to every bin of a frozen labelling; reads
+// the resident matrix and the call's own CSR over the labels, nothing of a fit
+struct RecruitArgs {
+    const double *X;       // [N][Dp] the resident samples
+    const double *Y;       // [nq][Dp] the rows to score, zero padded like X
+    int D, Dp, nq;
+    const int *bin_ptr;    // [B+1] CSR over the labelled samples ...
+    const int *memb_id;    // ... their sample indices, grouped by bin
+    int B, m, metric;
+    double *dist;          // [nq][B]
+};
+constexpr int kRecruitChunk = 16384;   // rows of Y uploaded and scored per launch
+constexpr int kRecruitMaxBins = 8192;
+void launch_recruit(const RecruitArgs &a, hipStream_t s);
+// bin[q] = strict-'>' argmin over dist[q][0 .. B) (-1: all +inf), mind[q] its distance, margin[q] = runner-up minus it (+inf
+// without a finite runner-up)
+void launch_recruit_reduce(const double *dist, int nq, int B, int *bin, double *mind, double *margin, hipStream_t s);
 
 // label / bucket helpers
 void launch_fill_i32(int *p, int v, int n, hipStream_t s);

@@ -1,0 +1,258 @@
+// Hull distances of NEW rows (not samples) to every bin of a frozen labelling (chb_recruit_rows) for gfx950.
+//
+// What a fit does for a resident row -- find_nearest_from_cluster (distance_matrix.py:47-62) per bin, then
+// calculate_distance (hull_distance.py:90-108) to the hull of those members -- for rows Y that are not part of the
+// resident matrix, in ONE kernel and without any of the fit's state: no member codes, no "query is a member" exclusion,
+// no gate, no flag list, no shortlist stage.
+//
+// One 256-thread workgroup owns (64 rows of Y) x (one bin), tile_kernel's pattern (topm_kernels.hip): the bin's members
+// are streamed in tiles of 64 rows, a 64 x 64 tile of squared distances is accumulated with a 4 x 4 register micro-tile
+// per thread (fp64 VALU; LDS-staged transposed k-chunks, double buffered), and the 16 lanes that share a row keep its
+// sorted (distance, index) list in registers (select_into).  Once the last tile is in, the same 16 lanes solve the
+// row's hull problem in place: lane a's list entry is vertex a, the matrix core forms the Gram tile of (p_a - y) from
+// the vertex rows (read straight from L2: they were streamed a moment ago) and the 16-lane active-set solver of the
+// hull kernels (hull_solve16.h) runs on it.  One store per (row, bin).  The staging buffers and the solver's Gram tiles
+// share the workgroup's LDS (the first is dead when the second is written).
+//
+// Numerics: the selection arithmetic is chb_pairwise_distance's, bit for bit -- every squared distance is
+// sum_k (y_k - p_k)^2 accumulated sequentially in k with separate multiply and add (fp contraction is off from the
+// pragma below on), then a correctly rounded sqrt; members are ordered by (distance, sample index).  The solver is
+// compiled exactly as in qp_kernels.hip (its header is included above the pragma).
+//
+// A bin is never cut into member ranges: one bin of N members gives ceil(rows / 64) work items that each stream all N
+// member rows.  A second small kernel reduces each row of B distances to bin, minimum and margin.
+#include "chb_internal.h"
+#include "hull_solve16.h"
+
+#include <limits.h>
+#include <math.h>
+
+#pragma clang fp contract(off)
+
+#include "topm_select.h"
+
+namespace chb {
+namespace {
+
+// LDS of a workgroup: the tile loop's staging buffers, then the solver's Gram tiles and exchange rows
+struct RecruitStage {
+    double q[2][kKChunk][kLdsStride];
+    double p[2][kKChunk][kLdsStride];
+    int mid[2][kPTile];
+};
+struct RecruitSolve {
+    double Qt[4][4][16][kQ16Ld];   // [wavefront][16-lane group][row][col], padded
+    double sv[4][4][16];
+};
+union RecruitLds {
+    RecruitStage st;
+    RecruitSolve so;
+};
+
+// (two wavefronts per SIMD, like tile_kernel: at the solver's three the tile loop's lists and micro-tile would spill)
+__global__ __launch_bounds__(256, 2) void recruit_kernel(RecruitArgs a, int nqt, int total)
+{
+    __shared__ __attribute__((aligned(16))) RecruitLds lds;
+
+    // XCD-aware order: blocks b and b+8 share an XCD (and its L2), so hand each XCD a contiguous range of work
+    // items; consecutive items share a bin, i.e. the same member rows.
+    const int per = (total + 7) >> 3;
+    const int W = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
+    if (W >= total) return;
+    const int c = W / nqt, qt = W - c * nqt;
+
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tx = tid & 15, ty = tid >> 4;
+    const int gbase = lane & 48;
+    const int srow = tid >> 2, skp = tid & 3;
+
+    const int mb = a.bin_ptr[c], nmem = a.bin_ptr[c + 1] - mb;
+    const int pos0 = qt * kQTile;
+    const int m = a.m;
+
+    // list state of my 4 rows: this lane holds entry #tx
+    double ld[4], tau[4];
+    int li[4], lc[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { ld[i] = kInf; li[i] = INT_MAX; lc[i] = 0; tau[i] = kInf; }
+
+    // staging role: thread (srow, skp) moves feature columns [2*skp, 2*skp+1] of one row per chunk
+    int sq = pos0 + srow;
+    if (sq >= a.nq) sq = a.nq - 1;
+    const double *qrow = a.Y + (size_t)sq * a.Dp + 2 * skp;
+    const double *prow = a.X + 2 * skp;
+    const int nch = a.Dp / kKChunk;
+    const int ntile = (nmem + kPTile - 1) / kPTile;
+    const int nsteps = ntile * nch;
+
+    double2 rq, rp;
+    int pmid = -1;
+    int nt = 0, nc = 0;  // (tile, chunk) of the step being prefetched
+    auto prefetch = [&]() {
+        if (nc == 0) {
+            const int e = nt * kPTile + srow;
+            pmid = e < nmem ? a.memb_id[mb + e] : -1;
+            prow = a.X + (size_t)(pmid < 0 ? 0 : pmid) * a.Dp + 2 * skp;
+        }
+        rq = *reinterpret_cast<const double2 *>(qrow + nc * kKChunk);
+        rp = *reinterpret_cast<const double2 *>(prow + nc * kKChunk);
+    };
+    auto stash = [&](int buf) {
+        lds.st.q[buf][2 * skp][srow] = rq.x;
+        lds.st.q[buf][2 * skp + 1][srow] = rq.y;
+        lds.st.p[buf][2 * skp][srow] = rp.x;
+        lds.st.p[buf][2 * skp + 1][srow] = rp.y;
+        if (nc == 0 && skp == 0) lds.st.mid[nt & 1][srow] = pmid;
+        if (++nc == nch) { nc = 0; ++nt; }
+    };
+
+    double acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
+
+    if (nsteps > 0) { prefetch(); stash(0); }
+    __syncthreads();
+
+    int ct = 0, cc = 0;  // (tile, chunk) of the step being computed
+    for (int step = 0; step < nsteps; ++step) {
+        const int buf = step & 1;
+        const bool has_next = step + 1 < nsteps;
+        if (has_next) prefetch();
+        // keep the global loads of the next chunk in flight across the whole compute block: the
+        // scheduler must neither sink them nor hoist the LDS stores that consume them
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < kKChunk; ++k) {
+            const double2 qa = *reinterpret_cast<const double2 *>(&lds.st.q[buf][k][4 * ty]);
+            const double2 qb = *reinterpret_cast<const double2 *>(&lds.st.q[buf][k][4 * ty + 2]);
+            const double2 pa = *reinterpret_cast<const double2 *>(&lds.st.p[buf][k][2 * tx]);
+            const double2 pb = *reinterpret_cast<const double2 *>(&lds.st.p[buf][k][32 + 2 * tx]);
+            const double q[4] = {qa.x, qa.y, qb.x, qb.y};
+            const double p[4] = {pa.x, pa.y, pb.x, pb.y};
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const double df = q[i] - p[j];
+                    acc[i][j] = acc[i][j] + df * df;
+                }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (has_next) stash(buf ^ 1);
+        __syncthreads();
+        if (++cc == nch) {
+            // tile finished: offer its 64 members to the lists
+            int mid[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) mid[j] = lds.st.mid[ct & 1][(j < 2) ? 2 * tx + j : 32 + 2 * tx + (j - 2)];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const bool qvalid = pos0 + 4 * ty + i < a.nq;
+                double s[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    s[j] = (qvalid && mid[j] >= 0) ? acc[i][j] : kInf;
+                    acc[i][j] = 0.0;
+                }
+                select_into<16, 4>(s, mid, ld[i], li[i], lc[i], tau[i], m, tx, gbase);
+            }
+            cc = 0; ++ct;
+        }
+    }
+    __syncthreads();   // the staging buffers (the last tile's member ids among them) become the solver's tiles
+
+    // ---- the hull problems of my wavefront's 16 rows, four at a time (one per 16-lane group): row i of every group
+    int nn[4], idv[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { nn[i] = lc[i]; idv[i] = tx < lc[i] ? li[i] : -1; }
+    const int row = lane & 15, kq = lane >> 4;
+    const int Dk = (a.D + 7) & ~7;
+#pragma unroll 1
+    for (int i = 0; i < 4; ++i) {
+        const int n = nn[0], idm = idv[0];
+        // phase 1: Gram of the shifted vertices, one matrix-core tile per problem (lane (row, kq): vertex `row`,
+        // features 4 kq .. 4 kq + 3 of every 16); a missing vertex reads the query row: y = 0
+#pragma unroll 1
+        for (int p = 0; p < 4; ++p) {
+            const int np = __shfl(n, 16 * p, 64);
+            const int id = __shfl(idm, 16 * p + row, 64);
+            if (np <= 0) continue;   // wave-uniform
+            const double *qptr = a.Y + (size_t)(pos0 + 4 * (4 * w + p) + i) * a.Dp + 4 * kq;   // (np > 0: a row of the chunk)
+            const double *vptr = id >= 0 ? a.X + (size_t)id * a.Dp + 4 * kq : qptr;
+            f64x4 g = {0.0, 0.0, 0.0, 0.0}, d0 = g, d1 = g;
+            gram_tile16_rows<false>(vptr, vptr, qptr, Dk, kq, g, d0, d1);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) lds.so.Qt[w][p][kq + 4 * r][row] = g[r];
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wavefront's LDS writes have landed
+        // phase 2: one problem per 16-lane group
+        const int qpos = pos0 + 4 * ty + i;
+        double dist = kInf;
+        if (n > 0) {
+            double alpha = 0.0;
+            const double val = solve16(&lds.so.Qt[w][kq][0][0], &lds.so.sv[w][kq][0], n, a.metric, lane, alpha);
+            dist = sqrt(fmax(val, 0.0));
+        }
+        if (tx == 0 && qpos < a.nq) a.dist[(size_t)qpos * a.B + c] = dist;
+        __builtin_amdgcn_wave_barrier();   // the tiles are rewritten by the next row's phase 1
+        nn[0] = nn[1]; nn[1] = nn[2]; nn[2] = nn[3];
+        idv[0] = idv[1]; idv[1] = idv[2]; idv[2] = idv[3];
+    }
+}
+
+// strict-'>' scan over each row of B distances (algorithm.py:57: lowest index among equal minima, -1 when every entry
+// is +inf), the minimum and the margin = smallest distance of any OTHER bin minus the minimum (+inf without a finite
+// runner-up, never inf - inf).  8 lanes per row.
+__global__ __launch_bounds__(256) void recruit_reduce_kernel(const double *dist, int nq, int B, int *bin, double *mind,
+                                                             double *margin)
+{
+    const int j = threadIdx.x & 7;
+    const int q = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 3);
+    const bool valid = q < nq;
+    double best = kInf, runner = kInf;
+    int bc = -1;
+    if (valid) {
+        const double *row = dist + (size_t)q * B;
+        for (int c = j; c < B; c += 8) {
+            const double d = row[c];
+            if (best > d) { runner = best; best = d; bc = c; }
+            else if (runner > d) runner = d;
+        }
+    }
+#pragma unroll
+    for (int off = 1; off < 8; off <<= 1) {
+        const double ob = __shfl_xor(best, off, 64), orr = __shfl_xor(runner, off, 64);
+        const int oc = __shfl_xor(bc, off, 64);
+        // the other side wins on a smaller distance, or on the same (finite) distance with the lower bin
+        const bool take = ob < best || (ob == best && oc >= 0 && (bc < 0 || oc < bc));
+        const double lose = take ? best : ob;
+        runner = fmin(fmin(runner, orr), lose);
+        if (take) { best = ob; bc = oc; }
+    }
+    if (!valid || j != 0) return;
+    bin[q] = bc;
+    mind[q] = best;
+    margin[q] = runner == kInf ? kInf : runner - best;
+}
+
+}  // namespace
+
+void launch_recruit(const RecruitArgs &a, hipStream_t s)
+{
+    if (a.nq <= 0 || a.B <= 0) return;
+    const int nqt = (a.nq + kQTile - 1) / kQTile;
+    const int total = nqt * a.B;
+    const int grid = ((total + 7) / 8) * 8;
+    hipLaunchKernelGGL(recruit_kernel, dim3(grid), dim3(256), 0, s, a, nqt, total);
+}
+
+void launch_recruit_reduce(const double *dist, int nq, int B, int *bin, double *mind, double *margin, hipStream_t s)
+{
+    if (nq <= 0) return;
+    hipLaunchKernelGGL(recruit_reduce_kernel, dim3((nq + 31) / 32), dim3(256), 0, s, dist, nq, B, bin, mind, margin);
+}
+
+}  // namespace chb

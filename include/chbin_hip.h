@@ -97,6 +97,30 @@ int chb_pairwise_distance(chb_ctx *h, int64_t row_begin, int64_t row_end, double
 int chb_topm_per_bin(chb_ctx *h, const int64_t *labels, int64_t B, int m, const int64_t *query_idx,
                      int64_t Q, int64_t *nbr_idx, double *nbr_dist, int32_t *nbr_cnt);
 
+/* Hull distance of NEW rows (not samples) to every bin of a frozen labelling: recruiting contigs that were not part of
+ * the fit (the ones cli/features.py:60-64 drops under ContigLengthFilterBp, or a later assembly's) into finished bins.
+ * For row q and bin c: among {p : labels[p] == c} the (up to) m members nearest to Y[q] by
+ * (distance, index), distance = sqrt of the k-sequential unfused sum of squared differences (the
+ * arithmetic of chb_pairwise_distance); dist_out[q*B + c] = distance from Y[q] to their hull under the
+ * context's metric (chb_set_metric); +inf for a bin without members.  Nothing is excluded: a row equal
+ * to a sample has that sample as a candidate (distance 0).
+ * bin_out[q] = the bin the reference's strict-'>' scan (algorithm.py:57) picks over dist_out's row: lowest
+ * index among equal minima, -1 when every entry is +inf.  min_dist_out / margin_out as in
+ * chb_fit_cluster_ex (margin +inf without a finite runner-up, never inf - inf).
+ * labels[N] outside [0, B) count as unassigned (as chb_topm_per_bin).  dist_out, min_dist_out, margin_out
+ * may each be NULL; bin_out may be NULL if dist_out is not.  Q = 0 is a no-op.
+ *   - limits: m <= 16 and B <= 8192, CHB_EUNSUPPORTED beyond (the plain kernels for up to CHB_MAX_NEIGHBORS do not serve
+ *     this call); D must be the resident samples' D (CHB_EINVAL);
+ *   - the call reads the resident matrix and `labels` and nothing else: it uses no state of a fit and leaves every counter,
+ *     memo and switch of the context as it found it.  While a stepwise fit is open (chb_fit_begin, until the next
+ *     chb_set_samples* / chb_fit_cluster* / chb_topm_per_bin) it is refused with CHB_ESTATE and the fit stays usable;
+ *   - Y is uploaded and scored in chunks of 16384 rows (chb_counter "recruit_chunk"): the kernels on the context's stream,
+ *     the copies of the neighbouring chunks under them on a second stream of the context, through pinned staging buffers
+ *     the context keeps (two chunks of rows and of results); Y and the outputs may be ordinary pageable memory;
+ *   - one GPU: with a communicator (world > 1) each rank scores the rows it is given, there is no collective. */
+int chb_recruit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q,
+                     int64_t D, int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out);
+
 /* distance_matrix.py:47-62 find_nearest_from_cluster with the reference's exact signature: the
  * caller supplies one row of a distance matrix (any provenance) and the current labels; selects
  * among {p : labels[p] == c} the (up to) m smallest by (row[p], p).  out_idx[m] (-1 padded). */
@@ -224,7 +248,8 @@ int chb_profile_reset(chb_ctx *h);
  * "topm_fallback" | "topm_base" | "topm_update" | "hull_qp" | "slow_path" | "argmin" | "bucket" |
  * "pool" (upkeep of the shortlist stage's threshold pools: build once per fit, open + commit per batch) |
  * "prefilter_retry" (the exact two-sweep selection for the work items a pool batch's launch left on its overflow list) |
- * "pairwise" | "kmer_count".  For m <= 16 "hull_qp" is the fused selection + hull-distance kernel and
+ * "pairwise" | "kmer_count" | "recruit" (chb_recruit_rows: selection + hull kernel and the row reduction of one chunk; work
+ * units = (row, bin) pairs).  For m <= 16 "hull_qp" is the fused selection + hull-distance kernel and
  * "slow_path" the exact path for what it leaves over; "rescore*" then only appear for m > 16 or CHB_FUSED=0. */
 int chb_profile_get(chb_ctx *h, const char *kernel, double *total_ms, int64_t *launches,
                     double *work_units);
@@ -248,7 +273,7 @@ int chb_fit_stats(chb_ctx *h, int64_t *out4);
  * batch needed further rounds), "pool_batches" (batches of the last fit whose base shortlist launch took its thresholds
  * from the pools), "pool_state" (0 undecided = on, 1 kept on, -1 turned off because the shortlists came out long),
  * "pool_candidates" / "pool_pairs" (sampled shortlist lengths behind that decision), "exchanges" (framed all-gathers of the last fit under an exchange: one per batch for the
- * label guess, one per round) */
+ * label guess, one per round), "recruit_chunk" (rows per launch of chb_recruit_rows: a constant) */
 int chb_counter(chb_ctx *h, const char *name, int64_t *out);
 
 #ifdef __cplusplus
