@@ -283,7 +283,8 @@ struct chb_ctx {
     bool pool_fit = false;      // inside chb_fit_cluster (the stepwise entry points and chb_topm_per_bin never use pools)
     bool pool_valid = false;    // the pools on the device match the labels
     bool pool_holes = true;     // the open batch may hold labelled samples (their pool slots are holes until the commit)
-    int pool_state = 0;         // this fit: 0 undecided = on, 1 kept on, -1 off (its shortlists came out long: overlapping bins)
+    int pool_state = 0;         // this fit: 0 undecided = on, 1 kept on, -1 off (its shortlists came out long: overlapping bins;
+                                // or tile skipping never loads more than 30 % of the tiles: FitRun::note_verdict has both rules)
     int pool_batches = 0;
     long long pool_cand = 0, pool_pairs = 0;
     long long pool_off_key = -1;   // (bins, neighbours, metric) of the fit that turned them off on these samples
@@ -1196,6 +1197,573 @@ std::vector<int> to_i32(const int64_t *p, size_t n)
     return v;
 }
 
+// ======== chb_fit_cluster_ex, stage by stage: its arguments are checked (fit_check_args), the fit is started
+// (fit_begin_impl) and a FitScope takes over what the call sets on the context; a FitRun then carries the fit through its
+// sweeps -- per sweep upload_perm, order_sweep, per batch run_batch and report_batch, then end_sweep.
+
+// null checks, range checks and the up-front scan of the permutations
+int fit_check_args(chb_ctx *h, const int64_t *initial_bins, const int64_t *perms, int64_t n_move, int max_iter,
+                   const int64_t *labels_out, const double *min_dist_out, const double *margin_out)
+{
+    if (!h || !initial_bins || !labels_out) return fail(CHB_EINVAL, "null argument");
+    if (margin_out && !min_dist_out) return fail(CHB_EINVAL, "margin_out needs min_dist_out");
+    if (margin_out && h->world > 1) return fail(CHB_EUNSUPPORTED, "margin report is single-GPU");
+    if (n_move > 0 && !perms) return fail(CHB_EINVAL, "perms is null");
+    if (max_iter < 0 || n_move < 0 || n_move > h->N) return fail(CHB_EINVAL, "bad n_move/max_iter");
+    HIPCHK(hipSetDevice(h->dev));
+    if (h->world > 1 && !h->comm && !h->hook) return fail(CHB_ESTATE, "world > 1 but chb_comm_init was not called");
+    if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
+    // every permutation entry is range-checked BEFORE anything runs (a min / max pass the compiler vectorises), so a
+    // bad entry in a late sweep cannot surface after earlier sweeps have already run; duplicates inside a sweep
+    // are rejected while that sweep is converted for its upload (bitmap), and any error return closes the fit
+    int64_t lo = 0, hi = 0;
+    const int64_t tot = (int64_t)max_iter * n_move;
+    for (int64_t i = 0; i < tot; ++i) { lo = std::min(lo, perms[i]); hi = std::max(hi, perms[i]); }
+    if (lo < 0 || hi >= h->N) return fail(CHB_EINVAL, "perm entry out of range");
+    return CHB_OK;
+}
+
+// default batch: 8192 positions on one GPU, growing with sqrt(world): the batch-member
+// (update) work per rank is ~K^2/world, the per-rank grids ~K/world.  Twice that from 300k contigs to move: every
+// batch rebuilds the CSR and the padded pack of ALL labelled contigs (cost ~ N per batch, ~ N^2 / K per sweep), while a
+// batch is a smaller share of the sweep and collides with itself no more often (measured: 115 against 124 ms per sweep
+// at 500k x 140 x 128, 517 against 538 at 1M x 146 x 200; 100k contigs are best served by 8192)
+// (round 5, with the pools' cheaper shortlist launches: four times from 750k contigs -- 1M x 146 x 200: 342 against 361 ms per
+//  sweep; 500k x 140 x 128 stays best at twice: 105.5 against 108.5)
+int fit_default_batch(const chb_ctx *h, int64_t n_move, int m, int batch)
+{
+    int Kmax = batch > 0 ? batch : 8192 * std::max(1, (int)std::lround(std::sqrt((double)h->world))) *
+                                       ((n_move >= 750000 && h->world == 1) ? 4 : (n_move >= 300000 ? 2 : 1));   // (sharded: as before)
+    if (m > kMaxM && batch <= 0) Kmax = std::min(Kmax, 512);   // the plain kernels: one wavefront per (contig, bin)
+    if (Kmax > n_move) Kmax = (int)std::max<int64_t>(n_move, 1);
+    return Kmax;
+}
+
+// What a chb_fit_cluster_ex call sets on a context with a started fit holds for that call only: the margin report, the fit's
+// persistent pack and threshold pools, the sweep's seating order, the switches the ranks agreed on, the look-ahead gate
+// (error returns inside the window).  An error return must not leave an open fit / batch behind either.
+struct FitScope {
+    chb_ctx *h;
+    bool skip, pack, spec;   // (the agreed switches hold for this fit only)
+    bool ok = false;
+    FitScope(chb_ctx *h_, bool want_margin) : h(h_), skip(h_->sw.allow_skip), pack(h_->sw.pp_allowed), spec(h_->sw.speculate)
+    {
+        h->want_margin = want_margin; h->pp_fit = true; h->pool_fit = true;
+    }
+    ~FitScope()
+    {
+        g_gate = Gate{};
+        h->sw.allow_skip = skip; h->sw.pp_allowed = pack; h->sw.speculate = spec;
+        h->pp_fit = false; h->pp_valid = false; h->pool_fit = false; h->pool_valid = false; h->qord_cur = nullptr; h->home_cur = nullptr;
+        if (!ok) { (void)hipStreamSynchronize(h->stream); h->fit_open = false; h->batch_open = false; }
+        h->want_margin = false;
+    }
+};
+
+// ---- the fit driver's hooks for the developer builds (product build: none)
+#ifdef CHB_DEV_KNOBS
+// tests of the exchange schedule (tests/test_gpu_world2.py): CHB_DEV_HOOK_SPEC=1 runs the look-ahead over the host-staged hook
+// (no gain, but the RCCL path's ORDER of exchanges); CHB_DEV_SKIP_STATS=<skipped>,<seen>,<unloaded> replaces this rank's
+// tile-skipping statistics of every batch; CHB_DEV_LOCAL_VERDICT=1: each rank decides from its OWN ones
+struct FitDev {
+    static bool hook_spec(const chb_ctx *h) { return h->dk.hook_spec; }
+    static bool local_verdict(const chb_ctx *h) { return h->dk.local_verdict; }
+    static void skip_stats(chb_ctx *h)
+    {
+        if (h->dk.skip_stats_on) for (int k = 0; k < 3; ++k) launch_fill_i32(h->fc_cur + kSlotSkipped + k, h->dk.skip_stats[k], 1, h->stream);
+    }
+    // CHB_PACK_REBUILD_AT=<rows>: rebuild (compact) the pack from that fill mark on -- tests of the rebuild path
+    static int64_t rebuild_mark(const chb_ctx *h) { return h->dk.pack_rebuild_at >= 0 ? h->dk.pack_rebuild_at : h->pp_mark; }
+    // CHB_DEV_ALL_DIST=<file> (tests/test_gpu_bin_distances.py; read per fit): with min_dist_out on one GPU, every hull distance
+    // of each movable contig's last visit -- row perm[t0 + i] of an N x B float64 array (NaN rows for contigs never visited),
+    // written raw to <file> when the fit succeeds.  (min_dist_out keeps the look-ahead off: nothing overwrites a batch's dist
+    // before it is copied.)
+    const char *all_path = nullptr;
+    std::vector<double> all;
+    void all_begin(const chb_ctx *h, bool wanted)
+    {
+        all_path = wanted ? getenv("CHB_DEV_ALL_DIST") : nullptr;
+        all.assign(all_path ? (size_t)h->N * (size_t)h->B : 0, NAN);
+    }
+    int all_rows(chb_ctx *h, const int64_t *ids, int K)   // (the batch's K x B distances, each row to its contig's)
+    {
+        if (!all_path) return CHB_OK;
+        std::vector<double> rows((size_t)K * h->B);
+        HIPCHK(hipMemcpy(rows.data(), h->dist.p, sizeof(double) * rows.size(), hipMemcpyDeviceToHost));
+        for (int i = 0; i < K; ++i)
+            memcpy(all.data() + (size_t)ids[i] * h->B, rows.data() + (size_t)i * h->B, sizeof(double) * h->B);
+        return CHB_OK;
+    }
+    int all_write() const
+    {
+        if (!all_path) return CHB_OK;
+        FILE *fp = fopen(all_path, "wb");
+        const bool ok = fp && fwrite(all.data(), sizeof(double), all.size(), fp) == all.size();
+        if (fp) fclose(fp);
+        return ok ? CHB_OK : fail(CHB_EINVAL, std::string("CHB_DEV_ALL_DIST: cannot write ") + all_path);
+    }
+};
+#else
+struct FitDev {
+    static bool hook_spec(const chb_ctx *) { return false; }
+    static bool local_verdict(const chb_ctx *) { return false; }
+    static void skip_stats(chb_ctx *) {}
+    static int64_t rebuild_mark(const chb_ctx *h) { return h->pp_mark; }
+    void all_begin(const chb_ctx *, bool) {}
+    int all_rows(chb_ctx *, const int64_t *, int) { return CHB_OK; }
+    int all_write() const { return CHB_OK; }
+};
+#endif
+
+// the positions [t0, t0 + K) of a sweep's permutation as one batch: this rank evaluates [q_lo, q_hi) of it, C per rank
+struct Geom { int64_t t0; int K, q_lo, q_hi, C; };
+
+// host-side batch state, saved where a look-ahead window opens (the device side of a gated-off batch never changed)
+struct LookaheadSnap {
+    int K, q_lo, q_hi, round_in_batch; bool lists_valid, batch_open, pp_batch, pp_valid, pool_valid; int *bq_cur, *fc_cur;
+    double hb, he; int64_t st[4]; size_t n_pending;
+    static LookaheadSnap save(const chb_ctx *h)
+    {
+        LookaheadSnap v{h->K, h->q_lo, h->q_hi, h->round_in_batch, h->lists_valid, h->batch_open, h->pp_batch, h->pp_valid, h->pool_valid,
+                        h->bq_cur, h->fc_cur, h->hint_base_members, h->hint_batch_entries, {0, 0, 0, 0}, h->pending.size()};
+        memcpy(v.st, h->stats, sizeof(v.st));
+        return v;
+    }
+    void restore(chb_ctx *h) const
+    {
+        h->K = K; h->q_lo = q_lo; h->q_hi = q_hi; h->round_in_batch = round_in_batch;
+        h->lists_valid = lists_valid; h->batch_open = batch_open; h->bq_cur = bq_cur; h->fc_cur = fc_cur;
+        h->pp_batch = pp_batch; h->pp_valid = pp_valid; h->pool_valid = pool_valid;
+        h->hint_base_members = hb; h->hint_batch_entries = he;
+        memcpy(h->stats, st, sizeof(st));
+        // the launches recorded inside the window were gated off (they returned at once): they are neither
+        // launches nor work of the profile
+        for (size_t i = n_pending; i < h->pending.size(); ++i) {
+            (void)hipEventDestroy(h->pending[i].a);
+            (void)hipEventDestroy(h->pending[i].b);
+        }
+        if (h->pending.size() > n_pending) h->pending.resize(n_pending);
+    }
+};
+
+struct FitRun {
+    // the call's arguments
+    chb_ctx *h;
+    const int64_t *perms;
+    int64_t n_move;
+    int max_iter;
+    int64_t *labels_out;
+    double *min_dist_out, *margin_out;
+    // fixed for the fit (can_spec: once the ranks have agreed on the switches)
+    int64_t N;
+    hipStream_t s;
+    int Kmax, world;
+    bool xchg;              // the rounds' labels travel through an all-gather: more than one rank, or CHB_FORCE_GATHER
+    bool can_spec = false;
+    // the sweeps
+    int it = 0;
+    int64_t assigned0 = 0, labelled = 0;   // labelled samples at the fit's start / after the last sweep
+    std::vector<int> prev;                 // labels before the current sweep
+    bool sweep_has_labelled = true;
+    std::vector<int64_t> batch_t0;         // first position of every batch of the sweep (empty: its batches order themselves)
+    std::vector<double> mind_host, mind2_host;
+    std::vector<uint64_t> seen_bits;
+    // the batches of a sweep
+    bool inflight = false;   // the batch's start and first round went out with its predecessor's look-ahead
+    bool spec_ok = false;    // (a failed guess switches the look-ahead off until a batch converges in one round again)
+    int slot = 0;            // verdict slot of the batch
+    FitDev dev;
+
+    FitRun(chb_ctx *h_, const int64_t *perms_, int64_t n_move_, int max_iter_, int Kmax_, int64_t *labels_out_,
+           double *min_dist_out_, double *margin_out_)
+        : h(h_), perms(perms_), n_move(n_move_), max_iter(max_iter_), labels_out(labels_out_), min_dist_out(min_dist_out_), margin_out(margin_out_), N(h_->N), s(h_->stream), Kmax(Kmax_), world(h_->world),
+          xchg((h_->comm != nullptr || h_->hook != nullptr) && (h_->world > 1 || h_->sw.force_gather))
+    {
+    }
+
+    const int64_t *perm() const { return perms + (int64_t)it * n_move; }   // the current sweep's
+    // the tag of the fit's next exchange (kind 1: a batch's label guess, 2: a round's labels)
+    int next_tag(int kind) { const int t = ((h->xseq & 0x7ffffff) << 4) | kind; h->xseq += 1; return t; }
+
+    // ---- more than one rank: agree on the fit before its first collective (fit_agree)
+    int fit_agree_switches(const int64_t *initial_bins)
+    {
+        h->xseq = 0;
+        if (xchg) {
+            FitAgree fa{};
+            const uint64_t hp = hash_i64(perms, (int64_t)max_iter * n_move), hi_ = hash_i64(initial_bins, N);
+            const int eq[FitAgree::kEq] = {0x43480005, h->B, h->m, (int)(n_move & 0x7fffffff), max_iter, Kmax, (int)(N & 0x7fffffff),
+                                           h->D, h->metric, h->fused ? 1 : 0, h->pf_fit ? 1 : 0, min_dist_out ? 1 : 0,
+                                           (int)(hp & 0x7fffffff), (int)((hp >> 32) & 0x7fffffff), (int)(hi_ & 0x7fffffff),
+                                           (int)((hi_ >> 32) & 0x7fffffff)};
+            memcpy(fa.v, eq, sizeof(eq));
+            fa.v[16] = h->skip_state; fa.v[17] = h->sw.speculate ? 1 : 0; fa.v[18] = h->sw.allow_skip ? 1 : 0; fa.v[19] = h->sw.pp_allowed ? 1 : 0;
+            fa.v[20] = h->pool_valid ? h->pool_state : -1;
+            const int rc = fit_agree(h, &fa);
+            if (rc) return rc;
+            h->skip_state = fa.v[16]; h->sw.speculate = fa.v[17] != 0; h->sw.allow_skip = fa.v[18] != 0; h->sw.pp_allowed = fa.v[19] != 0;
+            if (fa.v[20] < 0) { h->pool_state = -1; h->pool_valid = false; }
+        }
+        // (look-ahead under an exchange: the RCCL all-gather sits on the context's stream, so the first-changed position of
+        //  a round is computed on the device right behind it and feeds the same gate as on one GPU; every rank sees the same
+        //  labels, hence the same verdict, and the all-gathers of a gated-off batch move identical bytes between the ranks'
+        //  identical buffers.  The hook transport needs the host between rounds anyway.)
+        can_spec = h->sw.speculate && h->fused && (!xchg || (h->hook == nullptr && h->comm != nullptr) || FitDev::hook_spec(h)) &&
+                   min_dist_out == nullptr;
+        return CHB_OK;
+    }
+
+    // the labels the fit starts from, the NaN-filled reports
+    void begin_outputs()
+    {
+        dev.all_begin(h, min_dist_out && !xchg);
+        // (fit_begin_impl left the converted initial labels in pin_a; their upload and the kernels of the fit's start are
+        //  still running -- nothing below touches pin_a again before the sweep's final synchronisation)
+        prev.assign(h->pin_a.p, h->pin_a.p + N);
+        if (min_dist_out) {
+            for (int64_t i = 0; i < N; ++i) min_dist_out[i] = NAN;
+            mind_host.resize((size_t)Kmax);
+        }
+        if (margin_out) {
+            for (int64_t i = 0; i < N; ++i) margin_out[i] = NAN;
+            mind2_host.resize((size_t)Kmax);
+        }
+        for (int64_t i = 0; i < N; ++i) assigned0 += prev[(size_t)i] >= 0;
+        labelled = assigned0;
+    }
+
+    // the sweep's permutation: converted into its pinned staging buffer, checked for duplicates, uploaded
+    int upload_perm()
+    {
+        HIPCHK(h->perm.ensure((size_t)std::max<int64_t>(n_move, 1)));
+        HIPCHK(h->pin_c.ensure((size_t)std::max<int64_t>(n_move, 1)));
+        if (!n_move) return CHB_OK;
+        // (pin_c, the permutations' own staging buffer: the previous sweep's upload from it completed before that
+        //  sweep's final synchronisation, and the first sweep's conversion overlaps the kernels of the fit's start)
+        const int64_t *pm = perm();
+        seen_bits.assign((size_t)(N + 63) / 64, 0);
+        uint64_t dup = 0;
+        int any_lab = 0;   // does this sweep visit a sample that carries a label?  (sweep 1 normally does not)
+        for (int64_t i = 0; i < n_move; ++i) {
+            const int64_t v = pm[i];          // (in range: checked up front)
+            uint64_t &wd = seen_bits[(size_t)(v >> 6)];
+            const uint64_t bit = 1ull << (v & 63);
+            dup |= wd & bit;
+            wd |= bit;
+            h->pin_c.p[i] = (int)v;
+            any_lab |= prev[(size_t)v] >= 0;
+        }
+        sweep_has_labelled = any_lab != 0;
+        if (dup) return fail(CHB_EINVAL, "a sweep's permutation lists a sample twice");
+        HIPCHK(hipMemcpyAsync(h->perm.p, h->pin_c.p, sizeof(int) * n_move, hipMemcpyHostToDevice, s));
+        return CHB_OK;
+    }
+
+    Geom geom_at(int64_t t0) const
+    {
+        // sweep 1 starts from few labelled members: do not let a batch outnumber them by much
+        // (measured: a batch of up to 1.5x the labelled members costs no extra rounds and saves a batch)
+        int64_t members = (it == 0) ? (assigned0 + t0) * 3 / 2 : N;
+        int K = (int)std::min<int64_t>(Kmax, n_move - t0);
+        if (members < K) K = (int)std::max<int64_t>(std::min<int64_t>(64, n_move - t0), members);
+        K = std::min(K, Kmax);   // (the floor of 64 above must not exceed a caller's smaller batch: buffers hold Kmax)
+        // multi-GPU: rank r evaluates positions [r*C, (r+1)*C) of the batch; the label slices
+        // are exchanged with one in-place RCCL all-gather per round (KB-sized)
+        const int C = (K + world - 1) / world;
+        const int q_lo = std::min(K, h->rank * C);
+        return Geom{t0, K, q_lo, std::min(K, q_lo + C), C};
+    }
+
+    // the seating order of every batch of this sweep (tile skipping / threshold pools), in one launch: the batches are a
+    // function of the sweep alone.  (Not for sweeps of thousands of tiny batches: those order theirs one by one.)
+    int order_sweep()
+    {
+        h->qord_cur = nullptr; h->home_cur = nullptr;
+        batch_t0.clear();
+        if (!(h->pf_fit && h->fused && h->ckey.p != nullptr && n_move > 0 && (h->pool_valid || (h->sw.allow_skip && h->skip_state >= 0))))
+            return CHB_OK;
+        std::vector<int4> geo;
+        for (int64_t t = 0; t < n_move && geo.size() <= 4096;) {
+            const Geom g = geom_at(t);
+            geo.push_back(make_int4((int)g.t0, g.q_lo, g.q_hi, g.K));
+            batch_t0.push_back(t);
+            t += g.K;
+        }
+        if (geo.size() > 4096) { batch_t0.clear(); return CHB_OK; }
+        HIPCHK(h->geo_all.ensure(geo.size()));
+        HIPCHK(h->qord_all.ensure((size_t)n_move));
+        HIPCHK(h->home_all.ensure(geo.size() * (size_t)h->B));
+        // (pinned staging: the previous sweep's upload from it completed before that sweep's final synchronisation)
+        HIPCHK(h->pin_geo.ensure(geo.size()));
+        memcpy(h->pin_geo.p, geo.data(), sizeof(int4) * geo.size());
+        HIPCHK(hipMemcpyAsync(h->geo_all.p, h->pin_geo.p, sizeof(int4) * geo.size(), hipMemcpyHostToDevice, s));
+        Timed t(h, "bucket", (double)n_move);
+        launch_query_order_sweep(h->ckey.p, h->perm.p, h->geo_all.p, (int)geo.size(), h->B, h->qord_all.p, h->home_all.p, s);
+        return CHB_OK;
+    }
+
+    // after a round's kernels: (multi-GPU: exchange) + first-changed position on its way to the host
+    int finish_round(const Geom &g, int active, int slot_)
+    {
+        if (xchg) {
+            // this rank's frame {tag, skip and pool statistics of the batch's base shortlist launch, the pack's fill mark, label
+            // slice} -> all-gather -> every rank's labels into lab_new / lab_prev, first changed position, statistics summed over
+            // the ranks (gated kernels, not memcpys: inside a look-ahead window they must not run; single rank without exchange:
+            // the argmin kernel has already written lab_prev).  What comes home in the verdict slot is then the SAME on
+            // every rank -- first change, bin sizes (functions of the replicated labels), skip and pool statistics, arena mark --
+            // and with it every decision of this loop, in particular whether the next batch is enqueued ahead.
+            const int tag = next_tag(2);
+            const bool first = active == 0;
+            if (first) FitDev::skip_stats(h);
+            launch_xchg_pack(h->xg.p, h->rank, g.C, h->lab_new.p, tag, h->fc_cur, first, first && h->pp_batch, true, g.K, s);
+            { const int r_ = exchange_all_gather(h, h->xg.p, (size_t)(g.C + kXchgHdr), sizeof(int), ncclInt32); if (r_) return r_; }
+            launch_xchg_unpack(h->xg.p, world, g.C, g.K, tag, h->lab_new.p, h->lab_prev.p, active, h->fc_cur,
+                               first && !FitDev::local_verdict(h), h->xerr.p, s);
+        }
+        HIPCHK(hipMemcpyAsync(h->fc_host + kSlotInts * slot_, h->fc_cur, kSlotHome * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipEventRecord(h->fc_event[slot_], s));
+        return CHB_OK;
+    }
+
+    // the verdict as it came home (SlotWord); nullptr: the wait failed
+    const int *wait_verdict(int slot_)
+    {
+        const hipError_t e = hipEventSynchronize(h->fc_event[slot_]);
+        if (e != hipSuccess) { fail(CHB_EHIP, std::string("hipEventSynchronize(h->fc_event[slot]): ") + hipGetErrorString(e)); return nullptr; }
+        return h->fc_host + kSlotInts * slot_;
+    }
+
+    // What the host takes from a verdict besides the first change -- no HIP call in here.  The slot's statistics are written
+    // by the batch's one base shortlist launch: counted with the batch's first round only (later rounds of the same batch
+    // bring the same numbers home again).
+    void note_verdict(const int *v, bool first_round)
+    {
+        // (bin sizes of that batch, for the segment decision of the batches still to be enqueued)
+        h->hint_max_tiles = v[kSlotMaxTiles]; h->hint_total_tiles = v[kSlotTotalTiles];
+        // (the persistent pack's arena: rows handed out so far, as of that batch's start)
+        if (h->pp_valid && v[kSlotMark] > FitDev::rebuild_mark(h)) h->pp_rebuild = true;
+        if (!first_round) return;
+        // (what the tile skipping of its shortlist launch achieved: a fit whose first batches skip next to nothing turns it off)
+        if (v[kSlotSeen] > 0) {
+            h->skip_skipped += v[kSlotSkipped]; h->skip_seen += v[kSlotSeen]; h->skip_unloaded += v[kSlotUnloaded];
+            if (h->skip_state == 0 && ++h->skip_batches >= 3) {
+                // (it pays from a few per cent of the wave-tiles)
+                h->skip_state = ((h->skip_skipped + h->skip_unloaded) * 50 >= h->skip_seen + h->skip_unloaded) ? 1 : -1;
+                if (h->skip_state < 0) h->skip_off_key = skip_key(h);
+            }
+        }
+        // Where tile skipping never loads a third of a bin's tiles (500k x 140 x 128: 45 %), the threshold sweep is
+        // cheap already and the pools' price -- the looser thresholds of the contigs far out in their bins: long
+        // shortlists, retries, label guesses that fail -- is higher than what they save (113 against 105 ms per
+        // sweep there; 1M x 146 x 200, 19 % never loaded: 366 against 460): such a fit drops them
+        // (checked per batch: sweep 1's first batches stream bins of a few tiles, nothing to go by)
+        if (h->skip_state == 1 && h->pool_state >= 0 && v[kSlotSeen] > 0) {
+            const long long un = v[kSlotUnloaded], sn = v[kSlotSeen];
+            if (un * 10 > 3 * (sn + un)) { h->pool_state = -1; h->pool_off_key = skip_key(h); }
+        }
+        // (threshold pools: candidates per pair of that batch's base shortlist launch, as sampled; a fit whose first
+        //  batches admit far more than the exact threshold would -- overlapping bins -- goes back to the two sweeps
+        //  -- checked for EVERY batch: the pools of sweep 1's first batches hold whole bins and say nothing yet)
+        if (h->pool_state >= 0 && v[kSlotPoolPairs] > 0) {
+            const long long pc = v[kSlotPoolCand], pp = v[kSlotPoolPairs];
+            h->pool_cand += pc; h->pool_pairs += pp;
+            if (++h->pool_batches >= 3 && h->pool_state == 0) h->pool_state = 1;
+            // (the benchmark configurations admit m + 0.1 .. m + 0.4 per pair; from m + 3 on the loose thresholds cost the
+            //  update stage and the hull kernel more than the threshold sweep did)
+            if (pc > (long long)(h->m + 3) * pp) { h->pool_state = -1; h->pool_off_key = skip_key(h); }
+        }
+    }
+
+    // a round's verdict, waited for and taken note of; *f = its first changed position
+    int round_verdict(int slot_, bool first_round, int *f)
+    {
+        const int *v = wait_verdict(slot_);
+        if (!v) return CHB_EHIP;
+        *f = v[kSlotFirstChange];
+        note_verdict(v, first_round);
+        return CHB_OK;
+    }
+
+    // batch start + guess + round 0, nothing read back
+    int open_batch(const Geom &g, int slot_)
+    {
+        h->bq_cur = h->perm.p + g.t0;   // the batch's sample indices: a window of the sweep's permutation
+        h->fc_cur = h->first_change.p + kSlotInts * slot_;
+        if (!batch_t0.empty()) {
+            const size_t bi = (size_t)(std::lower_bound(batch_t0.begin(), batch_t0.end(), g.t0) - batch_t0.begin());
+            h->qord_cur = h->qord_all.p + g.t0 + g.q_lo; h->home_cur = h->home_all.p + bi * (size_t)h->B;
+        }
+        h->hint_base_members = (double)((it == 0) ? assigned0 + g.t0 : labelled - g.K);
+        h->hint_batch_entries = (double)((it == 0) ? g.K : 2 * g.K);
+        h->argmin_in_place = !xchg;
+        int r = batch_begin_dev(h, g.K, g.q_lo, g.q_hi, false);
+        if (r) return r;
+        h->pool_holes = sweep_has_labelled;   // (an all-unlabelled batch leaves no holes for its commit to look for)
+        // starting labels of the rounds: last sweep's label, or for still-unlabelled contigs
+        // (sweep 1) the bin whose m-th nearest outside member is closest
+        if (h->fused && !h->lists_valid) launch_guess_near(h->tau.p, h->lab_old.p, g.q_lo, g.q_hi, h->B, h->Kcap, h->lab_prev.p, s);
+        else launch_guess(h->l0d.p, h->l0c.p, h->lab_old.p, g.q_lo, g.q_hi, h->B, h->m, h->Kcap, h->lab_prev.p, s);
+        if (xchg) {
+            const int tag = next_tag(1);
+            launch_xchg_pack(h->xg.p, h->rank, g.C, h->lab_prev.p, tag, h->fc_cur, false, false, false, g.K, s);
+            { const int r_ = exchange_all_gather(h, h->xg.p, (size_t)(g.C + kXchgHdr), sizeof(int), ncclInt32); if (r_) return r_; }
+            launch_xchg_unpack(h->xg.p, world, g.C, g.K, tag, h->lab_prev.p, nullptr, 0, h->fc_cur, false, h->xerr.p, s);
+        }
+        r = batch_round_dev(h, 0);
+        if (r) return r;
+        return finish_round(g, 0, slot_);
+    }
+
+    // A batch = start (selection against the members outside it), a label guess, then rounds until the first changed
+    // position is past its end.  On one GPU the NEXT batch is enqueued while the first round's verdict is still on its way
+    // to the host: its kernels (and this batch's commit) carry a gate on that verdict and return at once if the round
+    // did not converge, in which case the remaining rounds run and the next batch is enqueued again.
+    // The stream never drains while rounds converge at once -- the common case after sweep 1's start;
+    // a failed guess switches the look-ahead off until a batch converges in one round again.
+    int run_batch(const Geom &g)
+    {
+        const int K = g.K;
+        int rc;
+        if (!inflight) { rc = open_batch(g, slot); if (rc) return rc; }
+        const int64_t t1 = g.t0 + K;
+        // (a batch start that has to build or rebuild the persistent pack stays outside the look-ahead window)
+        const bool skip_would = h->sw.allow_skip && h->nsh > 1 && h->skip_state >= 0 && h->ckey.p != nullptr;
+        const bool pack_sync = h->pp_fit && h->sw.pp_allowed && h->fused && h->cand.p && !skip_would &&
+                               (!h->pp_valid || h->pp_rebuild);
+        const bool spec = spec_ok && t1 < n_move && !pack_sync;
+        LookaheadSnap snap{};
+        if (spec) {
+            snap = LookaheadSnap::save(h);
+            g_gate = Gate{h->first_change.p + kSlotInts * slot, K};   // "this batch's round 0 changed nothing"
+            rc = batch_commit_dev(h, h->lab_prev.p);
+            if (rc) return rc;
+            rc = open_batch(geom_at(t1), slot ^ 1);
+            if (rc) return rc;
+            g_gate = Gate{};
+        }
+        int f = K;
+        rc = round_verdict(slot, true, &f);
+        if (rc) return rc;
+        if (f >= K) {
+            inflight = spec;   // the next batch's first round is already running
+            if (spec) h->stats_lookahead += 1;
+            spec_ok = can_spec;
+            return CHB_OK;
+        }
+        // the guess was off at position f: everything enqueued behind the gate has skipped itself
+        if (spec) { snap.restore(h); spec_ok = false; h->stats_lookahead_failed += 1; }
+        for (int active = f + 1; active < K; active = f + 1) {
+            rc = batch_round_dev(h, active);
+            if (rc) return rc;
+            rc = finish_round(g, active, slot);
+            if (rc) return rc;
+            rc = round_verdict(slot, false, &f);
+            if (rc) return rc;
+            if (f >= K) break;
+        }
+        inflight = false;
+        return CHB_OK;
+    }
+
+    // min_dist_out / margin_out of the batch's contigs (the look-ahead is off: nothing has overwritten them)
+    int report_batch(const Geom &g)
+    {
+        if (!min_dist_out) return CHB_OK;
+        const int K = g.K;
+        const int64_t *ids = perm() + g.t0;
+        if (xchg)
+            { const int r_ = exchange_all_gather(h, h->mind.p, (size_t)g.C, sizeof(double), ncclFloat64); if (r_) return r_; }
+        HIPCHK(hipMemcpyAsync(mind_host.data(), h->mind.p, sizeof(double) * K, hipMemcpyDeviceToHost, s));
+        if (margin_out)
+            HIPCHK(hipMemcpyAsync(mind2_host.data(), h->mind2.p, sizeof(double) * K, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (int i = 0; i < K; ++i) min_dist_out[ids[i]] = mind_host[(size_t)i];
+        // (runner-up +inf: no other bin has a member -- +inf also when no bin has one, not inf - inf)
+        if (margin_out)
+            for (int i = 0; i < K; ++i) {
+                const double w = mind_host[(size_t)i], r = mind2_host[(size_t)i];
+                margin_out[ids[i]] = r == INFINITY ? INFINITY : r - w;
+            }
+        return dev.all_rows(h, ids, K);
+    }
+
+    // ---- the batches of this sweep
+    int run_sweep()
+    {
+        int rc = upload_perm();
+        if (rc) return rc;
+        rc = order_sweep();
+        if (rc) return rc;
+        inflight = false; spec_ok = can_spec; slot = 0;
+        for (int64_t t0 = 0; t0 < n_move;) {
+            const Geom g = geom_at(t0);
+            rc = run_batch(g);
+            if (rc) return rc;
+            rc = report_batch(g);
+            if (rc) return rc;
+            if (!inflight) {   // (otherwise the commit went out with the look-ahead)
+                rc = batch_commit_dev(h, h->lab_prev.p);
+                if (rc) return rc;
+            } else {
+                slot ^= 1;
+            }
+            h->stats[0] += 1;
+            t0 += g.K;
+        }
+        h->stats[3] += n_move * (int64_t)h->B;
+        return CHB_OK;
+    }
+
+    // the sweep's labels come home with the device's error words; *diff = labels the sweep changed (algorithm.py:63)
+    int end_sweep(int64_t *diff)
+    {
+        HIPCHK(h->pin_b.ensure((size_t)N));
+        HIPCHK(hipMemcpyAsync(h->pin_b.p, h->labels.p, sizeof(int) * N, hipMemcpyDeviceToHost, s));
+        if (h->fused && h->short_cnt.p)   // (spare words of the first verdict slot)
+            HIPCHK(hipMemcpyAsync(h->fc_host + kSlotShortCnt, h->short_cnt.p, sizeof(int), hipMemcpyDeviceToHost, s));
+        h->fc_host[kSlotPackErr] = 0;
+        if (h->pp_ctl.p)
+            HIPCHK(hipMemcpyAsync(h->fc_host + kSlotPackErr, h->pp_ctl.p + 2, sizeof(int), hipMemcpyDeviceToHost, s));
+        std::vector<int> xend;
+        if (xchg) {
+            // every rank's "a rank was out of step" record: all ranks then leave the sweep with the same status
+            xend.assign((size_t)4 * world, 0);
+            HIPCHK(hipMemcpyAsync(h->agree.p + 4 * h->rank, h->xerr.p, 4 * sizeof(int), hipMemcpyDeviceToDevice, s));
+            { const int r_ = exchange_all_gather(h, h->agree.p, 4, sizeof(int), ncclInt32); if (r_) return r_; }
+            HIPCHK(hipMemcpyAsync(xend.data(), h->agree.p, sizeof(int) * xend.size(), hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipStreamSynchronize(s));
+        for (int r = 0; r < (int)xend.size() / 4; ++r)
+            if (xend[(size_t)4 * r] != 0) {
+                HIPCHK(hipMemsetAsync(h->xerr.p, 0, 4 * sizeof(int), s));
+                const int *e = xend.data() + 4 * r;
+                return fail(CHB_ESTATE, "internal error: the ranks' exchanges fell out of step (rank " + std::to_string(r) + " was at exchange " +
+                                        std::to_string(e[1] >> 4) + " kind " + std::to_string(e[1] & 15) + " when rank " + std::to_string(e[3]) +
+                                        " sent exchange " + std::to_string(e[2] >> 4) + " kind " + std::to_string(e[2] & 15) +
+                                        "); labels not returned");
+            }
+        if (h->fc_host[kSlotPackErr] != 0)
+            return fail(CHB_ESTATE, "internal error: the persistent member pack ran out of rows; labels not returned");
+        if (h->fused && h->short_cnt.p && h->fc_host[kSlotShortCnt] != 0) {
+            h->short_seen = h->fc_host[kSlotShortCnt];
+            return fail(CHB_ESTATE, "internal error: " + std::to_string(h->fc_host[kSlotShortCnt]) + " (position, bin) shortlists of this sweep came "
+                        "out short of min(num_neighbors, bin size) candidates or held a wild index; labels not returned");
+        }
+        // (one pass: change count, label count and the caller's int64 copy -- the last sweep's is what stays)
+        const int *pb = h->pin_b.p;
+        const int *pv = prev.data();
+        *diff = 0;
+        labelled = 0;
+        for (int64_t i = 0; i < N; ++i) {
+            const int v = pb[i];
+            *diff += pv[i] != v;
+            labelled += v >= 0;
+            labels_out[i] = v;
+        }
+        return CHB_OK;
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -1574,466 +2142,50 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
                        int64_t n_move, int m, int max_iter, int batch, int64_t *labels_out,
                        int *iters_run, int64_t *changed_per_iter, double *min_dist_out, double *margin_out)
 {
-    if (!h || !initial_bins || !labels_out) return fail(CHB_EINVAL, "null argument");
-    if (margin_out && !min_dist_out) return fail(CHB_EINVAL, "margin_out needs min_dist_out");
-    if (margin_out && h->world > 1) return fail(CHB_EUNSUPPORTED, "margin report is single-GPU");
-    h->want_margin = margin_out != nullptr;
-    struct MarginOff { chb_ctx *h; ~MarginOff() { h->want_margin = false; } } margin_off{h};
-    if (n_move > 0 && !perms) return fail(CHB_EINVAL, "perms is null");
-    if (max_iter < 0 || n_move < 0 || n_move > h->N) return fail(CHB_EINVAL, "bad n_move/max_iter");
-    HIPCHK(hipSetDevice(h->dev));
-    if (h->world > 1 && !h->comm && !h->hook) return fail(CHB_ESTATE, "world > 1 but chb_comm_init was not called");
-    if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
-    // every permutation entry is range-checked BEFORE anything runs (a min / max pass the compiler vectorises), so a
-    // bad entry in a late sweep cannot surface after earlier sweeps have already run; duplicates inside a sweep
-    // are rejected while that sweep is converted for its upload (bitmap), and any error return closes the fit
-    {
-        int64_t lo = 0, hi = 0;
-        const int64_t tot = (int64_t)max_iter * n_move;
-        for (int64_t i = 0; i < tot; ++i) { lo = std::min(lo, perms[i]); hi = std::max(hi, perms[i]); }
-        if (lo < 0 || hi >= h->N) return fail(CHB_EINVAL, "perm entry out of range");
-    }
-    int rc = fit_begin_impl(h, B, initial_bins, m, /*sync=*/false);
+    int rc = fit_check_args(h, initial_bins, perms, n_move, max_iter, labels_out, min_dist_out, margin_out);
+    if (rc) return rc;
+    rc = fit_begin_impl(h, B, initial_bins, m, /*sync=*/false);
     if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }   // (an upload from pin_a may be in flight: the next call rewrites it)
     h->stepwise = false;
-    struct FitCloser {   // an error return must not leave an open fit / batch behind
-        chb_ctx *h; bool ok = false;
-        ~FitCloser() { if (!ok) { (void)hipStreamSynchronize(h->stream); h->fit_open = false; h->batch_open = false; } }
-    } fit_closer{h};
-    const int64_t N = h->N;
-    h->pp_fit = true; h->stats_pp_batches = 0; h->stats_pp_builds = 0;
-    struct PackOff {
-        chb_ctx *h;
-        ~PackOff() { h->pp_fit = false; h->pp_valid = false; h->pool_fit = false; h->pool_valid = false; h->qord_cur = nullptr; h->home_cur = nullptr; }
-    } pack_off{h};
+    FitScope scope(h, margin_out != nullptr);
+    h->stats_pp_batches = 0; h->stats_pp_builds = 0;
     // threshold pools: built from the initial labels (the CSR of the fit's start is still in place), unless an earlier fit
-    // over the same samples, bins and neighbour count found that they do not pay (overlapping bins: long shortlists)
-    h->pool_fit = true; h->stats_pool_batches = 0;
+    // over the same samples, bins and neighbour count found that they do not pay (overlapping bins: long shortlists; or tile
+    // skipping that never loads 30 % of the tiles)
+    h->stats_pool_batches = 0;
     h->pool_state = (h->pool_off_key == skip_key(h)) ? -1 : 0;
     h->pool_batches = 0; h->pool_cand = 0; h->pool_pairs = 0;
     if (h->pool_state >= 0) { rc = pool_build(h); if (rc) return rc; }
-    std::vector<uint64_t> seen_bits;
-    // default batch: 8192 positions on one GPU, growing with sqrt(world): the batch-member
-    // (update) work per rank is ~K^2/world, the per-rank grids ~K/world.  Twice that from 300k contigs to move: every
-    // batch rebuilds the CSR and the padded pack of ALL labelled contigs (cost ~ N per batch, ~ N^2 / K per sweep), while a
-    // batch is a smaller share of the sweep and collides with itself no more often (measured: 115 against 124 ms per sweep
-    // at 500k x 140 x 128, 517 against 538 at 1M x 146 x 200; 100k contigs are best served by 8192)
-    // (round 5, with the pools' cheaper shortlist launches: four times from 750k contigs -- 1M x 146 x 200: 342 against 361 ms per
-    //  sweep; 500k x 140 x 128 stays best at twice: 105.5 against 108.5)
-    int Kmax = batch > 0 ? batch : 8192 * std::max(1, (int)std::lround(std::sqrt((double)h->world))) *
-                                       ((n_move >= 750000 && h->world == 1) ? 4 : (n_move >= 300000 ? 2 : 1));   // (sharded: as before)
-    if (m > kMaxM && batch <= 0) Kmax = std::min(Kmax, 512);   // the plain kernels: one wavefront per (contig, bin)
-    if (Kmax > n_move) Kmax = (int)std::max<int64_t>(n_move, 1);
+    const int Kmax = fit_default_batch(h, n_move, m, batch);
     h->last_batch = Kmax;
     rc = ensure_batch_buffers(h, Kmax);
     if (rc) return rc;
-    hipStream_t s = h->stream;
     memset(h->stats, 0, sizeof(h->stats));
     h->stats_seg_batches = 0;
     h->stats_lookahead = 0; h->stats_lookahead_failed = 0;
 
-    // ---- more than one rank: agree on the fit before its first collective (fit_agree above)
-    const bool xchg_fit = (h->comm != nullptr || h->hook != nullptr) && (h->world > 1 || h->sw.force_gather);
-    struct SwitchRestore {   // (the agreed switches hold for this fit only)
-        chb_ctx *h; bool skip, pack, spec;
-        ~SwitchRestore() { h->sw.allow_skip = skip; h->sw.pp_allowed = pack; h->sw.speculate = spec; }
-    } switch_restore{h, h->sw.allow_skip, h->sw.pp_allowed, h->sw.speculate};
-    h->xseq = 0;
-    if (xchg_fit) {
-        FitAgree fa{};
-        const uint64_t hp = hash_i64(perms, (int64_t)max_iter * n_move), hi_ = hash_i64(initial_bins, h->N);
-        const int eq[FitAgree::kEq] = {0x43480005, (int)B, m, (int)(n_move & 0x7fffffff), max_iter, Kmax, (int)(h->N & 0x7fffffff),
-                                       h->D, h->metric, h->fused ? 1 : 0, h->pf_fit ? 1 : 0, min_dist_out ? 1 : 0,
-                                       (int)(hp & 0x7fffffff), (int)((hp >> 32) & 0x7fffffff), (int)(hi_ & 0x7fffffff),
-                                       (int)((hi_ >> 32) & 0x7fffffff)};
-        memcpy(fa.v, eq, sizeof(eq));
-        fa.v[16] = h->skip_state; fa.v[17] = h->sw.speculate ? 1 : 0; fa.v[18] = h->sw.allow_skip ? 1 : 0; fa.v[19] = h->sw.pp_allowed ? 1 : 0;
-        fa.v[20] = h->pool_valid ? h->pool_state : -1;
-        rc = fit_agree(h, &fa);
-        if (rc) return rc;
-        h->skip_state = fa.v[16]; h->sw.speculate = fa.v[17] != 0; h->sw.allow_skip = fa.v[18] != 0; h->sw.pp_allowed = fa.v[19] != 0;
-        if (fa.v[20] < 0) { h->pool_state = -1; h->pool_valid = false; }
-    }
-#ifdef CHB_DEV_KNOBS
-    // developer builds, tests of the exchange schedule (tests/test_gpu_world2.py): CHB_DEV_HOOK_SPEC=1 runs the look-ahead over
-    // the host-staged hook (no gain, but the RCCL path's ORDER of exchanges); CHB_DEV_SKIP_STATS=<skipped>,<seen>,<unloaded>
-    // replaces this rank's tile-skipping statistics of every batch; CHB_DEV_LOCAL_VERDICT=1: each rank decides from its OWN ones
-    const bool dev_hook_spec = h->dk.hook_spec, dev_local_verdict = h->dk.local_verdict;
-    // CHB_DEV_ALL_DIST=<file> (tests/test_gpu_bin_distances.py; read per fit): with min_dist_out on one GPU, every hull distance
-    // of each movable contig's last visit -- row perm[t0 + i] of an N x B float64 array (NaN rows for contigs never visited),
-    // written raw to <file> when the fit succeeds.  (min_dist_out keeps the look-ahead off: nothing overwrites a batch's dist
-    // before it is copied.)
-    const char *dev_all_path = (min_dist_out && !xchg_fit) ? getenv("CHB_DEV_ALL_DIST") : nullptr;
-    std::vector<double> dev_all(dev_all_path ? (size_t)N * (size_t)h->B : 0, NAN);
-#else
-    const bool dev_hook_spec = false, dev_local_verdict = false;
-#endif
-
-    // (fit_begin_impl left the converted initial labels in pin_a; their upload and the kernels of the fit's start are
-    //  still running -- nothing below touches pin_a again before the sweep's final synchronisation)
-    std::vector<int> prev(h->pin_a.p, h->pin_a.p + N);
-    std::vector<double> mind_host, mind2_host;
-    if (min_dist_out) {
-        for (int64_t i = 0; i < N; ++i) min_dist_out[i] = NAN;
-        mind_host.resize((size_t)Kmax);
-    }
-    if (margin_out) {
-        for (int64_t i = 0; i < N; ++i) margin_out[i] = NAN;
-        mind2_host.resize((size_t)Kmax);
-    }
-    int64_t assigned0 = 0;
-    for (int64_t i = 0; i < N; ++i) assigned0 += prev[(size_t)i] >= 0;
-    int64_t labelled = assigned0;
-
-    int it = 0;
+    FitRun run(h, perms, n_move, max_iter, Kmax, labels_out, min_dist_out, margin_out);
+    rc = run.fit_agree_switches(initial_bins);
+    if (rc) return rc;
+    run.begin_outputs();
     bool wrote_out = false;
-    bool sweep_has_labelled = true;
-    for (; it < max_iter; ++it) {
-        const int64_t *perm = perms + (int64_t)it * n_move;
-        HIPCHK(h->perm.ensure((size_t)std::max<int64_t>(n_move, 1)));
-        HIPCHK(h->pin_c.ensure((size_t)std::max<int64_t>(n_move, 1)));
-        if (n_move) {
-            // (pin_c, the permutations' own staging buffer: the previous sweep's upload from it completed before that
-            //  sweep's final synchronisation, and the first sweep's conversion overlaps the kernels of the fit's start)
-            seen_bits.assign((size_t)(N + 63) / 64, 0);
-            uint64_t dup = 0;
-            int any_lab = 0;   // does this sweep visit a sample that carries a label?  (sweep 1 normally does not)
-            for (int64_t i = 0; i < n_move; ++i) {
-                const int64_t v = perm[i];          // (in range: checked up front)
-                uint64_t &wd = seen_bits[(size_t)(v >> 6)];
-                const uint64_t bit = 1ull << (v & 63);
-                dup |= wd & bit;
-                wd |= bit;
-                h->pin_c.p[i] = (int)v;
-                any_lab |= prev[(size_t)v] >= 0;
-            }
-            sweep_has_labelled = any_lab != 0;
-            if (dup) return fail(CHB_EINVAL, "a sweep's permutation lists a sample twice");
-            HIPCHK(hipMemcpyAsync(h->perm.p, h->pin_c.p, sizeof(int) * n_move, hipMemcpyHostToDevice, s));
-        }
-        // ---- the batches of this sweep.  A batch = start (selection against the members outside it), a
-        // label guess, then rounds until the first changed position is past its end.  On one GPU the
-        // NEXT batch is enqueued while the first round's verdict is still on its way to the host: its
-        // kernels (and this batch's commit) carry a gate on that verdict and return at once if the round
-        // did not converge, in which case the remaining rounds run and the next batch is enqueued again.
-        // The stream never drains while rounds converge at once -- the common case after sweep 1's start;
-        // a failed guess switches the look-ahead off until a batch converges in one round again.
-        const int world = h->world;
-        const bool xchg = (h->comm != nullptr || h->hook != nullptr) && (world > 1 || h->sw.force_gather);
-        // (look-ahead under an exchange: the RCCL all-gather sits on the context's stream, so the first-changed position of
-        //  a round is computed on the device right behind it and feeds the same gate as on one GPU; every rank sees the same
-        //  labels, hence the same verdict, and the all-gathers of a gated-off batch move identical bytes between the ranks'
-        //  identical buffers.  The hook transport needs the host between rounds anyway.)
-        const bool can_spec = h->sw.speculate && h->fused && (!xchg || (h->hook == nullptr && h->comm != nullptr) || dev_hook_spec) &&
-                              min_dist_out == nullptr;
-        // the tag of the fit's next exchange (kind 1: a batch's label guess, 2: a round's labels)
-        auto next_tag = [&](int kind) { const int t = ((h->xseq & 0x7ffffff) << 4) | kind; h->xseq += 1; return t; };
-        struct Geom { int64_t t0; int K, q_lo, q_hi, C; };
-        auto geom_at = [&](int64_t t0) {
-            // sweep 1 starts from few labelled members: do not let a batch outnumber them by much
-            // (measured: a batch of up to 1.5x the labelled members costs no extra rounds and saves a batch)
-            int64_t members = (it == 0) ? (assigned0 + t0) * 3 / 2 : N;
-            int K = (int)std::min<int64_t>(Kmax, n_move - t0);
-            if (members < K) K = (int)std::max<int64_t>(std::min<int64_t>(64, n_move - t0), members);
-            K = std::min(K, Kmax);   // (the floor of 64 above must not exceed a caller's smaller batch: buffers hold Kmax)
-            // multi-GPU: rank r evaluates positions [r*C, (r+1)*C) of the batch; the label slices
-            // are exchanged with one in-place RCCL all-gather per round (KB-sized)
-            const int C = (K + world - 1) / world;
-            const int q_lo = std::min(K, h->rank * C);
-            return Geom{t0, K, q_lo, std::min(K, q_lo + C), C};
-        };
-        // the seating order of every batch of this sweep (tile skipping / threshold pools), in one launch: the batches are a
-        // function of the sweep alone.  (Not for sweeps of thousands of tiny batches: those order theirs one by one.)
-        h->qord_cur = nullptr; h->home_cur = nullptr;
-        std::vector<int64_t> batch_t0;
-        if (h->pf_fit && h->fused && h->ckey.p != nullptr && n_move > 0 && (h->pool_valid || (h->sw.allow_skip && h->skip_state >= 0))) {
-            std::vector<int4> geo;
-            for (int64_t t = 0; t < n_move && geo.size() <= 4096;) {
-                const Geom g = geom_at(t);
-                geo.push_back(make_int4((int)g.t0, g.q_lo, g.q_hi, g.K));
-                batch_t0.push_back(t);
-                t += g.K;
-            }
-            if (geo.size() <= 4096) {
-                HIPCHK(h->geo_all.ensure(geo.size()));
-                HIPCHK(h->qord_all.ensure((size_t)n_move));
-                HIPCHK(h->home_all.ensure(geo.size() * (size_t)h->B));
-                // (pinned staging: the previous sweep's upload from it completed before that sweep's final synchronisation)
-                HIPCHK(h->pin_geo.ensure(geo.size()));
-                memcpy(h->pin_geo.p, geo.data(), sizeof(int4) * geo.size());
-                HIPCHK(hipMemcpyAsync(h->geo_all.p, h->pin_geo.p, sizeof(int4) * geo.size(), hipMemcpyHostToDevice, s));
-                Timed t(h, "bucket", (double)n_move);
-                launch_query_order_sweep(h->ckey.p, h->perm.p, h->geo_all.p, (int)geo.size(), h->B, h->qord_all.p, h->home_all.p, s);
-            } else {
-                batch_t0.clear();
-            }
-        }
-        // after a round's kernels: (multi-GPU: exchange) + first-changed position on its way to the host
-        auto finish_round = [&](const Geom &g, int active, int slot) -> int {
-            if (xchg) {
-                // this rank's frame {tag, statistics of the batch's base shortlist launch and pack, label slice} -> all-gather
-                // -> every rank's labels into lab_new / lab_prev, first changed position, statistics summed over the ranks
-                // (gated kernels, not memcpys: inside a look-ahead window they must not run; single rank without exchange:
-                // the argmin kernel has already written lab_prev).  What comes home in the verdict slot is then the SAME on
-                // every rank -- first change, bin sizes (functions of the replicated labels), skip statistics, arena mark --
-                // and with it every decision of this loop, in particular whether the next batch is enqueued ahead.
-                const int tag = next_tag(2);
-                const bool first = active == 0;
-#ifdef CHB_DEV_KNOBS
-                if (first && h->dk.skip_stats_on) for (int k = 0; k < 3; ++k) launch_fill_i32(h->fc_cur + kSlotSkipped + k, h->dk.skip_stats[k], 1, s);
-#endif
-                launch_xchg_pack(h->xg.p, h->rank, g.C, h->lab_new.p, tag, h->fc_cur, first, first && h->pp_batch, true, g.K, s);
-                { const int r_ = exchange_all_gather(h, h->xg.p, (size_t)(g.C + kXchgHdr), sizeof(int), ncclInt32); if (r_) return r_; }
-                launch_xchg_unpack(h->xg.p, world, g.C, g.K, tag, h->lab_new.p, h->lab_prev.p, active, h->fc_cur,
-                                   first && !dev_local_verdict, h->xerr.p, s);
-            }
-            HIPCHK(hipMemcpyAsync(h->fc_host + kSlotInts * slot, h->fc_cur, kSlotHome * sizeof(int), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipEventRecord(h->fc_event[slot], s));
-            return CHB_OK;
-        };
-        auto wait_round = [&](const Geom &g, int active, int slot, int *f) -> int {
-            HIPCHK(hipEventSynchronize(h->fc_event[slot]));
-            const int *v = h->fc_host + kSlotInts * slot;   // (the verdict as it came home: SlotWord)
-            *f = v[kSlotFirstChange];
-            // (bin sizes of that batch, for the segment decision of the batches still to be enqueued; and what the tile
-            //  skipping of its shortlist launch achieved: a fit whose first batches skip next to nothing turns it off)
-            h->hint_max_tiles = v[kSlotMaxTiles]; h->hint_total_tiles = v[kSlotTotalTiles];
-            // (the persistent pack's arena: rows handed out so far, as of that batch's start)
-            {
-                int64_t mark_at = h->pp_mark;
-#ifdef CHB_DEV_KNOBS   // CHB_PACK_REBUILD_AT=<rows>: rebuild (compact) the pack from that fill mark on -- tests of the rebuild path
-                if (h->dk.pack_rebuild_at >= 0) mark_at = h->dk.pack_rebuild_at;
-#endif
-                if (h->pp_valid && v[kSlotMark] > mark_at) h->pp_rebuild = true;
-            }
-            // (the slot's statistics are written by the batch's one base shortlist launch: counted with the batch's first
-            //  round only -- later rounds of the same batch bring the same three numbers home again)
-            if (active == 0 && v[kSlotSeen] > 0) {
-                h->skip_skipped += v[kSlotSkipped]; h->skip_seen += v[kSlotSeen]; h->skip_unloaded += v[kSlotUnloaded];
-                if (h->skip_state == 0 && ++h->skip_batches >= 3)
-                {
-                    // (it pays from a few per cent of the wave-tiles)
-                    h->skip_state = ((h->skip_skipped + h->skip_unloaded) * 50 >= h->skip_seen + h->skip_unloaded) ? 1 : -1;
-                    if (h->skip_state < 0) h->skip_off_key = skip_key(h);
-                    // Where tile skipping never loads a third of a bin's tiles (500k x 140 x 128: 45 %), the threshold sweep is
-                    // cheap already and the pools' price -- the looser thresholds of the contigs far out in their bins: long
-                    // shortlists, retries, label guesses that fail -- is higher than what they save (113 against 105 ms per
-                    // sweep there; 1M x 146 x 200, 19 % never loaded: 366 against 460): such a fit drops them
-                    // (checked per batch below: sweep 1's first batches stream bins of a few tiles, nothing to go by)
-                }
-            }
-            if (active == 0 && h->skip_state == 1 && h->pool_state >= 0 && v[kSlotSeen] > 0) {
-                const long long un = v[kSlotUnloaded], sn = v[kSlotSeen];
-                if (un * 10 > 3 * (sn + un)) { h->pool_state = -1; h->pool_off_key = skip_key(h); }
-            }
-            // (threshold pools: candidates per pair of that batch's base shortlist launch, as sampled; a fit whose first
-            //  batches admit far more than the exact threshold would -- overlapping bins -- goes back to the two sweeps)
-            //  -- checked for EVERY batch: the pools of sweep 1's first batches hold whole bins and say nothing yet)
-            if (active == 0 && h->pool_state >= 0 && v[kSlotPoolPairs] > 0) {
-                const long long pc = v[kSlotPoolCand], pp = v[kSlotPoolPairs];
-                h->pool_cand += pc; h->pool_pairs += pp;
-                if (++h->pool_batches >= 3 && h->pool_state == 0) h->pool_state = 1;
-                // (the benchmark configurations admit m + 0.1 .. m + 0.4 per pair; from m + 3 on the loose thresholds cost the
-                //  update stage and the hull kernel more than the threshold sweep did)
-                if (pc > (long long)(h->m + 3) * pp) { h->pool_state = -1; h->pool_off_key = skip_key(h); }
-            }
-            (void)active; (void)g;
-            return CHB_OK;
-        };
-        // batch start + guess + round 0, nothing read back
-        auto open_batch = [&](const Geom &g, int slot) -> int {
-            h->bq_cur = h->perm.p + g.t0;   // the batch's sample indices: a window of the sweep's permutation
-            h->fc_cur = h->first_change.p + kSlotInts * slot;
-            if (!batch_t0.empty()) {
-                const size_t bi = (size_t)(std::lower_bound(batch_t0.begin(), batch_t0.end(), g.t0) - batch_t0.begin());
-                h->qord_cur = h->qord_all.p + g.t0 + g.q_lo; h->home_cur = h->home_all.p + bi * (size_t)h->B;
-            }
-            h->hint_base_members = (double)((it == 0) ? assigned0 + g.t0 : labelled - g.K);
-            h->hint_batch_entries = (double)((it == 0) ? g.K : 2 * g.K);
-            h->argmin_in_place = !xchg;
-            int r = batch_begin_dev(h, g.K, g.q_lo, g.q_hi, false);
-            if (r) return r;
-            h->pool_holes = sweep_has_labelled;   // (an all-unlabelled batch leaves no holes for its commit to look for)
-            // starting labels of the rounds: last sweep's label, or for still-unlabelled contigs
-            // (sweep 1) the bin whose m-th nearest outside member is closest
-            if (h->fused && !h->lists_valid) launch_guess_near(h->tau.p, h->lab_old.p, g.q_lo, g.q_hi, h->B, h->Kcap, h->lab_prev.p, s);
-            else launch_guess(h->l0d.p, h->l0c.p, h->lab_old.p, g.q_lo, g.q_hi, h->B, h->m, h->Kcap, h->lab_prev.p, s);
-            if (xchg) {
-                const int tag = next_tag(1);
-                launch_xchg_pack(h->xg.p, h->rank, g.C, h->lab_prev.p, tag, h->fc_cur, false, false, false, g.K, s);
-                { const int r_ = exchange_all_gather(h, h->xg.p, (size_t)(g.C + kXchgHdr), sizeof(int), ncclInt32); if (r_) return r_; }
-                launch_xchg_unpack(h->xg.p, world, g.C, g.K, tag, h->lab_prev.p, nullptr, 0, h->fc_cur, false, h->xerr.p, s);
-            }
-            r = batch_round_dev(h, 0);
-            if (r) return r;
-            return finish_round(g, 0, slot);
-        };
-        struct Snap {   // host-side batch state (the device side of a gated-off batch never changed)
-            int K, q_lo, q_hi, round_in_batch; bool lists_valid, batch_open, pp_batch, pp_valid, pool_valid; int *bq_cur, *fc_cur;
-            double hb, he; int64_t st[4]; size_t n_pending;
-        };
-        auto save = [&]() {
-            Snap v{h->K, h->q_lo, h->q_hi, h->round_in_batch, h->lists_valid, h->batch_open, h->pp_batch, h->pp_valid, h->pool_valid, h->bq_cur, h->fc_cur,
-                   h->hint_base_members, h->hint_batch_entries, {0, 0, 0, 0}, h->pending.size()};
-            memcpy(v.st, h->stats, sizeof(v.st));
-            return v;
-        };
-        auto restore = [&](const Snap &v) {
-            h->K = v.K; h->q_lo = v.q_lo; h->q_hi = v.q_hi; h->round_in_batch = v.round_in_batch;
-            h->lists_valid = v.lists_valid; h->batch_open = v.batch_open; h->bq_cur = v.bq_cur; h->fc_cur = v.fc_cur;
-            h->pp_batch = v.pp_batch; h->pp_valid = v.pp_valid; h->pool_valid = v.pool_valid;
-            h->hint_base_members = v.hb; h->hint_batch_entries = v.he;
-            memcpy(h->stats, v.st, sizeof(v.st));
-            // the launches recorded inside the window were gated off (they returned at once): they are neither
-            // launches nor work of the profile
-            for (size_t i = v.n_pending; i < h->pending.size(); ++i) {
-                (void)hipEventDestroy(h->pending[i].a);
-                (void)hipEventDestroy(h->pending[i].b);
-            }
-            if (h->pending.size() > v.n_pending) h->pending.resize(v.n_pending);
-        };
-        struct GateReset { ~GateReset() { g_gate = Gate{}; } } gate_reset;   // (error returns inside the window)
-
-        int64_t t0 = 0;
-        bool inflight = false, spec_ok = can_spec;
-        int slot = 0;
-        while (t0 < n_move) {
-            const Geom g = geom_at(t0);
-            const int K = g.K;
-            if (!inflight) { rc = open_batch(g, slot); if (rc) return rc; }
-            const int64_t t1 = t0 + K;
-            // (a batch start that has to build or rebuild the persistent pack stays outside the look-ahead window)
-            const bool skip_would = h->sw.allow_skip && h->nsh > 1 && h->skip_state >= 0 && h->ckey.p != nullptr;
-            const bool pack_sync = h->pp_fit && h->sw.pp_allowed && h->fused && h->cand.p && !skip_would &&
-                                   (!h->pp_valid || h->pp_rebuild);
-            const bool spec = spec_ok && t1 < n_move && !pack_sync;
-            Snap snap{};
-            if (spec) {
-                snap = save();
-                g_gate = Gate{h->first_change.p + kSlotInts * slot, K};   // "this batch's round 0 changed nothing"
-                rc = batch_commit_dev(h, h->lab_prev.p);
-                if (rc) return rc;
-                rc = open_batch(geom_at(t1), slot ^ 1);
-                if (rc) return rc;
-                g_gate = Gate{};
-            }
-            int f = K;
-            rc = wait_round(g, 0, slot, &f);
-            if (rc) return rc;
-            if (f < K) {
-                // the guess was off at position f: everything enqueued behind the gate has skipped itself
-                if (spec) { restore(snap); spec_ok = false; h->stats_lookahead_failed += 1; }
-                int active = f + 1;
-                while (active < K) {
-                    rc = batch_round_dev(h, active);
-                    if (rc) return rc;
-                    rc = finish_round(g, active, slot);
-                    if (rc) return rc;
-                    rc = wait_round(g, active, slot, &f);
-                    if (rc) return rc;
-                    if (f >= K) break;
-                    active = f + 1;
-                }
-                inflight = false;
-            } else {
-                inflight = spec;   // the next batch's first round is already running
-                if (spec) h->stats_lookahead += 1;
-                spec_ok = can_spec;
-            }
-            if (min_dist_out && xchg)
-                { const int r_ = exchange_all_gather(h, h->mind.p, (size_t)g.C, sizeof(double), ncclFloat64); if (r_) return r_; }
-            if (min_dist_out) {
-                HIPCHK(hipMemcpyAsync(mind_host.data(), h->mind.p, sizeof(double) * K, hipMemcpyDeviceToHost, s));
-                if (margin_out)
-                    HIPCHK(hipMemcpyAsync(mind2_host.data(), h->mind2.p, sizeof(double) * K, hipMemcpyDeviceToHost, s));
-                HIPCHK(hipStreamSynchronize(s));
-                for (int i = 0; i < K; ++i) min_dist_out[perm[t0 + i]] = mind_host[(size_t)i];
-                // (runner-up +inf: no other bin has a member -- +inf also when no bin has one, not inf - inf)
-                if (margin_out)
-                    for (int i = 0; i < K; ++i) {
-                        const double w = mind_host[(size_t)i], r = mind2_host[(size_t)i];
-                        margin_out[perm[t0 + i]] = r == INFINITY ? INFINITY : r - w;
-                    }
-#ifdef CHB_DEV_KNOBS
-                if (dev_all_path) {   // (the batch's K x B distances, each row to its contig's)
-                    std::vector<double> rows((size_t)K * h->B);
-                    HIPCHK(hipMemcpy(rows.data(), h->dist.p, sizeof(double) * rows.size(), hipMemcpyDeviceToHost));
-                    for (int i = 0; i < K; ++i)
-                        memcpy(dev_all.data() + (size_t)perm[t0 + i] * h->B, rows.data() + (size_t)i * h->B, sizeof(double) * h->B);
-                }
-#endif
-            }
-            if (!inflight) {   // (otherwise the commit went out with the look-ahead)
-                rc = batch_commit_dev(h, h->lab_prev.p);
-                if (rc) return rc;
-            } else {
-                slot ^= 1;
-            }
-            h->stats[0] += 1;
-            t0 = t1;
-        }
-        h->stats[3] += n_move * (int64_t)h->B;
-        HIPCHK(h->pin_b.ensure((size_t)N));
-        HIPCHK(hipMemcpyAsync(h->pin_b.p, h->labels.p, sizeof(int) * N, hipMemcpyDeviceToHost, s));
-        if (h->fused && h->short_cnt.p)   // (spare words of the first verdict slot)
-            HIPCHK(hipMemcpyAsync(h->fc_host + kSlotShortCnt, h->short_cnt.p, sizeof(int), hipMemcpyDeviceToHost, s));
-        h->fc_host[kSlotPackErr] = 0;
-        if (h->pp_ctl.p)
-            HIPCHK(hipMemcpyAsync(h->fc_host + kSlotPackErr, h->pp_ctl.p + 2, sizeof(int), hipMemcpyDeviceToHost, s));
-        std::vector<int> xend;
-        if (xchg) {
-            // every rank's "a rank was out of step" record: all ranks then leave the sweep with the same status
-            xend.assign((size_t)4 * world, 0);
-            HIPCHK(hipMemcpyAsync(h->agree.p + 4 * h->rank, h->xerr.p, 4 * sizeof(int), hipMemcpyDeviceToDevice, s));
-            { const int r_ = exchange_all_gather(h, h->agree.p, 4, sizeof(int), ncclInt32); if (r_) return r_; }
-            HIPCHK(hipMemcpyAsync(xend.data(), h->agree.p, sizeof(int) * xend.size(), hipMemcpyDeviceToHost, s));
-        }
-        HIPCHK(hipStreamSynchronize(s));
-        for (int r = 0; r < (int)xend.size() / 4; ++r)
-            if (xend[(size_t)4 * r] != 0) {
-                HIPCHK(hipMemsetAsync(h->xerr.p, 0, 4 * sizeof(int), s));
-                const int *e = xend.data() + 4 * r;
-                return fail(CHB_ESTATE, "internal error: the ranks' exchanges fell out of step (rank " + std::to_string(r) + " was at exchange " +
-                                        std::to_string(e[1] >> 4) + " kind " + std::to_string(e[1] & 15) + " when rank " + std::to_string(e[3]) +
-                                        " sent exchange " + std::to_string(e[2] >> 4) + " kind " + std::to_string(e[2] & 15) +
-                                        "); labels not returned");
-            }
-        if (h->fc_host[kSlotPackErr] != 0)
-            return fail(CHB_ESTATE, "internal error: the persistent member pack ran out of rows; labels not returned");
-        if (h->fused && h->short_cnt.p && h->fc_host[kSlotShortCnt] != 0) {
-            h->short_seen = h->fc_host[kSlotShortCnt];
-            return fail(CHB_ESTATE, "internal error: " + std::to_string(h->fc_host[kSlotShortCnt]) + " (position, bin) shortlists of this sweep came "
-                        "out short of min(num_neighbors, bin size) candidates or held a wild index; labels not returned");
-        }
-        int64_t diff = 0;  // algorithm.py:63
-        labelled = 0;
-        {   // (one pass: change count, label count and the caller's int64 copy -- the last sweep's is what stays)
-            const int *pb = h->pin_b.p;
-            const int *pv = prev.data();
-            for (int64_t i = 0; i < N; ++i) {
-                const int v = pb[i];
-                diff += pv[i] != v;
-                labelled += v >= 0;
-                labels_out[i] = v;
-            }
-        }
+    for (; run.it < max_iter; ++run.it) {
+        int64_t diff = 0;
+        rc = run.run_sweep();
+        if (rc) return rc;
+        rc = run.end_sweep(&diff);
+        if (rc) return rc;
         wrote_out = true;
-        if (changed_per_iter) changed_per_iter[it] = diff;
-        if (diff == 0) { ++it; break; }  // algorithm.py:64-66
-        if (it + 1 < max_iter) prev.assign(h->pin_b.p, h->pin_b.p + N);   // algorithm.py:71-72
+        if (changed_per_iter) changed_per_iter[run.it] = diff;
+        if (diff == 0) { ++run.it; break; }  // algorithm.py:64-66
+        if (run.it + 1 < max_iter) run.prev.assign(h->pin_b.p, h->pin_b.p + h->N);   // algorithm.py:71-72
     }
     if (!wrote_out)
-        for (int64_t i = 0; i < N; ++i) labels_out[i] = prev[(size_t)i];
-    if (iters_run) *iters_run = it;
-#ifdef CHB_DEV_KNOBS
-    if (dev_all_path) {
-        FILE *fp = fopen(dev_all_path, "wb");
-        const bool ok = fp && fwrite(dev_all.data(), sizeof(double), dev_all.size(), fp) == dev_all.size();
-        if (fp) fclose(fp);
-        if (!ok) return fail(CHB_EINVAL, std::string("CHB_DEV_ALL_DIST: cannot write ") + dev_all_path);
-    }
-#endif
-    fit_closer.ok = true;
+        for (int64_t i = 0; i < h->N; ++i) labels_out[i] = run.prev[(size_t)i];
+    if (iters_run) *iters_run = run.it;
+    rc = run.dev.all_write();
+    if (rc) return rc;
+    scope.ok = true;
     return CHB_OK;
 }
 

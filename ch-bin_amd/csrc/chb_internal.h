@@ -7,7 +7,7 @@
 
 namespace chb {
 
-// Speculative continuation (chb_api.hip: chb_fit_cluster): the kernels of the next batch are enqueued
+// Speculative continuation (chb_api.hip: FitRun::run_batch): the kernels of the next batch are enqueued
 // before the host knows whether the current batch's round has converged; they carry a gate and return at
 // once unless *flag >= need (flag = the current batch's first-changed position, need = its size).
 struct Gate {
@@ -404,7 +404,8 @@ void launch_guess(const double *list_d, const int *list_cnt, const int *lab_old,
 void launch_guess_near(const float *tau, const int *lab_old, int p0, int p1, int B, int Kcap, int *lab_prev,
                        hipStream_t s);
 // ---- a batch's verdict slot (chb_api.hip: chb_ctx::fc_cur on the device, fc_host in pinned memory): kSlotInts ints, of
-// which a round's verdict brings the first kSlotHome home in one copy
+// which a round's verdict brings the first kSlotHome home in one copy (FitRun::finish_round sends it, wait_verdict hands
+// it to note_verdict, where the host's rules about tile skipping, pools and the pack's rebuild read it)
 enum SlotWord {
     kSlotFirstChange = 0,   // first changed position of the round (K: none)
     kSlotMaxTiles = 1,      // tiles of the batch's largest bin ...
@@ -422,7 +423,7 @@ enum SlotWord {
 };
 constexpr int kSlotInts = 16;
 // ---- framed exchange of the sharded loop (aux_kernels.hip): a rank's slice of a round's all-gather = kXchgHdr header
-// words (FrameWord) + the C labels of its positions
+// words (FrameWord: {tag, skipped, seen, unloaded, mark, pool candidates, pool pairs, 0}) + the C labels of its positions
 enum FrameWord {
     kFrameTag = 0,          // exchange number of the fit << 4 | kind
     kFrameSkipped = 1,      // the sender's kSlotSkipped / kSlotSeen / kSlotUnloaded, ...
