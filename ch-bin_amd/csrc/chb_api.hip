@@ -111,47 +111,32 @@ struct Pending {
     double work;
 };
 
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;
+// A buffer that frees itself: device memory (DevBuf), or pinned host staging (PinBuf; labels, permutations: asynchronous
+// copies at DMA speed instead of the driver's bounce-buffer path for pageable memory)
+template <typename T, bool kPinned>
+struct Buf {
+    T *p = nullptr; size_t cap = 0;
     hipError_t ensure(size_t n)
     {
         if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        hipError_t e = hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T));
+        release();
+        const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+        hipError_t e = kPinned ? hipHostMalloc((void **)&p, bytes, hipHostMallocDefault) : hipMalloc((void **)&p, bytes);
         if (e == hipSuccess) cap = n;
         return e;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
-};
-
-// pinned host staging (labels, permutations): asynchronous copies at DMA speed instead of the driver's
-// bounce-buffer path for pageable memory
-template <typename T>
-struct PinBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t n)
+    hipError_t ensure_zeroed(size_t n, hipStream_t s)   // (all of it zeroed on s whenever this allocated or grew it)
     {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; cap = 0;
-        hipError_t e = hipHostMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T), hipHostMallocDefault);
-        if (e == hipSuccess) cap = n;
-        return e;
+        const size_t had = cap;
+        const hipError_t e = ensure(n);
+        return (e != hipSuccess || cap == had) ? e : hipMemsetAsync(p, 0, sizeof(T) * cap, s);
     }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-    PinBuf() = default;
-    PinBuf(const PinBuf &) = delete;
-    PinBuf &operator=(const PinBuf &) = delete;
-    ~PinBuf() { release(); }
+    void release() { if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p)); p = nullptr; cap = 0; }
+    Buf() = default; Buf(const Buf &) = delete; Buf &operator=(const Buf &) = delete;
+    ~Buf() { release(); }
 };
+template <typename T> using DevBuf = Buf<T, false>;
+template <typename T> using PinBuf = Buf<T, true>;
 
 }  // namespace
 
@@ -165,16 +150,10 @@ struct PackBufs {
         hipError_t e;
         if ((e = Z.ensure((rows + 64) * Dz)) != hipSuccess) return e;   // + slack: whole 32-row tiles are read
         DevBuf<float> *f[] = {&bias, &sn, &cs, &cb};
-        for (auto *b : f)
-            if ((e = b->ensure(rows + 64)) != hipSuccess) return e;
+        for (auto *b : f) if ((e = b->ensure(rows + 64)) != hipSuccess) return e;
         if ((e = bb.ensure(4 * B)) != hipSuccess) return e;
         if ((e = tsn.ensure(rows / 32 + B + 68)) != hipSuccess) return e;   // (+ 64: the tile-skipping kernel reads 64 at a time)
         return pad_ptr.ensure(B + 1);
-    }
-    void release()
-    {
-        Z.release(); bias.release(); sn.release(); cs.release(); cb.release();
-        bb.release(); tsn.release(); pad_ptr.release();
     }
     chb::MemberPack view()
     {
@@ -278,7 +257,7 @@ struct chb_ctx {
     // threshold pools of the shortlist stage (prefilter_kernels.hip, "threshold pools"): for every (bin, home bin) the 32
     // base members of the bin nearest to the home bin's centre; built at a fit's start, maintained by every commit
     DevBuf<unsigned short> pool_Z;
-    DevBuf<int> pool_id, pool_hole, pool_ok, pool_stat;
+    DevBuf<int> pool_id, pool_hole, pool_ok;
     DevBuf<float> pool_key, pool_sn, pool_tsn;
     bool pool_fit = false;      // inside chb_fit_cluster (the stepwise entry points and chb_topm_per_bin never use pools)
     bool pool_valid = false;    // the pools on the device match the labels
@@ -475,6 +454,7 @@ int ensure_batch_buffers(chb_ctx *h, int Kcap)
 {
     const size_t B = h->B, m = h->m, K = Kcap;
     const size_t Kpad = K + (size_t)h->world;   // allgather of ceil(K/world)-sized slices
+    const size_t flag_tiles = B * ((K + kQTile - 1) / kQTile);   // (bin, query tile) flags of the shortlist stage's overflow
     HIPCHK(h->bq.ensure(K));
     HIPCHK(h->lab_old.ensure(K));
     HIPCHK(h->lab_prev.ensure(Kpad));
@@ -482,7 +462,7 @@ int ensure_batch_buffers(chb_ctx *h, int Kcap)
     HIPCHK(h->first_change.ensure(2 * kSlotInts));
     h->fc_cur = h->first_change.p;
     HIPCHK(h->xg.ensure(Kpad + (size_t)(kXchgHdr + 1) * (size_t)h->world));
-    { const size_t had = h->xerr.cap; HIPCHK(h->xerr.ensure(4)); if (!had) HIPCHK(hipMemsetAsync(h->xerr.p, 0, 4 * sizeof(int), h->stream)); }
+    HIPCHK(h->xerr.ensure_zeroed(4, h->stream));
     HIPCHK(h->mind.ensure(Kpad));
     HIPCHK(h->mind2.ensure(Kpad));
     HIPCHK(h->dist.ensure(K * B));
@@ -495,7 +475,7 @@ int ensure_batch_buffers(chb_ctx *h, int Kcap)
     HIPCHK(h->l1i.ensure(K * B * m));
     HIPCHK(h->l0c.ensure(K * B));
     HIPCHK(h->l1c.ensure(K * B));
-    { const size_t had = h->cnt.cap; HIPCHK(h->cnt.ensure(B * (size_t)kShells)); if (h->cnt.cap != had) HIPCHK(hipMemsetAsync(h->cnt.p, 0, sizeof(int) * h->cnt.cap, h->stream)); }
+    HIPCHK(h->cnt.ensure_zeroed(B * (size_t)kShells, h->stream));
     HIPCHK(h->bin_ptr.ensure(B + 1));
     HIPCHK(h->cursor.ensure(B * (size_t)kShells));
     HIPCHK(h->memb_id.ensure((size_t)h->N));
@@ -510,12 +490,12 @@ int ensure_batch_buffers(chb_ctx *h, int Kcap)
         HIPCHK(h->active.ensure(K * B));
         HIPCHK(h->n_active.ensure(1));
         HIPCHK(h->act_blk.ensure((K * B + 4095) / 4096 + 1));
-        HIPCHK(h->flags64.ensure(B * ((K + kQTile - 1) / kQTile)));
-        HIPCHK(h->flaglist.ensure(B * ((K + kQTile - 1) / kQTile)));
+        HIPCHK(h->flags64.ensure(flag_tiles));
+        HIPCHK(h->flaglist.ensure(flag_tiles));
         HIPCHK(h->nflag.ensure(1));
-        HIPCHK(h->flaglist2.ensure(B * ((K + kQTile - 1) / kQTile)));
+        HIPCHK(h->flaglist2.ensure(flag_tiles));
         HIPCHK(h->nflag2.ensure(1));
-        launch_fill_i32(h->flags64.p, 0, (int)(B * ((K + kQTile - 1) / kQTile)), h->stream);   // kept zero by its consumer
+        launch_fill_i32(h->flags64.p, 0, (int)flag_tiles, h->stream);   // kept zero by its consumer
         HIPCHK(h->overflow.ensure(1));
         HIPCHK(h->pk.ensure((size_t)h->N + 32 * B, B, (size_t)h->Dz));
         HIPCHK(h->pk2.ensure(2 * K + 32 * B, B, (size_t)h->Dz));
@@ -534,7 +514,7 @@ int ensure_batch_buffers(chb_ctx *h, int Kcap)
             }
             HIPCHK(h->slow.ensure(K * B));
             HIPCHK(h->n_slow.ensure(1));
-            { const size_t had = h->short_cnt.cap; HIPCHK(h->short_cnt.ensure(1)); if (!had) HIPCHK(hipMemsetAsync(h->short_cnt.p, 0, sizeof(int), h->stream)); }
+            HIPCHK(h->short_cnt.ensure_zeroed(1, h->stream));
             HIPCHK(h->tau.ensure(K * B));
         }
     }
@@ -665,7 +645,7 @@ int pack_state_build(chb_ctx *h)
     HIPCHK(h->pp_row.ensure((size_t)h->N));
     DevBuf<int> *pb[] = {&h->pp_start, &h->pp_cap, &h->pp_fill, &h->pp_live, &h->pp_nt};
     for (auto *b : pb) HIPCHK(b->ensure(B + 1));
-    { const size_t had = h->pp_ctl.cap; HIPCHK(h->pp_ctl.ensure(4)); if (!had) HIPCHK(hipMemsetAsync(h->pp_ctl.p, 0, 4 * sizeof(int), h->stream)); }
+    HIPCHK(h->pp_ctl.ensure_zeroed(4, h->stream));
     HIPCHK(h->pp_ovf.ensure((size_t)std::max(h->Kcap, 1)));
     HIPCHK(h->pp_dest.ensure((size_t)std::max(h->Kcap, 1)));
     // (room to grow: were all N samples labelled and spread evenly, a bin would hold N / B rows -- half as much again)
@@ -706,6 +686,7 @@ int pool_build(chb_ctx *h)
         h->pool_tsn.ensure(B * B + 64) != hipSuccess || h->pool_ok.ensure(B * B) != hipSuccess) {
         (void)hipGetLastError();   // (no room: the fit keeps the two-sweep launch)
         h->pool_Z.release(); h->pool_id.release(); h->pool_hole.release(); h->pool_key.release(); h->pool_sn.release();
+        h->pool_tsn.release(); h->pool_ok.release();
         return CHB_OK;
     }
     {
@@ -836,138 +817,185 @@ int dev_shortlist_report(chb_ctx *, const ShortlistArgs &, bool, bool, bool) { r
 int dev_shortlist_check(chb_ctx *, bool, const int *) { return CHB_OK; }
 #endif
 
-// bq already holds the K sample indices (device).  need_lists: the caller wants the exact base lists
-// L0 (chb_topm_per_bin); the fit loop of the fused path (m <= 16) works on the shortlists directly.
-int batch_begin_dev(chb_ctx *h, int K, int q_lo, int q_hi, bool need_lists)
-{
-    const bool fusedp = h->fused && !need_lists;
-    h->lists_valid = !fusedp;
-    h->K = K; h->q_lo = q_lo; h->q_hi = q_hi;
-    h->round_in_batch = 0;
-    h->round_active = 0;
-    hipStream_t s = h->stream;
-    // segmented bins: the plan is made by the CSR scan on the device, but only if the host will also enqueue the two
-    // segment launches -- which it does when the bin sizes it saw last (one or two batches old) say that a bin may
-    // have more than kSegMinTiles tiles and four times the average
+// ---- a batch start (batch_begin_dev): what it will do is decided first -- BatchPlan's constructor from the context alone,
+// settle_batch where that allocates, launches or fails -- then its launches follow as stages, in the order they are enqueued
+struct BatchPlan {
+    bool fusedp;         // the fit loop's fused path (m <= 16) works on the shortlists directly: no exact base lists
+    bool pf_base_path;   // the base members go through the shortlist stage
+    bool skip_on, pp_now = false, pool_on = false;   // tile skipping, persistent pack, threshold pools serve this batch
     SegPlan sp{};
-    const bool pf_base_path = h->pf_fit && h->cand.p;
-    // tile skipping: on until the fit's first batches have shown that it skips (next to) nothing
-    const bool skip_on = pf_base_path && h->sw.allow_skip && h->nsh > 1 && h->skip_state >= 0 && h->ckey.p != nullptr;
-    if (pf_base_path && h->seg_gflag.p) {
-        sp.nseg = h->seg_nseg.p; sp.items = h->seg_items.p; sp.gflag = h->seg_gflag.p; sp.lists = h->seg_lists.p;
-        sp.cap = 16 * h->seg_gcap; sp.gcap = h->seg_gcap;
-        const long long est = (long long)h->hint_max_tiles * 3 / 2 + 8;
-        sp.launch = h->sw.allow_segments && h->Dz <= 160 && est > kSegMinTiles && est * h->B > 3LL * std::max(1, h->hint_total_tiles);
-        if (sp.launch) {
-            HIPCHK(h->seg_lists.ensure((size_t)h->seg_gcap * 16 * (size_t)h->Kcap * (size_t)shortlist_list_len(h->m)));
-            sp.lists = h->seg_lists.p;
+    int *qord_p, *home_p;   // the queries' seats (read under skip_on / pool_on only)
+    BatchPlan(const chb_ctx *h, bool need_lists)   // (a pure function of the context: no HIP call, nothing written)
+    {
+        fusedp = h->fused && !need_lists;
+        pf_base_path = h->pf_fit && h->cand.p;
+        // tile skipping: on until the fit's first batches have shown that it skips (next to) nothing
+        skip_on = pf_base_path && h->sw.allow_skip && h->nsh > 1 && h->skip_state >= 0 && h->ckey.p != nullptr;
+        // segmented bins: the plan is made by the CSR scan on the device, but only if the host will also enqueue the two
+        // segment launches -- which it does when the bin sizes it saw last (one or two batches old) say that a bin may
+        // have more than kSegMinTiles tiles and four times the average
+        if (pf_base_path && h->seg_gflag.p) {
+            sp.nseg = h->seg_nseg.p; sp.items = h->seg_items.p; sp.gflag = h->seg_gflag.p; sp.lists = h->seg_lists.p;
+            sp.cap = 16 * h->seg_gcap; sp.gcap = h->seg_gcap;
+            const long long est = (long long)h->hint_max_tiles * 3 / 2 + 8;
+            sp.launch = h->sw.allow_segments && h->Dz <= 160 && est > kSegMinTiles && est * h->B > 3LL * std::max(1, h->hint_total_tiles);
         }
+        const bool swept = h->qord_cur != nullptr;   // (seated by the fit loop, for the whole sweep)
+        qord_p = swept ? h->qord_cur : h->qord.p; home_p = swept ? h->home_cur : h->home.p;
+    }
+};
+
+// before the launches: the segment lists' allocation, the pack's (re)build; which of pack and pools serve this batch and stay valid
+int settle_batch(chb_ctx *h, BatchPlan &p)
+{
+    if (p.sp.launch) {
+        HIPCHK(h->seg_lists.ensure((size_t)h->seg_gcap * 16 * (size_t)h->Kcap * (size_t)shortlist_list_len(h->m)));
+        p.sp.lists = h->seg_lists.p;
     }
     // the persistent base pack serves the fit loop's batches whenever the shortlist launch does not skip tiles (whose
     // shell order needs the rebuild); built / rebuilt only outside a look-ahead window
-    bool pp_now = false;
-    if (h->pp_fit && h->sw.pp_allowed && fusedp && pf_base_path && !skip_on) {
+    if (h->pp_fit && h->sw.pp_allowed && p.fusedp && p.pf_base_path && !p.skip_on) {
         if ((!h->pp_valid || h->pp_rebuild) && g_gate.flag == nullptr) { const int r_ = pack_state_build(h); if (r_) return r_; }
-        pp_now = h->pp_valid;
+        p.pp_now = h->pp_valid;
     }
-    if (!pp_now) h->pp_valid = false;   // (this batch's commit will not maintain the pack)
-    h->pp_batch = pp_now;
+    if (!p.pp_now) h->pp_valid = false;   // (this batch's commit will not maintain the pack)
+    h->pp_batch = p.pp_now;
     // threshold pools: the base shortlist launch streams a bin once where a pool tile gives the threshold
-    if (!(h->pool_fit && fusedp && pf_base_path)) h->pool_valid = false;   // (this batch will not maintain them)
-    if (h->pool_state < 0) h->pool_valid = false;                          // (turned off for this fit: no upkeep either)
-    const bool pool_on = h->pool_valid && h->pool_state >= 0;
-    if (pp_now) {
+    if (!(h->pool_fit && p.fusedp && p.pf_base_path)) h->pool_valid = false;   // (this batch will not maintain them)
+    if (h->pool_state < 0) h->pool_valid = false;                              // (turned off for this fit: no upkeep either)
+    p.pool_on = h->pool_valid && h->pool_state >= 0;
+    return CHB_OK;
+}
+
+// the batch is opened in the base members' CSR (the pack's, or rebuilt) and in the pools
+void open_batch(chb_ctx *h, const BatchPlan &p)
+{
+    const SegPlan *seg = p.sp.gflag ? &p.sp : nullptr;
+    if (p.pp_now) {
         // the batch is opened (its members' rows become holes) and tiles per bin / statistics / segment plan written:
         // one launch instead of count + scan + fill + gather
-        Timed t(h, "bucket", (double)K);
-        launch_pack_state_start(h->pack_state(), h->pk.view(), h->D, h->Dz, h->labels.p, h->inb.p, h->bq_cur, K, h->lab_old.p,
-                                h->B, sp.gflag ? &sp : nullptr, h->fc_cur + kSlotMaxTiles, h->nflag.p, s);
+        Timed t(h, "bucket", (double)h->K);
+        launch_pack_state_start(h->pack_state(), h->pk.view(), h->D, h->Dz, h->labels.p, h->inb.p, h->bq_cur, h->K, h->lab_old.p,
+                                h->B, seg, h->fc_cur + kSlotMaxTiles, h->nflag.p, h->stream);
         h->stats_pp_batches += 1;
     } else {
         // (the batch is opened -- labels remembered, members marked -- inside the CSR count's launch)
         Timed t(h, "bucket", (double)h->N);
-        launch_bucket_base(h->labels.p, h->inb.p, (int)h->N, h->B, h->cnt.p, h->bin_ptr.p,
-                           h->cursor.p, h->memb_id.p, h->pk.pad_ptr.p, h->nflag.p, s, h->bq_cur, K, h->lab_old.p,
-                           sp.gflag ? &sp : nullptr, h->fc_cur + kSlotMaxTiles, pf_base_path ? h->ms.p : nullptr,
-                           skip_on ? h->shell_inv.p : nullptr, skip_on ? h->nsh : 1);
+        launch_bucket_base(h->labels.p, h->inb.p, (int)h->N, h->B, h->cnt.p, h->bin_ptr.p, h->cursor.p, h->memb_id.p,
+                           h->pk.pad_ptr.p, h->nflag.p, h->stream, h->bq_cur, h->K, h->lab_old.p, seg, h->fc_cur + kSlotMaxTiles,
+                           p.pf_base_path ? h->ms.p : nullptr, p.skip_on ? h->shell_inv.p : nullptr, p.skip_on ? h->nsh : 1);
     }
     if (h->pool_valid) {
         // (the batch's samples are marked: their slots in the pools are holes while it is open)
-        Timed t(h, "pool", (double)K);
-        launch_pool_open(h->pool_view(), h->inb.p, h->D, h->Dz, h->B, h->nflag2.p, s);
+        Timed t(h, "pool", (double)h->K);
+        launch_pool_open(h->pool_view(), h->inb.p, h->D, h->Dz, h->B, h->nflag2.p, h->stream);
     }
     h->pool_holes = true;
+}
+
+// what the base shortlist launch reads besides the CSR: the fit's overflow counter, a rebuilt CSR's pack, the queries' seats
+void shortlist_inputs(chb_ctx *h, const BatchPlan &p)
+{
+    // (flags64 is all zero here: launch_topm_flagged clears what it serves)
+    if (!h->overflow_total_valid) { launch_fill_i32(h->overflow.p, 0, 1, h->stream); h->overflow_total_valid = true; }
+    if (!p.pp_now) {
+        // the members' shadow rows (relative to their bin's centre) gathered into padded CSR order, and the per-bin
+        // bounds: one launch
+        Timed t(h, "bucket", 0.0);
+        launch_pack_build(h->Zs.p, h->ms.p, h->D, h->Dz, h->memb_id.p, h->bin_ptr.p, h->B, (int)h->N, h->pk.view(), p.skip_on, h->stream);
+    }
+    if (!(p.skip_on || p.pool_on) || h->qord_cur != nullptr) return;   // (seated by position; done for the whole sweep)
+    Timed t(h, "bucket", 0.0);   // (the queries are seated in the order of their nearest bin centre)
+    launch_query_order(h->ckey.p, h->bq_cur, h->q_lo, h->q_hi, h->B, h->qord.p, h->home.p, h->stream);
+}
+
+int base_shortlist_args(chb_ctx *h, const BatchPlan &p, ShortlistArgs &pa)
+{
+    pa = h->shortlist_args(h->q_lo, h->q_hi);
+    pa.P = h->pk.view(); pa.bin_ptr = h->bin_ptr.p; pa.memb_id = h->memb_id.p;
+    if (p.pp_now) {   // (a bin = its region: first row, tiles in use; a row's sample, -1 for a hole)
+        pa.P.pad_ptr = h->pp_start.p; pa.P.nt = h->pp_nt.p;
+        pa.bin_ptr = h->pp_start.p; pa.memb_id = h->pp_memb.p;
+    }
+    pa.cand = h->cand.p; pa.cand_cnt = h->cand_cnt.p; pa.cand_cap = kCandCap; pa.seg = p.sp;
+    if (p.fusedp) pa.tau_out = h->tau.p;
+    if (p.sp.launch) h->stats_seg_batches += 1;
+    if (p.skip_on) { pa.qord = p.qord_p; pa.home = p.home_p; pa.skip = 1; pa.skip_stat = h->fc_cur + kSlotSkipped; }
+    if (p.pool_on) {
+        pa.qord = p.qord_p; pa.home = p.home_p; pa.ckey = h->ckey.p; pa.pool = h->pool_view();
+        pa.pool_stat = h->fc_cur + kSlotPoolCand;
+        h->stats_pool_batches += 1;
+    }
+    return dev_shortlist_args(h, pa, p.skip_on, p.pp_now);
+}
+
+// two-stage exact selection: fp16 matrix-core shortlist, exact fp64 on the shortlist,
+// brute force only for (query tile, bin) pairs whose shortlist overflowed
+int base_shortlist(chb_ctx *h, const BatchPlan &p, const ShortlistArgs &pa)
+{
+    {
+        Timed t(h, "prefilter", (double)(h->q_hi - h->q_lo) * h->hint_base_members);
+        launch_shortlist(pa, h->flags64.p, sl_bpw(h), h->stream);
+    }
+    if (p.pool_on) {
+        // second chance for the pairs whose pool threshold was too loose for a 128-entry shortlist: the exact two-sweep
+        // selection on the overflow list's work items; only what overflows again goes to the brute-force kernel
+        Timed t(h, "prefilter_retry", 0.0);
+        ShortlistArgs pb = pa;
+        pb.worklist = h->flaglist.p; pb.nwork = h->nflag.p; pb.flaglist = h->flaglist2.p; pb.nflag = h->nflag2.p;
+        launch_shortlist_worklist(pb, h->flags64.p, h->stream);
+    }
+    return dev_shortlist_report(h, pa, p.skip_on, p.pool_on, p.pp_now);
+}
+
+// (a = the exact selection over the base members, lists to L0: here for the pairs whose shortlist overflowed)
+int finish_base_lists(chb_ctx *h, const BatchPlan &p, TopmArgs a)
+{
+    if (!p.fusedp) {
+        RescoreArgs ra = h->rescore_args(h->q_lo, h->q_hi);
+        ra.out = h->L0();
+        Timed t(h, "rescore", (double)(h->q_hi - h->q_lo) * h->B);
+        launch_rescore(ra, h->stream);
+    } else {
+        // overflowed (query tile, bin) pairs: the brute-force kernel's exact top-m becomes the shortlist
+        a.out = Lists{nullptr, nullptr, nullptr};
+        a.cand_out = h->cand.p; a.cand_cnt_out = h->cand_cnt.p; a.cand_cap = kCandCap;
+        a.tau_out = h->tau.p; a.S = h->shadow_scale;
+    }
+    {
+        Timed t(h, "topm_fallback", 0.0);   // the brute-force kernel's work list: what the second chance left, where it ran
+        launch_topm_flagged(a, h->flags64.p, p.pool_on ? h->flaglist2.p : h->flaglist.p, p.pool_on ? h->nflag2.p : h->nflag.p, h->stream);
+    }
+    return p.fusedp && !p.pp_now ? dev_shortlist_check(h, p.skip_on, p.qord_p) : CHB_OK;
+}
+
+// no shortlist stage: the brute-force fp64 selection over all base members
+void base_topm_plain(chb_ctx *h, const TopmArgs &a)
+{
+    Timed t(h, "topm_base", (double)(h->q_hi - h->q_lo) * h->hint_base_members);
+    if (h->m > kMaxM) launch_topm_generic(a, h->stream); else launch_topm(a, h->stream);
+}
+
+// bq already holds the K sample indices (device).  need_lists: the caller wants the exact base lists
+// L0 (chb_topm_per_bin); the fit loop of the fused path (m <= 16) works on the shortlists directly.
+int batch_begin_dev(chb_ctx *h, int K, int q_lo, int q_hi, bool need_lists)
+{
+    BatchPlan p(h, need_lists);
+    h->lists_valid = !p.fusedp; h->K = K; h->q_lo = q_lo; h->q_hi = q_hi;
+    h->round_in_batch = 0; h->round_active = 0;
+    { const int r_ = settle_batch(h, p); if (r_) return r_; }
+    open_batch(h, p);
     TopmArgs a = h->topm_args(q_lo, q_hi);
     a.bin_ptr = h->bin_ptr.p; a.memb_id = h->memb_id.p; a.out = h->L0();
-    if (pp_now) { a.bin_ptr = h->pp_start.p; a.bin_cnt = h->pp_fill.p; a.memb_id = h->pp_memb.p; }
-    if (pf_base_path) {
-        // two-stage exact selection: fp16 matrix-core shortlist, exact fp64 on the shortlist,
-        // brute force only for (query tile, bin) pairs whose shortlist overflowed
-        // (flags64 is all zero here: launch_topm_flagged clears what it serves)
-        if (!h->overflow_total_valid) { launch_fill_i32(h->overflow.p, 0, 1, s); h->overflow_total_valid = true; }
-        if (!pp_now) {
-            // the members' shadow rows (relative to their bin's centre) gathered into padded CSR order, and the per-bin
-            // bounds: one launch
-            Timed t(h, "bucket", 0.0);
-            launch_pack_build(h->Zs.p, h->ms.p, h->D, h->Dz, h->memb_id.p, h->bin_ptr.p, h->B, (int)h->N, h->pk.view(), skip_on, s);
-        }
-        int *qord_p = h->qord.p, *home_p = h->home.p;
-        if ((skip_on || pool_on) && h->qord_cur != nullptr) { qord_p = h->qord_cur; home_p = h->home_cur; }   // (done for the whole sweep)
-        else if (skip_on || pool_on) {   // (the queries are seated in the order of their nearest bin centre)
-            Timed t(h, "bucket", 0.0);
-            launch_query_order(h->ckey.p, h->bq_cur, q_lo, q_hi, h->B, h->qord.p, h->home.p, s);
-        }
-        ShortlistArgs pa = h->shortlist_args(q_lo, q_hi);
-        pa.P = h->pk.view(); pa.bin_ptr = h->bin_ptr.p; pa.memb_id = h->memb_id.p;
-        if (pp_now) {   // (a bin = its region: first row, tiles in use; a row's sample, -1 for a hole)
-            pa.P.pad_ptr = h->pp_start.p; pa.P.nt = h->pp_nt.p;
-            pa.bin_ptr = h->pp_start.p; pa.memb_id = h->pp_memb.p;
-        }
-        pa.cand = h->cand.p; pa.cand_cnt = h->cand_cnt.p; pa.cand_cap = kCandCap; pa.seg = sp;
-        if (fusedp) pa.tau_out = h->tau.p;
-        if (sp.launch) h->stats_seg_batches += 1;
-        if (skip_on) { pa.qord = qord_p; pa.home = home_p; pa.skip = 1; pa.skip_stat = h->fc_cur + kSlotSkipped; }
-        if (pool_on) {
-            pa.qord = qord_p; pa.home = home_p; pa.ckey = h->ckey.p; pa.pool = h->pool_view();
-            pa.pool_stat = h->fc_cur + kSlotPoolCand;
-            h->stats_pool_batches += 1;
-        }
-        { const int r_ = dev_shortlist_args(h, pa, skip_on, pp_now); if (r_) return r_; }
-        {
-            Timed t(h, "prefilter", (double)(q_hi - q_lo) * h->hint_base_members);
-            launch_shortlist(pa, h->flags64.p, sl_bpw(h), s);
-        }
-        const int *fb_list = h->flaglist.p, *fb_n = h->nflag.p;   // the brute-force kernel's work list
-        if (pool_on) {
-            // second chance for the pairs whose pool threshold was too loose for a 128-entry shortlist: the exact two-sweep
-            // selection on the overflow list's work items; only what overflows again goes to the brute-force kernel
-            Timed t(h, "prefilter_retry", 0.0);
-            ShortlistArgs pb = pa;
-            pb.worklist = h->flaglist.p; pb.nwork = h->nflag.p; pb.flaglist = h->flaglist2.p; pb.nflag = h->nflag2.p;
-            launch_shortlist_worklist(pb, h->flags64.p, s);
-            fb_list = h->flaglist2.p; fb_n = h->nflag2.p;
-        }
-        { const int r_ = dev_shortlist_report(h, pa, skip_on, pool_on, pp_now); if (r_) return r_; }
-        if (!fusedp) {
-            RescoreArgs ra = h->rescore_args(q_lo, q_hi);
-            ra.out = h->L0();
-            Timed t(h, "rescore", (double)(q_hi - q_lo) * h->B);
-            launch_rescore(ra, s);
-        } else {
-            // overflowed (query tile, bin) pairs: the brute-force kernel's exact top-m becomes the shortlist
-            a.out = Lists{nullptr, nullptr, nullptr};
-            a.cand_out = h->cand.p; a.cand_cnt_out = h->cand_cnt.p; a.cand_cap = kCandCap;
-            a.tau_out = h->tau.p; a.S = h->shadow_scale;
-        }
-        {
-            Timed t(h, "topm_fallback", 0.0);
-            launch_topm_flagged(a, h->flags64.p, fb_list, fb_n, s);
-        }
-        if (fusedp && !pp_now) { const int r_ = dev_shortlist_check(h, skip_on, qord_p); if (r_) return r_; }
-    } else {
-        Timed t(h, "topm_base", (double)(q_hi - q_lo) * h->hint_base_members);
-        if (h->m > kMaxM) launch_topm_generic(a, s); else launch_topm(a, s);
-    }
+    if (p.pp_now) { a.bin_ptr = h->pp_start.p; a.bin_cnt = h->pp_fill.p; a.memb_id = h->pp_memb.p; }
+    if (p.pf_base_path) {
+        ShortlistArgs pa{};
+        shortlist_inputs(h, p);
+        int r_ = base_shortlist_args(h, p, pa);
+        if (!r_) r_ = base_shortlist(h, p, pa);
+        if (!r_) r_ = finish_base_lists(h, p, a);
+        if (r_) return r_;
+    } else base_topm_plain(h, a);
     HIPCHK(hipGetLastError());
     h->batch_open = true;
     return CHB_OK;
@@ -1802,40 +1830,15 @@ int chb_destroy(chb_ctx *h)
     if (!h) return CHB_OK;
     (void)hipSetDevice(h->dev);
     (void)hipStreamSynchronize(h->stream);
+    if (h->rc_copy) (void)hipStreamSynchronize(h->rc_copy);
     drain_profile(h);
     if (h->comm && rccl()) { (void)rccl()->CommDestroy(h->comm); h->comm = nullptr; }
-    DevBuf<int> *ib[] = {&h->labels, &h->inb, &h->bq, &h->lab_old, &h->lab_prev, &h->lab_new,
-                         &h->first_change, &h->l0i, &h->l1i, &h->l0c, &h->l1c, &h->l2i, &h->l2c, &h->cnt, &h->bin_ptr,
-                         &h->cursor, &h->memb_id, &h->cnt2, &h->bin_ptr2, &h->cursor2, &h->memb2_id,
-                         &h->memb2_code, &h->perm, &h->xq, &h->xhull, &h->xcnt, &h->cand, &h->cand_cnt, &h->flags64, &h->flaglist, &h->nflag, &h->overflow, &h->flaglist2, &h->nflag2};
-    for (auto *b : ib) b->release();
-    DevBuf<double> *db[] = {&h->X, &h->mind, &h->mind2, &h->dist, &h->l0d, &h->l1d, &h->l2d, &h->xdist, &h->xalpha, &h->xpts};
-    for (auto *b : db) b->release();
-    h->Gs.release(); h->Zs.release(); h->gq.release(); h->ms.release(); h->mu_g.release();
-    h->colsum_part.release(); h->rmax.release(); h->pk.release(); h->pk2.release(); h->qn.release();
-    h->centers.release();
-    h->active.release(); h->n_active.release(); h->act_blk.release();
-    for (int i = 0; i < 2; ++i) { h->candu[i].release(); h->candu_cnt[i].release(); }
-    h->slow.release(); h->n_slow.release(); h->tau.release(); h->short_cnt.release(); h->agree.release();
-    h->xg.release(); h->xerr.release();
-    h->pool_Z.release(); h->pool_id.release(); h->pool_hole.release(); h->pool_ok.release(); h->pool_stat.release();
-    h->pool_key.release(); h->pool_sn.release(); h->pool_tsn.release();
-    h->pp_start.release(); h->pp_cap.release(); h->pp_fill.release(); h->pp_live.release(); h->pp_nt.release();
-    h->pp_memb.release(); h->pp_row.release(); h->pp_ctl.release(); h->pp_ovf.release(); h->pp_dest.release();
-    h->seg_nseg.release(); h->seg_gflag.release(); h->seg_items.release(); h->seg_lists.release();
-    h->shell_inv.release(); h->ckey.release(); h->qord.release(); h->home.release();
-    h->qord_all.release(); h->home_all.release(); h->geo_all.release();
-    if (h->rc_copy) { (void)hipStreamSynchronize(h->rc_copy); (void)hipStreamDestroy(h->rc_copy); }
-    for (int i = 0; i < 2; ++i) {
-        h->rc_Y[i].release(); h->rc_dist[i].release(); h->rc_min[i].release(); h->rc_margin[i].release(); h->rc_bin[i].release();
-        h->rc_hY[i].release(); h->rc_hdist[i].release(); h->rc_hmin[i].release(); h->rc_hmargin[i].release(); h->rc_hbin[i].release();
-        hipEvent_t ev[] = {h->rc_up[i], h->rc_done[i], h->rc_down[i]};
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    }
-    h->rc_ptr.release(); h->rc_memb.release(); h->rc_hptr.release(); h->rc_hmemb.release();
-    (void)hipStreamDestroy(h->stream);
+    // the handles without an owner; the buffers (DevBuf / PinBuf, PackBufs) free themselves when `delete h` destroys them
+    hipEvent_t ev[] = {h->rc_up[0], h->rc_up[1], h->rc_done[0], h->rc_done[1], h->rc_down[0], h->rc_down[1], h->fc_event[0], h->fc_event[1]};
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    if (h->rc_copy) (void)hipStreamDestroy(h->rc_copy);
     if (h->fc_host) (void)hipHostFree(h->fc_host);
-    for (int i = 0; i < 2; ++i) if (h->fc_event[i]) (void)hipEventDestroy(h->fc_event[i]);
+    (void)hipStreamDestroy(h->stream);
     delete h;
     return CHB_OK;
 }
@@ -1998,9 +2001,8 @@ int chb_pairwise_distance(chb_ctx *h, int64_t r0, int64_t r1, double *out)
             e = hipMemcpyAsync(out + (a - r0) * h->N, buf.p, sizeof(double) * (b - a) * h->N,
                                hipMemcpyDeviceToHost, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) { buf.release(); return fail(CHB_EHIP, hipGetErrorString(e)); }
+        if (e != hipSuccess) return fail(CHB_EHIP, hipGetErrorString(e));
     }
-    buf.release();
     return CHB_OK;
 }
 
@@ -2519,7 +2521,6 @@ int chb_find_nearest_from_row(chb_ctx *h, int64_t c, const int64_t *labels, cons
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out.data(), di.p, sizeof(int) * (m + 1), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    dl.release(); di.release(); dr.release();
     if (e != hipSuccess) return fail(CHB_EHIP, hipGetErrorString(e));
     for (int i = 0; i < m; ++i) out_idx[i] = out[(size_t)i];
     *out_cnt = out[(size_t)m];
@@ -2644,7 +2645,6 @@ int chb_kmer_frequencies(chb_ctx *h, const unsigned char *seq, const int64_t *of
     if (counts_out)
         HIPCHK(hipMemcpyAsync(counts_out, dcnt.p, sizeof(uint32_t) * (size_t)n * dim, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    dseq.release(); doff.release(); dptr.release(); dtab.release(); dcnt.release(); dfreq.release();
     return CHB_OK;
 }
 
