@@ -22,6 +22,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -176,10 +177,139 @@ struct Switches {
     bool allow_skip = true;       // CHB_TILE_SKIP=0: never (A/B tests)
 };
 
+// ---- the context's parts: each feature owns its buffers, host flags, verdict on the running fit, statistics and view for
+// the kernels.  fit_reset: what a fit's start resets; fit_scope: what holds inside a chb_fit_cluster_ex call only (FitScope).
+
+// The persistent base pack (prefilter_kernels.hip): the member pack kept across the batches of a fit
+struct PersistentPack {
+    DevBuf<int> start, cap, fill, live, nt, memb, row, ctl, ovf, dest;
+    int arena_rows = 0;
+    int64_t mark = 0;       // rows handed out from which on the host asks for a rebuild (pack_state_build)
+    bool fit = false;       // inside chb_fit_cluster (the stepwise entry points and chb_topm_per_bin always rebuild)
+    bool valid = false;     // the pack on the device matches the labels
+    bool batch = false;     // the open batch was started on it
+    bool rebuild = false;   // much of the arena is used up: the next batch start outside a look-ahead window rebuilds
+    int64_t stat_batches = 0, stat_builds = 0;
+    chb::PackState view() { return chb::PackState{start.p, cap.p, fill.p, live.p, nt.p, memb.p, row.p, ctl.p, ovf.p, dest.p, arena_rows}; }
+    void fit_reset() { valid = false; batch = false; rebuild = false; }
+    void fit_scope(bool in) { fit = in; if (in) { stat_batches = 0; stat_builds = 0; } else valid = false; }
+};
+
+// Threshold pools of the shortlist stage (prefilter_kernels.hip, "threshold pools"): for every (bin, home bin) the 32
+// base members of the bin nearest to the home bin's centre; built at a fit's start, maintained by every commit
+struct ThresholdPools {
+    DevBuf<unsigned short> Z;
+    DevBuf<int> id, hole, ok;
+    DevBuf<float> key, sn, tsn;
+    bool fit = false;      // inside chb_fit_cluster (the stepwise entry points and chb_topm_per_bin never use pools)
+    bool valid = false;    // the pools on the device match the labels
+    bool holes = true;     // the open batch may hold labelled samples (their pool slots are holes until the commit)
+    int state = 0;         // this fit: 0 undecided = on, 1 kept on, -1 off (its shortlists came out long: overlapping bins;
+                           // or tile skipping never loads more than 30 % of the tiles: FitRun::note_verdict has both rules)
+    int batches = 0;
+    long long cand = 0, pairs = 0;
+    long long off_key = -1;   // (bins, neighbours, metric) of the fit that turned them off on these samples
+    int64_t stat_batches = 0;
+    chb::PoolState view() { return chb::PoolState{Z.p, id.p, key.p, sn.p, hole.p, tsn.p, ok.p}; }
+    void release() { Z.release(); id.release(); hole.release(); key.release(); sn.release(); tsn.release(); ok.release(); }
+    void fit_reset(bool off) { stat_batches = 0; state = off ? -1 : 0; batches = 0; cand = 0; pairs = 0; }
+    void fit_scope(bool in) { fit = in; if (!in) valid = false; }
+};
+
+// Tile skipping in the base shortlist launch, and the queries' seats it and the pools need
+struct Seating {
+    // shells: the CSR of the base members is keyed (bin, shell of the member's distance from the bin's centre), outermost
+    // shell first, so that the rows of a 32-row tile have similar norms (tile skipping in the shortlist kernel)
+    DevBuf<float> shell_inv;
+    int nsh = 1;
+    // tile skipping (needs the shells above and queries seated by nearest bin centre): nearest-centre keys, the seating
+    // order, and the fit's verdict on whether it pays (0 undecided = on, 1 on, -1 off)
+    DevBuf<unsigned long long> ckey;
+    DevBuf<int> qord, home;
+    // (the fit loop orders the positions of ALL batches of a sweep in one launch; the open batch's part: qord_cur / home_cur)
+    DevBuf<int> qord_all, home_all;
+    DevBuf<int4> geo_all;
+    PinBuf<int4> pin_geo;
+    int *qord_cur = nullptr, *home_cur = nullptr;
+    int state = 0, batches = 0;
+    long long off_key = -1;   // (bins, neighbours, metric) of the fit that found nothing to skip on these samples
+    long long skipped = 0, seen = 0, unloaded = 0;
+    void fit_reset(bool off) { state = off ? -1 : 0; batches = 0; skipped = 0; seen = 0; unloaded = 0; }
+    void unseat() { qord_cur = nullptr; home_cur = nullptr; }   // (no sweep-wide seating: a sweep's start, a fit's end)
+};
+
+// Bins far larger than the rest are cut into segments for the shortlist stage (SegPlan, prefilter_kernels.hip): plan
+// buffers, and the bin sizes last seen by the host (they come home with the rounds' verdicts)
+struct Segments {
+    DevBuf<int> nseg, gflag;
+    DevBuf<int4> items;
+    DevBuf<float> lists;
+    int gcap = 0;
+    int hint_max_tiles = 0, hint_total_tiles = 0;
+    int64_t stat_batches = 0;   // batches of the last fit that ran the segment launches
+};
+
+// chb_recruit_rows: a chunk of the new rows (padded like X), its distances and row reductions, the call's CSR over the
+// labels -- the call's own buffers, nothing of a fit.  Two of each per-chunk buffer, on the device and pinned on the
+// host: while the kernels of chunk k run on the context's stream, copy brings chunk k + 1 up and chunk k - 1 down
+// (up / done / down: upload, kernels, download of the chunk in that half are through)
+struct Recruit {
+    DevBuf<double> Y[2], dist[2], min[2], margin[2];
+    DevBuf<int> bin[2], ptr, memb;
+    PinBuf<double> hY[2], hdist[2], hmin[2], hmargin[2];
+    PinBuf<int> hbin[2], hptr, hmemb;
+    hipStream_t copy = nullptr;
+    hipEvent_t up[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr}, down[2] = {nullptr, nullptr};
+};
+
+// Multi-GPU: one context per process per GPU, RCCL communicator over all ranks
+struct Exchange {
+    ncclComm_t comm = nullptr;
+    // host-staged exchange (chb_comm_init_hook): the same sharded loop with the all-gathers done by a
+    // caller-supplied function on host buffers -- MPI, gloo, pipes; also how two ranks can share one GPU
+    chb_allgather_fn hook = nullptr;
+    void *hook_user = nullptr;
+    std::vector<char> send, recv;
+    DevBuf<int> agree;   // chb_bcast_samples: {status, N, D, root} of every rank; chb_fit_cluster: the fit's agreement table
+    // framed exchange of the sharded loop (aux_kernels.hip: xchg_pack / xchg_unpack): every rank's {header, label slice},
+    // the number of the fit's next exchange (part of the tag every frame carries), and the device's "a rank was out of
+    // step" record {flag, my tag, its tag, rank}
+    DevBuf<int> xg, xerr;
+    int seq = 0;
+};
+
+struct Profile {
+    int level = 0;   // 0 off, 1 every kernel, 2 only the two dominant ones (cheap enough for a timed region)
+    std::map<std::string, ProfEntry> acc;
+    std::vector<Pending> pending;
+};
+
+// What describes the open batch on the host.  LookaheadSnap saves and restores it by copy: anything added here is put
+// back as it was after a failed look-ahead.
+struct BatchState {
+    int K = 0, q_lo = 0, q_hi = 0;
+    int round_in_batch = 0;     // rounds alternate between the list sets 1 and 2 (the other = previous)
+    bool lists_valid = false;   // the open batch was started with need_lists (chb_topm_per_bin)
+    bool open = false;
+    int *bq_cur = nullptr;      // the open batch's sample indices: bq.p, or a window of perm (no copy)
+    int *fc_cur = nullptr;      // slot of the open batch (first_change.p + 0 / kSlotInts), words as SlotWord names them: bin sizes, skip /
+                                // pool statistics and the pack's fill mark ride home with the verdict in one copy of kSlotHome ints
+    double hint_base_members = 0.0, hint_batch_entries = 0.0;   // work-unit hints for the profile (pairs = queries x members streamed)
+};
+
 struct chb_ctx {
     int dev = 0;
     Switches sw;
     hipStream_t stream = nullptr;
+    int rank = 0, world = 1;
+    PersistentPack pp;
+    ThresholdPools pool;
+    Seating seat;
+    Segments seg;
+    Recruit rc;
+    Exchange xchg;
+    Profile prof;
+    BatchState batch;
     // samples
     DevBuf<double> X;
     int64_t N = 0;
@@ -190,22 +320,16 @@ struct chb_ctx {
     bool fit_open = false;
     bool stepwise = false;   // the open fit was begun by chb_fit_begin (the caller drives its batches): chb_recruit_rows refuses
     DevBuf<int> labels, inb;
-    // batch state
-    int K = 0, Kcap = 0, q_lo = 0, q_hi = 0;
-    bool batch_open = false;
+    // batch buffers (the open batch itself: `batch`)
+    int Kcap = 0;
     DevBuf<int> bq, lab_old, lab_prev, lab_new, first_change;
-    int *bq_cur = nullptr;      // the open batch's sample indices: bq.p, or a window of perm (no copy)
     int *fc_host = nullptr;     // pinned landing places of the two verdict slots (kSlotInts ints each, as on the device)
-    int *fc_cur = nullptr;      // slot of the open batch (first_change.p + 0 / kSlotInts), words as SlotWord names them: bin
-                                // sizes, skip / pool statistics and the pack's fill mark ride home with the verdict in
-                                // one copy of kSlotHome ints
     hipEvent_t fc_event[2] = {nullptr, nullptr};
     bool argmin_in_place = false;   // chb_fit_cluster without exchange: argmin also stores the label to lab_prev
     DevBuf<double> mind, mind2, dist;   // winning hull distance, runner-up (margin report), all distances
     bool want_margin = false;
     DevBuf<double> l0d, l1d, l2d;
     DevBuf<int> l0i, l1i, l0c, l1c, l2i, l2c;
-    int round_in_batch = 0;   // rounds alternate between the list sets 1 and 2 (the other = previous)
     int64_t round_active = 0; // `active` of the open batch's last chb_batch_round: may not decrease (include/chbin_hip.h)
     DevBuf<int> cnt, bin_ptr, cursor, memb_id;
     DevBuf<int> cnt2, bin_ptr2, cursor2, memb2_id, memb2_code;
@@ -229,106 +353,19 @@ struct chb_ctx {
     // the base stage's tau (bound of the m-th nearest distance), the exact path's work list
     bool fused = false;
     bool pf_fit = false;        // this fit uses the shortlist stage (use_prefilter, D <= 160, m <= 16)
-    bool lists_valid = false;   // the open batch was started with need_lists (chb_topm_per_bin)
     DevBuf<int> candu[2], candu_cnt[2], slow, n_slow;
+    DevBuf<float> tau;
     // the shortlist stage's contract as checked by the fused kernels (FusedArgs::short_cnt): pairs of this fit whose base
     // shortlist held fewer than min(m, bin size) candidates or a wild index -- any is an internal error of the fit
     DevBuf<int> short_cnt;
-    DevBuf<int> agree;   // chb_bcast_samples: {status, N, D, root} of every rank; chb_fit_cluster: the fit's agreement table
-    // framed exchange of the sharded loop (aux_kernels.hip: xchg_pack / xchg_unpack): every rank's {header, label slice},
-    // the number of the fit's next exchange (part of the tag every frame carries), and the device's "a rank was out of
-    // step" record {flag, my tag, its tag, rank}
-    DevBuf<int> xg, xerr;
-    int xseq = 0;
-    // the persistent base pack (prefilter_kernels.hip): the member pack kept across the batches of a fit
-    DevBuf<int> pp_start, pp_cap, pp_fill, pp_live, pp_nt, pp_memb, pp_row, pp_ctl, pp_ovf, pp_dest;
-    int pp_arena_rows = 0;
-    int64_t pp_mark = 0;       // rows handed out from which on the host asks for a rebuild (pack_state_build)
-    bool pp_fit = false;       // inside chb_fit_cluster (the stepwise entry points and chb_topm_per_bin always rebuild)
-    bool pp_valid = false;     // the pack on the device matches the labels
-    bool pp_batch = false;     // the open batch was started on it
-    bool pp_rebuild = false;   // much of the arena is used up: the next batch start outside a look-ahead window rebuilds
-    int64_t stats_pp_batches = 0, stats_pp_builds = 0;
-    chb::PackState pack_state()
-    {
-        return chb::PackState{pp_start.p, pp_cap.p, pp_fill.p, pp_live.p, pp_nt.p, pp_memb.p, pp_row.p, pp_ctl.p, pp_ovf.p,
-                              pp_dest.p, pp_arena_rows};
-    }
-    // threshold pools of the shortlist stage (prefilter_kernels.hip, "threshold pools"): for every (bin, home bin) the 32
-    // base members of the bin nearest to the home bin's centre; built at a fit's start, maintained by every commit
-    DevBuf<unsigned short> pool_Z;
-    DevBuf<int> pool_id, pool_hole, pool_ok;
-    DevBuf<float> pool_key, pool_sn, pool_tsn;
-    bool pool_fit = false;      // inside chb_fit_cluster (the stepwise entry points and chb_topm_per_bin never use pools)
-    bool pool_valid = false;    // the pools on the device match the labels
-    bool pool_holes = true;     // the open batch may hold labelled samples (their pool slots are holes until the commit)
-    int pool_state = 0;         // this fit: 0 undecided = on, 1 kept on, -1 off (its shortlists came out long: overlapping bins;
-                                // or tile skipping never loads more than 30 % of the tiles: FitRun::note_verdict has both rules)
-    int pool_batches = 0;
-    long long pool_cand = 0, pool_pairs = 0;
-    long long pool_off_key = -1;   // (bins, neighbours, metric) of the fit that turned them off on these samples
-    int64_t stats_pool_batches = 0;
-    chb::PoolState pool_view()
-    {
-        return chb::PoolState{pool_Z.p, pool_id.p, pool_key.p, pool_sn.p, pool_hole.p, pool_tsn.p, pool_ok.p};
-    }
-    int64_t short_seen = 0;
-    // bins far larger than the rest are cut into segments for the shortlist stage (SegPlan, prefilter_kernels.hip): plan
-    // buffers, and the bin sizes last seen by the host (they come home with the rounds' verdicts)
-    DevBuf<int> seg_nseg, seg_gflag;
-    DevBuf<int4> seg_items;
-    DevBuf<float> seg_lists;
-    int seg_gcap = 0;
-    int hint_max_tiles = 0, hint_total_tiles = 0;
-    // shells: the CSR of the base members is keyed (bin, shell of the member's distance from the bin's centre), outermost
-    // shell first, so that the rows of a 32-row tile have similar norms (tile skipping in the shortlist kernel)
-    DevBuf<float> shell_inv;
-    int nsh = 1;
-    // tile skipping in the base shortlist launch (needs the shells above and queries seated by nearest bin centre):
-    // nearest-centre keys, the seating order, and the fit's verdict on whether it pays (0 undecided = on, 1 on, -1 off)
-    DevBuf<unsigned long long> ckey;
-    DevBuf<int> qord, home;
-    // (the fit loop orders the positions of ALL batches of a sweep in one launch; the open batch's part: qord_cur / home_cur)
-    DevBuf<int> qord_all, home_all;
-    DevBuf<int4> geo_all;
-    PinBuf<int4> pin_geo;
-    int *qord_cur = nullptr, *home_cur = nullptr;
-    int skip_state = 0, skip_batches = 0;
-    long long skip_off_key = -1;   // (bins, neighbours, metric) of the fit that found nothing to skip on these samples
-    long long last_batch = 0;
-    long long skip_skipped = 0, skip_seen = 0, skip_unloaded = 0;
-    DevBuf<float> tau;
-    // chb_recruit_rows: a chunk of the new rows (padded like X), its distances and row reductions, the call's CSR over the
-    // labels -- the call's own buffers, nothing of a fit.  Two of each per-chunk buffer, on the device and pinned on the
-    // host: while the kernels of chunk k run on the context's stream, rc_copy brings chunk k + 1 up and chunk k - 1 down
-    // (rc_up / rc_done / rc_down: upload, kernels, download of the chunk in that half are through)
-    DevBuf<double> rc_Y[2], rc_dist[2], rc_min[2], rc_margin[2];
-    DevBuf<int> rc_bin[2], rc_ptr, rc_memb;
-    PinBuf<double> rc_hY[2], rc_hdist[2], rc_hmin[2], rc_hmargin[2];
-    PinBuf<int> rc_hbin[2], rc_hptr, rc_hmemb;
-    hipStream_t rc_copy = nullptr;
-    hipEvent_t rc_up[2] = {nullptr, nullptr}, rc_done[2] = {nullptr, nullptr}, rc_down[2] = {nullptr, nullptr};
     // scratch for the indexed / explicit-point entry points
     DevBuf<int> xq, xhull, xcnt;
     DevBuf<double> xdist, xalpha, xpts;
-    // profiling
-    int prof = 0;   // 0 off, 1 every kernel, 2 only the two dominant ones (cheap enough for a timed region)
-    std::map<std::string, ProfEntry> prof_acc;
-    std::vector<Pending> pending;
-    int64_t stats[4] = {0, 0, 0, 0};
-    int64_t stats_seg_batches = 0;   // batches of the last fit that ran the segment launches
-    int64_t stats_lookahead = 0;     // batches of the last fit whose successor was enqueued ahead of their verdict and kept
-    int64_t stats_lookahead_failed = 0;   // ... and discarded (the batch needed further rounds)
-    // multi-GPU: one context per process per GPU, RCCL communicator over all ranks
-    ncclComm_t comm = nullptr;
-    int rank = 0, world = 1;
-    // host-staged exchange (chb_comm_init_hook): the same sharded loop with the all-gathers done by a
-    // caller-supplied function on host buffers -- MPI, gloo, pipes; also how two ranks can share one GPU
-    chb_allgather_fn hook = nullptr;
-    void *hook_user = nullptr;
-    std::vector<char> hook_send, hook_recv;
-    // work-unit hints for the profile (pairs = queries x members streamed)
-    double hint_base_members = 0.0, hint_batch_entries = 0.0;
+    // the last fit: chb_fit_stats, its speculative batch size, batches whose successor was enqueued ahead of their verdict
+    // and kept, ... and discarded (the batch needed further rounds)
+    std::array<int64_t, 4> stats{};
+    long long last_batch = 0;
+    int64_t stats_lookahead = 0, stats_lookahead_failed = 0;
 #ifdef CHB_DEV_KNOBS
     // developer builds: the switches of the tests and tools/ (read_switches; the Makefile says what each does), their state
     struct DevKnobs {
@@ -347,15 +384,15 @@ struct chb_ctx {
     Lists L0() { return Lists{l0d.p, l0i.p, l0c.p}; }
     Lists L1() { return Lists{l1d.p, l1i.p, l1c.p}; }
     Lists L2() { return Lists{l2d.p, l2i.p, l2c.p}; }
-    Lists Lcur() { return (round_in_batch & 1) ? L2() : L1(); }
-    Lists Lprev() { return (round_in_batch & 1) ? L1() : L2(); }
+    Lists Lcur() { return (batch.round_in_batch & 1) ? L2() : L1(); }
+    Lists Lprev() { return (batch.round_in_batch & 1) ? L1() : L2(); }
 
     // The kernels' argument blocks for the positions [lo, hi) of the open batch, with the fields that every launch of a
     // kind shares; a call site adds only what makes it different, and what nobody sets stays zero.
     TopmArgs topm_args(int lo, int hi)
     {
         TopmArgs a{};
-        a.X = X.p; a.Dp = Dp; a.bq = bq_cur; a.pos_begin = lo; a.pos_end = hi; a.B = B; a.m = m; a.Kcap = Kcap;
+        a.X = X.p; a.Dp = Dp; a.bq = batch.bq_cur; a.pos_begin = lo; a.pos_end = hi; a.B = B; a.m = m; a.Kcap = Kcap;
         return a;
     }
     // (query side, geometry, scale, overflow counter, the brute-force kernel's work list -- its counter reset by the CSR kernels)
@@ -363,28 +400,28 @@ struct chb_ctx {
     {
         ShortlistArgs a{};
         a.Gs = Gs.p; a.gq = reinterpret_cast<const float2 *>(gq.p); a.qn = reinterpret_cast<const float2 *>(qn.p);
-        a.Dz = Dz; a.S = shadow_scale; a.bq = bq_cur; a.pos_begin = lo; a.pos_end = hi; a.B = B; a.m = m; a.Kcap = Kcap;
+        a.Dz = Dz; a.S = shadow_scale; a.bq = batch.bq_cur; a.pos_begin = lo; a.pos_end = hi; a.B = B; a.m = m; a.Kcap = Kcap;
         a.overflow = overflow.p; a.flaglist = flaglist.p; a.nflag = nflag.p;
         return a;
     }
     RescoreArgs rescore_args(int lo, int hi)   // (candidates: the base shortlists)
     {
         RescoreArgs a{};
-        a.X = X.p; a.Dp = Dp; a.bq = bq_cur; a.pos_begin = lo; a.pos_end = hi; a.B = B; a.m = m; a.Kcap = Kcap;
+        a.X = X.p; a.Dp = Dp; a.bq = batch.bq_cur; a.pos_begin = lo; a.pos_end = hi; a.B = B; a.m = m; a.Kcap = Kcap;
         a.cand = cand.p; a.cand_cnt = cand_cnt.p; a.cand_cap = kCandCap;
         return a;
     }
     QpArgs qp_args(int lo, int hi)
     {
         QpArgs a{};
-        a.X = X.p; a.D = D; a.Dp = Dp; a.bq = bq_cur; a.pos_begin = lo; a.pos_end = hi; a.B = B; a.m = m; a.Kcap = Kcap;
+        a.X = X.p; a.D = D; a.Dp = Dp; a.bq = batch.bq_cur; a.pos_begin = lo; a.pos_end = hi; a.B = B; a.m = m; a.Kcap = Kcap;
         a.dist = dist.p; a.metric = metric;
         return a;
     }
     FusedArgs fused_args(int lo, int hi)
     {
         FusedArgs a{};
-        a.X = X.p; a.n_samples = N; a.D = D; a.Dp = Dp; a.bq = bq_cur; a.pos_begin = lo; a.pos_end = hi;
+        a.X = X.p; a.n_samples = N; a.D = D; a.Dp = Dp; a.bq = batch.bq_cur; a.pos_begin = lo; a.pos_end = hi;
         a.B = B; a.m = m; a.Kcap = Kcap; a.dist = dist.p; a.metric = metric;
         return a;
     }
@@ -395,19 +432,19 @@ struct chb_ctx {
 static int exchange_all_gather(chb_ctx *h, void *buf, size_t count, size_t elem, ncclDataType_t dt)
 {
     char *b = static_cast<char *>(buf);
-    if (h->hook != nullptr) {
+    if (h->xchg.hook != nullptr) {
         const size_t bytes = count * elem;
-        h->hook_send.resize(bytes);
-        h->hook_recv.resize(bytes * (size_t)h->world);
-        HIPCHK(hipMemcpyAsync(h->hook_send.data(), b + (size_t)h->rank * bytes, bytes, hipMemcpyDeviceToHost, h->stream));
+        h->xchg.send.resize(bytes);
+        h->xchg.recv.resize(bytes * (size_t)h->world);
+        HIPCHK(hipMemcpyAsync(h->xchg.send.data(), b + (size_t)h->rank * bytes, bytes, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->hook(h->hook_user, h->hook_send.data(), h->hook_recv.data(), bytes) != 0)
+        if (h->xchg.hook(h->xchg.hook_user, h->xchg.send.data(), h->xchg.recv.data(), bytes) != 0)
             return fail(CHB_EHIP, "the exchange hook reported a failure");
-        HIPCHK(hipMemcpyAsync(b, h->hook_recv.data(), bytes * (size_t)h->world, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(b, h->xchg.recv.data(), bytes * (size_t)h->world, hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));   // (hook_recv is reused by the next exchange)
         return CHB_OK;
     }
-    NCCLCHK(rccl()->AllGather(b + (size_t)h->rank * count * elem, b, count, dt, h->comm, h->stream));
+    NCCLCHK(rccl()->AllGather(b + (size_t)h->rank * count * elem, b, count, dt, h->xchg.comm, h->stream));
     return CHB_OK;
 }
 
@@ -418,7 +455,7 @@ struct Timed {
     Pending p;
     bool on;
     Timed(chb_ctx *h_, const char *name, double work)
-        : h(h_), on(h_->prof == 1 || (h_->prof == 2 && (!strcmp(name, "prefilter") || !strcmp(name, "hull_qp"))))
+        : h(h_), on(h_->prof.level == 1 || (h_->prof.level == 2 && (!strcmp(name, "prefilter") || !strcmp(name, "hull_qp"))))
     {
         if (!on) return;
         p.name = name; p.work = work;
@@ -430,22 +467,22 @@ struct Timed {
     {
         if (!on) return;
         (void)hipEventRecord(p.b, h->stream);
-        h->pending.push_back(p);
+        h->prof.pending.push_back(p);
     }
 };
 
 void drain_profile(chb_ctx *h)
 {
-    for (auto &p : h->pending) {
+    for (auto &p : h->prof.pending) {
         (void)hipEventSynchronize(p.b);
         float ms = 0.f;
         (void)hipEventElapsedTime(&ms, p.a, p.b);
-        auto &e = h->prof_acc[p.name];
+        auto &e = h->prof.acc[p.name];
         e.ms += ms; e.launches += 1; e.work += p.work;
         (void)hipEventDestroy(p.a);
         (void)hipEventDestroy(p.b);
     }
-    h->pending.clear();
+    h->prof.pending.clear();
 }
 
 long long skip_key(const chb_ctx *h) { return (long long)h->B | ((long long)h->m << 32) | ((long long)h->metric << 40); }
@@ -460,9 +497,9 @@ int ensure_batch_buffers(chb_ctx *h, int Kcap)
     HIPCHK(h->lab_prev.ensure(Kpad));
     HIPCHK(h->lab_new.ensure(Kpad));
     HIPCHK(h->first_change.ensure(2 * kSlotInts));
-    h->fc_cur = h->first_change.p;
-    HIPCHK(h->xg.ensure(Kpad + (size_t)(kXchgHdr + 1) * (size_t)h->world));
-    HIPCHK(h->xerr.ensure_zeroed(4, h->stream));
+    h->batch.fc_cur = h->first_change.p;
+    HIPCHK(h->xchg.xg.ensure(Kpad + (size_t)(kXchgHdr + 1) * (size_t)h->world));
+    HIPCHK(h->xchg.xerr.ensure_zeroed(4, h->stream));
     HIPCHK(h->mind.ensure(Kpad));
     HIPCHK(h->mind2.ensure(Kpad));
     HIPCHK(h->dist.ensure(K * B));
@@ -499,12 +536,12 @@ int ensure_batch_buffers(chb_ctx *h, int Kcap)
         HIPCHK(h->overflow.ensure(1));
         HIPCHK(h->pk.ensure((size_t)h->N + 32 * B, B, (size_t)h->Dz));
         HIPCHK(h->pk2.ensure(2 * K + 32 * B, B, (size_t)h->Dz));
-        h->seg_gcap = (int)std::min<size_t>(64, B / 4 + 1);
-        HIPCHK(h->qord.ensure(K));
-        HIPCHK(h->home.ensure(B));
-        HIPCHK(h->seg_nseg.ensure(1));
-        HIPCHK(h->seg_gflag.ensure(B));
-        HIPCHK(h->seg_items.ensure(16 * (size_t)h->seg_gcap));
+        h->seg.gcap = (int)std::min<size_t>(64, B / 4 + 1);
+        HIPCHK(h->seat.qord.ensure(K));
+        HIPCHK(h->seat.home.ensure(B));
+        HIPCHK(h->seg.nseg.ensure(1));
+        HIPCHK(h->seg.gflag.ensure(B));
+        HIPCHK(h->seg.items.ensure(16 * (size_t)h->seg.gcap));
         // (seg_lists -- giant slots x 16 segments x K x list length floats, 0.27 / 0.86 GB at 1M x 200 bins for m = 5 / 15 --
         //  is allocated by the first batch that really runs the segment launches: batch_begin_dev)
         if (h->fused) {
@@ -540,8 +577,7 @@ int fit_begin_impl(chb_ctx *h, int64_t B, const int64_t *initial, int m, bool sy
     // (a fit that found nothing to skip settles it for later fits over the same samples with the same bin count,
     //  neighbour count and metric -- the verdict depends on all three)
     // (wide rows, Dz > 160: the plain two-sweep builds only -- no tile skipping, pools or segments)
-    h->skip_state = (h->skip_off_key == skip_key(h) || h->Dz > 160) ? -1 : 0;
-    h->skip_batches = 0; h->skip_skipped = 0; h->skip_seen = 0; h->skip_unloaded = 0;
+    h->seat.fit_reset(h->seat.off_key == skip_key(h) || h->Dz > 160);
     h->fused = h->sw.allow_fused && h->pf_fit && fused_supported(m, h->Dp);
     HIPCHK(h->pin_a.ensure((size_t)h->N));
     int *lab = h->pin_a.p;
@@ -555,7 +591,7 @@ int fit_begin_impl(chb_ctx *h, int64_t B, const int64_t *initial, int m, bool sy
     {   // bin sizes as the first batch will see them (later ones come home with the rounds' verdicts)
         int64_t mx = 0, tot = 0;
         for (int64_t c = 0; c < B; ++c) { const int64_t t = (bin_size[(size_t)c] + 31) / 32; mx = std::max(mx, t); tot += t; }
-        h->hint_max_tiles = (int)mx; h->hint_total_tiles = (int)std::min<int64_t>(tot, 0x7fffffff);
+        h->seg.hint_max_tiles = (int)mx; h->seg.hint_total_tiles = (int)std::min<int64_t>(tot, 0x7fffffff);
     }
     HIPCHK(h->labels.ensure((size_t)h->N));
     HIPCHK(h->inb.ensure((size_t)h->N));
@@ -565,7 +601,7 @@ int fit_begin_impl(chb_ctx *h, int64_t B, const int64_t *initial, int m, bool sy
     HIPCHK(hipMemsetAsync(h->cnt.p, 0, sizeof(int) * h->cnt.cap, h->stream));   // (kept zero by scan_kernel from here on)
     HIPCHK(h->bin_ptr.ensure((size_t)B + 1));
     HIPCHK(h->cursor.ensure((size_t)B * kShells));
-    h->nsh = 1;
+    h->seat.nsh = 1;
     HIPCHK(h->memb_id.ensure((size_t)h->N));
     if (h->pf_fit) {
         // Bin centres for the shortlist stage: the mean of each bin's initially labelled members
@@ -584,32 +620,31 @@ int fit_begin_impl(chb_ctx *h, int64_t B, const int64_t *initial, int m, bool sy
         // N x B x 8 bytes (51 MB at 100k x 64, 1.6 GB at 1M x 200, 65 GB at 1M x 8192): a table that does not fit the
         // device sends the fit to the brute-force selection (as a feature width beyond the shortlist stage's does) instead
         // of failing it
-        if (h->qn.ensure((size_t)h->N * (size_t)B * 2) != hipSuccess || h->ckey.ensure((size_t)h->N) != hipSuccess) {
+        if (h->qn.ensure((size_t)h->N * (size_t)B * 2) != hipSuccess || h->seat.ckey.ensure((size_t)h->N) != hipSuccess) {
             (void)hipGetLastError();
-            h->qn.release(); h->ckey.release();
+            h->qn.release(); h->seat.ckey.release();
             h->pf_fit = false; h->fused = false;
         }
     }
     if (h->pf_fit) {
         {
             Timed t(h, "query_norms", (double)h->N * (double)B);
-            launch_query_norms(h->X.p, h->D, h->Dp, (int)h->N, h->B, h->centers.p, h->shadow_scale, h->qn.p, h->ckey.p, h->stream);
+            launch_query_norms(h->X.p, h->D, h->Dp, (int)h->N, h->B, h->centers.p, h->shadow_scale, h->qn.p, h->seat.ckey.p, h->stream);
         }
         // the unit of the CSR's shell key per bin (from the initially labelled members; fixed for the fit)
         int nsh = kShells;
         while (nsh > 1 && (int64_t)B * nsh > kMaxKeys) nsh >>= 1;
-        HIPCHK(h->shell_inv.ensure((size_t)B));
-        launch_shell_scale(h->ms.p, h->memb_id.p, h->bin_ptr.p, h->B, nsh, h->shell_inv.p, h->stream);
-        h->nsh = nsh;
+        HIPCHK(h->seat.shell_inv.ensure((size_t)B));
+        launch_shell_scale(h->ms.p, h->memb_id.p, h->bin_ptr.p, h->B, nsh, h->seat.shell_inv.p, h->stream);
+        h->seat.nsh = nsh;
         HIPCHK(hipGetLastError());
     }
     if (sync) HIPCHK(hipStreamSynchronize(h->stream));
-    h->fit_open = true; h->batch_open = false; h->Kcap = 0;
+    h->fit_open = true; h->batch.open = false; h->Kcap = 0;
     h->overflow_total_valid = false;
-    h->short_seen = 0;
     if (h->short_cnt.p) HIPCHK(hipMemsetAsync(h->short_cnt.p, 0, sizeof(int), h->stream));
-    h->pp_valid = false; h->pp_batch = false; h->pp_rebuild = false;
-    if (h->pp_ctl.p) HIPCHK(hipMemsetAsync(h->pp_ctl.p, 0, 4 * sizeof(int), h->stream));
+    h->pp.fit_reset();
+    if (h->pp.ctl.p) HIPCHK(hipMemsetAsync(h->pp.ctl.p, 0, 4 * sizeof(int), h->stream));
     return CHB_OK;
 }
 
@@ -629,37 +664,37 @@ int pack_state_build(chb_ctx *h)
     // batch never holds more than N samples.
     {
         const int64_t K = std::max(h->Kcap, 1);
-        h->pp_mark = std::min<int64_t>(5 * h->N + 512 * (int64_t)B, (int64_t)arena - (3 * h->N + 5 * K + 128 * (int64_t)B));
-        if (h->pp_mark < 7 * h->N / 2 + 128 * (int64_t)B) { h->pp_valid = false; h->pp_fit = false; return CHB_OK; }   // (capped arena)
+        h->pp.mark = std::min<int64_t>(5 * h->N + 512 * (int64_t)B, (int64_t)arena - (3 * h->N + 5 * K + 128 * (int64_t)B));
+        if (h->pp.mark < 7 * h->N / 2 + 128 * (int64_t)B) { h->pp.valid = false; h->pp.fit = false; return CHB_OK; }   // (capped arena)
     }
-    if (h->pp_arena_rows < arena || !h->pp_memb.p) {
-        if (h->pk.ensure((size_t)arena, B, (size_t)h->Dz) != hipSuccess || h->pp_memb.ensure((size_t)arena + 64) != hipSuccess) {
+    if (h->pp.arena_rows < arena || !h->pp.memb.p) {
+        if (h->pk.ensure((size_t)arena, B, (size_t)h->Dz) != hipSuccess || h->pp.memb.ensure((size_t)arena + 64) != hipSuccess) {
             (void)hipGetLastError();   // (no room for the arena: this fit rebuilds its pack per batch)
-            h->pp_memb.release();
+            h->pp.memb.release();
             HIPCHK(h->pk.ensure((size_t)h->N + 32 * B, B, (size_t)h->Dz));
-            h->pp_arena_rows = 0; h->pp_valid = false; h->pp_fit = false;
+            h->pp.arena_rows = 0; h->pp.valid = false; h->pp.fit = false;
             return CHB_OK;
         }
-        h->pp_arena_rows = arena;
+        h->pp.arena_rows = arena;
     }
-    HIPCHK(h->pp_row.ensure((size_t)h->N));
-    DevBuf<int> *pb[] = {&h->pp_start, &h->pp_cap, &h->pp_fill, &h->pp_live, &h->pp_nt};
+    HIPCHK(h->pp.row.ensure((size_t)h->N));
+    DevBuf<int> *pb[] = {&h->pp.start, &h->pp.cap, &h->pp.fill, &h->pp.live, &h->pp.nt};
     for (auto *b : pb) HIPCHK(b->ensure(B + 1));
-    HIPCHK(h->pp_ctl.ensure_zeroed(4, h->stream));
-    HIPCHK(h->pp_ovf.ensure((size_t)std::max(h->Kcap, 1)));
-    HIPCHK(h->pp_dest.ensure((size_t)std::max(h->Kcap, 1)));
+    HIPCHK(h->pp.ctl.ensure_zeroed(4, h->stream));
+    HIPCHK(h->pp.ovf.ensure((size_t)std::max(h->Kcap, 1)));
+    HIPCHK(h->pp.dest.ensure((size_t)std::max(h->Kcap, 1)));
     // (room to grow: were all N samples labelled and spread evenly, a bin would hold N / B rows -- half as much again)
     const int grow = (int)std::min<int64_t>((3 * h->N / 2) / std::max<int64_t>(h->B, 1) + 64, 0x3fffffff);
     {
         Timed t(h, "bucket", (double)h->N);
         launch_bucket_base(h->labels.p, h->inb.p, (int)h->N, h->B, h->cnt.p, h->bin_ptr.p, h->cursor.p, h->memb_id.p, nullptr,
                            nullptr, h->stream);
-        launch_pack_state_build(h->pack_state(), h->pk.view(), h->Zs.p, h->ms.p, h->D, h->Dz, h->memb_id.p, h->bin_ptr.p, h->B,
+        launch_pack_state_build(h->pp.view(), h->pk.view(), h->Zs.p, h->ms.p, h->D, h->Dz, h->memb_id.p, h->bin_ptr.p, h->B,
                                 (int)h->N, grow, h->stream);
     }
     HIPCHK(hipGetLastError());
-    h->pp_valid = true; h->pp_rebuild = false;
-    h->stats_pp_builds += 1;
+    h->pp.valid = true; h->pp.rebuild = false;
+    h->pp.stat_builds += 1;
     return CHB_OK;
 }
 
@@ -669,32 +704,31 @@ int pack_state_build(chb_ctx *h)
 constexpr size_t kPoolMaxBytes = (size_t)1 << 30;
 int pool_build(chb_ctx *h)
 {
-    h->pool_valid = false;
+    h->pool.valid = false;
     const size_t B = h->B, slots = B * B * (size_t)kPoolRows;
     // (m > 8: the 16-lane hull kernel pays for every candidate beyond 16 with extra rows and second tiles -- with the pools'
     //  17.4 instead of 16.8 candidates per pair at m = 15 it ran 34.4 instead of 28.8 ms per sweep, more than the shortlist
     //  kernel saved (5.1 instead of 5.9): those fits keep the two sweeps)
-    if (!h->sw.pool_allowed || !h->fused || !h->pf_fit || h->ckey.p == nullptr || B < 2 || h->m > 8 || h->Dz > 160 ||
+    if (!h->sw.pool_allowed || !h->fused || !h->pf_fit || h->seat.ckey.p == nullptr || B < 2 || h->m > 8 || h->Dz > 160 ||
         slots * (size_t)h->Dz * sizeof(unsigned short) > kPoolMaxBytes)
         return CHB_OK;
     // (small fits: a bin of a few tiles has no threshold sweep worth replacing, while the pools' build and upkeep are per
     //  fit and per batch -- BASELINE configs[1], 10k x 32 = 10 tiles per bin, went from 1.45 to 1.85 ms per sweep with them.
     //  From 16 tiles per bin on average; CHB_POOL_TAU=2 keeps them whatever the size)
     if (!h->sw.pool_force && (size_t)h->N < 512 * B) return CHB_OK;
-    if (h->pool_Z.ensure(slots * (size_t)h->Dz) != hipSuccess || h->pool_id.ensure(slots) != hipSuccess ||
-        h->pool_hole.ensure(slots) != hipSuccess || h->pool_key.ensure(slots) != hipSuccess || h->pool_sn.ensure(slots) != hipSuccess ||
-        h->pool_tsn.ensure(B * B + 64) != hipSuccess || h->pool_ok.ensure(B * B) != hipSuccess) {
+    if (h->pool.Z.ensure(slots * (size_t)h->Dz) != hipSuccess || h->pool.id.ensure(slots) != hipSuccess ||
+        h->pool.hole.ensure(slots) != hipSuccess || h->pool.key.ensure(slots) != hipSuccess || h->pool.sn.ensure(slots) != hipSuccess ||
+        h->pool.tsn.ensure(B * B + 64) != hipSuccess || h->pool.ok.ensure(B * B) != hipSuccess) {
         (void)hipGetLastError();   // (no room: the fit keeps the two-sweep launch)
-        h->pool_Z.release(); h->pool_id.release(); h->pool_hole.release(); h->pool_key.release(); h->pool_sn.release();
-        h->pool_tsn.release(); h->pool_ok.release();
+        h->pool.release();
         return CHB_OK;
     }
     {
         Timed t(h, "pool", (double)h->N);
-        launch_pool_build(h->pool_view(), h->Zs.p, h->ms.p, h->qn.p, h->D, h->Dz, h->memb_id.p, h->bin_ptr.p, h->B, h->stream);
+        launch_pool_build(h->pool.view(), h->Zs.p, h->ms.p, h->qn.p, h->D, h->Dz, h->memb_id.p, h->bin_ptr.p, h->B, h->stream);
     }
     HIPCHK(hipGetLastError());
-    h->pool_valid = true;
+    h->pool.valid = true;
     return CHB_OK;
 }
 
@@ -750,9 +784,9 @@ int dev_shortlist_args(chb_ctx *h, ShortlistArgs &pa, bool skip_on, bool pp_now)
         HIPCHK(d.viol.ensure(8));
         HIPCHK(hipMemsetAsync(d.viol.p, 0, 8 * sizeof(int), h->stream));
         pa.viol = d.viol.p;
-        pa.viol_rows = pp_now ? (long long)h->pp_arena_rows : (long long)h->N + 32LL * h->B + 64;
+        pa.viol_rows = pp_now ? (long long)h->pp.arena_rows : (long long)h->N + 32LL * h->B + 64;
         pa.viol_pool_rows = (long long)h->B * h->B * kPoolRows;
-        pa.viol_members = pp_now ? (long long)h->pp_arena_rows : (long long)h->N;
+        pa.viol_members = pp_now ? (long long)h->pp.arena_rows : (long long)h->N;
     }
     return CHB_OK;
 }
@@ -767,7 +801,7 @@ int dev_shortlist_report(chb_ctx *h, const ShortlistArgs &pa, bool skip_on, bool
         HIPCHK(hipMemcpy(hv, d.viol.p, sizeof(hv), hipMemcpyDeviceToHost));
         if (hv[0] != 0) {
             fprintf(stderr, "[chb bounds] code %d: %d %d %d %d %d %d (workgroup %d); skip %d pool %d pp %d K %d q %d..%d\n", hv[0], hv[1],
-                    hv[2], hv[3], hv[4], hv[5], hv[6], hv[7], (int)skip_on, (int)pool_on, (int)pp_now, h->K, h->q_lo, h->q_hi);
+                    hv[2], hv[3], hv[4], hv[5], hv[6], hv[7], (int)skip_on, (int)pool_on, (int)pp_now, h->batch.K, h->batch.q_lo, h->batch.q_hi);
             return fail(CHB_ESTATE, "shortlist bounds check failed");
         }
     }
@@ -786,7 +820,7 @@ int dev_shortlist_report(chb_ctx *h, const ShortlistArgs &pa, bool skip_on, bool
 int dev_shortlist_check(chb_ctx *h, bool skip_on, const int *qord)
 {
     auto &d = h->dk;
-    const int q_lo = h->q_lo, q_hi = h->q_hi;
+    const int q_lo = h->batch.q_lo, q_hi = h->batch.q_hi;
     if (d.inject_short > 0 && ++d.batches == d.inject_short)
         launch_inject_short(h->cand_cnt.p, h->B, h->Kcap, q_lo, h->bin_ptr.p, h->m, h->stream);
     if (!d.sl_validate) return CHB_OK;
@@ -803,7 +837,7 @@ int dev_shortlist_check(chb_ctx *h, bool skip_on, const int *qord)
         if (herr[0] >= 5 && skip_on && q_hi - q_lo <= 256) {
             const int nq = q_hi - q_lo;
             std::vector<int> qo(nq);
-            HIPCHK(hipMemcpy(qo.data(), h->qord.p, 4 * (size_t)nq, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(qo.data(), h->seat.qord.p, 4 * (size_t)nq, hipMemcpyDeviceToHost));
             for (int i = 0; i < nq; ++i) fprintf(stderr, "  i %d qord %d\n", i, qo[i]);
         }
         return fail(CHB_ESTATE, "shortlist validation failed");
@@ -830,18 +864,18 @@ struct BatchPlan {
         fusedp = h->fused && !need_lists;
         pf_base_path = h->pf_fit && h->cand.p;
         // tile skipping: on until the fit's first batches have shown that it skips (next to) nothing
-        skip_on = pf_base_path && h->sw.allow_skip && h->nsh > 1 && h->skip_state >= 0 && h->ckey.p != nullptr;
+        skip_on = pf_base_path && h->sw.allow_skip && h->seat.nsh > 1 && h->seat.state >= 0 && h->seat.ckey.p != nullptr;
         // segmented bins: the plan is made by the CSR scan on the device, but only if the host will also enqueue the two
         // segment launches -- which it does when the bin sizes it saw last (one or two batches old) say that a bin may
         // have more than kSegMinTiles tiles and four times the average
-        if (pf_base_path && h->seg_gflag.p) {
-            sp.nseg = h->seg_nseg.p; sp.items = h->seg_items.p; sp.gflag = h->seg_gflag.p; sp.lists = h->seg_lists.p;
-            sp.cap = 16 * h->seg_gcap; sp.gcap = h->seg_gcap;
-            const long long est = (long long)h->hint_max_tiles * 3 / 2 + 8;
-            sp.launch = h->sw.allow_segments && h->Dz <= 160 && est > kSegMinTiles && est * h->B > 3LL * std::max(1, h->hint_total_tiles);
+        if (pf_base_path && h->seg.gflag.p) {
+            sp.nseg = h->seg.nseg.p; sp.items = h->seg.items.p; sp.gflag = h->seg.gflag.p; sp.lists = h->seg.lists.p;
+            sp.cap = 16 * h->seg.gcap; sp.gcap = h->seg.gcap;
+            const long long est = (long long)h->seg.hint_max_tiles * 3 / 2 + 8;
+            sp.launch = h->sw.allow_segments && h->Dz <= 160 && est > kSegMinTiles && est * h->B > 3LL * std::max(1, h->seg.hint_total_tiles);
         }
-        const bool swept = h->qord_cur != nullptr;   // (seated by the fit loop, for the whole sweep)
-        qord_p = swept ? h->qord_cur : h->qord.p; home_p = swept ? h->home_cur : h->home.p;
+        const bool swept = h->seat.qord_cur != nullptr;   // (seated by the fit loop, for the whole sweep)
+        qord_p = swept ? h->seat.qord_cur : h->seat.qord.p; home_p = swept ? h->seat.home_cur : h->seat.home.p;
     }
 };
 
@@ -849,21 +883,21 @@ struct BatchPlan {
 int settle_batch(chb_ctx *h, BatchPlan &p)
 {
     if (p.sp.launch) {
-        HIPCHK(h->seg_lists.ensure((size_t)h->seg_gcap * 16 * (size_t)h->Kcap * (size_t)shortlist_list_len(h->m)));
-        p.sp.lists = h->seg_lists.p;
+        HIPCHK(h->seg.lists.ensure((size_t)h->seg.gcap * 16 * (size_t)h->Kcap * (size_t)shortlist_list_len(h->m)));
+        p.sp.lists = h->seg.lists.p;
     }
     // the persistent base pack serves the fit loop's batches whenever the shortlist launch does not skip tiles (whose
     // shell order needs the rebuild); built / rebuilt only outside a look-ahead window
-    if (h->pp_fit && h->sw.pp_allowed && p.fusedp && p.pf_base_path && !p.skip_on) {
-        if ((!h->pp_valid || h->pp_rebuild) && g_gate.flag == nullptr) { const int r_ = pack_state_build(h); if (r_) return r_; }
-        p.pp_now = h->pp_valid;
+    if (h->pp.fit && h->sw.pp_allowed && p.fusedp && p.pf_base_path && !p.skip_on) {
+        if ((!h->pp.valid || h->pp.rebuild) && g_gate.flag == nullptr) { const int r_ = pack_state_build(h); if (r_) return r_; }
+        p.pp_now = h->pp.valid;
     }
-    if (!p.pp_now) h->pp_valid = false;   // (this batch's commit will not maintain the pack)
-    h->pp_batch = p.pp_now;
+    if (!p.pp_now) h->pp.valid = false;   // (this batch's commit will not maintain the pack)
+    h->pp.batch = p.pp_now;
     // threshold pools: the base shortlist launch streams a bin once where a pool tile gives the threshold
-    if (!(h->pool_fit && p.fusedp && p.pf_base_path)) h->pool_valid = false;   // (this batch will not maintain them)
-    if (h->pool_state < 0) h->pool_valid = false;                              // (turned off for this fit: no upkeep either)
-    p.pool_on = h->pool_valid && h->pool_state >= 0;
+    if (!(h->pool.fit && p.fusedp && p.pf_base_path)) h->pool.valid = false;   // (this batch will not maintain them)
+    if (h->pool.state < 0) h->pool.valid = false;                              // (turned off for this fit: no upkeep either)
+    p.pool_on = h->pool.valid && h->pool.state >= 0;
     return CHB_OK;
 }
 
@@ -874,23 +908,23 @@ void open_batch(chb_ctx *h, const BatchPlan &p)
     if (p.pp_now) {
         // the batch is opened (its members' rows become holes) and tiles per bin / statistics / segment plan written:
         // one launch instead of count + scan + fill + gather
-        Timed t(h, "bucket", (double)h->K);
-        launch_pack_state_start(h->pack_state(), h->pk.view(), h->D, h->Dz, h->labels.p, h->inb.p, h->bq_cur, h->K, h->lab_old.p,
-                                h->B, seg, h->fc_cur + kSlotMaxTiles, h->nflag.p, h->stream);
-        h->stats_pp_batches += 1;
+        Timed t(h, "bucket", (double)h->batch.K);
+        launch_pack_state_start(h->pp.view(), h->pk.view(), h->D, h->Dz, h->labels.p, h->inb.p, h->batch.bq_cur, h->batch.K, h->lab_old.p,
+                                h->B, seg, h->batch.fc_cur + kSlotMaxTiles, h->nflag.p, h->stream);
+        h->pp.stat_batches += 1;
     } else {
         // (the batch is opened -- labels remembered, members marked -- inside the CSR count's launch)
         Timed t(h, "bucket", (double)h->N);
         launch_bucket_base(h->labels.p, h->inb.p, (int)h->N, h->B, h->cnt.p, h->bin_ptr.p, h->cursor.p, h->memb_id.p,
-                           h->pk.pad_ptr.p, h->nflag.p, h->stream, h->bq_cur, h->K, h->lab_old.p, seg, h->fc_cur + kSlotMaxTiles,
-                           p.pf_base_path ? h->ms.p : nullptr, p.skip_on ? h->shell_inv.p : nullptr, p.skip_on ? h->nsh : 1);
+                           h->pk.pad_ptr.p, h->nflag.p, h->stream, h->batch.bq_cur, h->batch.K, h->lab_old.p, seg, h->batch.fc_cur + kSlotMaxTiles,
+                           p.pf_base_path ? h->ms.p : nullptr, p.skip_on ? h->seat.shell_inv.p : nullptr, p.skip_on ? h->seat.nsh : 1);
     }
-    if (h->pool_valid) {
+    if (h->pool.valid) {
         // (the batch's samples are marked: their slots in the pools are holes while it is open)
-        Timed t(h, "pool", (double)h->K);
-        launch_pool_open(h->pool_view(), h->inb.p, h->D, h->Dz, h->B, h->nflag2.p, h->stream);
+        Timed t(h, "pool", (double)h->batch.K);
+        launch_pool_open(h->pool.view(), h->inb.p, h->D, h->Dz, h->B, h->nflag2.p, h->stream);
     }
-    h->pool_holes = true;
+    h->pool.holes = true;
 }
 
 // what the base shortlist launch reads besides the CSR: the fit's overflow counter, a rebuilt CSR's pack, the queries' seats
@@ -904,27 +938,27 @@ void shortlist_inputs(chb_ctx *h, const BatchPlan &p)
         Timed t(h, "bucket", 0.0);
         launch_pack_build(h->Zs.p, h->ms.p, h->D, h->Dz, h->memb_id.p, h->bin_ptr.p, h->B, (int)h->N, h->pk.view(), p.skip_on, h->stream);
     }
-    if (!(p.skip_on || p.pool_on) || h->qord_cur != nullptr) return;   // (seated by position; done for the whole sweep)
+    if (!(p.skip_on || p.pool_on) || h->seat.qord_cur != nullptr) return;   // (seated by position; done for the whole sweep)
     Timed t(h, "bucket", 0.0);   // (the queries are seated in the order of their nearest bin centre)
-    launch_query_order(h->ckey.p, h->bq_cur, h->q_lo, h->q_hi, h->B, h->qord.p, h->home.p, h->stream);
+    launch_query_order(h->seat.ckey.p, h->batch.bq_cur, h->batch.q_lo, h->batch.q_hi, h->B, h->seat.qord.p, h->seat.home.p, h->stream);
 }
 
 int base_shortlist_args(chb_ctx *h, const BatchPlan &p, ShortlistArgs &pa)
 {
-    pa = h->shortlist_args(h->q_lo, h->q_hi);
+    pa = h->shortlist_args(h->batch.q_lo, h->batch.q_hi);
     pa.P = h->pk.view(); pa.bin_ptr = h->bin_ptr.p; pa.memb_id = h->memb_id.p;
     if (p.pp_now) {   // (a bin = its region: first row, tiles in use; a row's sample, -1 for a hole)
-        pa.P.pad_ptr = h->pp_start.p; pa.P.nt = h->pp_nt.p;
-        pa.bin_ptr = h->pp_start.p; pa.memb_id = h->pp_memb.p;
+        pa.P.pad_ptr = h->pp.start.p; pa.P.nt = h->pp.nt.p;
+        pa.bin_ptr = h->pp.start.p; pa.memb_id = h->pp.memb.p;
     }
     pa.cand = h->cand.p; pa.cand_cnt = h->cand_cnt.p; pa.cand_cap = kCandCap; pa.seg = p.sp;
     if (p.fusedp) pa.tau_out = h->tau.p;
-    if (p.sp.launch) h->stats_seg_batches += 1;
-    if (p.skip_on) { pa.qord = p.qord_p; pa.home = p.home_p; pa.skip = 1; pa.skip_stat = h->fc_cur + kSlotSkipped; }
+    if (p.sp.launch) h->seg.stat_batches += 1;
+    if (p.skip_on) { pa.qord = p.qord_p; pa.home = p.home_p; pa.skip = 1; pa.skip_stat = h->batch.fc_cur + kSlotSkipped; }
     if (p.pool_on) {
-        pa.qord = p.qord_p; pa.home = p.home_p; pa.ckey = h->ckey.p; pa.pool = h->pool_view();
-        pa.pool_stat = h->fc_cur + kSlotPoolCand;
-        h->stats_pool_batches += 1;
+        pa.qord = p.qord_p; pa.home = p.home_p; pa.ckey = h->seat.ckey.p; pa.pool = h->pool.view();
+        pa.pool_stat = h->batch.fc_cur + kSlotPoolCand;
+        h->pool.stat_batches += 1;
     }
     return dev_shortlist_args(h, pa, p.skip_on, p.pp_now);
 }
@@ -934,7 +968,7 @@ int base_shortlist_args(chb_ctx *h, const BatchPlan &p, ShortlistArgs &pa)
 int base_shortlist(chb_ctx *h, const BatchPlan &p, const ShortlistArgs &pa)
 {
     {
-        Timed t(h, "prefilter", (double)(h->q_hi - h->q_lo) * h->hint_base_members);
+        Timed t(h, "prefilter", (double)(h->batch.q_hi - h->batch.q_lo) * h->batch.hint_base_members);
         launch_shortlist(pa, h->flags64.p, sl_bpw(h), h->stream);
     }
     if (p.pool_on) {
@@ -952,9 +986,9 @@ int base_shortlist(chb_ctx *h, const BatchPlan &p, const ShortlistArgs &pa)
 int finish_base_lists(chb_ctx *h, const BatchPlan &p, TopmArgs a)
 {
     if (!p.fusedp) {
-        RescoreArgs ra = h->rescore_args(h->q_lo, h->q_hi);
+        RescoreArgs ra = h->rescore_args(h->batch.q_lo, h->batch.q_hi);
         ra.out = h->L0();
-        Timed t(h, "rescore", (double)(h->q_hi - h->q_lo) * h->B);
+        Timed t(h, "rescore", (double)(h->batch.q_hi - h->batch.q_lo) * h->B);
         launch_rescore(ra, h->stream);
     } else {
         // overflowed (query tile, bin) pairs: the brute-force kernel's exact top-m becomes the shortlist
@@ -972,7 +1006,7 @@ int finish_base_lists(chb_ctx *h, const BatchPlan &p, TopmArgs a)
 // no shortlist stage: the brute-force fp64 selection over all base members
 void base_topm_plain(chb_ctx *h, const TopmArgs &a)
 {
-    Timed t(h, "topm_base", (double)(h->q_hi - h->q_lo) * h->hint_base_members);
+    Timed t(h, "topm_base", (double)(h->batch.q_hi - h->batch.q_lo) * h->batch.hint_base_members);
     if (h->m > kMaxM) launch_topm_generic(a, h->stream); else launch_topm(a, h->stream);
 }
 
@@ -981,13 +1015,13 @@ void base_topm_plain(chb_ctx *h, const TopmArgs &a)
 int batch_begin_dev(chb_ctx *h, int K, int q_lo, int q_hi, bool need_lists)
 {
     BatchPlan p(h, need_lists);
-    h->lists_valid = !p.fusedp; h->K = K; h->q_lo = q_lo; h->q_hi = q_hi;
-    h->round_in_batch = 0; h->round_active = 0;
+    h->batch.lists_valid = !p.fusedp; h->batch.K = K; h->batch.q_lo = q_lo; h->batch.q_hi = q_hi;
+    h->batch.round_in_batch = 0; h->round_active = 0;
     { const int r_ = settle_batch(h, p); if (r_) return r_; }
     open_batch(h, p);
     TopmArgs a = h->topm_args(q_lo, q_hi);
     a.bin_ptr = h->bin_ptr.p; a.memb_id = h->memb_id.p; a.out = h->L0();
-    if (p.pp_now) { a.bin_ptr = h->pp_start.p; a.bin_cnt = h->pp_fill.p; a.memb_id = h->pp_memb.p; }
+    if (p.pp_now) { a.bin_ptr = h->pp.start.p; a.bin_cnt = h->pp.fill.p; a.memb_id = h->pp.memb.p; }
     if (p.pf_base_path) {
         ShortlistArgs pa{};
         shortlist_inputs(h, p);
@@ -997,7 +1031,7 @@ int batch_begin_dev(chb_ctx *h, int K, int q_lo, int q_hi, bool need_lists)
         if (r_) return r_;
     } else base_topm_plain(h, a);
     HIPCHK(hipGetLastError());
-    h->batch_open = true;
+    h->batch.open = true;
     return CHB_OK;
 }
 
@@ -1005,7 +1039,7 @@ int batch_begin_dev(chb_ctx *h, int K, int q_lo, int q_hi, bool need_lists)
 // the batch's own entries as a padded pack, and the update-mode shortlist launch over it, less its thresholds and candidates
 ShortlistArgs batch_entry_shortlist(chb_ctx *h, int lo, int hi)
 {
-    launch_pack_centered(h->X.p, h->D, h->Dp, h->memb2_id.p, h->memb2_code.p, h->bin_ptr2.p, h->B, 2 * h->K,
+    launch_pack_centered(h->X.p, h->D, h->Dp, h->memb2_id.p, h->memb2_code.p, h->bin_ptr2.p, h->B, 2 * h->batch.K,
                          h->centers.p, h->mu_g.p, h->shadow_scale, h->Dz, h->pk2.view(), h->stream);
     ShortlistArgs pa = h->shortlist_args(lo, hi);
     pa.P = h->pk2.view(); pa.bin_ptr = h->bin_ptr2.p; pa.memb_id = h->memb2_id.p; pa.update = true;
@@ -1017,11 +1051,11 @@ ShortlistArgs batch_entry_shortlist(chb_ctx *h, int lo, int hi)
 void round_fused(chb_ctx *h, int lo, int hi, TopmArgs a)
 {
     hipStream_t s = h->stream;
-    const int cur = h->round_in_batch & 1;
+    const int cur = h->batch.round_in_batch & 1;
     ShortlistArgs pa = batch_entry_shortlist(h, lo, hi);
     pa.tau_in = h->tau.p; pa.cand = h->candu[cur].p; pa.cand_cnt = h->candu_cnt[cur].p; pa.cand_cap = kCandCapU;
     {
-        Timed t(h, "prefilter_update", (double)(hi - lo) * h->hint_batch_entries);
+        Timed t(h, "prefilter_update", (double)(hi - lo) * h->batch.hint_batch_entries);
         launch_shortlist(pa, h->flags64.p, sl_bpw(h), s);
     }
     {
@@ -1033,9 +1067,9 @@ void round_fused(chb_ctx *h, int lo, int hi, TopmArgs a)
     }
     FusedArgs f = h->fused_args(lo, hi);
     f.cand = h->cand.p; f.cand_cnt = h->cand_cnt.p; f.candu = h->candu[cur].p; f.candu_cnt = h->candu_cnt[cur].p;
-    if (h->round_in_batch > 0) { f.candp = h->candu[cur ^ 1].p; f.candp_cnt = h->candu_cnt[cur ^ 1].p; }
+    if (h->batch.round_in_batch > 0) { f.candp = h->candu[cur ^ 1].p; f.candp_cnt = h->candu_cnt[cur ^ 1].p; }
     f.slow = h->slow.p; f.n_slow = h->n_slow.p; f.bin_ptr = h->bin_ptr.p; f.short_cnt = h->short_cnt.p;
-    if (h->pp_batch) f.bin_size = h->pp_live.p;
+    if (h->pp.batch) f.bin_size = h->pp.live.p;
     {
         Timed t(h, "hull_qp", (double)(hi - lo) * h->B);
         launch_hull_select_qp(f, h->sw.fused_stripe, h->sw.fused_ptr64, s);
@@ -1064,7 +1098,7 @@ int round_lists_shortlist(chb_ctx *h, int lo, int hi, const TopmArgs &a)
     ShortlistArgs pa = batch_entry_shortlist(h, lo, hi);
     pa.seed = h->L0(); pa.cand = h->cand.p; pa.cand_cnt = h->cand_cnt.p; pa.cand_cap = kCandCap;
     {
-        Timed t(h, "prefilter_update", (double)(hi - lo) * h->hint_batch_entries);
+        Timed t(h, "prefilter_update", (double)(hi - lo) * h->batch.hint_batch_entries);
         launch_shortlist(pa, h->flags64.p, sl_bpw(h), s);
         // the (position, bin) pairs with a non-empty shortlist, for rescore_kernel
         launch_compact_active(h->cand_cnt.p, lo, hi, h->B, h->Kcap, h->act_blk.p, h->active.p, h->n_active.p, s);
@@ -1090,7 +1124,7 @@ int round_lists_shortlist(chb_ctx *h, int lo, int hi, const TopmArgs &a)
 // list-based, brute force: the exact selection over all of the batch's entries
 void round_lists_plain(chb_ctx *h, int lo, int hi, const TopmArgs &a)
 {
-    Timed t(h, "topm_update", (double)(hi - lo) * h->hint_batch_entries);
+    Timed t(h, "topm_update", (double)(hi - lo) * h->batch.hint_batch_entries);
     if (h->m > kMaxM) launch_topm_generic(a, h->stream); else launch_topm(a, h->stream);
 }
 
@@ -1098,14 +1132,14 @@ void round_lists_plain(chb_ctx *h, int lo, int hi, const TopmArgs &a)
 int batch_round_dev(chb_ctx *h, int active)
 {
     hipStream_t s = h->stream;
-    const int lo = std::max(active, h->q_lo), hi = h->q_hi;
-    if (hi <= lo) launch_fill_i32(h->fc_cur + kSlotFirstChange, h->K, 1, s);
-    const bool fusedp = h->fused && h->lists_valid == false;
+    const int lo = std::max(active, h->batch.q_lo), hi = h->batch.q_hi;
+    if (hi <= lo) launch_fill_i32(h->batch.fc_cur + kSlotFirstChange, h->batch.K, 1, s);
+    const bool fusedp = h->fused && h->batch.lists_valid == false;
     if (hi > lo) {
         {
-            Timed t(h, "bucket", (double)h->K);
-            launch_bucket_batch(h->lab_prev.p, h->lab_old.p, h->bq_cur, h->K, h->B, h->cnt2.p, h->bin_ptr2.p, h->cursor2.p,
-                                h->memb2_id.p, h->memb2_code.p, h->pk2.pad_ptr.p, h->fc_cur + kSlotFirstChange,
+            Timed t(h, "bucket", (double)h->batch.K);
+            launch_bucket_batch(h->lab_prev.p, h->lab_old.p, h->batch.bq_cur, h->batch.K, h->B, h->cnt2.p, h->bin_ptr2.p, h->cursor2.p,
+                                h->memb2_id.p, h->memb2_code.p, h->pk2.pad_ptr.p, h->batch.fc_cur + kSlotFirstChange,
                                 fusedp ? h->n_slow.p : nullptr, h->nflag.p, s, (h->pf_fit && h->pk2.bb.p) ? h->pk2.bb.p : nullptr);
         }
         TopmArgs a = h->topm_args(lo, hi);
@@ -1118,47 +1152,47 @@ int batch_round_dev(chb_ctx *h, int active)
             QpArgs q = h->qp_args(lo, hi);
             q.lists = h->Lcur();
             // a (position, bin) whose vertex list is the one of the previous round keeps its distance
-            q.prev = h->round_in_batch > 0 ? h->Lprev() : Lists{nullptr, nullptr, nullptr};
+            q.prev = h->batch.round_in_batch > 0 ? h->Lprev() : Lists{nullptr, nullptr, nullptr};
             Timed t(h, "hull_qp", (double)(hi - lo) * h->B);
             if (h->m > kMaxM) launch_hull_generic(q, s); else launch_hull_qp(q, s);
         }
         {
             Timed t(h, "argmin", (double)(hi - lo));
             launch_argmin(h->dist.p, h->lab_old.p, h->lab_prev.p, lo, hi, h->B, h->lab_new.p, h->mind.p,
-                          h->want_margin ? h->mind2.p : nullptr, h->fc_cur + kSlotFirstChange, h->argmin_in_place, s);
+                          h->want_margin ? h->mind2.p : nullptr, h->batch.fc_cur + kSlotFirstChange, h->argmin_in_place, s);
         }
         h->stats[2] += (int64_t)(hi - lo) * h->B;
     }
     HIPCHK(hipGetLastError());
     h->stats[1] += 1;
-    h->round_in_batch += 1;
+    h->batch.round_in_batch += 1;
     return CHB_OK;
 }
 
 int batch_commit_dev(chb_ctx *h, const int *final_dev)
 {
     hipStream_t s = h->stream;
-    if (h->pp_batch)
+    if (h->pp.batch)
         // ... and the rows put back into the persistent pack (in place, or appended to the new bin), then full regions moved
-        launch_pack_state_commit(h->pack_state(), h->pk.view(), h->X.p, h->D, h->Dp, h->bq_cur, h->K, h->labels.p, h->B,
+        launch_pack_state_commit(h->pp.view(), h->pk.view(), h->X.p, h->D, h->Dp, h->batch.bq_cur, h->batch.K, h->labels.p, h->B,
                                  h->centers.p, h->mu_g.p, h->shadow_scale, h->Zs.p, h->Dz, h->ms.p, final_dev, h->lab_old.p,
                                  h->inb.p, s);
     else if (h->pf_fit && h->centers.p)
         // final labels out, batch marks cleared, and the members' shadow rows recomputed against their
         // new bin's centre: one launch
-        launch_sample_shadow(h->X.p, h->D, h->Dp, h->bq_cur, h->K, h->labels.p, h->B, h->centers.p, h->mu_g.p,
+        launch_sample_shadow(h->X.p, h->D, h->Dp, h->batch.bq_cur, h->batch.K, h->labels.p, h->B, h->centers.p, h->mu_g.p,
                              h->shadow_scale, h->Zs.p, h->Dz, h->ms.p, final_dev, h->inb.p, s);
     else
-        launch_batch_close(h->labels.p, h->inb.p, h->bq_cur, final_dev, h->K, s);
-    if (h->pool_valid) {
+        launch_batch_close(h->labels.p, h->inb.p, h->batch.bq_cur, final_dev, h->batch.K, s);
+    if (h->pool.valid) {
         // (labels and shadow rows are final: holes resolved, the batch's arrivals offered to their new bins' pools)
-        Timed t(h, "pool", (double)h->K);
-        launch_pool_commit(h->pool_view(), h->Zs.p, h->ms.p, h->qn.p, h->D, h->Dz, h->bq_cur, h->K, final_dev, h->lab_old.p,
-                           h->labels.p, h->B, h->pool_holes, s);
+        Timed t(h, "pool", (double)h->batch.K);
+        launch_pool_commit(h->pool.view(), h->Zs.p, h->ms.p, h->qn.p, h->D, h->Dz, h->batch.bq_cur, h->batch.K, final_dev, h->lab_old.p,
+                           h->labels.p, h->B, h->pool.holes, s);
     }
     HIPCHK(hipGetLastError());
-    h->batch_open = false;
-    h->pp_batch = false;
+    h->batch.open = false;
+    h->pp.batch = false;
     return CHB_OK;
 }
 
@@ -1197,12 +1231,12 @@ int fit_agree(chb_ctx *h, FitAgree *mine)
 {
     constexpr int W = FitAgree::W;
     const int world = h->world;
-    HIPCHK(h->agree.ensure((size_t)W * world));
+    HIPCHK(h->xchg.agree.ensure((size_t)W * world));
     std::vector<int> all((size_t)W * world, 0);
     memcpy(all.data() + (size_t)W * h->rank, mine->v, sizeof(int) * W);
-    HIPCHK(hipMemcpyAsync(h->agree.p + (size_t)W * h->rank, mine->v, sizeof(int) * W, hipMemcpyHostToDevice, h->stream));
-    { const int r_ = exchange_all_gather(h, h->agree.p, (size_t)W, sizeof(int), ncclInt32); if (r_) return r_; }
-    HIPCHK(hipMemcpyAsync(all.data(), h->agree.p, sizeof(int) * all.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->xchg.agree.p + (size_t)W * h->rank, mine->v, sizeof(int) * W, hipMemcpyHostToDevice, h->stream));
+    { const int r_ = exchange_all_gather(h, h->xchg.agree.p, (size_t)W, sizeof(int), ncclInt32); if (r_) return r_; }
+    HIPCHK(hipMemcpyAsync(all.data(), h->xchg.agree.p, sizeof(int) * all.size(), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     for (int r = 0; r < world; ++r)
         for (int k = 0; k < FitAgree::kEq; ++k)
@@ -1239,7 +1273,7 @@ int fit_check_args(chb_ctx *h, const int64_t *initial_bins, const int64_t *perms
     if (n_move > 0 && !perms) return fail(CHB_EINVAL, "perms is null");
     if (max_iter < 0 || n_move < 0 || n_move > h->N) return fail(CHB_EINVAL, "bad n_move/max_iter");
     HIPCHK(hipSetDevice(h->dev));
-    if (h->world > 1 && !h->comm && !h->hook) return fail(CHB_ESTATE, "world > 1 but chb_comm_init was not called");
+    if (h->world > 1 && !h->xchg.comm && !h->xchg.hook) return fail(CHB_ESTATE, "world > 1 but chb_comm_init was not called");
     if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
     // every permutation entry is range-checked BEFORE anything runs (a min / max pass the compiler vectorises), so a
     // bad entry in a late sweep cannot surface after earlier sweeps have already run; duplicates inside a sweep
@@ -1276,14 +1310,14 @@ struct FitScope {
     bool ok = false;
     FitScope(chb_ctx *h_, bool want_margin) : h(h_), skip(h_->sw.allow_skip), pack(h_->sw.pp_allowed), spec(h_->sw.speculate)
     {
-        h->want_margin = want_margin; h->pp_fit = true; h->pool_fit = true;
+        h->want_margin = want_margin; h->pp.fit_scope(true); h->pool.fit_scope(true);
     }
     ~FitScope()
     {
         g_gate = Gate{};
         h->sw.allow_skip = skip; h->sw.pp_allowed = pack; h->sw.speculate = spec;
-        h->pp_fit = false; h->pp_valid = false; h->pool_fit = false; h->pool_valid = false; h->qord_cur = nullptr; h->home_cur = nullptr;
-        if (!ok) { (void)hipStreamSynchronize(h->stream); h->fit_open = false; h->batch_open = false; }
+        h->pp.fit_scope(false); h->pool.fit_scope(false); h->seat.unseat();
+        if (!ok) { (void)hipStreamSynchronize(h->stream); h->fit_open = false; h->batch.open = false; }
         h->want_margin = false;
     }
 };
@@ -1298,10 +1332,10 @@ struct FitDev {
     static bool local_verdict(const chb_ctx *h) { return h->dk.local_verdict; }
     static void skip_stats(chb_ctx *h)
     {
-        if (h->dk.skip_stats_on) for (int k = 0; k < 3; ++k) launch_fill_i32(h->fc_cur + kSlotSkipped + k, h->dk.skip_stats[k], 1, h->stream);
+        if (h->dk.skip_stats_on) for (int k = 0; k < 3; ++k) launch_fill_i32(h->batch.fc_cur + kSlotSkipped + k, h->dk.skip_stats[k], 1, h->stream);
     }
     // CHB_PACK_REBUILD_AT=<rows>: rebuild (compact) the pack from that fill mark on -- tests of the rebuild path
-    static int64_t rebuild_mark(const chb_ctx *h) { return h->dk.pack_rebuild_at >= 0 ? h->dk.pack_rebuild_at : h->pp_mark; }
+    static int64_t rebuild_mark(const chb_ctx *h) { return h->dk.pack_rebuild_at >= 0 ? h->dk.pack_rebuild_at : h->pp.mark; }
     // CHB_DEV_ALL_DIST=<file> (tests/test_gpu_bin_distances.py; read per fit): with min_dist_out on one GPU, every hull distance
     // of each movable contig's last visit -- row perm[t0 + i] of an N x B float64 array (NaN rows for contigs never visited),
     // written raw to <file> when the fit succeeds.  (min_dist_out keeps the look-ahead off: nothing overwrites a batch's dist
@@ -1336,7 +1370,7 @@ struct FitDev {
     static bool hook_spec(const chb_ctx *) { return false; }
     static bool local_verdict(const chb_ctx *) { return false; }
     static void skip_stats(chb_ctx *) {}
-    static int64_t rebuild_mark(const chb_ctx *h) { return h->pp_mark; }
+    static int64_t rebuild_mark(const chb_ctx *h) { return h->pp.mark; }
     void all_begin(const chb_ctx *, bool) {}
     int all_rows(chb_ctx *, const int64_t *, int) { return CHB_OK; }
     int all_write() const { return CHB_OK; }
@@ -1348,29 +1382,21 @@ struct Geom { int64_t t0; int K, q_lo, q_hi, C; };
 
 // host-side batch state, saved where a look-ahead window opens (the device side of a gated-off batch never changed)
 struct LookaheadSnap {
-    int K, q_lo, q_hi, round_in_batch; bool lists_valid, batch_open, pp_batch, pp_valid, pool_valid; int *bq_cur, *fc_cur;
-    double hb, he; int64_t st[4]; size_t n_pending;
+    BatchState batch; bool pp_batch, pp_valid, pool_valid; std::array<int64_t, 4> stats; size_t n_pending;
     static LookaheadSnap save(const chb_ctx *h)
     {
-        LookaheadSnap v{h->K, h->q_lo, h->q_hi, h->round_in_batch, h->lists_valid, h->batch_open, h->pp_batch, h->pp_valid, h->pool_valid,
-                        h->bq_cur, h->fc_cur, h->hint_base_members, h->hint_batch_entries, {0, 0, 0, 0}, h->pending.size()};
-        memcpy(v.st, h->stats, sizeof(v.st));
-        return v;
+        return LookaheadSnap{h->batch, h->pp.batch, h->pp.valid, h->pool.valid, h->stats, h->prof.pending.size()};
     }
     void restore(chb_ctx *h) const
     {
-        h->K = K; h->q_lo = q_lo; h->q_hi = q_hi; h->round_in_batch = round_in_batch;
-        h->lists_valid = lists_valid; h->batch_open = batch_open; h->bq_cur = bq_cur; h->fc_cur = fc_cur;
-        h->pp_batch = pp_batch; h->pp_valid = pp_valid; h->pool_valid = pool_valid;
-        h->hint_base_members = hb; h->hint_batch_entries = he;
-        memcpy(h->stats, st, sizeof(st));
+        h->batch = batch; h->pp.batch = pp_batch; h->pp.valid = pp_valid; h->pool.valid = pool_valid; h->stats = stats;
         // the launches recorded inside the window were gated off (they returned at once): they are neither
         // launches nor work of the profile
-        for (size_t i = n_pending; i < h->pending.size(); ++i) {
-            (void)hipEventDestroy(h->pending[i].a);
-            (void)hipEventDestroy(h->pending[i].b);
+        for (size_t i = n_pending; i < h->prof.pending.size(); ++i) {
+            (void)hipEventDestroy(h->prof.pending[i].a);
+            (void)hipEventDestroy(h->prof.pending[i].b);
         }
-        if (h->pending.size() > n_pending) h->pending.resize(n_pending);
+        if (h->prof.pending.size() > n_pending) h->prof.pending.resize(n_pending);
     }
 };
 
@@ -1405,18 +1431,18 @@ struct FitRun {
     FitRun(chb_ctx *h_, const int64_t *perms_, int64_t n_move_, int max_iter_, int Kmax_, int64_t *labels_out_,
            double *min_dist_out_, double *margin_out_)
         : h(h_), perms(perms_), n_move(n_move_), max_iter(max_iter_), labels_out(labels_out_), min_dist_out(min_dist_out_), margin_out(margin_out_), N(h_->N), s(h_->stream), Kmax(Kmax_), world(h_->world),
-          xchg((h_->comm != nullptr || h_->hook != nullptr) && (h_->world > 1 || h_->sw.force_gather))
+          xchg((h_->xchg.comm != nullptr || h_->xchg.hook != nullptr) && (h_->world > 1 || h_->sw.force_gather))
     {
     }
 
     const int64_t *perm() const { return perms + (int64_t)it * n_move; }   // the current sweep's
     // the tag of the fit's next exchange (kind 1: a batch's label guess, 2: a round's labels)
-    int next_tag(int kind) { const int t = ((h->xseq & 0x7ffffff) << 4) | kind; h->xseq += 1; return t; }
+    int next_tag(int kind) { const int t = ((h->xchg.seq & 0x7ffffff) << 4) | kind; h->xchg.seq += 1; return t; }
 
     // ---- more than one rank: agree on the fit before its first collective (fit_agree)
     int fit_agree_switches(const int64_t *initial_bins)
     {
-        h->xseq = 0;
+        h->xchg.seq = 0;
         if (xchg) {
             FitAgree fa{};
             const uint64_t hp = hash_i64(perms, (int64_t)max_iter * n_move), hi_ = hash_i64(initial_bins, N);
@@ -1425,18 +1451,18 @@ struct FitRun {
                                            (int)(hp & 0x7fffffff), (int)((hp >> 32) & 0x7fffffff), (int)(hi_ & 0x7fffffff),
                                            (int)((hi_ >> 32) & 0x7fffffff)};
             memcpy(fa.v, eq, sizeof(eq));
-            fa.v[16] = h->skip_state; fa.v[17] = h->sw.speculate ? 1 : 0; fa.v[18] = h->sw.allow_skip ? 1 : 0; fa.v[19] = h->sw.pp_allowed ? 1 : 0;
-            fa.v[20] = h->pool_valid ? h->pool_state : -1;
+            fa.v[16] = h->seat.state; fa.v[17] = h->sw.speculate ? 1 : 0; fa.v[18] = h->sw.allow_skip ? 1 : 0; fa.v[19] = h->sw.pp_allowed ? 1 : 0;
+            fa.v[20] = h->pool.valid ? h->pool.state : -1;
             const int rc = fit_agree(h, &fa);
             if (rc) return rc;
-            h->skip_state = fa.v[16]; h->sw.speculate = fa.v[17] != 0; h->sw.allow_skip = fa.v[18] != 0; h->sw.pp_allowed = fa.v[19] != 0;
-            if (fa.v[20] < 0) { h->pool_state = -1; h->pool_valid = false; }
+            h->seat.state = fa.v[16]; h->sw.speculate = fa.v[17] != 0; h->sw.allow_skip = fa.v[18] != 0; h->sw.pp_allowed = fa.v[19] != 0;
+            if (fa.v[20] < 0) { h->pool.state = -1; h->pool.valid = false; }
         }
         // (look-ahead under an exchange: the RCCL all-gather sits on the context's stream, so the first-changed position of
         //  a round is computed on the device right behind it and feeds the same gate as on one GPU; every rank sees the same
         //  labels, hence the same verdict, and the all-gathers of a gated-off batch move identical bytes between the ranks'
         //  identical buffers.  The hook transport needs the host between rounds anyway.)
-        can_spec = h->sw.speculate && h->fused && (!xchg || (h->hook == nullptr && h->comm != nullptr) || FitDev::hook_spec(h)) &&
+        can_spec = h->sw.speculate && h->fused && (!xchg || (h->xchg.hook == nullptr && h->xchg.comm != nullptr) || FitDev::hook_spec(h)) &&
                    min_dist_out == nullptr;
         return CHB_OK;
     }
@@ -1506,9 +1532,9 @@ struct FitRun {
     // function of the sweep alone.  (Not for sweeps of thousands of tiny batches: those order theirs one by one.)
     int order_sweep()
     {
-        h->qord_cur = nullptr; h->home_cur = nullptr;
+        h->seat.unseat();
         batch_t0.clear();
-        if (!(h->pf_fit && h->fused && h->ckey.p != nullptr && n_move > 0 && (h->pool_valid || (h->sw.allow_skip && h->skip_state >= 0))))
+        if (!(h->pf_fit && h->fused && h->seat.ckey.p != nullptr && n_move > 0 && (h->pool.valid || (h->sw.allow_skip && h->seat.state >= 0))))
             return CHB_OK;
         std::vector<int4> geo;
         for (int64_t t = 0; t < n_move && geo.size() <= 4096;) {
@@ -1518,15 +1544,15 @@ struct FitRun {
             t += g.K;
         }
         if (geo.size() > 4096) { batch_t0.clear(); return CHB_OK; }
-        HIPCHK(h->geo_all.ensure(geo.size()));
-        HIPCHK(h->qord_all.ensure((size_t)n_move));
-        HIPCHK(h->home_all.ensure(geo.size() * (size_t)h->B));
+        HIPCHK(h->seat.geo_all.ensure(geo.size()));
+        HIPCHK(h->seat.qord_all.ensure((size_t)n_move));
+        HIPCHK(h->seat.home_all.ensure(geo.size() * (size_t)h->B));
         // (pinned staging: the previous sweep's upload from it completed before that sweep's final synchronisation)
-        HIPCHK(h->pin_geo.ensure(geo.size()));
-        memcpy(h->pin_geo.p, geo.data(), sizeof(int4) * geo.size());
-        HIPCHK(hipMemcpyAsync(h->geo_all.p, h->pin_geo.p, sizeof(int4) * geo.size(), hipMemcpyHostToDevice, s));
+        HIPCHK(h->seat.pin_geo.ensure(geo.size()));
+        memcpy(h->seat.pin_geo.p, geo.data(), sizeof(int4) * geo.size());
+        HIPCHK(hipMemcpyAsync(h->seat.geo_all.p, h->seat.pin_geo.p, sizeof(int4) * geo.size(), hipMemcpyHostToDevice, s));
         Timed t(h, "bucket", (double)n_move);
-        launch_query_order_sweep(h->ckey.p, h->perm.p, h->geo_all.p, (int)geo.size(), h->B, h->qord_all.p, h->home_all.p, s);
+        launch_query_order_sweep(h->seat.ckey.p, h->perm.p, h->seat.geo_all.p, (int)geo.size(), h->B, h->seat.qord_all.p, h->seat.home_all.p, s);
         return CHB_OK;
     }
 
@@ -1543,12 +1569,12 @@ struct FitRun {
             const int tag = next_tag(2);
             const bool first = active == 0;
             if (first) FitDev::skip_stats(h);
-            launch_xchg_pack(h->xg.p, h->rank, g.C, h->lab_new.p, tag, h->fc_cur, first, first && h->pp_batch, true, g.K, s);
-            { const int r_ = exchange_all_gather(h, h->xg.p, (size_t)(g.C + kXchgHdr), sizeof(int), ncclInt32); if (r_) return r_; }
-            launch_xchg_unpack(h->xg.p, world, g.C, g.K, tag, h->lab_new.p, h->lab_prev.p, active, h->fc_cur,
-                               first && !FitDev::local_verdict(h), h->xerr.p, s);
+            launch_xchg_pack(h->xchg.xg.p, h->rank, g.C, h->lab_new.p, tag, h->batch.fc_cur, first, first && h->pp.batch, true, g.K, s);
+            { const int r_ = exchange_all_gather(h, h->xchg.xg.p, (size_t)(g.C + kXchgHdr), sizeof(int), ncclInt32); if (r_) return r_; }
+            launch_xchg_unpack(h->xchg.xg.p, world, g.C, g.K, tag, h->lab_new.p, h->lab_prev.p, active, h->batch.fc_cur,
+                               first && !FitDev::local_verdict(h), h->xchg.xerr.p, s);
         }
-        HIPCHK(hipMemcpyAsync(h->fc_host + kSlotInts * slot_, h->fc_cur, kSlotHome * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h->fc_host + kSlotInts * slot_, h->batch.fc_cur, kSlotHome * sizeof(int), hipMemcpyDeviceToHost, s));
         HIPCHK(hipEventRecord(h->fc_event[slot_], s));
         return CHB_OK;
     }
@@ -1567,17 +1593,17 @@ struct FitRun {
     void note_verdict(const int *v, bool first_round)
     {
         // (bin sizes of that batch, for the segment decision of the batches still to be enqueued)
-        h->hint_max_tiles = v[kSlotMaxTiles]; h->hint_total_tiles = v[kSlotTotalTiles];
+        h->seg.hint_max_tiles = v[kSlotMaxTiles]; h->seg.hint_total_tiles = v[kSlotTotalTiles];
         // (the persistent pack's arena: rows handed out so far, as of that batch's start)
-        if (h->pp_valid && v[kSlotMark] > FitDev::rebuild_mark(h)) h->pp_rebuild = true;
+        if (h->pp.valid && v[kSlotMark] > FitDev::rebuild_mark(h)) h->pp.rebuild = true;
         if (!first_round) return;
         // (what the tile skipping of its shortlist launch achieved: a fit whose first batches skip next to nothing turns it off)
         if (v[kSlotSeen] > 0) {
-            h->skip_skipped += v[kSlotSkipped]; h->skip_seen += v[kSlotSeen]; h->skip_unloaded += v[kSlotUnloaded];
-            if (h->skip_state == 0 && ++h->skip_batches >= 3) {
+            h->seat.skipped += v[kSlotSkipped]; h->seat.seen += v[kSlotSeen]; h->seat.unloaded += v[kSlotUnloaded];
+            if (h->seat.state == 0 && ++h->seat.batches >= 3) {
                 // (it pays from a few per cent of the wave-tiles)
-                h->skip_state = ((h->skip_skipped + h->skip_unloaded) * 50 >= h->skip_seen + h->skip_unloaded) ? 1 : -1;
-                if (h->skip_state < 0) h->skip_off_key = skip_key(h);
+                h->seat.state = ((h->seat.skipped + h->seat.unloaded) * 50 >= h->seat.seen + h->seat.unloaded) ? 1 : -1;
+                if (h->seat.state < 0) h->seat.off_key = skip_key(h);
             }
         }
         // Where tile skipping never loads a third of a bin's tiles (500k x 140 x 128: 45 %), the threshold sweep is
@@ -1585,20 +1611,20 @@ struct FitRun {
         // shortlists, retries, label guesses that fail -- is higher than what they save (113 against 105 ms per
         // sweep there; 1M x 146 x 200, 19 % never loaded: 366 against 460): such a fit drops them
         // (checked per batch: sweep 1's first batches stream bins of a few tiles, nothing to go by)
-        if (h->skip_state == 1 && h->pool_state >= 0 && v[kSlotSeen] > 0) {
+        if (h->seat.state == 1 && h->pool.state >= 0 && v[kSlotSeen] > 0) {
             const long long un = v[kSlotUnloaded], sn = v[kSlotSeen];
-            if (un * 10 > 3 * (sn + un)) { h->pool_state = -1; h->pool_off_key = skip_key(h); }
+            if (un * 10 > 3 * (sn + un)) { h->pool.state = -1; h->pool.off_key = skip_key(h); }
         }
         // (threshold pools: candidates per pair of that batch's base shortlist launch, as sampled; a fit whose first
         //  batches admit far more than the exact threshold would -- overlapping bins -- goes back to the two sweeps
         //  -- checked for EVERY batch: the pools of sweep 1's first batches hold whole bins and say nothing yet)
-        if (h->pool_state >= 0 && v[kSlotPoolPairs] > 0) {
+        if (h->pool.state >= 0 && v[kSlotPoolPairs] > 0) {
             const long long pc = v[kSlotPoolCand], pp = v[kSlotPoolPairs];
-            h->pool_cand += pc; h->pool_pairs += pp;
-            if (++h->pool_batches >= 3 && h->pool_state == 0) h->pool_state = 1;
+            h->pool.cand += pc; h->pool.pairs += pp;
+            if (++h->pool.batches >= 3 && h->pool.state == 0) h->pool.state = 1;
             // (the benchmark configurations admit m + 0.1 .. m + 0.4 per pair; from m + 3 on the loose thresholds cost the
             //  update stage and the hull kernel more than the threshold sweep did)
-            if (pc > (long long)(h->m + 3) * pp) { h->pool_state = -1; h->pool_off_key = skip_key(h); }
+            if (pc > (long long)(h->m + 3) * pp) { h->pool.state = -1; h->pool.off_key = skip_key(h); }
         }
     }
 
@@ -1615,27 +1641,27 @@ struct FitRun {
     // batch start + guess + round 0, nothing read back
     int open_batch(const Geom &g, int slot_)
     {
-        h->bq_cur = h->perm.p + g.t0;   // the batch's sample indices: a window of the sweep's permutation
-        h->fc_cur = h->first_change.p + kSlotInts * slot_;
+        h->batch.bq_cur = h->perm.p + g.t0;   // the batch's sample indices: a window of the sweep's permutation
+        h->batch.fc_cur = h->first_change.p + kSlotInts * slot_;
         if (!batch_t0.empty()) {
             const size_t bi = (size_t)(std::lower_bound(batch_t0.begin(), batch_t0.end(), g.t0) - batch_t0.begin());
-            h->qord_cur = h->qord_all.p + g.t0 + g.q_lo; h->home_cur = h->home_all.p + bi * (size_t)h->B;
+            h->seat.qord_cur = h->seat.qord_all.p + g.t0 + g.q_lo; h->seat.home_cur = h->seat.home_all.p + bi * (size_t)h->B;
         }
-        h->hint_base_members = (double)((it == 0) ? assigned0 + g.t0 : labelled - g.K);
-        h->hint_batch_entries = (double)((it == 0) ? g.K : 2 * g.K);
+        h->batch.hint_base_members = (double)((it == 0) ? assigned0 + g.t0 : labelled - g.K);
+        h->batch.hint_batch_entries = (double)((it == 0) ? g.K : 2 * g.K);
         h->argmin_in_place = !xchg;
         int r = batch_begin_dev(h, g.K, g.q_lo, g.q_hi, false);
         if (r) return r;
-        h->pool_holes = sweep_has_labelled;   // (an all-unlabelled batch leaves no holes for its commit to look for)
+        h->pool.holes = sweep_has_labelled;   // (an all-unlabelled batch leaves no holes for its commit to look for)
         // starting labels of the rounds: last sweep's label, or for still-unlabelled contigs
         // (sweep 1) the bin whose m-th nearest outside member is closest
-        if (h->fused && !h->lists_valid) launch_guess_near(h->tau.p, h->lab_old.p, g.q_lo, g.q_hi, h->B, h->Kcap, h->lab_prev.p, s);
+        if (h->fused && !h->batch.lists_valid) launch_guess_near(h->tau.p, h->lab_old.p, g.q_lo, g.q_hi, h->B, h->Kcap, h->lab_prev.p, s);
         else launch_guess(h->l0d.p, h->l0c.p, h->lab_old.p, g.q_lo, g.q_hi, h->B, h->m, h->Kcap, h->lab_prev.p, s);
         if (xchg) {
             const int tag = next_tag(1);
-            launch_xchg_pack(h->xg.p, h->rank, g.C, h->lab_prev.p, tag, h->fc_cur, false, false, false, g.K, s);
-            { const int r_ = exchange_all_gather(h, h->xg.p, (size_t)(g.C + kXchgHdr), sizeof(int), ncclInt32); if (r_) return r_; }
-            launch_xchg_unpack(h->xg.p, world, g.C, g.K, tag, h->lab_prev.p, nullptr, 0, h->fc_cur, false, h->xerr.p, s);
+            launch_xchg_pack(h->xchg.xg.p, h->rank, g.C, h->lab_prev.p, tag, h->batch.fc_cur, false, false, false, g.K, s);
+            { const int r_ = exchange_all_gather(h, h->xchg.xg.p, (size_t)(g.C + kXchgHdr), sizeof(int), ncclInt32); if (r_) return r_; }
+            launch_xchg_unpack(h->xchg.xg.p, world, g.C, g.K, tag, h->lab_prev.p, nullptr, 0, h->batch.fc_cur, false, h->xchg.xerr.p, s);
         }
         r = batch_round_dev(h, 0);
         if (r) return r;
@@ -1655,9 +1681,9 @@ struct FitRun {
         if (!inflight) { rc = open_batch(g, slot); if (rc) return rc; }
         const int64_t t1 = g.t0 + K;
         // (a batch start that has to build or rebuild the persistent pack stays outside the look-ahead window)
-        const bool skip_would = h->sw.allow_skip && h->nsh > 1 && h->skip_state >= 0 && h->ckey.p != nullptr;
-        const bool pack_sync = h->pp_fit && h->sw.pp_allowed && h->fused && h->cand.p && !skip_would &&
-                               (!h->pp_valid || h->pp_rebuild);
+        const bool skip_would = h->sw.allow_skip && h->seat.nsh > 1 && h->seat.state >= 0 && h->seat.ckey.p != nullptr;
+        const bool pack_sync = h->pp.fit && h->sw.pp_allowed && h->fused && h->cand.p && !skip_would &&
+                               (!h->pp.valid || h->pp.rebuild);
         const bool spec = spec_ok && t1 < n_move && !pack_sync;
         LookaheadSnap snap{};
         if (spec) {
@@ -1750,20 +1776,20 @@ struct FitRun {
         if (h->fused && h->short_cnt.p)   // (spare words of the first verdict slot)
             HIPCHK(hipMemcpyAsync(h->fc_host + kSlotShortCnt, h->short_cnt.p, sizeof(int), hipMemcpyDeviceToHost, s));
         h->fc_host[kSlotPackErr] = 0;
-        if (h->pp_ctl.p)
-            HIPCHK(hipMemcpyAsync(h->fc_host + kSlotPackErr, h->pp_ctl.p + 2, sizeof(int), hipMemcpyDeviceToHost, s));
+        if (h->pp.ctl.p)
+            HIPCHK(hipMemcpyAsync(h->fc_host + kSlotPackErr, h->pp.ctl.p + 2, sizeof(int), hipMemcpyDeviceToHost, s));
         std::vector<int> xend;
         if (xchg) {
             // every rank's "a rank was out of step" record: all ranks then leave the sweep with the same status
             xend.assign((size_t)4 * world, 0);
-            HIPCHK(hipMemcpyAsync(h->agree.p + 4 * h->rank, h->xerr.p, 4 * sizeof(int), hipMemcpyDeviceToDevice, s));
-            { const int r_ = exchange_all_gather(h, h->agree.p, 4, sizeof(int), ncclInt32); if (r_) return r_; }
-            HIPCHK(hipMemcpyAsync(xend.data(), h->agree.p, sizeof(int) * xend.size(), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(h->xchg.agree.p + 4 * h->rank, h->xchg.xerr.p, 4 * sizeof(int), hipMemcpyDeviceToDevice, s));
+            { const int r_ = exchange_all_gather(h, h->xchg.agree.p, 4, sizeof(int), ncclInt32); if (r_) return r_; }
+            HIPCHK(hipMemcpyAsync(xend.data(), h->xchg.agree.p, sizeof(int) * xend.size(), hipMemcpyDeviceToHost, s));
         }
         HIPCHK(hipStreamSynchronize(s));
         for (int r = 0; r < (int)xend.size() / 4; ++r)
             if (xend[(size_t)4 * r] != 0) {
-                HIPCHK(hipMemsetAsync(h->xerr.p, 0, 4 * sizeof(int), s));
+                HIPCHK(hipMemsetAsync(h->xchg.xerr.p, 0, 4 * sizeof(int), s));
                 const int *e = xend.data() + 4 * r;
                 return fail(CHB_ESTATE, "internal error: the ranks' exchanges fell out of step (rank " + std::to_string(r) + " was at exchange " +
                                         std::to_string(e[1] >> 4) + " kind " + std::to_string(e[1] & 15) + " when rank " + std::to_string(e[3]) +
@@ -1772,11 +1798,9 @@ struct FitRun {
             }
         if (h->fc_host[kSlotPackErr] != 0)
             return fail(CHB_ESTATE, "internal error: the persistent member pack ran out of rows; labels not returned");
-        if (h->fused && h->short_cnt.p && h->fc_host[kSlotShortCnt] != 0) {
-            h->short_seen = h->fc_host[kSlotShortCnt];
+        if (h->fused && h->short_cnt.p && h->fc_host[kSlotShortCnt] != 0)
             return fail(CHB_ESTATE, "internal error: " + std::to_string(h->fc_host[kSlotShortCnt]) + " (position, bin) shortlists of this sweep came "
                         "out short of min(num_neighbors, bin size) candidates or held a wild index; labels not returned");
-        }
         // (one pass: change count, label count and the caller's int64 copy -- the last sweep's is what stays)
         const int *pb = h->pin_b.p;
         const int *pv = prev.data();
@@ -1830,13 +1854,13 @@ int chb_destroy(chb_ctx *h)
     if (!h) return CHB_OK;
     (void)hipSetDevice(h->dev);
     (void)hipStreamSynchronize(h->stream);
-    if (h->rc_copy) (void)hipStreamSynchronize(h->rc_copy);
+    if (h->rc.copy) (void)hipStreamSynchronize(h->rc.copy);
     drain_profile(h);
-    if (h->comm && rccl()) { (void)rccl()->CommDestroy(h->comm); h->comm = nullptr; }
+    if (h->xchg.comm && rccl()) { (void)rccl()->CommDestroy(h->xchg.comm); h->xchg.comm = nullptr; }
     // the handles without an owner; the buffers (DevBuf / PinBuf, PackBufs) free themselves when `delete h` destroys them
-    hipEvent_t ev[] = {h->rc_up[0], h->rc_up[1], h->rc_done[0], h->rc_done[1], h->rc_down[0], h->rc_down[1], h->fc_event[0], h->fc_event[1]};
+    hipEvent_t ev[] = {h->rc.up[0], h->rc.up[1], h->rc.done[0], h->rc.done[1], h->rc.down[0], h->rc.down[1], h->fc_event[0], h->fc_event[1]};
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    if (h->rc_copy) (void)hipStreamDestroy(h->rc_copy);
+    if (h->rc.copy) (void)hipStreamDestroy(h->rc.copy);
     if (h->fc_host) (void)hipHostFree(h->fc_host);
     (void)hipStreamDestroy(h->stream);
     delete h;
@@ -1865,14 +1889,14 @@ static int samples_upload(chb_ctx *h, const double *X, int64_t N, int64_t D, boo
                                 h->stream));
     }
     h->N = N; h->D = (int)D; h->Dp = Dp;
-    h->fit_open = false; h->batch_open = false; h->stepwise = false;
+    h->fit_open = false; h->batch.open = false; h->stepwise = false;
     return CHB_OK;
 }
 
 // everything that is a function of the resident X alone (global mean, scale, query-side shadow rows)
 static int samples_finish(chb_ctx *h)
 {
-    h->skip_off_key = -1; h->pool_off_key = -1;
+    h->seat.off_key = -1; h->pool.off_key = -1;
     const int64_t N = h->N, D = h->D;
     const int Dp = h->Dp;
     // the shortlist stage (prefilter_kernels.hip) keeps its query fragments in registers: D <= 157 in the narrow builds,
@@ -1936,7 +1960,7 @@ int chb_set_samples_device(chb_ctx *h, const double *X, int64_t N, int64_t D)
 int chb_bcast_samples(chb_ctx *h, const double *X, int64_t N, int64_t D, int root)
 {
     if (!h) return fail(CHB_EINVAL, "null context");
-    if (!h->comm) return fail(CHB_ESTATE, "chb_bcast_samples needs chb_comm_init (RCCL)");
+    if (!h->xchg.comm) return fail(CHB_ESTATE, "chb_bcast_samples needs chb_comm_init (RCCL)");
     if (root < 0 || root >= h->world) return fail(CHB_EINVAL, "bad root");
     // Every rank reports {its own status, N, D, root} BEFORE the collective: a rank that returned early (no matrix on the
     // root, an allocation that failed) or ranks that disagree about the shape would otherwise leave the others blocked in
@@ -1946,13 +1970,13 @@ int chb_bcast_samples(chb_ctx *h, const double *X, int64_t N, int64_t D, int roo
     {
         const std::string my_err = g_err;
         const int world = h->world;
-        HIPCHK(h->agree.ensure((size_t)4 * world));
+        HIPCHK(h->xchg.agree.ensure((size_t)4 * world));
         std::vector<int> all((size_t)4 * world, 0);
         int *mine = all.data() + 4 * h->rank;
         mine[0] = rc; mine[1] = (int)(N & 0x7fffffff); mine[2] = (int)(D & 0x7fffffff); mine[3] = root;
-        HIPCHK(hipMemcpyAsync(h->agree.p + 4 * h->rank, mine, 4 * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        NCCLCHK(rccl()->AllGather(h->agree.p + 4 * h->rank, h->agree.p, 4, ncclInt32, h->comm, h->stream));
-        HIPCHK(hipMemcpyAsync(all.data(), h->agree.p, sizeof(int) * all.size(), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(h->xchg.agree.p + 4 * h->rank, mine, 4 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        NCCLCHK(rccl()->AllGather(h->xchg.agree.p + 4 * h->rank, h->xchg.agree.p, 4, ncclInt32, h->xchg.comm, h->stream));
+        HIPCHK(hipMemcpyAsync(all.data(), h->xchg.agree.p, sizeof(int) * all.size(), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
         if (rc) return fail(rc, my_err);
         for (int r = 0; r < world; ++r) {
@@ -1965,7 +1989,7 @@ int chb_bcast_samples(chb_ctx *h, const double *X, int64_t N, int64_t D, int roo
         }
     }
     // the padded resident copy goes out as it lies on the root: one RCCL broadcast over xGMI
-    NCCLCHK(rccl()->Broadcast(h->X.p, h->X.p, (size_t)N * (size_t)h->Dp, ncclDouble, root, h->comm, h->stream));
+    NCCLCHK(rccl()->Broadcast(h->X.p, h->X.p, (size_t)N * (size_t)h->Dp, ncclDouble, root, h->xchg.comm, h->stream));
     return samples_finish(h);
 }
 
@@ -1975,9 +1999,9 @@ int chb_comm_info(chb_ctx *h, int *rank, int *world, int *comm_ranks, int *trans
     if (rank) *rank = h->rank;
     if (world) *world = h->world;
     int cnt = 0;
-    if (h->comm && rccl()) NCCLCHK(rccl()->CommCount(h->comm, &cnt));
+    if (h->xchg.comm && rccl()) NCCLCHK(rccl()->CommCount(h->xchg.comm, &cnt));
     if (comm_ranks) *comm_ranks = cnt;
-    if (transport) *transport = h->comm ? 1 : (h->hook ? 2 : 0);
+    if (transport) *transport = h->xchg.comm ? 1 : (h->xchg.hook ? 2 : 0);
     return CHB_OK;
 }
 
@@ -2014,7 +2038,7 @@ int chb_fit_begin(chb_ctx *h, int64_t B, const int64_t *initial_bins, int m)
     if (rc == CHB_OK) h->stepwise = true;
     // (the stepwise batches have no loop that reads the skip statistics and could turn the tile-skipping builds off
     //  where they do not pay: they run the ordinary builds)
-    if (rc == CHB_OK) h->skip_state = -1;
+    if (rc == CHB_OK) h->seat.state = -1;
     return rc;
 }
 
@@ -2022,7 +2046,7 @@ int chb_batch_begin(chb_ctx *h, const int64_t *perm_slice, int64_t K, int64_t q_
 {
     if (!h || !perm_slice) return fail(CHB_EINVAL, "null argument");
     if (!h->fit_open) return fail(CHB_ESTATE, "chb_fit_begin has not been called");
-    if (h->batch_open) return fail(CHB_ESTATE, "previous batch not committed");
+    if (h->batch.open) return fail(CHB_ESTATE, "previous batch not committed");
     if (K <= 0 || K > (1 << 24) || q_lo < 0 || q_hi > K || q_lo > q_hi)
         return fail(CHB_EINVAL, "bad batch geometry");
     HIPCHK(hipSetDevice(h->dev));
@@ -2040,8 +2064,8 @@ int chb_batch_begin(chb_ctx *h, const int64_t *perm_slice, int64_t K, int64_t q_
     }
     if ((int)K > h->Kcap) { int rc = ensure_batch_buffers(h, (int)K); if (rc) return rc; }
     std::vector<int> v = to_i32(perm_slice, (size_t)K);
-    h->bq_cur = h->bq.p;
-    HIPCHK(hipMemcpyAsync(h->bq_cur, v.data(), sizeof(int) * K, hipMemcpyHostToDevice, h->stream));
+    h->batch.bq_cur = h->bq.p;
+    HIPCHK(hipMemcpyAsync(h->batch.bq_cur, v.data(), sizeof(int) * K, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return batch_begin_dev(h, (int)K, (int)q_lo, (int)q_hi, false);
 }
@@ -2060,8 +2084,8 @@ int chb_batch_round(chb_ctx *h, const int64_t *lab_prev, int64_t active, int64_t
                     double *min_dist)
 {
     if (!h || !lab_prev || !lab_new) return fail(CHB_EINVAL, "null argument");
-    if (!h->batch_open) return fail(CHB_ESTATE, "no open batch");
-    const int K = h->K;
+    if (!h->batch.open) return fail(CHB_ESTATE, "no open batch");
+    const int K = h->batch.K;
     // (host checks before anything is enqueued: a refused call leaves the batch open and as it was)
     if (active < 0 || active > K) return fail(CHB_EINVAL, "active must be in [0, K]");
     // the rounds keep the distance of a (position, bin) pair whose candidates are those of the previous round: that round
@@ -2075,7 +2099,7 @@ int chb_batch_round(chb_ctx *h, const int64_t *lab_prev, int64_t active, int64_t
     h->argmin_in_place = false;
     int rc = batch_round_dev(h, (int)active);
     if (rc) return rc;
-    const int lo = std::max((int)active, h->q_lo), hi = h->q_hi;
+    const int lo = std::max((int)active, h->batch.q_lo), hi = h->batch.q_hi;
     if (hi > lo) {
         std::vector<int> ln((size_t)(hi - lo));
         HIPCHK(hipMemcpyAsync(ln.data(), h->lab_new.p + lo, sizeof(int) * (hi - lo), hipMemcpyDeviceToHost, h->stream));
@@ -2092,11 +2116,11 @@ int chb_batch_round(chb_ctx *h, const int64_t *lab_prev, int64_t active, int64_t
 int chb_batch_guess(chb_ctx *h, int64_t *guess)
 {
     if (!h || !guess) return fail(CHB_EINVAL, "null argument");
-    if (!h->batch_open) return fail(CHB_ESTATE, "no open batch");
+    if (!h->batch.open) return fail(CHB_ESTATE, "no open batch");
     HIPCHK(hipSetDevice(h->dev));
-    const int lo = h->q_lo, hi = h->q_hi;
+    const int lo = h->batch.q_lo, hi = h->batch.q_hi;
     if (hi <= lo) return CHB_OK;
-    if (h->fused && !h->lists_valid) launch_guess_near(h->tau.p, h->lab_old.p, lo, hi, h->B, h->Kcap, h->lab_prev.p, h->stream);
+    if (h->fused && !h->batch.lists_valid) launch_guess_near(h->tau.p, h->lab_old.p, lo, hi, h->B, h->Kcap, h->lab_prev.p, h->stream);
     else launch_guess(h->l0d.p, h->l0c.p, h->lab_old.p, lo, hi, h->B, h->m, h->Kcap, h->lab_prev.p, h->stream);
     HIPCHK(hipGetLastError());
     std::vector<int> g((size_t)(hi - lo));
@@ -2109,11 +2133,11 @@ int chb_batch_guess(chb_ctx *h, int64_t *guess)
 int chb_batch_commit(chb_ctx *h, const int64_t *final_labels)
 {
     if (!h || !final_labels) return fail(CHB_EINVAL, "null argument");
-    if (!h->batch_open) return fail(CHB_ESTATE, "no open batch");
-    { const int rc = check_label_range(final_labels, h->K, h->B, "final_labels"); if (rc) return rc; }
+    if (!h->batch.open) return fail(CHB_ESTATE, "no open batch");
+    { const int rc = check_label_range(final_labels, h->batch.K, h->B, "final_labels"); if (rc) return rc; }
     HIPCHK(hipSetDevice(h->dev));
-    std::vector<int> v = to_i32(final_labels, (size_t)h->K);
-    HIPCHK(hipMemcpyAsync(h->lab_prev.p, v.data(), sizeof(int) * h->K, hipMemcpyHostToDevice, h->stream));
+    std::vector<int> v = to_i32(final_labels, (size_t)h->batch.K);
+    HIPCHK(hipMemcpyAsync(h->lab_prev.p, v.data(), sizeof(int) * h->batch.K, hipMemcpyHostToDevice, h->stream));
     int rc = batch_commit_dev(h, h->lab_prev.p);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -2150,21 +2174,16 @@ int chb_fit_cluster_ex(chb_ctx *h, int64_t B, const int64_t *initial_bins, const
     if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }   // (an upload from pin_a may be in flight: the next call rewrites it)
     h->stepwise = false;
     FitScope scope(h, margin_out != nullptr);
-    h->stats_pp_batches = 0; h->stats_pp_builds = 0;
     // threshold pools: built from the initial labels (the CSR of the fit's start is still in place), unless an earlier fit
     // over the same samples, bins and neighbour count found that they do not pay (overlapping bins: long shortlists; or tile
     // skipping that never loads 30 % of the tiles)
-    h->stats_pool_batches = 0;
-    h->pool_state = (h->pool_off_key == skip_key(h)) ? -1 : 0;
-    h->pool_batches = 0; h->pool_cand = 0; h->pool_pairs = 0;
-    if (h->pool_state >= 0) { rc = pool_build(h); if (rc) return rc; }
+    h->pool.fit_reset(h->pool.off_key == skip_key(h));
+    if (h->pool.state >= 0) { rc = pool_build(h); if (rc) return rc; }
     const int Kmax = fit_default_batch(h, n_move, m, batch);
     h->last_batch = Kmax;
     rc = ensure_batch_buffers(h, Kmax);
     if (rc) return rc;
-    memset(h->stats, 0, sizeof(h->stats));
-    h->stats_seg_batches = 0;
-    h->stats_lookahead = 0; h->stats_lookahead_failed = 0;
+    h->stats.fill(0); h->seg.stat_batches = 0; h->stats_lookahead = 0; h->stats_lookahead_failed = 0;
 
     FitRun run(h, perms, n_move, max_iter, Kmax, labels_out, min_dist_out, margin_out);
     rc = run.fit_agree_switches(initial_bins);
@@ -2217,12 +2236,12 @@ int chb_topm_per_bin(chb_ctx *h, const int64_t *labels, int64_t B, int m, const 
         int K = 0;
         while (t0 + K < Q && K < Kmax && seen.insert(query_idx[t0 + K]).second) ++K;
         std::vector<int> v = to_i32(query_idx + t0, (size_t)K);
-        h->bq_cur = h->bq.p;
-        HIPCHK(hipMemcpyAsync(h->bq_cur, v.data(), sizeof(int) * K, hipMemcpyHostToDevice, s));
+        h->batch.bq_cur = h->bq.p;
+        HIPCHK(hipMemcpyAsync(h->batch.bq_cur, v.data(), sizeof(int) * K, hipMemcpyHostToDevice, s));
         rc = batch_begin_dev(h, K, 0, K, true);
         if (rc) return rc;
         // every other query of the chunk is an ordinary member: code "pos != i"
-        launch_bucket_batch(h->lab_old.p, nullptr, h->bq_cur, K, h->B, h->cnt2.p, h->bin_ptr2.p,
+        launch_bucket_batch(h->lab_old.p, nullptr, h->batch.bq_cur, K, h->B, h->cnt2.p, h->bin_ptr2.p,
                             h->cursor2.p, h->memb2_id.p, h->memb2_code.p, nullptr, nullptr, nullptr, nullptr, s);
         TopmArgs a = h->topm_args(0, K);
         a.bin_ptr = h->bin_ptr2.p; a.memb_id = h->memb2_id.p; a.memb_code = h->memb2_code.p;
@@ -2360,61 +2379,61 @@ hipError_t recruit_chunks(chb_ctx *h, RecruitArgs a, const double *Y, int64_t Q,
                           double *dist_out, double *min_dist_out, double *margin_out)
 {
 #define RCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
-    hipStream_t s = h->stream, c = h->rc_copy;
+    hipStream_t s = h->stream, c = h->rc.copy;
     const int64_t D = a.D, Dp = a.Dp, B = a.B;
     const int64_t n = (Q + chunk - 1) / chunk;
     auto rows = [&](int64_t k) { return (int)std::min<int64_t>(chunk, Q - k * chunk); };
     auto upload = [&](int64_t k) -> hipError_t {
         const int b = (int)(k & 1), nq = rows(k);
-        RCHK(hipEventSynchronize(h->rc_up[b]));          // the pinned half: its last upload (chunk k - 2) has left it
-        RCHK(hipStreamWaitEvent(c, h->rc_done[b], 0));   // the device half: the kernels of chunk k - 2 have read it
+        RCHK(hipEventSynchronize(h->rc.up[b]));          // the pinned half: its last upload (chunk k - 2) has left it
+        RCHK(hipStreamWaitEvent(c, h->rc.done[b], 0));   // the device half: the kernels of chunk k - 2 have read it
         for (int r0 = 0; r0 < nq; r0 += kRecruitPiece) {
             const int nr = std::min(kRecruitPiece, nq - r0);
-            double *dst = h->rc_hY[b].p + (size_t)r0 * Dp;
+            double *dst = h->rc.hY[b].p + (size_t)r0 * Dp;
             const double *src = Y + (k * chunk + r0) * D;
             for (int r = 0; r < nr; ++r, dst += Dp, src += D) {
                 memcpy(dst, src, sizeof(double) * D);
                 for (int64_t j = D; j < Dp; ++j) dst[j] = 0.0;
             }
-            RCHK(hipMemcpyAsync(h->rc_Y[b].p + (size_t)r0 * Dp, h->rc_hY[b].p + (size_t)r0 * Dp, sizeof(double) * (size_t)nr * Dp,
+            RCHK(hipMemcpyAsync(h->rc.Y[b].p + (size_t)r0 * Dp, h->rc.hY[b].p + (size_t)r0 * Dp, sizeof(double) * (size_t)nr * Dp,
                                 hipMemcpyHostToDevice, c));
         }
-        return hipEventRecord(h->rc_up[b], c);
+        return hipEventRecord(h->rc.up[b], c);
     };
     auto download = [&](int64_t k) -> hipError_t {
         const int b = (int)(k & 1), nq = rows(k);
-        RCHK(hipStreamWaitEvent(c, h->rc_done[b], 0));
+        RCHK(hipStreamWaitEvent(c, h->rc.done[b], 0));
         if (dist_out)
-            RCHK(hipMemcpyAsync(h->rc_hdist[b].p, h->rc_dist[b].p, sizeof(double) * (size_t)nq * (size_t)B, hipMemcpyDeviceToHost, c));
-        if (min_dist_out) RCHK(hipMemcpyAsync(h->rc_hmin[b].p, h->rc_min[b].p, sizeof(double) * nq, hipMemcpyDeviceToHost, c));
-        if (margin_out) RCHK(hipMemcpyAsync(h->rc_hmargin[b].p, h->rc_margin[b].p, sizeof(double) * nq, hipMemcpyDeviceToHost, c));
-        if (bin_out) RCHK(hipMemcpyAsync(h->rc_hbin[b].p, h->rc_bin[b].p, sizeof(int) * nq, hipMemcpyDeviceToHost, c));
-        return hipEventRecord(h->rc_down[b], c);
+            RCHK(hipMemcpyAsync(h->rc.hdist[b].p, h->rc.dist[b].p, sizeof(double) * (size_t)nq * (size_t)B, hipMemcpyDeviceToHost, c));
+        if (min_dist_out) RCHK(hipMemcpyAsync(h->rc.hmin[b].p, h->rc.min[b].p, sizeof(double) * nq, hipMemcpyDeviceToHost, c));
+        if (margin_out) RCHK(hipMemcpyAsync(h->rc.hmargin[b].p, h->rc.margin[b].p, sizeof(double) * nq, hipMemcpyDeviceToHost, c));
+        if (bin_out) RCHK(hipMemcpyAsync(h->rc.hbin[b].p, h->rc.bin[b].p, sizeof(int) * nq, hipMemcpyDeviceToHost, c));
+        return hipEventRecord(h->rc.down[b], c);
     };
     auto unpack = [&](int64_t k) -> hipError_t {
         const int b = (int)(k & 1), nq = rows(k);
         const int64_t t0 = k * chunk;
-        RCHK(hipEventSynchronize(h->rc_down[b]));
-        if (dist_out) memcpy(dist_out + t0 * B, h->rc_hdist[b].p, sizeof(double) * (size_t)nq * (size_t)B);
-        if (min_dist_out) memcpy(min_dist_out + t0, h->rc_hmin[b].p, sizeof(double) * nq);
-        if (margin_out) memcpy(margin_out + t0, h->rc_hmargin[b].p, sizeof(double) * nq);
+        RCHK(hipEventSynchronize(h->rc.down[b]));
+        if (dist_out) memcpy(dist_out + t0 * B, h->rc.hdist[b].p, sizeof(double) * (size_t)nq * (size_t)B);
+        if (min_dist_out) memcpy(min_dist_out + t0, h->rc.hmin[b].p, sizeof(double) * nq);
+        if (margin_out) memcpy(margin_out + t0, h->rc.hmargin[b].p, sizeof(double) * nq);
         if (bin_out)
-            for (int i = 0; i < nq; ++i) bin_out[t0 + i] = h->rc_hbin[b].p[i];
+            for (int i = 0; i < nq; ++i) bin_out[t0 + i] = h->rc.hbin[b].p[i];
         return hipSuccess;
     };
     RCHK(upload(0));
     for (int64_t k = 0; k < n; ++k) {
         const int b = (int)(k & 1), nq = rows(k);
-        RCHK(hipStreamWaitEvent(s, h->rc_up[b], 0));
-        RCHK(hipStreamWaitEvent(s, h->rc_down[b], 0));   // (chunk k - 2 has been copied out of this half's results)
-        a.Y = h->rc_Y[b].p; a.dist = h->rc_dist[b].p; a.nq = nq;
+        RCHK(hipStreamWaitEvent(s, h->rc.up[b], 0));
+        RCHK(hipStreamWaitEvent(s, h->rc.down[b], 0));   // (chunk k - 2 has been copied out of this half's results)
+        a.Y = h->rc.Y[b].p; a.dist = h->rc.dist[b].p; a.nq = nq;
         {
             Timed t(h, "recruit", (double)nq * (double)B);
             launch_recruit(a, s);
-            launch_recruit_reduce(h->rc_dist[b].p, nq, (int)B, h->rc_bin[b].p, h->rc_min[b].p, h->rc_margin[b].p, s);
+            launch_recruit_reduce(h->rc.dist[b].p, nq, (int)B, h->rc.bin[b].p, h->rc.min[b].p, h->rc.margin[b].p, s);
         }
         RCHK(hipGetLastError());
-        RCHK(hipEventRecord(h->rc_done[b], s));
+        RCHK(hipEventRecord(h->rc.done[b], s));
         if (k + 1 < n) RCHK(upload(k + 1));
         RCHK(download(k));
         if (k > 0) RCHK(unpack(k - 1));
@@ -2436,60 +2455,60 @@ int chb_recruit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const 
     if (D != h->D) return fail(CHB_EINVAL, "the rows must have the resident samples' number of columns");
     if (m > kMaxM) return fail(CHB_EUNSUPPORTED, "chb_recruit_rows supports at most 16 neighbours");
     if (B > kRecruitMaxBins) return fail(CHB_EUNSUPPORTED, "chb_recruit_rows supports at most 8192 bins");
-    if (h->batch_open || (h->fit_open && h->stepwise))
+    if (h->batch.open || (h->fit_open && h->stepwise))
         return fail(CHB_ESTATE, "a stepwise fit is open on this context (chb_fit_begin): chb_set_samples ends it");
     if (Q == 0) return CHB_OK;
     HIPCHK(hipSetDevice(h->dev));
     hipStream_t s = h->stream;
     const int64_t N = h->N;
     const int Dp = h->Dp;
-    if (!h->rc_copy) {
-        HIPCHK(hipStreamCreateWithFlags(&h->rc_copy, hipStreamNonBlocking));
+    if (!h->rc.copy) {
+        HIPCHK(hipStreamCreateWithFlags(&h->rc.copy, hipStreamNonBlocking));
         for (int i = 0; i < 2; ++i) {
-            HIPCHK(hipEventCreateWithFlags(&h->rc_up[i], hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&h->rc_done[i], hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&h->rc_down[i], hipEventDisableTiming));
+            HIPCHK(hipEventCreateWithFlags(&h->rc.up[i], hipEventDisableTiming));
+            HIPCHK(hipEventCreateWithFlags(&h->rc.done[i], hipEventDisableTiming));
+            HIPCHK(hipEventCreateWithFlags(&h->rc.down[i], hipEventDisableTiming));
         }
     }
     // CSR over the labels (host counting sort into pinned memory; members of a bin in index order -- the selection does
     // not depend on it)
-    HIPCHK(h->rc_hptr.ensure((size_t)B + 1));
-    int *ptr = h->rc_hptr.p;
+    HIPCHK(h->rc.hptr.ensure((size_t)B + 1));
+    int *ptr = h->rc.hptr.p;
     std::fill(ptr, ptr + B + 1, 0);
     for (int64_t i = 0; i < N; ++i)
         if (labels[i] >= 0 && labels[i] < B) ++ptr[labels[i] + 1];
     for (int64_t c = 0; c < B; ++c) ptr[c + 1] += ptr[c];
     const size_t n_memb = (size_t)std::max(ptr[B], 1);
-    HIPCHK(h->rc_hmemb.ensure(n_memb));
+    HIPCHK(h->rc.hmemb.ensure(n_memb));
     {
         std::vector<int> cur(ptr, ptr + B);
         for (int64_t i = 0; i < N; ++i)
-            if (labels[i] >= 0 && labels[i] < B) h->rc_hmemb.p[cur[(size_t)labels[i]]++] = (int)i;
+            if (labels[i] >= 0 && labels[i] < B) h->rc.hmemb.p[cur[(size_t)labels[i]]++] = (int)i;
     }
     const int64_t chunk = std::min<int64_t>(Q, kRecruitChunk);
     const int halves = Q > chunk ? 2 : 1;
-    HIPCHK(h->rc_ptr.ensure((size_t)B + 1));
-    HIPCHK(h->rc_memb.ensure(n_memb));
+    HIPCHK(h->rc.ptr.ensure((size_t)B + 1));
+    HIPCHK(h->rc.memb.ensure(n_memb));
     for (int i = 0; i < halves; ++i) {
-        HIPCHK(h->rc_Y[i].ensure((size_t)chunk * Dp));
-        HIPCHK(h->rc_hY[i].ensure((size_t)chunk * Dp));
-        HIPCHK(h->rc_dist[i].ensure((size_t)chunk * (size_t)B));
-        if (dist_out) HIPCHK(h->rc_hdist[i].ensure((size_t)chunk * (size_t)B));
-        HIPCHK(h->rc_bin[i].ensure((size_t)chunk));
-        HIPCHK(h->rc_hbin[i].ensure((size_t)chunk));
-        HIPCHK(h->rc_min[i].ensure((size_t)chunk));
-        HIPCHK(h->rc_hmin[i].ensure((size_t)chunk));
-        HIPCHK(h->rc_margin[i].ensure((size_t)chunk));
-        HIPCHK(h->rc_hmargin[i].ensure((size_t)chunk));
+        HIPCHK(h->rc.Y[i].ensure((size_t)chunk * Dp));
+        HIPCHK(h->rc.hY[i].ensure((size_t)chunk * Dp));
+        HIPCHK(h->rc.dist[i].ensure((size_t)chunk * (size_t)B));
+        if (dist_out) HIPCHK(h->rc.hdist[i].ensure((size_t)chunk * (size_t)B));
+        HIPCHK(h->rc.bin[i].ensure((size_t)chunk));
+        HIPCHK(h->rc.hbin[i].ensure((size_t)chunk));
+        HIPCHK(h->rc.min[i].ensure((size_t)chunk));
+        HIPCHK(h->rc.hmin[i].ensure((size_t)chunk));
+        HIPCHK(h->rc.margin[i].ensure((size_t)chunk));
+        HIPCHK(h->rc.hmargin[i].ensure((size_t)chunk));
     }
-    HIPCHK(hipMemcpyAsync(h->rc_ptr.p, ptr, sizeof(int) * ((size_t)B + 1), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->rc_memb.p, h->rc_hmemb.p, sizeof(int) * n_memb, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->rc.ptr.p, ptr, sizeof(int) * ((size_t)B + 1), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->rc.memb.p, h->rc.hmemb.p, sizeof(int) * n_memb, hipMemcpyHostToDevice, s));
     RecruitArgs a{};
-    a.X = h->X.p; a.D = h->D; a.Dp = Dp; a.bin_ptr = h->rc_ptr.p; a.memb_id = h->rc_memb.p;
+    a.X = h->X.p; a.D = h->D; a.Dp = Dp; a.bin_ptr = h->rc.ptr.p; a.memb_id = h->rc.memb.p;
     a.B = (int)B; a.m = m; a.metric = h->metric;
     const hipError_t e = recruit_chunks(h, a, Y, Q, chunk, bin_out, dist_out, min_dist_out, margin_out);
     if (e != hipSuccess) {   // nothing of this call stays in flight behind the error
-        (void)hipStreamSynchronize(h->rc_copy);
+        (void)hipStreamSynchronize(h->rc.copy);
         (void)hipStreamSynchronize(s);
         return fail(CHB_EHIP, hipGetErrorString(e));
     }
@@ -2551,10 +2570,10 @@ int chb_comm_init(chb_ctx *h, const char *id128, int rank, int world)
     if (world < 1 || rank < 0 || rank >= world) return fail(CHB_EINVAL, "bad rank/world");
     if (!rccl()) return fail(CHB_EUNSUPPORTED, "librccl could not be loaded");
     HIPCHK(hipSetDevice(h->dev));
-    if (h->comm) { (void)rccl()->CommDestroy(h->comm); h->comm = nullptr; }
+    if (h->xchg.comm) { (void)rccl()->CommDestroy(h->xchg.comm); h->xchg.comm = nullptr; }
     ncclUniqueId id;
     memcpy(id.internal, id128, NCCL_UNIQUE_ID_BYTES);
-    NCCLCHK(rccl()->CommInitRank(&h->comm, world, id, rank));
+    NCCLCHK(rccl()->CommInitRank(&h->xchg.comm, world, id, rank));
     h->rank = rank; h->world = world;
     h->Kcap = 0;
     return CHB_OK;
@@ -2565,8 +2584,8 @@ int chb_comm_init_hook(chb_ctx *h, int rank, int world, chb_allgather_fn fn, voi
     if (!h || !fn) return fail(CHB_EINVAL, "null argument");
     if (world < 1 || rank < 0 || rank >= world) return fail(CHB_EINVAL, "bad rank/world");
     HIPCHK(hipSetDevice(h->dev));
-    if (h->comm && rccl()) { (void)rccl()->CommDestroy(h->comm); h->comm = nullptr; }
-    h->hook = fn; h->hook_user = user;
+    if (h->xchg.comm && rccl()) { (void)rccl()->CommDestroy(h->xchg.comm); h->xchg.comm = nullptr; }
+    h->xchg.hook = fn; h->xchg.hook_user = user;
     h->rank = rank; h->world = world;
     h->Kcap = 0;
     return CHB_OK;
@@ -2575,13 +2594,13 @@ int chb_comm_init_hook(chb_ctx *h, int rank, int world, chb_allgather_fn fn, voi
 int chb_comm_destroy(chb_ctx *h)
 {
     if (!h) return CHB_OK;
-    h->hook = nullptr; h->hook_user = nullptr;
-    if (h->comm && rccl()) {
+    h->xchg.hook = nullptr; h->xchg.hook_user = nullptr;
+    if (h->xchg.comm && rccl()) {
         (void)hipSetDevice(h->dev);
         (void)hipStreamSynchronize(h->stream);
-        (void)rccl()->CommDestroy(h->comm);
+        (void)rccl()->CommDestroy(h->xchg.comm);
     }
-    h->comm = nullptr; h->rank = 0; h->world = 1;
+    h->xchg.comm = nullptr; h->rank = 0; h->world = 1;
     return CHB_OK;
 }
 
@@ -2652,7 +2671,7 @@ int chb_profile_enable(chb_ctx *h, int on)
 {
     if (!h) return fail(CHB_EINVAL, "null context");
     drain_profile(h);
-    h->prof = on < 0 ? 0 : (on > 2 ? 1 : on);
+    h->prof.level = on < 0 ? 0 : (on > 2 ? 1 : on);
     return CHB_OK;
 }
 
@@ -2660,7 +2679,7 @@ int chb_profile_reset(chb_ctx *h)
 {
     if (!h) return fail(CHB_EINVAL, "null context");
     drain_profile(h);
-    h->prof_acc.clear();
+    h->prof.acc.clear();
     return CHB_OK;
 }
 
@@ -2670,93 +2689,74 @@ int chb_profile_get(chb_ctx *h, const char *kernel, double *total_ms, int64_t *l
     (void)hipStreamSynchronize(h->stream);
     drain_profile(h);
     ProfEntry e;
-    auto it = h->prof_acc.find(kernel);
-    if (it != h->prof_acc.end()) e = it->second;
+    auto it = h->prof.acc.find(kernel);
+    if (it != h->prof.acc.end()) e = it->second;
     if (total_ms) *total_ms = e.ms;
     if (launches) *launches = e.launches;
     if (work_units) *work_units = e.work;
     return CHB_OK;
 }
 
+// one device int, brought home on the context's stream (p == nullptr: 0)
+static int read_device_int(chb_ctx *h, const int *p, int64_t *out)
+{
+    int v = 0;
+    if (p) {
+        HIPCHK(hipMemcpyAsync(&v, p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    *out = v;
+    return CHB_OK;
+}
+
+// the base shortlists' lengths of the last batch, bin by bin (none without the shortlist stage or before the first batch)
+static int last_batch_cand_cnt(chb_ctx *h, std::vector<int> *cnt)
+{
+    if (!h->cand_cnt.p || h->batch.K <= 0) return CHB_OK;
+    std::vector<int> v((size_t)h->Kcap * h->B);
+    HIPCHK(hipMemcpyAsync(v.data(), h->cand_cnt.p, sizeof(int) * v.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int c = 0; c < h->B; ++c) cnt->insert(cnt->end(), v.begin() + (size_t)c * h->Kcap, v.begin() + (size_t)c * h->Kcap + h->batch.K);
+    return CHB_OK;
+}
+
+// the counters the host keeps
+#define CTR(name, expr) {name, [](const chb_ctx *h) -> int64_t { return expr; }}
+static const struct { const char *name; int64_t (*get)(const chb_ctx *); } kHostCounters[] = {
+    CTR("lookahead_batches", h->stats_lookahead), CTR("lookahead_failed", h->stats_lookahead_failed), CTR("exchanges", h->xchg.seq),
+    CTR("pack_incremental_batches", h->pp.stat_batches), CTR("pack_builds", h->pp.stat_builds),
+    CTR("pool_batches", h->pool.stat_batches), CTR("pool_state", h->pool.state), CTR("pool_candidates", h->pool.cand),
+    CTR("pool_pairs", h->pool.pairs), CTR("fused_enabled", h->fused ? 1 : 0), CTR("segment_batches", h->seg.stat_batches),
+    CTR("batch_size", h->last_batch),   // (speculative batch size of the last fit)
+    // tile skipping of the last fit: its verdict (0 undecided, 1 kept on, -1 turned off) and the sampled wave-tile counters
+    CTR("tile_skip_state", h->seat.state), CTR("tile_skipped", h->seat.skipped), CTR("tile_seen", h->seat.seen),
+    CTR("tile_unloaded", h->seat.unloaded), CTR("last_batch_k", h->batch.K),
+    CTR("recruit_chunk", kRecruitChunk),   // rows per launch of chb_recruit_rows
+    CTR("prefilter_enabled", (h->sw.use_prefilter && h->shadow_ok) ? 1 : 0),
+};
+#undef CTR
+
 int chb_counter(chb_ctx *h, const char *name, int64_t *out)
 {
     if (!h || !name || !out) return fail(CHB_EINVAL, "null argument");
     *out = 0;
-    if (!strcmp(name, "prefilter_overflow")) {
-        if (h->overflow.p && h->overflow_total_valid) {
-            int v = 0;
-            HIPCHK(hipMemcpyAsync(&v, h->overflow.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            *out = v;
-        }
+    if (!strcmp(name, "prefilter_overflow")) return read_device_int(h, h->overflow_total_valid ? h->overflow.p : nullptr, out);
+    // pairs of the last fit that broke the shortlist stage's contract (0, or the fit failed)
+    if (!strcmp(name, "shortlist_short")) return read_device_int(h, h->short_cnt.p, out);
+    // pairs the fused kernel left to the exact path
+    if (!strcmp(name, "slow_pairs_last_round")) return read_device_int(h, h->fused ? h->n_slow.p : nullptr, out);
+    // "shortlist_le<N>_last_batch": pairs of the last batch with <= N candidates
+    const bool sum = !strcmp(name, "shortlist_sum_last_batch"), le = !strncmp(name, "shortlist_le", 12);
+    if (sum || le || !strcmp(name, "shortlist_max_last_batch")) {
+        std::vector<int> cnt;
+        { const int rc = last_batch_cand_cnt(h, &cnt); if (rc) return rc; }
+        const int lim = le ? atoi(name + 12) : 0;
+        for (const int x : cnt)
+            *out = le ? *out + (x <= lim) : sum ? *out + x : std::max<int64_t>(*out, x);
         return CHB_OK;
     }
-    if (!strcmp(name, "lookahead_batches")) { *out = h->stats_lookahead; return CHB_OK; }
-    if (!strcmp(name, "lookahead_failed")) { *out = h->stats_lookahead_failed; return CHB_OK; }
-    if (!strcmp(name, "exchanges")) { *out = h->xseq; return CHB_OK; }
-    if (!strcmp(name, "pack_incremental_batches")) { *out = h->stats_pp_batches; return CHB_OK; }
-    if (!strcmp(name, "pack_builds")) { *out = h->stats_pp_builds; return CHB_OK; }
-    if (!strcmp(name, "pool_batches")) { *out = h->stats_pool_batches; return CHB_OK; }
-    if (!strcmp(name, "pool_state")) { *out = h->pool_state; return CHB_OK; }
-    if (!strcmp(name, "pool_candidates")) { *out = h->pool_cand; return CHB_OK; }
-    if (!strcmp(name, "pool_pairs")) { *out = h->pool_pairs; return CHB_OK; }
-    if (!strcmp(name, "shortlist_short")) {   // pairs of the last fit that broke the shortlist stage's contract (0, or the fit failed)
-        if (h->short_cnt.p) {
-            int v = 0;
-            HIPCHK(hipMemcpyAsync(&v, h->short_cnt.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            *out = v;
-        }
-        return CHB_OK;
-    }
-    if (!strcmp(name, "shortlist_sum_last_batch") || !strcmp(name, "shortlist_max_last_batch")) {
-        if (h->cand_cnt.p && h->K > 0) {
-            std::vector<int> v((size_t)h->Kcap * h->B);
-            HIPCHK(hipMemcpyAsync(v.data(), h->cand_cnt.p, sizeof(int) * v.size(), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            int64_t sum = 0, mx = 0;
-            for (int c = 0; c < h->B; ++c)
-                for (int i = 0; i < h->K; ++i) {
-                    const int x = v[(size_t)c * h->Kcap + i];
-                    sum += x; if (x > mx) mx = x;
-                }
-            *out = name[10] == 's' ? sum : mx;
-        }
-        return CHB_OK;
-    }
-    if (!strncmp(name, "shortlist_le", 12)) {   // "shortlist_le<N>_last_batch": pairs of the last batch with <= N candidates
-        const int lim = atoi(name + 12);
-        if (h->cand_cnt.p && h->K > 0) {
-            std::vector<int> v((size_t)h->Kcap * h->B);
-            HIPCHK(hipMemcpyAsync(v.data(), h->cand_cnt.p, sizeof(int) * v.size(), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            int64_t n = 0;
-            for (int c = 0; c < h->B; ++c)
-                for (int i = 0; i < h->K; ++i) n += v[(size_t)c * h->Kcap + i] <= lim;
-            *out = n;
-        }
-        return CHB_OK;
-    }
-    if (!strcmp(name, "slow_pairs_last_round")) {   // pairs the fused kernel left to the exact path
-        if (h->n_slow.p && h->fused) {
-            int v = 0;
-            HIPCHK(hipMemcpyAsync(&v, h->n_slow.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            *out = v;
-        }
-        return CHB_OK;
-    }
-    if (!strcmp(name, "fused_enabled")) { *out = h->fused ? 1 : 0; return CHB_OK; }
-    if (!strcmp(name, "segment_batches")) { *out = h->stats_seg_batches; return CHB_OK; }
-    // tile skipping of the last fit: its verdict (0 undecided, 1 kept on, -1 turned off) and the sampled wave-tile counters
-    if (!strcmp(name, "batch_size")) { *out = h->last_batch; return CHB_OK; }   // (speculative batch size of the last fit)
-    if (!strcmp(name, "tile_skip_state")) { *out = h->skip_state; return CHB_OK; }
-    if (!strcmp(name, "tile_skipped")) { *out = h->skip_skipped; return CHB_OK; }
-    if (!strcmp(name, "tile_seen")) { *out = h->skip_seen; return CHB_OK; }
-    if (!strcmp(name, "tile_unloaded")) { *out = h->skip_unloaded; return CHB_OK; }
-    if (!strcmp(name, "recruit_chunk")) { *out = kRecruitChunk; return CHB_OK; }   // rows per launch of chb_recruit_rows
-    if (!strcmp(name, "last_batch_k")) { *out = h->K; return CHB_OK; }
-    if (!strcmp(name, "prefilter_enabled")) { *out = (h->sw.use_prefilter && h->shadow_ok) ? 1 : 0; return CHB_OK; }
+    for (const auto &c : kHostCounters)
+        if (!strcmp(name, c.name)) { *out = c.get(h); return CHB_OK; }
     return fail(CHB_EINVAL, "unknown counter");
 }
 

@@ -25,7 +25,7 @@ COUNTERS = ("prefilter_overflow", "lookahead_batches", "lookahead_failed", "exch
             "segment_batches", "batch_size", "tile_skip_state", "tile_skipped", "tile_seen", "tile_unloaded", "last_batch_k",
             "prefilter_enabled")
 MUST_BE_SEEN = ("pack_incremental_batches", "pack_builds", "pool_batches", "segment_batches", "tile_seen",
-                "lookahead_batches", "launches:prefilter_retry", "launches:rescore", "launches:topm_base")
+                "lookahead_batches", "lookahead_failed", "launches:prefilter_retry", "launches:rescore", "launches:topm_base")
 
 # name, switches, (N, D, B, m), make_synthetic keywords, sweeps, batch, extra step ("topm": a chb_topm_per_bin query under
 # the final labels; "stepwise": one batch driven through chb_batch_begin / round / commit)
@@ -35,6 +35,9 @@ CASES = [
     ("odd_m15", {}, (700, 200, 4, 15), dict(seed=204, sigma=6e-3, mix=0.5, n_seed=3), 4, 150, "topm"),
     ("m20", {}, (600, 64, 4, 20), dict(seed=21, sigma=8e-3, mix=0.5, n_seed=24), 2, 200, None),
     ("lookahead", {}, (6000, 136, 12, 5), dict(seed=7, sigma=1.5e-3, mix=0.0), 3, 512, "stepwise"),
+    # overlapping bins in small batches (the data of tests/test_gpu_world2.py's SCHED_DATA): look-aheads that fail, so that
+    # the host state saved where the window opened is put back
+    ("lookahead_fails", {}, (3000, 136, 8, 5), dict(S=1, seed=3008, sigma=4.5e-3, mix=0.4, n_seed=8), 3, 32, None),
     ("pack", {"CHB_TILE_SKIP": "0"}, (6000, 136, 12, 5), dict(seed=6012, sigma=6e-3, mix=0.5, n_seed=12), 4, 512, None),
     ("pack_m15", {"CHB_TILE_SKIP": "0"}, (2500, 140, 9, 15), dict(S=5, seed=2509, sigma=4e-3, mix=0.3, n_seed=20), 3, 400, None),
     ("pack_off", {"CHB_TILE_SKIP": "0", "CHB_PACK_INCR": "0"}, (2500, 136, 9, 5), dict(seed=2509, sigma=4e-3, mix=0.3), 3, 400, None),
