@@ -7,12 +7,16 @@ HIP library or a GPU is missing.
 """
 from . import synth  # noqa: F401
 
-__all__ = ["synth", "recruit"]
+__all__ = ["synth", "recruit", "audit"]
 
 
 def __getattr__(name):
-    # chbin_amd.recruit = clustering.recruit, resolved on first use (importing the package stays free of ctypes work)
+    # chbin_amd.recruit = clustering.recruit, chbin_amd.audit = clustering.audit, resolved on first use (importing the
+    # package stays free of ctypes work)
     if name == "recruit":
         from .clustering import recruit
         return recruit
+    if name == "audit":
+        from .clustering import audit
+        return audit
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -42,6 +42,8 @@ SIGNATURES = {
                                    C.c_void_p, _i32p]),
     "chb_recruit_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "chb_audit_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "chb_find_nearest_from_row": (C.c_int, [C.c_void_p, C.c_int64, _i64p, _f64p, C.c_int64, C.c_int,
                                             _i64p, C.POINTER(C.c_int32)]),
     "chb_hull_distance_batch": (C.c_int, [C.c_void_p, _i64p, C.c_int64, _i64p, C.c_int, _f64p,
@@ -206,6 +208,28 @@ class Context:
         check(self._lib.chb_recruit_rows(self._h, labels.ctypes.data, int(B), int(m), Y.ctypes.data, Q, D,
                                          bins.ctypes.data, None if dist is None else dist.ctypes.data,
                                          mind.ctypes.data, margin.ctypes.data))
+        return bins, dist, mind, margin
+
+    def audit_rows(self, labels, B, m, rows=None, want_dist=True):
+        """chb_audit_rows: leave-one-out hull distance of the RESIDENT rows `rows` (sample indices, repeats allowed; None:
+        every row in order) to every bin of the frozen `labels`; a row is withheld from its own bin's candidates.
+        Returns (bins [Q], dist [Q, B] or None, min_dist [Q], margin [Q])."""
+        labels = np.ascontiguousarray(labels, dtype=np.int64)
+        if labels.shape != (self.N,):
+            raise ValueError("labels must have one entry per resident sample")
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.int64)
+            if rows.ndim != 1:
+                raise ValueError("rows must be a 1-D array of sample indices")
+        Q = self.N if rows is None else rows.shape[0]
+        bins = np.empty(Q, dtype=np.int64)
+        dist = np.empty((Q, int(B)), dtype=np.float64) if want_dist else None
+        mind = np.empty(Q, dtype=np.float64)
+        margin = np.empty(Q, dtype=np.float64)
+        check(self._lib.chb_audit_rows(self._h, labels.ctypes.data, int(B), int(m),
+                                       None if rows is None else rows.ctypes.data, Q,
+                                       bins.ctypes.data, None if dist is None else dist.ctypes.data,
+                                       mind.ctypes.data, margin.ctypes.data))
         return bins, dist, mind, margin
 
     def find_nearest_from_row(self, c, labels, row, m):

@@ -93,3 +93,35 @@ def recruit(
         bins, dist, _, _ = ctx.recruit_rows(labels, int(num_clusters), int(num_neighbors), rows,
                                             want_dist=return_distances)
     return (bins, dist) if return_distances else bins
+
+
+def audit(
+    samples: np.ndarray,
+    labels: np.ndarray,
+    num_clusters: int,
+    num_neighbors: int = 15,
+    metric: str = "convex",
+    qp_solver: str = "quadprog",
+    rows: np.ndarray = None,
+    return_distances: bool = False,
+):
+    """How well every contig sits in a finished labelling (no counterpart in the reference, which only logs "Exit due to
+    max iteration limit": algorithm.py:74-75): for every sample in `rows` (indices into `samples`; None: all of them) the
+    step of algorithm.py:49-58 against the frozen `labels` with that sample taken out of its own bin -- per bin the
+    `num_neighbors` nearest other members, the distance to their hull, the strict-'>' argmin over the bins.  Seeds,
+    unassigned rows and labellings that did not come from fit_cluster are scored alike.  Nothing changes.
+
+    Returns (bins, min_dist, margin) -- the bin the row would choose now (-1 where no bin has another member), its hull
+    distance, and the gap to the runner-up bin (+inf without one) -- and with return_distances also
+    distances [len(rows), num_clusters]."""
+    if metric not in ("convex", "affine", "affine-qp"):
+        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
+    check_solver(qp_solver)                                              # solve_qp.py:132
+
+    samples = np.ascontiguousarray(samples, dtype=np.float64)
+    ctx = default_context()
+    ctx.set_samples_cached(samples)
+    with ctx.using_metric(metric):
+        bins, dist, mind, margin = ctx.audit_rows(labels, int(num_clusters), int(num_neighbors), rows,
+                                                  want_dist=return_distances)
+    return (bins, mind, margin, dist) if return_distances else (bins, mind, margin)

@@ -252,12 +252,13 @@ struct Segments {
 // chb_recruit_rows: a chunk of the new rows (padded like X), its distances and row reductions, the call's CSR over the
 // labels -- the call's own buffers, nothing of a fit.  Two of each per-chunk buffer, on the device and pinned on the
 // host: while the kernels of chunk k run on the context's stream, copy brings chunk k + 1 up and chunk k - 1 down
-// (up / done / down: upload, kernels, download of the chunk in that half are through)
+// (up / done / down: upload, kernels, download of the chunk in that half are through).  chb_audit_rows runs through the
+// same buffers: what it sends up per chunk is qid, the chunk's sample indices, in place of Y.
 struct Recruit {
     DevBuf<double> Y[2], dist[2], min[2], margin[2];
-    DevBuf<int> bin[2], ptr, memb;
+    DevBuf<int> bin[2], qid[2], ptr, memb;
     PinBuf<double> hY[2], hdist[2], hmin[2], hmargin[2];
-    PinBuf<int> hbin[2], hptr, hmemb;
+    PinBuf<int> hbin[2], hqid[2], hptr, hmemb;
     hipStream_t copy = nullptr;
     hipEvent_t up[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr}, down[2] = {nullptr, nullptr};
 };
@@ -318,7 +319,7 @@ struct chb_ctx {
     int B = 0, m = 0;
     int metric = 0;   // CHB_METRIC_CONVEX / CHB_METRIC_AFFINE
     bool fit_open = false;
-    bool stepwise = false;   // the open fit was begun by chb_fit_begin (the caller drives its batches): chb_recruit_rows refuses
+    bool stepwise = false;   // the open fit was begun by chb_fit_begin (the caller drives its batches): chb_recruit_rows / chb_audit_rows refuse
     DevBuf<int> labels, inb;
     // batch buffers (the open batch itself: `batch`)
     int Kcap = 0;
@@ -2370,16 +2371,19 @@ namespace {
 
 constexpr int kRecruitPiece = 2048;   // rows per host-to-device copy of a chunk
 
-// The chunks of one chb_recruit_rows call, pipelined: the rows of chunk k are packed (zero-padded to Dp) into pinned
-// memory and copied up on rc_copy piece by piece, so the copy of a piece runs under the packing of the next; the kernels
-// run on the context's stream; the results come down on rc_copy into pinned memory and are unpacked by the host.  The
-// order of a step -- kernels of k, upload of k + 1, download of k, unpack of k - 1 -- keeps rc_copy from queueing an
-// upload behind a download that waits for kernels.  Everything asynchronous reads and writes context-owned memory.
-hipError_t recruit_chunks(chb_ctx *h, RecruitArgs a, const double *Y, int64_t Q, int64_t chunk, int64_t *bin_out,
-                          double *dist_out, double *min_dist_out, double *margin_out)
+// The chunks of one chb_recruit_rows or chb_audit_rows call, pipelined: the rows of chunk k are packed (zero-padded to
+// Dp) into pinned memory and copied up on rc_copy piece by piece, so the copy of a piece runs under the packing of the
+// next; the kernels run on the context's stream; the results come down on rc_copy into pinned memory and are unpacked by
+// the host.  The order of a step -- kernels of k, upload of k + 1, download of k, unpack of k - 1 -- keeps rc_copy from
+// queueing an upload behind a download that waits for kernels.  Everything asynchronous reads and writes context-owned
+// memory.  Y == nullptr is the audit: no row goes up, only the chunk's sample indices as int32 (row_idx, already checked
+// against N; nullptr: position = sample), and the kernel reads the rows from the resident matrix.
+hipError_t recruit_chunks(chb_ctx *h, RecruitArgs a, const double *Y, const int64_t *row_idx, int64_t Q, int64_t chunk,
+                          int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
 {
 #define RCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
     hipStream_t s = h->stream, c = h->rc.copy;
+    const bool audit = !Y;
     const int64_t D = a.D, Dp = a.Dp, B = a.B;
     const int64_t n = (Q + chunk - 1) / chunk;
     auto rows = [&](int64_t k) { return (int)std::min<int64_t>(chunk, Q - k * chunk); };
@@ -2387,6 +2391,13 @@ hipError_t recruit_chunks(chb_ctx *h, RecruitArgs a, const double *Y, int64_t Q,
         const int b = (int)(k & 1), nq = rows(k);
         RCHK(hipEventSynchronize(h->rc.up[b]));          // the pinned half: its last upload (chunk k - 2) has left it
         RCHK(hipStreamWaitEvent(c, h->rc.done[b], 0));   // the device half: the kernels of chunk k - 2 have read it
+        if (audit) {   // the chunk's sample indices and nothing else
+            int *ids = h->rc.hqid[b].p;
+            const int64_t t0 = k * chunk;
+            for (int i = 0; i < nq; ++i) ids[i] = (int)(row_idx ? row_idx[t0 + i] : t0 + i);
+            RCHK(hipMemcpyAsync(h->rc.qid[b].p, ids, sizeof(int) * nq, hipMemcpyHostToDevice, c));
+            return hipEventRecord(h->rc.up[b], c);
+        }
         for (int r0 = 0; r0 < nq; r0 += kRecruitPiece) {
             const int nr = std::min(kRecruitPiece, nq - r0);
             double *dst = h->rc.hY[b].p + (size_t)r0 * Dp;
@@ -2426,9 +2437,9 @@ hipError_t recruit_chunks(chb_ctx *h, RecruitArgs a, const double *Y, int64_t Q,
         const int b = (int)(k & 1), nq = rows(k);
         RCHK(hipStreamWaitEvent(s, h->rc.up[b], 0));
         RCHK(hipStreamWaitEvent(s, h->rc.down[b], 0));   // (chunk k - 2 has been copied out of this half's results)
-        a.Y = h->rc.Y[b].p; a.dist = h->rc.dist[b].p; a.nq = nq;
+        a.Y = audit ? nullptr : h->rc.Y[b].p; a.qid = audit ? h->rc.qid[b].p : nullptr; a.dist = h->rc.dist[b].p; a.nq = nq;
         {
-            Timed t(h, "recruit", (double)nq * (double)B);
+            Timed t(h, audit ? "audit" : "recruit", (double)nq * (double)B);
             launch_recruit(a, s);
             launch_recruit_reduce(h->rc.dist[b].p, nq, (int)B, h->rc.bin[b].p, h->rc.min[b].p, h->rc.margin[b].p, s);
         }
@@ -2442,22 +2453,11 @@ hipError_t recruit_chunks(chb_ctx *h, RecruitArgs a, const double *Y, int64_t Q,
 #undef RCHK
 }
 
-}  // namespace
-
-int chb_recruit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
-                     int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
+// What chb_recruit_rows and chb_audit_rows do once their arguments are checked: the CSR over the labels, the context's
+// chunk buffers, the pipelined chunks.  Y: the new rows (recruit), or nullptr for the resident rows row_idx (audit).
+int recruit_run(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, const int64_t *row_idx, int64_t Q,
+                int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
 {
-    if (!h) return fail(CHB_EINVAL, "null context");
-    if (Q < 0 || B < 1 || m < 1) return fail(CHB_EINVAL, "Q < 0, B < 1 or m < 1");
-    if (Q > 0 && (!labels || !Y)) return fail(CHB_EINVAL, "null argument");
-    if (!bin_out && !dist_out) return fail(CHB_EINVAL, "bin_out and dist_out are both null");
-    if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
-    if (D != h->D) return fail(CHB_EINVAL, "the rows must have the resident samples' number of columns");
-    if (m > kMaxM) return fail(CHB_EUNSUPPORTED, "chb_recruit_rows supports at most 16 neighbours");
-    if (B > kRecruitMaxBins) return fail(CHB_EUNSUPPORTED, "chb_recruit_rows supports at most 8192 bins");
-    if (h->batch.open || (h->fit_open && h->stepwise))
-        return fail(CHB_ESTATE, "a stepwise fit is open on this context (chb_fit_begin): chb_set_samples ends it");
-    if (Q == 0) return CHB_OK;
     HIPCHK(hipSetDevice(h->dev));
     hipStream_t s = h->stream;
     const int64_t N = h->N;
@@ -2490,8 +2490,13 @@ int chb_recruit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const 
     HIPCHK(h->rc.ptr.ensure((size_t)B + 1));
     HIPCHK(h->rc.memb.ensure(n_memb));
     for (int i = 0; i < halves; ++i) {
-        HIPCHK(h->rc.Y[i].ensure((size_t)chunk * Dp));
-        HIPCHK(h->rc.hY[i].ensure((size_t)chunk * Dp));
+        if (Y) {
+            HIPCHK(h->rc.Y[i].ensure((size_t)chunk * Dp));
+            HIPCHK(h->rc.hY[i].ensure((size_t)chunk * Dp));
+        } else {
+            HIPCHK(h->rc.qid[i].ensure((size_t)chunk));
+            HIPCHK(h->rc.hqid[i].ensure((size_t)chunk));
+        }
         HIPCHK(h->rc.dist[i].ensure((size_t)chunk * (size_t)B));
         if (dist_out) HIPCHK(h->rc.hdist[i].ensure((size_t)chunk * (size_t)B));
         HIPCHK(h->rc.bin[i].ensure((size_t)chunk));
@@ -2506,13 +2511,51 @@ int chb_recruit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const 
     RecruitArgs a{};
     a.X = h->X.p; a.D = h->D; a.Dp = Dp; a.bin_ptr = h->rc.ptr.p; a.memb_id = h->rc.memb.p;
     a.B = (int)B; a.m = m; a.metric = h->metric;
-    const hipError_t e = recruit_chunks(h, a, Y, Q, chunk, bin_out, dist_out, min_dist_out, margin_out);
+    const hipError_t e = recruit_chunks(h, a, Y, row_idx, Q, chunk, bin_out, dist_out, min_dist_out, margin_out);
     if (e != hipSuccess) {   // nothing of this call stays in flight behind the error
         (void)hipStreamSynchronize(h->rc.copy);
         (void)hipStreamSynchronize(s);
         return fail(CHB_EHIP, hipGetErrorString(e));
     }
     return CHB_OK;
+}
+
+}  // namespace
+
+int chb_recruit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
+                     int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
+{
+    if (!h) return fail(CHB_EINVAL, "null context");
+    if (Q < 0 || B < 1 || m < 1) return fail(CHB_EINVAL, "Q < 0, B < 1 or m < 1");
+    if (Q > 0 && (!labels || !Y)) return fail(CHB_EINVAL, "null argument");
+    if (!bin_out && !dist_out) return fail(CHB_EINVAL, "bin_out and dist_out are both null");
+    if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
+    if (D != h->D) return fail(CHB_EINVAL, "the rows must have the resident samples' number of columns");
+    if (m > kMaxM) return fail(CHB_EUNSUPPORTED, "chb_recruit_rows supports at most 16 neighbours");
+    if (B > kRecruitMaxBins) return fail(CHB_EUNSUPPORTED, "chb_recruit_rows supports at most 8192 bins");
+    if (h->batch.open || (h->fit_open && h->stepwise))
+        return fail(CHB_ESTATE, "a stepwise fit is open on this context (chb_fit_begin): chb_set_samples ends it");
+    if (Q == 0) return CHB_OK;
+    return recruit_run(h, labels, B, m, Y, nullptr, Q, bin_out, dist_out, min_dist_out, margin_out);
+}
+
+int chb_audit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const int64_t *row_idx, int64_t Q,
+                   int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
+{
+    if (!h) return fail(CHB_EINVAL, "null context");
+    if (Q < 0 || B < 1 || m < 1) return fail(CHB_EINVAL, "Q < 0, B < 1 or m < 1");
+    if (Q > 0 && !labels) return fail(CHB_EINVAL, "null argument");
+    if (!bin_out && !dist_out) return fail(CHB_EINVAL, "bin_out and dist_out are both null");
+    if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
+    if (m > kMaxM) return fail(CHB_EUNSUPPORTED, "chb_audit_rows supports at most 16 neighbours");
+    if (B > kRecruitMaxBins) return fail(CHB_EUNSUPPORTED, "chb_audit_rows supports at most 8192 bins");
+    if (h->batch.open || (h->fit_open && h->stepwise))
+        return fail(CHB_ESTATE, "a stepwise fit is open on this context (chb_fit_begin): chb_set_samples ends it");
+    if (Q == 0) return CHB_OK;
+    if (!row_idx && Q != h->N) return fail(CHB_EINVAL, "row_idx is null (all rows): Q must be the number of resident samples");
+    for (int64_t q = 0; row_idx && q < Q; ++q)
+        if (row_idx[q] < 0 || row_idx[q] >= h->N) return fail(CHB_EINVAL, "row_idx entry outside [0, N)");
+    return recruit_run(h, labels, B, m, nullptr, row_idx, Q, bin_out, dist_out, min_dist_out, margin_out);
 }
 
 int chb_find_nearest_from_row(chb_ctx *h, int64_t c, const int64_t *labels, const double *row,

@@ -342,20 +342,22 @@ void launch_hull_qp_indexed(const double *X, int D, int Dp, const int *q, const 
                             const int *hull_cnt, int P, int m_max, int metric, double *dist,
                             double *alpha, hipStream_t s);
 
-// ---- recruit (recruit_kernels.hip): hull distance of NEW rows Y (not samples) to every bin of a frozen labelling; reads
-// the resident matrix and the call's own CSR over the labels, nothing of a fit
+// ---- recruit and audit (recruit_kernels.hip): hull distance of NEW rows Y (not samples), or of resident rows with the
+// row itself left out, to every bin of a frozen labelling; reads the resident matrix and the call's own CSR over the
+// labels, nothing of a fit
 struct RecruitArgs {
     const double *X;       // [N][Dp] the resident samples
-    const double *Y;       // [nq][Dp] the rows to score, zero padded like X
+    const double *Y;       // [nq][Dp] the rows to score, zero padded like X (recruit; null for audit)
+    const int *qid;        // [nq] audit: position q scores the resident sample qid[q], withheld from its own lists; null for recruit
     int D, Dp, nq;
     const int *bin_ptr;    // [B+1] CSR over the labelled samples ...
     const int *memb_id;    // ... their sample indices, grouped by bin
     int B, m, metric;
     double *dist;          // [nq][B]
 };
-constexpr int kRecruitChunk = 16384;   // rows of Y uploaded and scored per launch
+constexpr int kRecruitChunk = 16384;   // rows of Y uploaded (recruit) or positions of row_idx (audit) scored per launch
 constexpr int kRecruitMaxBins = 8192;
-void launch_recruit(const RecruitArgs &a, hipStream_t s);
+void launch_recruit(const RecruitArgs &a, hipStream_t s);   // (a.qid set: the audit instantiation)
 // bin[q] = strict-'>' argmin over dist[q][0 .. B) (-1: all +inf), mind[q] its distance, margin[q] = runner-up minus it (+inf
 // without a finite runner-up)
 void launch_recruit_reduce(const double *dist, int nq, int B, int *bin, double *mind, double *margin, hipStream_t s);

@@ -1,9 +1,10 @@
-// Hull distances of NEW rows (not samples) to every bin of a frozen labelling (chb_recruit_rows) for gfx950.
+// Hull distances of rows to every bin of a frozen labelling for gfx950: NEW rows that are not samples
+// (chb_recruit_rows), or resident rows with the row itself left out (chb_audit_rows).
 //
 // What a fit does for a resident row -- find_nearest_from_cluster (distance_matrix.py:47-62) per bin, then
-// calculate_distance (hull_distance.py:90-108) to the hull of those members -- for rows Y that are not part of the
-// resident matrix, in ONE kernel and without any of the fit's state: no member codes, no "query is a member" exclusion,
-// no gate, no flag list, no shortlist stage.
+// calculate_distance (hull_distance.py:90-108) to the hull of those members -- in ONE kernel and without any of the
+// fit's state: no member codes, no gate, no flag list, no shortlist stage.  For rows Y that are not part of the resident
+// matrix nothing is excluded; for a resident row the only exclusion is the row's own sample index.
 //
 // One 256-thread workgroup owns (64 rows of Y) x (one bin), tile_kernel's pattern (topm_kernels.hip): the bin's members
 // are streamed in tiles of 64 rows, a 64 x 64 tile of squared distances is accumulated with a 4 x 4 register micro-tile
@@ -21,6 +22,9 @@
 //
 // A bin is never cut into member ranges: one bin of N members gives ceil(rows / 64) work items that each stream all N
 // member rows.  A second small kernel reduces each row of B distances to bin, minimum and margin.
+//
+// chb_audit_rows runs the same kernel body on RESIDENT rows (template parameter kResident): the rows to score are samples
+// named by index, and a row is withheld from its own bin's candidates -- the leave-one-out step of algorithm.py:49-58.
 #include "chb_internal.h"
 #include "hull_solve16.h"
 
@@ -50,6 +54,11 @@ union RecruitLds {
 };
 
 // (two wavefronts per SIMD, like tile_kernel: at the solver's three the tile loop's lists and micro-tile would spill)
+//
+// kResident (chb_audit_rows): position q of the chunk is the resident sample a.qid[q] -- its row is read from X, nothing
+// is uploaded -- and that sample alone is withheld from its own lists (leave-one-out: algorithm.py:50).  Everything else,
+// the arithmetic included, is the same code; the `false` instantiation is chb_recruit_rows' kernel unchanged.
+template <bool kResident>
 __global__ __launch_bounds__(256, 2) void recruit_kernel(RecruitArgs a, int nqt, int total)
 {
     __shared__ __attribute__((aligned(16))) RecruitLds lds;
@@ -79,7 +88,15 @@ __global__ __launch_bounds__(256, 2) void recruit_kernel(RecruitArgs a, int nqt,
     // staging role: thread (srow, skp) moves feature columns [2*skp, 2*skp+1] of one row per chunk
     int sq = pos0 + srow;
     if (sq >= a.nq) sq = a.nq - 1;
-    const double *qrow = a.Y + (size_t)sq * a.Dp + 2 * skp;
+    const double *qrow;
+    if constexpr (kResident) qrow = a.X + (size_t)a.qid[sq] * a.Dp + 2 * skp;
+    else qrow = a.Y + (size_t)sq * a.Dp + 2 * skp;
+    // the sample ids of my 4 rows (a position past the chunk's end scores nothing: any id will do)
+    int own[4];
+    if constexpr (kResident) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) own[i] = a.qid[min(pos0 + 4 * ty + i, a.nq - 1)];
+    }
     const double *prow = a.X + 2 * skp;
     const int nch = a.Dp / kKChunk;
     const int ntile = (nmem + kPTile - 1) / kPTile;
@@ -153,7 +170,9 @@ __global__ __launch_bounds__(256, 2) void recruit_kernel(RecruitArgs a, int nqt,
                 double s[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    s[j] = (qvalid && mid[j] >= 0) ? acc[i][j] : kInf;
+                    bool offer = qvalid && mid[j] >= 0;
+                    if constexpr (kResident) offer = offer && mid[j] != own[i];   // only the row itself: a twin stays
+                    s[j] = offer ? acc[i][j] : kInf;
                     acc[i][j] = 0.0;
                 }
                 select_into<16, 4>(s, mid, ld[i], li[i], lc[i], tau[i], m, tx, gbase);
@@ -179,7 +198,10 @@ __global__ __launch_bounds__(256, 2) void recruit_kernel(RecruitArgs a, int nqt,
             const int np = __shfl(n, 16 * p, 64);
             const int id = __shfl(idm, 16 * p + row, 64);
             if (np <= 0) continue;   // wave-uniform
-            const double *qptr = a.Y + (size_t)(pos0 + 4 * (4 * w + p) + i) * a.Dp + 4 * kq;   // (np > 0: a row of the chunk)
+            // (np > 0: a row of the chunk; its sample id sits in the registers of group p, row i of which is own[0] by now)
+            const double *qptr;
+            if constexpr (kResident) qptr = a.X + (size_t)__shfl(own[0], 16 * p, 64) * a.Dp + 4 * kq;
+            else qptr = a.Y + (size_t)(pos0 + 4 * (4 * w + p) + i) * a.Dp + 4 * kq;
             const double *vptr = id >= 0 ? a.X + (size_t)id * a.Dp + 4 * kq : qptr;
             f64x4 g = {0.0, 0.0, 0.0, 0.0}, d0 = g, d1 = g;
             gram_tile16_rows<false>(vptr, vptr, qptr, Dk, kq, g, d0, d1);
@@ -200,6 +222,7 @@ __global__ __launch_bounds__(256, 2) void recruit_kernel(RecruitArgs a, int nqt,
         __builtin_amdgcn_wave_barrier();   // the tiles are rewritten by the next row's phase 1
         nn[0] = nn[1]; nn[1] = nn[2]; nn[2] = nn[3];
         idv[0] = idv[1]; idv[1] = idv[2]; idv[2] = idv[3];
+        if constexpr (kResident) { own[0] = own[1]; own[1] = own[2]; own[2] = own[3]; }
     }
 }
 
@@ -246,7 +269,8 @@ void launch_recruit(const RecruitArgs &a, hipStream_t s)
     const int nqt = (a.nq + kQTile - 1) / kQTile;
     const int total = nqt * a.B;
     const int grid = ((total + 7) / 8) * 8;
-    hipLaunchKernelGGL(recruit_kernel, dim3(grid), dim3(256), 0, s, a, nqt, total);
+    if (a.qid) hipLaunchKernelGGL(recruit_kernel<true>, dim3(grid), dim3(256), 0, s, a, nqt, total);
+    else hipLaunchKernelGGL(recruit_kernel<false>, dim3(grid), dim3(256), 0, s, a, nqt, total);
 }
 
 void launch_recruit_reduce(const double *dist, int nq, int B, int *bin, double *mind, double *margin, hipStream_t s)

@@ -121,6 +121,33 @@ int chb_topm_per_bin(chb_ctx *h, const int64_t *labels, int64_t B, int m, const 
 int chb_recruit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q,
                      int64_t D, int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out);
 
+/* Audit of a finished labelling: leave-one-out hull distance of RESIDENT rows to every bin of a frozen labelling -- the
+ * step of algorithm.py:49-58 for sample r = row_idx[q] against `labels`, with nothing moved.
+ * For position q, sample r and bin c: among {p : labels[p] == c, p != r} the (up to) m members nearest to X[r] by
+ * (distance, index), distance = sqrt of the k-sequential unfused sum of squared differences (the arithmetic of
+ * chb_pairwise_distance, bit for bit); dist_out[q*B + c] = distance from X[r] to their hull under the context's metric
+ * (chb_set_metric); +inf for a bin without another member.
+ * Only sample r itself is withheld (as chb_topm_per_bin, algorithm.py:50): another sample with the same coordinates
+ * stays a candidate, at distance 0.  labels[r] may be anything -- movable, seed, unassigned, out of range; labels
+ * outside [0, B) count as unassigned.
+ * bin_out / min_dist_out / margin_out as in chb_recruit_rows: the strict-'>' scan over dist_out's row (lowest index among
+ * equal minima, -1 when every entry is +inf), its distance, and the margin to the runner-up (+inf without a finite
+ * runner-up, never inf - inf).  dist_out, min_dist_out, margin_out may each be NULL; bin_out may be NULL if dist_out is
+ * not.
+ * row_idx == NULL means all rows 0 .. N-1 in order, and Q must then be N (CHB_EINVAL otherwise).  Otherwise every
+ * row_idx[q] must lie in [0, N): checked on the host before anything is enqueued, CHB_EINVAL otherwise; repeats are
+ * allowed.  Q = 0 is a no-op, with row_idx == NULL too (the one case in which Q need not be N).
+ *   - limits: m <= 16 and B <= 8192, CHB_EUNSUPPORTED beyond; without resident samples CHB_ESTATE;
+ *   - like chb_recruit_rows the call reads the resident matrix and `labels` and nothing else: it uses no state of a fit and
+ *     leaves every counter, memo and switch of the context as it found it.  While a stepwise fit is open it is refused
+ *     with CHB_ESTATE and the fit stays usable;
+ *   - no row is uploaded: the positions are scored in chunks of 16384 (chb_counter "recruit_chunk") of which only the
+ *     sample indices go to the device, as int32; kernels on the context's stream, the result copies of the neighbouring
+ *     chunks under them on the context's second stream, through the pinned buffers chb_recruit_rows uses;
+ *   - one GPU: with a communicator (world > 1) each rank scores the positions it is given, there is no collective. */
+int chb_audit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const int64_t *row_idx, int64_t Q,
+                   int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out);
+
 /* distance_matrix.py:47-62 find_nearest_from_cluster with the reference's exact signature: the
  * caller supplies one row of a distance matrix (any provenance) and the current labels; selects
  * among {p : labels[p] == c} the (up to) m smallest by (row[p], p).  out_idx[m] (-1 padded). */
@@ -249,7 +276,8 @@ int chb_profile_reset(chb_ctx *h);
  * "pool" (upkeep of the shortlist stage's threshold pools: build once per fit, open + commit per batch) |
  * "prefilter_retry" (the exact two-sweep selection for the work items a pool batch's launch left on its overflow list) |
  * "pairwise" | "kmer_count" | "recruit" (chb_recruit_rows: selection + hull kernel and the row reduction of one chunk; work
- * units = (row, bin) pairs).  For m <= 16 "hull_qp" is the fused selection + hull-distance kernel and
+ * units = (row, bin) pairs) | "audit" (chb_audit_rows: the same pair of launches for one chunk of resident rows; work units
+ * = (row, bin) pairs).  For m <= 16 "hull_qp" is the fused selection + hull-distance kernel and
  * "slow_path" the exact path for what it leaves over; "rescore*" then only appear for m > 16 or CHB_FUSED=0. */
 int chb_profile_get(chb_ctx *h, const char *kernel, double *total_ms, int64_t *launches,
                     double *work_units);
@@ -273,7 +301,7 @@ int chb_fit_stats(chb_ctx *h, int64_t *out4);
  * batch needed further rounds), "pool_batches" (batches of the last fit whose base shortlist launch took its thresholds
  * from the pools), "pool_state" (0 undecided = on, 1 kept on, -1 turned off because the shortlists came out long),
  * "pool_candidates" / "pool_pairs" (sampled shortlist lengths behind that decision), "exchanges" (framed all-gathers of the last fit under an exchange: one per batch for the
- * label guess, one per round), "recruit_chunk" (rows per launch of chb_recruit_rows: a constant) */
+ * label guess, one per round), "recruit_chunk" (rows per launch of chb_recruit_rows and chb_audit_rows: a constant) */
 int chb_counter(chb_ctx *h, const char *name, int64_t *out);
 
 #ifdef __cplusplus
