@@ -75,6 +75,10 @@ SIGNATURES = {
     "chb_counter": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]),
     "chb_kmer_dim": (C.c_int, [C.c_int]),
     "chb_kmer_frequencies": (C.c_int, [C.c_void_p, C.c_char_p, _i64p, C.c_int64, C.c_int, _f64p, C.c_void_p]),
+    "chb_kmer_profile_dim": (C.c_int, [_i32p, C.c_int]),
+    "chb_kmer_profiles": (C.c_int, [C.c_void_p, C.c_char_p, _i64p, C.c_int64, _i32p, C.c_int, _f64p, C.c_void_p]),
+    "chb_set_samples_from_sequences": (C.c_int, [C.c_void_p, C.c_char_p, _i64p, C.c_int64, _i32p, C.c_int, C.c_void_p,
+                                                 C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
 }
 
 
@@ -404,6 +408,53 @@ class Context:
         check(self._lib.chb_kmer_frequencies(self._h, b"".join(bs), offsets, len(bs), int(k), freq.reshape(-1),
                                               counts.ctypes.data_as(C.c_void_p) if counts is not None else None))
         return (freq, counts) if return_counts else freq
+
+    @staticmethod
+    def _pack_sequences(sequences):
+        bs = [s.encode() if isinstance(s, str) else bytes(s) for s in sequences]
+        offsets = np.zeros(len(bs) + 1, dtype=np.int64)
+        if bs:
+            offsets[1:] = np.cumsum([len(b) for b in bs])
+        return b"".join(bs), offsets, len(bs)
+
+    def _profile_dim(self, ks):
+        ks = np.ascontiguousarray(list(ks), dtype=np.int32).reshape(-1)
+        dim = self._lib.chb_kmer_profile_dim(ks, len(ks))
+        if dim <= 0:
+            check(dim)
+        return ks, int(dim)
+
+    def kmer_profiles(self, sequences, ks, return_counts=False):
+        """chb_kmer_profiles: the k-mer blocks of the list `ks` side by side (list order), all counted in one pass."""
+        ks, dim = self._profile_dim(ks)
+        seq, offsets, n = self._pack_sequences(sequences)
+        freq = np.zeros((n, dim), dtype=np.float64)
+        counts = np.zeros((n, dim), dtype=np.uint32) if return_counts else None
+        check(self._lib.chb_kmer_profiles(self._h, seq, offsets, n, ks, len(ks), freq.reshape(-1),
+                                           counts.ctypes.data_as(C.c_void_p) if counts is not None else None))
+        return (freq, counts) if return_counts else freq
+
+    def set_samples_from_sequences(self, sequences, ks, extra=None, extra_row=None, return_matrix=False):
+        """chb_set_samples_from_sequences: the resident samples become [k-mer blocks of `ks` | extra[extra_row]], built
+        on the device.  extra: [n_extra, S] (coverage), extra_row: [n] rows of it (None: row i of extra for contig i)."""
+        ks, dim = self._profile_dim(ks)
+        seq, offsets, n = self._pack_sequences(sequences)
+        n_extra = S = 0
+        if extra is not None:
+            extra = np.ascontiguousarray(extra, dtype=np.float64)
+            if extra.ndim != 2:
+                raise ValueError("extra must be a 2-D array")
+            n_extra, S = extra.shape
+        if extra_row is not None:
+            extra_row = np.ascontiguousarray(extra_row, dtype=np.int64).reshape(-1)
+            if len(extra_row) != n:
+                raise ValueError("extra_row needs one entry per sequence")
+        X = np.empty((n, dim + S), dtype=np.float64) if return_matrix else None
+        check(self._lib.chb_set_samples_from_sequences(
+            self._h, seq, offsets, n, ks, len(ks), None if extra is None else extra.ctypes.data, n_extra, S,
+            None if extra_row is None else extra_row.ctypes.data, None if X is None else X.ctypes.data))
+        self.N, self.D = n, dim + S
+        return X
 
     def fit_stats(self):
         out = np.zeros(4, dtype=np.int64)

@@ -472,4 +472,29 @@ void launch_kmer_count(const unsigned char *seq, const long long *offsets, const
                        int n_items, int k, int ncanon, const unsigned short *canon, unsigned int *counts,
                        double *freq, hipStream_t s);
 
+// ---- the same for a list of k values in one pass (kmer_multi_kernels.hip)
+// the list as the kernels see it: the blocks of ks[0], ks[1], ... side by side in list order
+struct KmerMultiPlan {
+    int nk, kmin, kmax;
+    int total_dim;   // sum of dim[]
+    int copies;      // LDS histograms per workgroup: 4 (one per wavefront) while they fit 48 KB with the codes, else 1
+    int k[7], dim[7];
+    int col_off[7];  // first column of the block
+    int tab_off[7];  // first entry of the block's 4^k table in the concatenated table
+};
+// total_dim, *plan and (optional) the per-k tables of kmer_canonical_table back to back; -1: nk outside 1..7 or a
+// repeated k, -2: a k outside [1, 7]
+int kmer_multi_plan(const int *ks, int nk, KmerMultiPlan *plan, std::vector<unsigned short> *table);
+int kmer_multi_chunk_positions();
+// the sequence is uploaded in chunks of whole contigs: at most this many bases and this many contigs (a longer contig alone)
+constexpr long long kKmerChunkBytes = 32LL << 20;
+constexpr long long kKmerChunkRows = 16384;
+// counts[n][total_dim] (zeroed here); out[i * ld + ...] = every block divided by its own sum and, with extra != nullptr,
+// the S columns extra[extra_row ? extra_row[i] : first_row + i][S] behind them.  item_ptr[i] = first work item of contig
+// i (one item per kmer_multi_chunk_positions() start positions of the L - kmin + 1 that begin a k-mer), n_items = their total
+void launch_kmer_multi(const unsigned char *seq, const long long *offsets, const int *item_ptr, int n_contigs, int n_items,
+                       const KmerMultiPlan &plan, const unsigned short *canon, unsigned int *counts, double *out,
+                       long long ld, const double *extra, const long long *extra_row, long long first_row, int S,
+                       hipStream_t s);
+
 }  // namespace chb

@@ -19,6 +19,12 @@ def kmer_frequencies(sequences, k: int = 4, device=None, return_counts: bool = F
     return _lib.default_context(device).kmer_frequencies(sequences, k, return_counts=return_counts)
 
 
+def kmer_profiles(sequences, ks, device=None):
+    """[n, sum of dims] float64: the blocks of kmer_frequencies(sequences, k) for the k of the list `ks` side by side,
+    in list order, all counted in one pass over the sequences (the reference's KmerK list, cli/features.py:85-92)."""
+    return _lib.default_context(device).kmer_profiles(sequences, ks)
+
+
 def canonical_kmers(k: int):
     """Column labels: the canonical k-mers in column order (smaller 2-bit code of the k-mer and its
     reverse complement, A<C<G<T, ascending)."""

@@ -264,6 +264,36 @@ int chb_kmer_dim(int k);
  * counts_out (optional) [n * dim] raw counts.  Needs a context only for its device and stream. */
 int chb_kmer_frequencies(chb_ctx *h, const unsigned char *seq, const int64_t *offsets, int64_t n, int k,
                          double *freq_out, uint32_t *counts_out);
+/* The same for a LIST of k values counted in one pass (the reference's KmerK is a comma list, cli/features.py:85-92,128:
+ * `4,5` gives 648 columns, `3,4,5` gives 680): the sequence is uploaded once, its bases are staged once per 4096 start
+ * positions, and every start position serves all k of the list.  The blocks keep the order of ks[] (not sorted), and
+ * every block is bit-identical to what chb_kmer_frequencies returns for that k alone.
+ *   - the sequence goes up in chunks of whole contigs, at most 32 MiB of bases (chb_counter "kmer_chunk_bytes") and
+ *     16384 contigs (chb_counter "kmer_chunk_rows") each, a longer contig as a chunk of its own, one chunk after the other
+ *     on the context's stream (no copy / compute overlap): sequence, offsets, work-item table, row map and counts take
+ *     the device memory of ONE chunk however many contigs there are.  What does grow with the call is the output matrix
+ *     and, in chb_set_samples_from_sequences, the table `extra` (n_extra x S).  chb_counter "kmer_chunks" = chunks of
+ *     the last call;
+ *   - every argument check runs on the host before anything is enqueued. */
+/* sum of chb_kmer_dim over ks[0..nk); ks distinct, each in [1,7], 1 <= nk <= 7: CHB_EINVAL / CHB_EUNSUPPORTED otherwise */
+int chb_kmer_profile_dim(const int *ks, int nk);
+/* freq_out[n * dim]: the blocks of ks[0], ks[1], ... side by side, each normalised by its own total (a block without a
+ * valid window: zeros); counts_out (optional) the raw counts in the same layout.  seq / offsets as for
+ * chb_kmer_frequencies, and the same checks of them; n = 0 is a no-op. */
+int chb_kmer_profiles(chb_ctx *h, const unsigned char *seq, const int64_t *offsets, int64_t n,
+                      const int *ks, int nk, double *freq_out, uint32_t *counts_out);
+/* The same matrix built on the device, widened by S extra columns (coverage): row i = [k-mer blocks | extra[extra_row[i]]],
+ * D = dim + S, and made the context's resident samples exactly as chb_set_samples_device(h, that matrix, n, D) would: the
+ * matrix is built in a temporary device buffer and handed to the routine behind chb_set_samples_device (one device-to-
+ * device copy more than strictly needed, accepted so that padded rows, shadow rows, memos and the end of an open stepwise
+ * fit are the same state by construction).  No feature value crosses the host boundary.
+ * extra: host [n_extra][S], may be NULL with S = 0; extra_row[n] (NULL = identity, then n_extra == n); every entry in
+ * [0, n_extra), checked on the host before anything is enqueued: a refused call (those checks, a repeated or unsupported
+ * k, nk outside 1..7, S < 0, n <= 0) leaves the resident samples untouched.  X_out (optional, host, n * D): a copy of the
+ * matrix.  With a communicator every rank calls it for itself: there is no collective in it. */
+int chb_set_samples_from_sequences(chb_ctx *h, const unsigned char *seq, const int64_t *offsets, int64_t n,
+                                   const int *ks, int nk, const double *extra, int64_t n_extra, int64_t S,
+                                   const int64_t *extra_row, double *X_out);
 
 /* ---- measurement: HIP-event timing of kernel launches on the context's stream.
  * on = 0 off, 1 every kernel, 2 only "prefilter" and "hull_qp" (the two that dominate a sweep: four
@@ -275,7 +305,8 @@ int chb_profile_reset(chb_ctx *h);
  * "topm_fallback" | "topm_base" | "topm_update" | "hull_qp" | "slow_path" | "argmin" | "bucket" |
  * "pool" (upkeep of the shortlist stage's threshold pools: build once per fit, open + commit per batch) |
  * "prefilter_retry" (the exact two-sweep selection for the work items a pool batch's launch left on its overflow list) |
- * "pairwise" | "kmer_count" | "recruit" (chb_recruit_rows: selection + hull kernel and the row reduction of one chunk; work
+ * "pairwise" | "kmer_count" | "kmer_multi" (chb_kmer_profiles / chb_set_samples_from_sequences: the counting and the
+ * finalise launch of one chunk; work units = bases) | "recruit" (chb_recruit_rows: selection + hull kernel and the row reduction of one chunk; work
  * units = (row, bin) pairs) | "audit" (chb_audit_rows: the same pair of launches for one chunk of resident rows; work units
  * = (row, bin) pairs).  For m <= 16 "hull_qp" is the fused selection + hull-distance kernel and
  * "slow_path" the exact path for what it leaves over; "rescore*" then only appear for m > 16 or CHB_FUSED=0. */
@@ -301,7 +332,9 @@ int chb_fit_stats(chb_ctx *h, int64_t *out4);
  * batch needed further rounds), "pool_batches" (batches of the last fit whose base shortlist launch took its thresholds
  * from the pools), "pool_state" (0 undecided = on, 1 kept on, -1 turned off because the shortlists came out long),
  * "pool_candidates" / "pool_pairs" (sampled shortlist lengths behind that decision), "exchanges" (framed all-gathers of the last fit under an exchange: one per batch for the
- * label guess, one per round), "recruit_chunk" (rows per launch of chb_recruit_rows and chb_audit_rows: a constant) */
+ * label guess, one per round), "recruit_chunk" (rows per launch of chb_recruit_rows and chb_audit_rows: a constant),
+ * "kmer_chunk_bytes" / "kmer_chunk_rows" (the most bases / contigs of one sequence chunk of chb_kmer_profiles and
+ * chb_set_samples_from_sequences: constants), "kmer_chunks" (chunks of the last such call) */
 int chb_counter(chb_ctx *h, const char *name, int64_t *out);
 
 #ifdef __cplusplus
