@@ -7,16 +7,19 @@ HIP library or a GPU is missing.
 """
 from . import synth  # noqa: F401
 
-__all__ = ["synth", "recruit", "audit"]
+__all__ = ["synth", "recruit", "audit", "bin_report"]
 
 
 def __getattr__(name):
-    # chbin_amd.recruit = clustering.recruit, chbin_amd.audit = clustering.audit, resolved on first use (importing the
-    # package stays free of ctypes work)
+    # chbin_amd.recruit = clustering.recruit, chbin_amd.audit = clustering.audit, chbin_amd.bin_report =
+    # clustering.bin_report, resolved on first use (importing the package stays free of ctypes work)
     if name == "recruit":
         from .clustering import recruit
         return recruit
     if name == "audit":
         from .clustering import audit
         return audit
+    if name == "bin_report":
+        from .clustering import bin_report
+        return bin_report
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -44,6 +44,8 @@ SIGNATURES = {
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "chb_audit_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "chb_bin_report": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "chb_find_nearest_from_row": (C.c_int, [C.c_void_p, C.c_int64, _i64p, _f64p, C.c_int64, C.c_int,
                                             _i64p, C.POINTER(C.c_int32)]),
     "chb_hull_distance_batch": (C.c_int, [C.c_void_p, _i64p, C.c_int64, _i64p, C.c_int, _f64p,
@@ -235,6 +237,32 @@ class Context:
                                        bins.ctypes.data, None if dist is None else dist.ctypes.data,
                                        mind.ctypes.data, margin.ctypes.data))
         return bins, dist, mind, margin
+
+    def bin_report(self, labels, B, m, rows=None):
+        """chb_bin_report: chb_audit_rows' answer for the RESIDENT rows `rows` (None: every row in order) summed up on the
+        device per (own bin a, bin b) pair; rows whose own label lies outside [0, B) are not scored.
+        Returns (confusion [B, B], unplaced [B], dcnt [B, B], dmin [B, B], dsum [B, B], n_skipped)."""
+        labels = np.ascontiguousarray(labels, dtype=np.int64)
+        if labels.shape != (self.N,):
+            raise ValueError("labels must have one entry per resident sample")
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.int64)
+            if rows.ndim != 1:
+                raise ValueError("rows must be a 1-D array of sample indices")
+        Q = self.N if rows is None else rows.shape[0]
+        B = int(B)
+        nb = max(B, 0) if B <= 8192 else 0   # (beyond the limit the call is refused before it writes anything)
+        confusion = np.empty((nb, nb), dtype=np.int64)
+        unplaced = np.empty(nb, dtype=np.int64)
+        dcnt = np.empty((nb, nb), dtype=np.int64)
+        dmin = np.empty((nb, nb), dtype=np.float64)
+        dsum = np.empty((nb, nb), dtype=np.float64)
+        skipped = C.c_int64(0)
+        check(self._lib.chb_bin_report(self._h, labels.ctypes.data, B, int(m),
+                                       None if rows is None else rows.ctypes.data, Q,
+                                       confusion.ctypes.data, unplaced.ctypes.data, dcnt.ctypes.data, dmin.ctypes.data,
+                                       dsum.ctypes.data, C.addressof(skipped)))
+        return confusion, unplaced, dcnt, dmin, dsum, int(skipped.value)
 
     def find_nearest_from_row(self, c, labels, row, m):
         labels = np.ascontiguousarray(labels, dtype=np.int64)

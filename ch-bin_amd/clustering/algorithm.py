@@ -1,4 +1,5 @@
 """Mirror of ch_bin/core/clustering/algorithm.py."""
+import dataclasses
 import logging
 
 import numpy as np
@@ -125,3 +126,59 @@ def audit(
         bins, dist, mind, margin = ctx.audit_rows(labels, int(num_clusters), int(num_neighbors), rows,
                                                   want_dist=return_distances)
     return (bins, mind, margin, dist) if return_distances else (bins, mind, margin)
+
+
+@dataclasses.dataclass
+class BinReport:
+    """What bin_report returns: per (own bin a, bin b) pair of a labelling, over the scored rows of bin a --
+    confusion[a, b] rows that would choose bin b now, unplaced[a] rows that would choose none, dcnt / dmin / dsum[a, b]
+    count, minimum (+inf without one) and sum of their finite leave-one-out hull distances to bin b; n_skipped rows whose
+    own label lies outside [0, num_clusters) and were not scored."""
+    confusion: np.ndarray
+    unplaced: np.ndarray
+    dcnt: np.ndarray
+    dmin: np.ndarray
+    dsum: np.ndarray
+    n_skipped: int
+
+    @property
+    def mean(self) -> np.ndarray:
+        """dsum / dcnt: mean hull distance of bin a's rows to bin b; NaN where dcnt is 0."""
+        out = np.full(self.dsum.shape, np.nan)
+        np.divide(self.dsum, self.dcnt, out=out, where=self.dcnt > 0)
+        return out
+
+    def confused_pairs(self, min_share: float = 0.05):
+        """[(a, b, share)] with a != b and share = confusion[a, b] / (bin a's scored rows, the unplaced ones included)
+        >= min_share: bin a's rows that would rather sit in bin b.  Largest share first, then by (a, b)."""
+        total = self.confusion.sum(axis=1) + self.unplaced
+        pairs = []
+        for a, b in zip(*np.nonzero(self.confusion)):
+            share = self.confusion[a, b] / total[a]
+            if a != b and share >= min_share:
+                pairs.append((int(a), int(b), float(share)))
+        return sorted(pairs, key=lambda t: (-t[2], t[0], t[1]))
+
+
+def bin_report(
+    samples: np.ndarray,
+    labels: np.ndarray,
+    num_clusters: int,
+    num_neighbors: int = 15,
+    metric: str = "convex",
+    qp_solver: str = "quadprog",
+    rows: np.ndarray = None,
+) -> BinReport:
+    """Which bins of a finished labelling bleed into each other (no counterpart in the reference): `audit` for the samples
+    in `rows` (None: all of them), reduced on the device by each row's own label -- per bin pair how many rows of bin a
+    would choose bin b now, and count / minimum / sum of their hull distances to it.  Only the num_clusters x num_clusters
+    tables come back; rows without a label in [0, num_clusters) are not scored.  Nothing changes."""
+    if metric not in ("convex", "affine", "affine-qp"):
+        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
+    check_solver(qp_solver)                                              # solve_qp.py:132
+
+    samples = np.ascontiguousarray(samples, dtype=np.float64)
+    ctx = default_context()
+    ctx.set_samples_cached(samples)
+    with ctx.using_metric(metric):
+        return BinReport(*ctx.bin_report(labels, int(num_clusters), int(num_neighbors), rows))

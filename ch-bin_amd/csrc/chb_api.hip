@@ -26,6 +26,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <string>
 #include <unordered_set>
@@ -253,12 +254,18 @@ struct Segments {
 // labels -- the call's own buffers, nothing of a fit.  Two of each per-chunk buffer, on the device and pinned on the
 // host: while the kernels of chunk k run on the context's stream, copy brings chunk k + 1 up and chunk k - 1 down
 // (up / done / down: upload, kernels, download of the chunk in that half are through).  chb_audit_rows runs through the
-// same buffers: what it sends up per chunk is qid, the chunk's sample indices, in place of Y.
+// same buffers: what it sends up per chunk is qid, the chunk's sample indices, in place of Y.  chb_bin_report is an audit
+// whose chunks are cut from the positions in label order: per chunk seg (each label's run, BinReportArgs) goes up as
+// well, nothing comes down, and the B x B tables rep_* (zeroed at the call's start) collect what the chunks' rows say.
 struct Recruit {
     DevBuf<double> Y[2], dist[2], min[2], margin[2];
     DevBuf<int> bin[2], qid[2], ptr, memb;
     PinBuf<double> hY[2], hdist[2], hmin[2], hmargin[2];
     PinBuf<int> hbin[2], hqid[2], hptr, hmemb;
+    DevBuf<int2> seg[2];
+    PinBuf<int2> hseg[2];
+    DevBuf<long long> rep_conf, rep_unplaced, rep_cnt;
+    DevBuf<double> rep_min, rep_sum;
     hipStream_t copy = nullptr;
     hipEvent_t up[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr}, down[2] = {nullptr, nullptr};
 };
@@ -2372,37 +2379,79 @@ namespace {
 
 constexpr int kRecruitPiece = 2048;   // rows per host-to-device copy of a chunk
 
+// chb_bin_report's part of a recruit_run call: the scored positions (those whose own label lies in [0, B)) in label
+// order -- a stable counting sort, so a label's positions keep the order of row_idx -- and the chunks cut from that
+// order: at most kRecruitChunk positions each, cut back to the last kReportBlock-row block boundary of the label a cut
+// would split, so that no summation block of dsum (BinReportArgs) lies in two chunks.
+struct ReportPlan {
+    std::vector<int> ord;            // [Qv] sample index of every scored position, grouped by label
+    std::vector<int64_t> lab_ptr;    // [B + 1] label a's run is ord[lab_ptr[a] .. lab_ptr[a + 1])
+    std::vector<int64_t> cut;        // chunk k is ord[cut[k] .. cut[k + 1])
+    BinReportArgs tables{};          // the context's tables (conf, unplaced, cnt, dmin, dsum)
+    void cut_chunks()
+    {
+        const int64_t Qv = (int64_t)ord.size();
+        cut.assign(1, 0);
+        while (cut.back() < Qv) {
+            int64_t c1 = std::min<int64_t>(Qv, cut.back() + kRecruitChunk);
+            if (c1 < Qv) {   // inside (or at the start of) the label whose run holds position c1
+                const size_t l = (size_t)(std::upper_bound(lab_ptr.begin(), lab_ptr.end(), c1) - lab_ptr.begin()) - 1;
+                c1 -= (c1 - lab_ptr[l]) % kReportBlock;
+            }
+            cut.push_back(c1);
+        }
+    }
+};
+
 // The chunks of one chb_recruit_rows or chb_audit_rows call, pipelined: the rows of chunk k are packed (zero-padded to
 // Dp) into pinned memory and copied up on rc_copy piece by piece, so the copy of a piece runs under the packing of the
 // next; the kernels run on the context's stream; the results come down on rc_copy into pinned memory and are unpacked by
 // the host.  The order of a step -- kernels of k, upload of k + 1, download of k, unpack of k - 1 -- keeps rc_copy from
 // queueing an upload behind a download that waits for kernels.  Everything asynchronous reads and writes context-owned
 // memory.  Y == nullptr is the audit: no row goes up, only the chunk's sample indices as int32 (row_idx, already checked
-// against N; nullptr: position = sample), and the kernel reads the rows from the resident matrix.
+// against N; nullptr: position = sample), and the kernel reads the rows from the resident matrix.  With a plan (rp:
+// chb_bin_report) the positions are the plan's, chunk k is the plan's cut k, each label's run in the chunk goes up beside
+// the indices and bin_report_kernel folds the chunk into the plan's tables behind the two audit kernels.  Outputs that
+// have no destination are neither downloaded nor unpacked.
 hipError_t recruit_chunks(chb_ctx *h, RecruitArgs a, const double *Y, const int64_t *row_idx, int64_t Q, int64_t chunk,
-                          int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
+                          int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out, const ReportPlan *rp)
 {
 #define RCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
     hipStream_t s = h->stream, c = h->rc.copy;
     const bool audit = !Y;
+    const bool any_out = bin_out || dist_out || min_dist_out || margin_out;
     const int64_t D = a.D, Dp = a.Dp, B = a.B;
-    const int64_t n = (Q + chunk - 1) / chunk;
-    auto rows = [&](int64_t k) { return (int)std::min<int64_t>(chunk, Q - k * chunk); };
+    const int64_t n = rp ? (int64_t)rp->cut.size() - 1 : (Q + chunk - 1) / chunk;
+    auto start = [&](int64_t k) { return rp ? rp->cut[(size_t)k] : k * chunk; };
+    auto rows = [&](int64_t k) { return (int)(std::min<int64_t>(start(k + 1), Q) - start(k)); };
+    int nseg[2] = {0, 0};   // runs of the chunk in each half
     auto upload = [&](int64_t k) -> hipError_t {
         const int b = (int)(k & 1), nq = rows(k);
         RCHK(hipEventSynchronize(h->rc.up[b]));          // the pinned half: its last upload (chunk k - 2) has left it
         RCHK(hipStreamWaitEvent(c, h->rc.done[b], 0));   // the device half: the kernels of chunk k - 2 have read it
         if (audit) {   // the chunk's sample indices and nothing else
             int *ids = h->rc.hqid[b].p;
-            const int64_t t0 = k * chunk;
-            for (int i = 0; i < nq; ++i) ids[i] = (int)(row_idx ? row_idx[t0 + i] : t0 + i);
+            const int64_t t0 = start(k);
+            if (rp) {
+                memcpy(ids, rp->ord.data() + t0, sizeof(int) * nq);
+                int2 *sg = h->rc.hseg[b].p;
+                int ns = 0;
+                size_t l = (size_t)(std::upper_bound(rp->lab_ptr.begin(), rp->lab_ptr.end(), t0) - rp->lab_ptr.begin()) - 1;
+                for (; l < (size_t)B && rp->lab_ptr[l] < t0 + nq; ++l)
+                    if (rp->lab_ptr[l + 1] > rp->lab_ptr[l]) sg[ns++] = make_int2((int)l, (int)(std::max(rp->lab_ptr[l], t0) - t0));
+                sg[ns] = make_int2(-1, nq);
+                nseg[b] = ns;
+                RCHK(hipMemcpyAsync(h->rc.seg[b].p, sg, sizeof(int2) * ((size_t)ns + 1), hipMemcpyHostToDevice, c));
+            } else {
+                for (int i = 0; i < nq; ++i) ids[i] = (int)(row_idx ? row_idx[t0 + i] : t0 + i);
+            }
             RCHK(hipMemcpyAsync(h->rc.qid[b].p, ids, sizeof(int) * nq, hipMemcpyHostToDevice, c));
             return hipEventRecord(h->rc.up[b], c);
         }
         for (int r0 = 0; r0 < nq; r0 += kRecruitPiece) {
             const int nr = std::min(kRecruitPiece, nq - r0);
             double *dst = h->rc.hY[b].p + (size_t)r0 * Dp;
-            const double *src = Y + (k * chunk + r0) * D;
+            const double *src = Y + (start(k) + r0) * D;
             for (int r = 0; r < nr; ++r, dst += Dp, src += D) {
                 memcpy(dst, src, sizeof(double) * D);
                 for (int64_t j = D; j < Dp; ++j) dst[j] = 0.0;
@@ -2424,7 +2473,7 @@ hipError_t recruit_chunks(chb_ctx *h, RecruitArgs a, const double *Y, const int6
     };
     auto unpack = [&](int64_t k) -> hipError_t {
         const int b = (int)(k & 1), nq = rows(k);
-        const int64_t t0 = k * chunk;
+        const int64_t t0 = start(k);
         RCHK(hipEventSynchronize(h->rc.down[b]));
         if (dist_out) memcpy(dist_out + t0 * B, h->rc.hdist[b].p, sizeof(double) * (size_t)nq * (size_t)B);
         if (min_dist_out) memcpy(min_dist_out + t0, h->rc.hmin[b].p, sizeof(double) * nq);
@@ -2437,27 +2486,34 @@ hipError_t recruit_chunks(chb_ctx *h, RecruitArgs a, const double *Y, const int6
     for (int64_t k = 0; k < n; ++k) {
         const int b = (int)(k & 1), nq = rows(k);
         RCHK(hipStreamWaitEvent(s, h->rc.up[b], 0));
-        RCHK(hipStreamWaitEvent(s, h->rc.down[b], 0));   // (chunk k - 2 has been copied out of this half's results)
+        if (any_out) RCHK(hipStreamWaitEvent(s, h->rc.down[b], 0));   // (chunk k - 2 has been copied out of this half's results)
         a.Y = audit ? nullptr : h->rc.Y[b].p; a.qid = audit ? h->rc.qid[b].p : nullptr; a.dist = h->rc.dist[b].p; a.nq = nq;
         {
             Timed t(h, audit ? "audit" : "recruit", (double)nq * (double)B);
             launch_recruit(a, s);
             launch_recruit_reduce(h->rc.dist[b].p, nq, (int)B, h->rc.bin[b].p, h->rc.min[b].p, h->rc.margin[b].p, s);
         }
+        if (rp) {
+            BinReportArgs r = rp->tables;
+            r.dist = h->rc.dist[b].p; r.bin = h->rc.bin[b].p; r.seg = h->rc.seg[b].p; r.nseg = nseg[b]; r.B = (int)B;
+            Timed t(h, "bin_report", (double)nq * (double)B);
+            launch_bin_report(r, s);
+        }
         RCHK(hipGetLastError());
         RCHK(hipEventRecord(h->rc.done[b], s));
         if (k + 1 < n) RCHK(upload(k + 1));
+        if (!any_out) continue;
         RCHK(download(k));
         if (k > 0) RCHK(unpack(k - 1));
     }
-    return unpack(n - 1);
+    return any_out ? unpack(n - 1) : hipSuccess;
 #undef RCHK
 }
 
 // What chb_recruit_rows and chb_audit_rows do once their arguments are checked: the CSR over the labels, the context's
 // chunk buffers, the pipelined chunks.  Y: the new rows (recruit), or nullptr for the resident rows row_idx (audit).
 int recruit_run(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, const int64_t *row_idx, int64_t Q,
-                int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
+                int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out, ReportPlan *rp = nullptr)
 {
     HIPCHK(hipSetDevice(h->dev));
     hipStream_t s = h->stream;
@@ -2487,7 +2543,7 @@ int recruit_run(chb_ctx *h, const int64_t *labels, int64_t B, int m, const doubl
             if (labels[i] >= 0 && labels[i] < B) h->rc.hmemb.p[cur[(size_t)labels[i]]++] = (int)i;
     }
     const int64_t chunk = std::min<int64_t>(Q, kRecruitChunk);
-    const int halves = Q > chunk ? 2 : 1;
+    const int halves = Q > chunk ? 2 : 1;   // (a plan's first cut is shorter than Q whenever it has a second)
     HIPCHK(h->rc.ptr.ensure((size_t)B + 1));
     HIPCHK(h->rc.memb.ensure(n_memb));
     for (int i = 0; i < halves; ++i) {
@@ -2506,13 +2562,32 @@ int recruit_run(chb_ctx *h, const int64_t *labels, int64_t B, int m, const doubl
         HIPCHK(h->rc.hmin[i].ensure((size_t)chunk));
         HIPCHK(h->rc.margin[i].ensure((size_t)chunk));
         HIPCHK(h->rc.hmargin[i].ensure((size_t)chunk));
+        if (rp) {   // a chunk holds at most one run per label
+            HIPCHK(h->rc.seg[i].ensure((size_t)std::min<int64_t>(B, chunk) + 1));
+            HIPCHK(h->rc.hseg[i].ensure((size_t)std::min<int64_t>(B, chunk) + 1));
+        }
+    }
+    if (rp) {
+        const size_t BB = (size_t)B * (size_t)B;
+        HIPCHK(h->rc.rep_conf.ensure(BB));
+        HIPCHK(h->rc.rep_unplaced.ensure((size_t)B));
+        HIPCHK(h->rc.rep_cnt.ensure(BB));
+        HIPCHK(h->rc.rep_min.ensure(BB));
+        HIPCHK(h->rc.rep_sum.ensure(BB));
+        HIPCHK(hipMemsetAsync(h->rc.rep_conf.p, 0, sizeof(long long) * BB, s));
+        HIPCHK(hipMemsetAsync(h->rc.rep_unplaced.p, 0, sizeof(long long) * (size_t)B, s));
+        HIPCHK(hipMemsetAsync(h->rc.rep_cnt.p, 0, sizeof(long long) * BB, s));
+        HIPCHK(hipMemsetAsync(h->rc.rep_sum.p, 0, sizeof(double) * BB, s));
+        launch_fill_f64(h->rc.rep_min.p, std::numeric_limits<double>::infinity(), BB, s);
+        rp->tables.conf = h->rc.rep_conf.p; rp->tables.unplaced = h->rc.rep_unplaced.p; rp->tables.cnt = h->rc.rep_cnt.p;
+        rp->tables.dmin = h->rc.rep_min.p; rp->tables.dsum = h->rc.rep_sum.p;
     }
     HIPCHK(hipMemcpyAsync(h->rc.ptr.p, ptr, sizeof(int) * ((size_t)B + 1), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(h->rc.memb.p, h->rc.hmemb.p, sizeof(int) * n_memb, hipMemcpyHostToDevice, s));
     RecruitArgs a{};
     a.X = h->X.p; a.D = h->D; a.Dp = Dp; a.bin_ptr = h->rc.ptr.p; a.memb_id = h->rc.memb.p;
     a.B = (int)B; a.m = m; a.metric = h->metric;
-    const hipError_t e = recruit_chunks(h, a, Y, row_idx, Q, chunk, bin_out, dist_out, min_dist_out, margin_out);
+    const hipError_t e = recruit_chunks(h, a, Y, row_idx, Q, chunk, bin_out, dist_out, min_dist_out, margin_out, rp);
     if (e != hipSuccess) {   // nothing of this call stays in flight behind the error
         (void)hipStreamSynchronize(h->rc.copy);
         (void)hipStreamSynchronize(s);
@@ -2557,6 +2632,63 @@ int chb_audit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const in
     for (int64_t q = 0; row_idx && q < Q; ++q)
         if (row_idx[q] < 0 || row_idx[q] >= h->N) return fail(CHB_EINVAL, "row_idx entry outside [0, N)");
     return recruit_run(h, labels, B, m, nullptr, row_idx, Q, bin_out, dist_out, min_dist_out, margin_out);
+}
+
+int chb_bin_report(chb_ctx *h, const int64_t *labels, int64_t B, int m, const int64_t *row_idx, int64_t Q,
+                   int64_t *confusion, int64_t *unplaced, int64_t *dcnt, double *dmin, double *dsum, int64_t *n_skipped)
+{
+    if (!h) return fail(CHB_EINVAL, "null context");
+    if (Q < 0 || B < 1 || m < 1) return fail(CHB_EINVAL, "Q < 0, B < 1 or m < 1");
+    if (Q > 0 && !labels) return fail(CHB_EINVAL, "null argument");
+    if (!confusion && !unplaced && !dcnt && !dmin && !dsum && !n_skipped) return fail(CHB_EINVAL, "every output is null");
+    if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
+    if (m > kMaxM) return fail(CHB_EUNSUPPORTED, "chb_bin_report supports at most 16 neighbours");
+    if (B > kRecruitMaxBins) return fail(CHB_EUNSUPPORTED, "chb_bin_report supports at most 8192 bins");
+    if (h->batch.open || (h->fit_open && h->stepwise))
+        return fail(CHB_ESTATE, "a stepwise fit is open on this context (chb_fit_begin): chb_set_samples ends it");
+    if (Q > 0 && !row_idx && Q != h->N) return fail(CHB_EINVAL, "row_idx is null (all rows): Q must be the number of resident samples");
+    for (int64_t q = 0; row_idx && q < Q; ++q)
+        if (row_idx[q] < 0 || row_idx[q] >= h->N) return fail(CHB_EINVAL, "row_idx entry outside [0, N)");
+    // the scored positions in label order (stable counting sort); the others are only counted
+    const size_t BB = (size_t)B * (size_t)B;
+    ReportPlan rp;
+    rp.lab_ptr.assign((size_t)B + 1, 0);
+    auto own = [&](int64_t q) { return labels[row_idx ? row_idx[q] : q]; };
+    int64_t Qv = 0;
+    for (int64_t q = 0; q < Q; ++q) {
+        const int64_t l = own(q);
+        if (l >= 0 && l < B) { ++rp.lab_ptr[(size_t)l + 1]; ++Qv; }
+    }
+    if (n_skipped) *n_skipped = Q - Qv;
+    if (Qv == 0) {   // nothing to score: the tables of a call without rows
+        if (confusion) std::fill(confusion, confusion + BB, (int64_t)0);
+        if (unplaced) std::fill(unplaced, unplaced + B, (int64_t)0);
+        if (dcnt) std::fill(dcnt, dcnt + BB, (int64_t)0);
+        if (dmin) std::fill(dmin, dmin + BB, std::numeric_limits<double>::infinity());
+        if (dsum) std::fill(dsum, dsum + BB, 0.0);
+        return CHB_OK;
+    }
+    for (int64_t c = 0; c < B; ++c) rp.lab_ptr[(size_t)c + 1] += rp.lab_ptr[(size_t)c];
+    rp.ord.resize((size_t)Qv);
+    {
+        std::vector<int64_t> cur(rp.lab_ptr.begin(), rp.lab_ptr.end() - 1);
+        for (int64_t q = 0; q < Q; ++q) {
+            const int64_t l = own(q);
+            if (l >= 0 && l < B) rp.ord[(size_t)cur[(size_t)l]++] = (int)(row_idx ? row_idx[q] : q);
+        }
+    }
+    rp.cut_chunks();
+    const int rc = recruit_run(h, labels, B, m, nullptr, nullptr, Qv, nullptr, nullptr, nullptr, nullptr, &rp);
+    if (rc != CHB_OK) return rc;
+    hipStream_t s = h->stream;
+    static_assert(sizeof(long long) == sizeof(int64_t), "the tables are copied out as they are");
+    if (confusion) HIPCHK(hipMemcpyAsync(confusion, h->rc.rep_conf.p, sizeof(int64_t) * BB, hipMemcpyDeviceToHost, s));
+    if (unplaced) HIPCHK(hipMemcpyAsync(unplaced, h->rc.rep_unplaced.p, sizeof(int64_t) * (size_t)B, hipMemcpyDeviceToHost, s));
+    if (dcnt) HIPCHK(hipMemcpyAsync(dcnt, h->rc.rep_cnt.p, sizeof(int64_t) * BB, hipMemcpyDeviceToHost, s));
+    if (dmin) HIPCHK(hipMemcpyAsync(dmin, h->rc.rep_min.p, sizeof(double) * BB, hipMemcpyDeviceToHost, s));
+    if (dsum) HIPCHK(hipMemcpyAsync(dsum, h->rc.rep_sum.p, sizeof(double) * BB, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return CHB_OK;
 }
 
 int chb_find_nearest_from_row(chb_ctx *h, int64_t c, const int64_t *labels, const double *row,

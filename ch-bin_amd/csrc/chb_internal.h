@@ -362,6 +362,25 @@ void launch_recruit(const RecruitArgs &a, hipStream_t s);   // (a.qid set: the a
 // without a finite runner-up)
 void launch_recruit_reduce(const double *dist, int nq, int B, int *bin, double *mind, double *margin, hipStream_t s);
 
+// ---- bin report (recruit_kernels.hip, chb_bin_report): an audit chunk's dist[nq][B] and bin[nq] folded into B x B tables
+// keyed (the row's own label, bin).  The chunk's positions are grouped by label; seg names each label's run.
+struct BinReportArgs {
+    const double *dist;    // [nq][B] the chunk's leave-one-out distances (recruit_kernel<true>)
+    const int *bin;        // [nq] the chunk's strict-'>' scan (recruit_reduce_kernel)
+    const int2 *seg;       // [nseg + 1] {label, first position of its run in the chunk}; the last entry is {-1, nq}
+    int nseg, B;
+    long long *conf;       // [B][B] rows of label a whose scan chose bin b
+    long long *unplaced;   // [B]    rows of label a whose scan chose no bin
+    long long *cnt;        // [B][B] finite distances of label a's rows to bin b ...
+    double *dmin, *dsum;   // [B][B] ... their minimum (+inf without one) and sum
+};
+// Rows per summation block of dsum: a label's rows are summed in blocks of this many consecutive positions of its run, each
+// block in order, the block sums in block order.  A run that starts in the middle of a chunk's label must start on a
+// block boundary of that label (the host cuts its chunks there), or the order would depend on the chunks.
+constexpr int kReportBlock = 64;
+void launch_bin_report(const BinReportArgs &a, hipStream_t s);
+void launch_fill_f64(double *p, double v, size_t n, hipStream_t s);
+
 // label / bucket helpers
 void launch_fill_i32(int *p, int v, int n, hipStream_t s);
 void launch_copy_i32(int *dst, const int *src, int n, hipStream_t s);   // (carries the look-ahead gate, like the fill)

@@ -25,6 +25,9 @@
 //
 // chb_audit_rows runs the same kernel body on RESIDENT rows (template parameter kResident): the rows to score are samples
 // named by index, and a row is withheld from its own bin's candidates -- the leave-one-out step of algorithm.py:49-58.
+//
+// chb_bin_report runs the audit's two kernels on positions grouped by their own label and a third, bin_report_kernel
+// (below), that folds each chunk's distances and bins into B x B tables keyed (own label, bin).
 #include "chb_internal.h"
 #include "hull_solve16.h"
 
@@ -261,7 +264,98 @@ __global__ __launch_bounds__(256) void recruit_reduce_kernel(const double *dist,
     margin[q] = runner == kInf ? kInf : runner - best;
 }
 
+// chb_bin_report: one chunk's dist[nq][B] and bin[nq] folded into the B x B tables keyed (the row's own label, bin).
+//
+// The chunk's positions are grouped by label (the host sorts them), seg names each label's run.  One workgroup owns
+// (one run) x (64 consecutive bins), lane = bin: a row's 64 distances are one 512-byte read.  The run is cut into blocks
+// of kReportBlock rows; wavefront w sums blocks w, w + 4, ... each in row order in a register (eight rows' loads are
+// issued ahead of the eight dependent adds), and after every round of four blocks the first wavefront adds the round's
+// block sums, in block order, onto the table's running sum.  So dsum[a][b] is: the finite distances of label a's rows in
+// the host's order, blocks of kReportBlock consecutive rows of the label summed in order from 0, the block sums added in
+// order from 0 -- whatever the chunks were, since a run starts on a block boundary of its label (BinReportArgs).
+// Counts, minima and the confusion counts (rows whose bin[q] is the lane's bin) do not depend on any order.
+// A (label, bin) cell is touched by one lane of one workgroup of a launch and the launches of a call follow each other on
+// one stream: the tables are updated by plain loads and stores, there is no atomic of any kind.
+__global__ __launch_bounds__(256) void bin_report_kernel(BinReportArgs a, int nbt)
+{
+    __shared__ double part[2][4][64];
+    __shared__ double wmin[4][64];
+    __shared__ int wcnt[4][64], wconf[4][64], wunp[4];
+
+    const int sg = (int)blockIdx.x / nbt, bt = (int)blockIdx.x - sg * nbt;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int2 s0 = a.seg[sg];
+    const int lab = s0.x, r0 = s0.y, r1 = a.seg[sg + 1].y;
+    const int b = bt * 64 + lane;
+    const bool on = b < a.B;
+    const size_t B = (size_t)a.B;
+    const double *col = a.dist + (on ? b : a.B - 1);   // (a lane past the last bin reads the last bin and stores nothing)
+    const size_t cell = (size_t)lab * B + (size_t)b;
+    const int nblk = (r1 - r0 + kReportBlock - 1) / kReportBlock;
+
+    double total = (w == 0 && on) ? a.dsum[cell] : 0.0;
+    double mn = kInf;
+    int cnt = 0, conf = 0, unp = 0;
+    auto fold = [&](double d, int bn, double &s) {
+        conf += bn == b;
+        unp += bn < 0;
+        if (d < kInf) { ++cnt; mn = fmin(mn, d); s = s + d; }
+    };
+    for (int t0 = 0; t0 < nblk; t0 += 4) {
+        const int t = t0 + w;
+        double s = 0.0;
+        if (t < nblk) {
+            const int q1 = min(r0 + (t + 1) * kReportBlock, r1);
+            int q = r0 + t * kReportBlock;
+            for (; q + 8 <= q1; q += 8) {
+                double d[8];
+                int bn[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) { d[u] = col[(size_t)(q + u) * B]; bn[u] = a.bin[q + u]; }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) fold(d[u], bn[u], s);
+            }
+            for (; q < q1; ++q) fold(col[(size_t)q * B], a.bin[q], s);
+        }
+        const int pb = (t0 >> 2) & 1;   // (two buffers: the first wavefront may still read round r while round r + 1 is written)
+        part[pb][w][lane] = s;
+        __syncthreads();
+        if (w == 0) {
+            const int nb = min(4, nblk - t0);
+            for (int i = 0; i < nb; ++i) total = total + part[pb][i][lane];
+        }
+    }
+    wmin[w][lane] = mn; wcnt[w][lane] = cnt; wconf[w][lane] = conf;
+    if (lane == 0) wunp[w] = unp;
+    __syncthreads();
+    if (w != 0 || !on) return;
+#pragma unroll
+    for (int i = 1; i < 4; ++i) { mn = fmin(mn, wmin[i][lane]); cnt += wcnt[i][lane]; conf += wconf[i][lane]; unp += wunp[i]; }
+    a.dsum[cell] = total;
+    if (cnt) { a.cnt[cell] += cnt; a.dmin[cell] = fmin(a.dmin[cell], mn); }
+    if (conf) a.conf[cell] += conf;
+    if (b == 0 && unp) a.unplaced[lab] += unp;
+}
+
+__global__ __launch_bounds__(256) void fill_f64_kernel(double *p, double v, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
 }  // namespace
+
+void launch_bin_report(const BinReportArgs &a, hipStream_t s)
+{
+    if (a.nseg <= 0 || a.B <= 0) return;
+    const int nbt = (a.B + 63) / 64;
+    hipLaunchKernelGGL(bin_report_kernel, dim3((unsigned)a.nseg * (unsigned)nbt), dim3(256), 0, s, a, nbt);
+}
+
+void launch_fill_f64(double *p, double v, size_t n, hipStream_t s)
+{
+    if (n > 0) hipLaunchKernelGGL(fill_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, v, n);
+}
 
 void launch_recruit(const RecruitArgs &a, hipStream_t s)
 {

@@ -148,6 +148,38 @@ int chb_recruit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const 
 int chb_audit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const int64_t *row_idx, int64_t Q,
                    int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out);
 
+/* Bin report: what chb_audit_rows says about a labelling, summed up per (own bin, other bin) pair on the device -- which
+ * bins bleed into each other and which are cleanly apart -- without a per-row value crossing the host boundary.
+ * The call is defined by chb_audit_rows on the same arguments: for every position q whose own label
+ * a = labels[row_idx[q]] lies in [0, B), with d[q][.] the audit's leave-one-out distances and bin[q] its strict-'>' scan:
+ *   confusion[a*B + bin[q]] += 1, or unplaced[a] += 1 where bin[q] == -1;
+ *   for every bin b with d[q][b] finite: dcnt[a*B + b] += 1, dmin[a*B + b] = min(., d[q][b]), dsum[a*B + b] += d[q][b];
+ *   dmin is +inf and dsum 0 where dcnt is 0.
+ * Positions whose own label lies outside [0, B) are not scored at all (no kernel work is spent on them); *n_skipped
+ * counts them.  Repeats in row_idx count as often as they occur.  confusion, dcnt, dmin, dsum: B*B, unplaced: B.
+ * Each output may be NULL; all six NULL is CHB_EINVAL.  Q = 0, or no position with a label in [0, B), gives zero / +inf
+ * tables and CHB_OK.
+ *   - row_idx == NULL, Q, the limits (m <= 16, B <= 8192: CHB_EUNSUPPORTED beyond), CHB_ESTATE without resident samples or
+ *     while a stepwise fit is open (the fit stays usable), and "uses no state of a fit and leaves every counter, memo and
+ *     switch of the context as it found it" are chb_audit_rows' rules; every check runs on the host before anything is
+ *     enqueued;
+ *   - the scored positions are put in label order by a stable counting sort on the host (a label's positions keep the
+ *     order of row_idx: ascending sample index for row_idx == NULL) and scored in chunks of at most 16384 cut from that
+ *     order; per chunk the int32 sample indices and the int32 {label, first position} of each label's run go up, nothing
+ *     comes down before the tables after the last chunk.  The tables live on the device, 32 bytes per (a, b) pair (24 for
+ *     dcnt / dmin / dsum, 8 for confusion), allocated by the context and zeroed at the call's start;
+ *   - determinism: there is no atomic, floating-point or other.  confusion, unplaced, dcnt and dmin are exact.  dsum[a][b]
+ *     is the sum of the finite d[q][b] of label a's positions in this guaranteed order: the label's positions, in the
+ *     order above, are taken in blocks of 64 consecutive positions (the last block may be shorter; positions whose
+ *     distance is not finite keep their place in a block and add nothing); each block is summed in order starting from
+ *     0, and the block sums are added in block order starting from 0.  No chunk boundary splits a block (a chunk that
+ *     would is cut up to 63 positions short), so dsum is bit-identical from call to call and does not depend on where the
+ *     chunks fall; row_idx == NULL and row_idx = 0 .. N-1 give the same bits;
+ *   - one GPU: with a communicator (world > 1) each rank reports on the positions it is given, there is no collective. */
+int chb_bin_report(chb_ctx *h, const int64_t *labels, int64_t B, int m, const int64_t *row_idx, int64_t Q,
+                   int64_t *confusion, int64_t *unplaced, int64_t *dcnt, double *dmin, double *dsum,
+                   int64_t *n_skipped);
+
 /* distance_matrix.py:47-62 find_nearest_from_cluster with the reference's exact signature: the
  * caller supplies one row of a distance matrix (any provenance) and the current labels; selects
  * among {p : labels[p] == c} the (up to) m smallest by (row[p], p).  out_idx[m] (-1 padded). */
@@ -308,7 +340,8 @@ int chb_profile_reset(chb_ctx *h);
  * "pairwise" | "kmer_count" | "kmer_multi" (chb_kmer_profiles / chb_set_samples_from_sequences: the counting and the
  * finalise launch of one chunk; work units = bases) | "recruit" (chb_recruit_rows: selection + hull kernel and the row reduction of one chunk; work
  * units = (row, bin) pairs) | "audit" (chb_audit_rows: the same pair of launches for one chunk of resident rows; work units
- * = (row, bin) pairs).  For m <= 16 "hull_qp" is the fused selection + hull-distance kernel and
+ * = (row, bin) pairs; chb_bin_report books its two audit launches here as well) | "bin_report" (chb_bin_report: the launch
+ * that folds one chunk's distances and bins into the B x B tables; work units = (row, bin) pairs).  For m <= 16 "hull_qp" is the fused selection + hull-distance kernel and
  * "slow_path" the exact path for what it leaves over; "rescore*" then only appear for m > 16 or CHB_FUSED=0. */
 int chb_profile_get(chb_ctx *h, const char *kernel, double *total_ms, int64_t *launches,
                     double *work_units);
@@ -332,7 +365,7 @@ int chb_fit_stats(chb_ctx *h, int64_t *out4);
  * batch needed further rounds), "pool_batches" (batches of the last fit whose base shortlist launch took its thresholds
  * from the pools), "pool_state" (0 undecided = on, 1 kept on, -1 turned off because the shortlists came out long),
  * "pool_candidates" / "pool_pairs" (sampled shortlist lengths behind that decision), "exchanges" (framed all-gathers of the last fit under an exchange: one per batch for the
- * label guess, one per round), "recruit_chunk" (rows per launch of chb_recruit_rows and chb_audit_rows: a constant),
+ * label guess, one per round), "recruit_chunk" (rows per launch of chb_recruit_rows, chb_audit_rows and -- at most -- chb_bin_report: a constant),
  * "kmer_chunk_bytes" / "kmer_chunk_rows" (the most bases / contigs of one sequence chunk of chb_kmer_profiles and
  * chb_set_samples_from_sequences: constants), "kmer_chunks" (chunks of the last such call) */
 int chb_counter(chb_ctx *h, const char *name, int64_t *out);
