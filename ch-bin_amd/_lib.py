@@ -44,6 +44,10 @@ SIGNATURES = {
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "chb_audit_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "chb_audit_rows_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "chb_recruit_rows_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "chb_bin_report": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "chb_find_nearest_from_row": (C.c_int, [C.c_void_p, C.c_int64, _i64p, _f64p, C.c_int64, C.c_int,
@@ -236,6 +240,59 @@ class Context:
                                        None if rows is None else rows.ctypes.data, Q,
                                        bins.ctypes.data, None if dist is None else dist.ctypes.data,
                                        mind.ctypes.data, margin.ctypes.data))
+        return bins, dist, mind, margin
+
+    @staticmethod
+    def _m_list(ms):
+        ms = np.ascontiguousarray(ms, dtype=np.intc)
+        if ms.ndim != 1:
+            raise ValueError("ms must be a 1-D list of neighbour counts")
+        return ms
+
+    def audit_rows_multi(self, labels, B, ms, rows=None, want_dist=True):
+        """chb_audit_rows_multi: audit_rows for every m of the list `ms` (distinct values in 1 .. 16, at most 16 of them,
+        any order) from one selection pass; slice j of every result is bit for bit audit_rows(labels, B, ms[j], rows).
+        Returns (bins [nm, Q], dist [nm, Q, B] or None, min_dist [nm, Q], margin [nm, Q])."""
+        labels = np.ascontiguousarray(labels, dtype=np.int64)
+        ms = self._m_list(ms)
+        if labels.shape != (self.N,):
+            raise ValueError("labels must have one entry per resident sample")
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.int64)
+            if rows.ndim != 1:
+                raise ValueError("rows must be a 1-D array of sample indices")
+        Q = self.N if rows is None else rows.shape[0]
+        nm = ms.shape[0]
+        bins = np.empty((nm, Q), dtype=np.int64)
+        dist = np.empty((nm, Q, int(B)), dtype=np.float64) if want_dist else None
+        mind = np.empty((nm, Q), dtype=np.float64)
+        margin = np.empty((nm, Q), dtype=np.float64)
+        check(self._lib.chb_audit_rows_multi(self._h, labels.ctypes.data, int(B), ms.ctypes.data, nm,
+                                             None if rows is None else rows.ctypes.data, Q,
+                                             bins.ctypes.data, None if dist is None else dist.ctypes.data,
+                                             mind.ctypes.data, margin.ctypes.data))
+        return bins, dist, mind, margin
+
+    def recruit_rows_multi(self, labels, B, ms, Y, want_dist=True):
+        """chb_recruit_rows_multi: recruit_rows for every m of the list `ms` from one selection pass; slice j of every
+        result is bit for bit recruit_rows(labels, B, ms[j], Y).
+        Returns (bins [nm, Q], dist [nm, Q, B] or None, min_dist [nm, Q], margin [nm, Q])."""
+        labels = np.ascontiguousarray(labels, dtype=np.int64)
+        ms = self._m_list(ms)
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim != 2:
+            raise ValueError("rows must be a 2-D array")
+        if labels.shape != (self.N,):
+            raise ValueError("labels must have one entry per resident sample")
+        Q, D = Y.shape
+        nm = ms.shape[0]
+        bins = np.empty((nm, Q), dtype=np.int64)
+        dist = np.empty((nm, Q, int(B)), dtype=np.float64) if want_dist else None
+        mind = np.empty((nm, Q), dtype=np.float64)
+        margin = np.empty((nm, Q), dtype=np.float64)
+        check(self._lib.chb_recruit_rows_multi(self._h, labels.ctypes.data, int(B), ms.ctypes.data, nm, Y.ctypes.data, Q, D,
+                                               bins.ctypes.data, None if dist is None else dist.ctypes.data,
+                                               mind.ctypes.data, margin.ctypes.data))
         return bins, dist, mind, margin
 
     def bin_report(self, labels, B, m, rows=None):

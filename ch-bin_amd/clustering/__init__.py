@@ -1,6 +1,6 @@
 """Host-side mirror of the reference package `ch_bin.core.clustering` (same function names,
 argument meaning and error behaviour) on top of libchbin_hip.so."""
-from .algorithm import BinReport, audit, bin_report, fit_cluster, recruit  # noqa: F401
+from .algorithm import BinReport, NeighborSweep, audit, bin_report, fit_cluster, neighbor_sweep, recruit  # noqa: F401
 from .distance_matrix import (  # noqa: F401
     create_distance_matrix,
     create_in_mem_distance_matrix,

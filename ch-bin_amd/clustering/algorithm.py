@@ -182,3 +182,71 @@ def bin_report(
     ctx.set_samples_cached(samples)
     with ctx.using_metric(metric):
         return BinReport(*ctx.bin_report(labels, int(num_clusters), int(num_neighbors), rows))
+
+
+@dataclasses.dataclass
+class NeighborSweep:
+    """What neighbor_sweep returns: `audit` of the same rows for every entry of `neighbors` -- bins / min_dist / margin
+    [len(neighbors), len(rows)] (row j = audit with num_neighbors = neighbors[j]), `rows` the scored sample indices, `own`
+    their labels in the audited labelling, `distances` [len(neighbors), len(rows), num_clusters] if asked for."""
+    neighbors: np.ndarray
+    rows: np.ndarray
+    own: np.ndarray
+    bins: np.ndarray
+    min_dist: np.ndarray
+    margin: np.ndarray
+    num_clusters: int
+    distances: np.ndarray = None
+
+    @property
+    def moved(self) -> np.ndarray:
+        """Per entry of `neighbors`: the scored rows with a label in [0, num_clusters) whose audit bin is another one
+        (no bin at all, -1, included)."""
+        labelled = (self.own >= 0) & (self.own < self.num_clusters)
+        return np.count_nonzero((self.bins != self.own[None, :]) & labelled[None, :], axis=1)
+
+    @property
+    def agreement(self) -> np.ndarray:
+        """[len(neighbors), len(neighbors)]: the share of scored rows on which two entries choose the same bin (both
+        choosing none counts as the same); 1 on the diagonal; NaN without a scored row."""
+        nm, Q = self.bins.shape
+        if Q == 0:
+            return np.full((nm, nm), np.nan)
+        return (self.bins[:, None, :] == self.bins[None, :, :]).sum(axis=2) / float(Q)
+
+    def stable(self, min_margin: float = 0.0) -> np.ndarray:
+        """Boolean per scored row: every entry of `neighbors` chooses the row's own label, with a margin above
+        `min_margin` (+inf, no runner-up bin, is above any).  False for rows without a label in [0, num_clusters)."""
+        labelled = (self.own >= 0) & (self.own < self.num_clusters)
+        return labelled & np.all((self.bins == self.own[None, :]) & (self.margin > min_margin), axis=0)
+
+
+def neighbor_sweep(
+    samples: np.ndarray,
+    labels: np.ndarray,
+    num_clusters: int,
+    neighbors=(1, 3, 5, 10, 15),
+    metric: str = "convex",
+    qp_solver: str = "quadprog",
+    rows: np.ndarray = None,
+    return_distances: bool = False,
+) -> NeighborSweep:
+    """Does a finished labelling hold up at other numbers of neighbours (no counterpart in the reference, whose default
+    configuration says 5 and whose function default says 15)?  `audit` of the samples in `rows` (None: all of them) for
+    every entry of `neighbors` (distinct values in 1 .. 16) at the cost of little more than the audit at the largest: one
+    selection pass on the device serves the whole list, and each entry's result is bit for bit what `audit` returns for it.
+    Nothing changes."""
+    if metric not in ("convex", "affine", "affine-qp"):
+        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
+    check_solver(qp_solver)                                              # solve_qp.py:132
+
+    samples = np.ascontiguousarray(samples, dtype=np.float64)
+    labels = np.ascontiguousarray(labels, dtype=np.int64)
+    neighbors = np.ascontiguousarray(neighbors, dtype=np.int64)
+    ctx = default_context()
+    ctx.set_samples_cached(samples)
+    with ctx.using_metric(metric):
+        bins, dist, mind, margin = ctx.audit_rows_multi(labels, int(num_clusters), neighbors, rows,
+                                                        want_dist=return_distances)
+    scored = np.arange(samples.shape[0], dtype=np.int64) if rows is None else np.ascontiguousarray(rows, dtype=np.int64)
+    return NeighborSweep(neighbors, scored, labels[scored], bins, mind, margin, int(num_clusters), dist)

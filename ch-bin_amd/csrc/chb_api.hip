@@ -254,7 +254,9 @@ struct Segments {
 // labels -- the call's own buffers, nothing of a fit.  Two of each per-chunk buffer, on the device and pinned on the
 // host: while the kernels of chunk k run on the context's stream, copy brings chunk k + 1 up and chunk k - 1 down
 // (up / done / down: upload, kernels, download of the chunk in that half are through).  chb_audit_rows runs through the
-// same buffers: what it sends up per chunk is qid, the chunk's sample indices, in place of Y.  chb_bin_report is an audit
+// same buffers: what it sends up per chunk is qid, the chunk's sample indices, in place of Y.  The calls for a list of m
+// (chb_*_rows_multi) cut their chunks shorter by the list's length, so that the list's result slices of a chunk fit the
+// result buffers of a single-m chunk.  chb_bin_report is an audit
 // whose chunks are cut from the positions in label order: per chunk seg (each label's run, BinReportArgs) goes up as
 // well, nothing comes down, and the B x B tables rep_* (zeroed at the call's start) collect what the chunks' rows say.
 struct Recruit {
@@ -268,6 +270,7 @@ struct Recruit {
     DevBuf<double> rep_min, rep_sum;
     hipStream_t copy = nullptr;
     hipEvent_t up[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr}, down[2] = {nullptr, nullptr};
+    int64_t multi_rows = 0;   // rows per launch of the last chb_audit_rows_multi / chb_recruit_rows_multi
 };
 
 // Multi-GPU: one context per process per GPU, RCCL communicator over all ranks
@@ -2412,9 +2415,12 @@ struct ReportPlan {
 // against N; nullptr: position = sample), and the kernel reads the rows from the resident matrix.  With a plan (rp:
 // chb_bin_report) the positions are the plan's, chunk k is the plan's cut k, each label's run in the chunk goes up beside
 // the indices and bin_report_kernel folds the chunk into the plan's tables behind the two audit kernels.  Outputs that
-// have no destination are neither downloaded nor unpacked.
+// have no destination are neither downloaded nor unpacked.  With a list of m (a.mmask; slot: list entry j's slice on the
+// device, where the slices lie in ascending order of m) a chunk's results are ns slices of nq rows each, reduced by one
+// launch over ns * nq rows, and unpacking puts slice slot[j] of the chunk at out + j * Q + t0.
 hipError_t recruit_chunks(chb_ctx *h, RecruitArgs a, const double *Y, const int64_t *row_idx, int64_t Q, int64_t chunk,
-                          int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out, const ReportPlan *rp)
+                          int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out, const ReportPlan *rp,
+                          const int *slot = nullptr, int ns = 1)
 {
 #define RCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
     hipStream_t s = h->stream, c = h->rc.copy;
@@ -2464,22 +2470,27 @@ hipError_t recruit_chunks(chb_ctx *h, RecruitArgs a, const double *Y, const int6
     auto download = [&](int64_t k) -> hipError_t {
         const int b = (int)(k & 1), nq = rows(k);
         RCHK(hipStreamWaitEvent(c, h->rc.done[b], 0));
+        const size_t nr = (size_t)nq * (size_t)ns;
         if (dist_out)
-            RCHK(hipMemcpyAsync(h->rc.hdist[b].p, h->rc.dist[b].p, sizeof(double) * (size_t)nq * (size_t)B, hipMemcpyDeviceToHost, c));
-        if (min_dist_out) RCHK(hipMemcpyAsync(h->rc.hmin[b].p, h->rc.min[b].p, sizeof(double) * nq, hipMemcpyDeviceToHost, c));
-        if (margin_out) RCHK(hipMemcpyAsync(h->rc.hmargin[b].p, h->rc.margin[b].p, sizeof(double) * nq, hipMemcpyDeviceToHost, c));
-        if (bin_out) RCHK(hipMemcpyAsync(h->rc.hbin[b].p, h->rc.bin[b].p, sizeof(int) * nq, hipMemcpyDeviceToHost, c));
+            RCHK(hipMemcpyAsync(h->rc.hdist[b].p, h->rc.dist[b].p, sizeof(double) * nr * (size_t)B, hipMemcpyDeviceToHost, c));
+        if (min_dist_out) RCHK(hipMemcpyAsync(h->rc.hmin[b].p, h->rc.min[b].p, sizeof(double) * nr, hipMemcpyDeviceToHost, c));
+        if (margin_out) RCHK(hipMemcpyAsync(h->rc.hmargin[b].p, h->rc.margin[b].p, sizeof(double) * nr, hipMemcpyDeviceToHost, c));
+        if (bin_out) RCHK(hipMemcpyAsync(h->rc.hbin[b].p, h->rc.bin[b].p, sizeof(int) * nr, hipMemcpyDeviceToHost, c));
         return hipEventRecord(h->rc.down[b], c);
     };
     auto unpack = [&](int64_t k) -> hipError_t {
         const int b = (int)(k & 1), nq = rows(k);
         const int64_t t0 = start(k);
         RCHK(hipEventSynchronize(h->rc.down[b]));
-        if (dist_out) memcpy(dist_out + t0 * B, h->rc.hdist[b].p, sizeof(double) * (size_t)nq * (size_t)B);
-        if (min_dist_out) memcpy(min_dist_out + t0, h->rc.hmin[b].p, sizeof(double) * nq);
-        if (margin_out) memcpy(margin_out + t0, h->rc.hmargin[b].p, sizeof(double) * nq);
-        if (bin_out)
-            for (int i = 0; i < nq; ++i) bin_out[t0 + i] = h->rc.hbin[b].p[i];
+        for (int j = 0; j < ns; ++j) {
+            const size_t from = (size_t)(slot ? slot[j] : 0) * (size_t)nq;
+            const int64_t to = (int64_t)j * Q + t0;
+            if (dist_out) memcpy(dist_out + to * B, h->rc.hdist[b].p + from * (size_t)B, sizeof(double) * (size_t)nq * (size_t)B);
+            if (min_dist_out) memcpy(min_dist_out + to, h->rc.hmin[b].p + from, sizeof(double) * nq);
+            if (margin_out) memcpy(margin_out + to, h->rc.hmargin[b].p + from, sizeof(double) * nq);
+            if (bin_out)
+                for (int i = 0; i < nq; ++i) bin_out[to + i] = h->rc.hbin[b].p[from + i];
+        }
         return hipSuccess;
     };
     RCHK(upload(0));
@@ -2489,9 +2500,10 @@ hipError_t recruit_chunks(chb_ctx *h, RecruitArgs a, const double *Y, const int6
         if (any_out) RCHK(hipStreamWaitEvent(s, h->rc.down[b], 0));   // (chunk k - 2 has been copied out of this half's results)
         a.Y = audit ? nullptr : h->rc.Y[b].p; a.qid = audit ? h->rc.qid[b].p : nullptr; a.dist = h->rc.dist[b].p; a.nq = nq;
         {
-            Timed t(h, audit ? "audit" : "recruit", (double)nq * (double)B);
+            Timed t(h, a.mmask ? (audit ? "audit_multi" : "recruit_multi") : (audit ? "audit" : "recruit"),
+                    (double)nq * (double)B * (double)ns);
             launch_recruit(a, s);
-            launch_recruit_reduce(h->rc.dist[b].p, nq, (int)B, h->rc.bin[b].p, h->rc.min[b].p, h->rc.margin[b].p, s);
+            launch_recruit_reduce(h->rc.dist[b].p, nq * ns, (int)B, h->rc.bin[b].p, h->rc.min[b].p, h->rc.margin[b].p, s);
         }
         if (rp) {
             BinReportArgs r = rp->tables;
@@ -2512,8 +2524,11 @@ hipError_t recruit_chunks(chb_ctx *h, RecruitArgs a, const double *Y, const int6
 
 // What chb_recruit_rows and chb_audit_rows do once their arguments are checked: the CSR over the labels, the context's
 // chunk buffers, the pipelined chunks.  Y: the new rows (recruit), or nullptr for the resident rows row_idx (audit).
+// ms / nm: the checked list of a chb_*_rows_multi call (m is then its largest entry): the chunks are kRecruitChunk / nm
+// rows, rounded down to whole 64-row tiles, so nm result slices of a chunk fill no more than a single-m chunk's buffers.
 int recruit_run(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, const int64_t *row_idx, int64_t Q,
-                int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out, ReportPlan *rp = nullptr)
+                int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out, ReportPlan *rp = nullptr,
+                const int *ms = nullptr, int nm = 0)
 {
     HIPCHK(hipSetDevice(h->dev));
     hipStream_t s = h->stream;
@@ -2542,7 +2557,17 @@ int recruit_run(chb_ctx *h, const int64_t *labels, int64_t B, int m, const doubl
         for (int64_t i = 0; i < N; ++i)
             if (labels[i] >= 0 && labels[i] < B) h->rc.hmemb.p[cur[(size_t)labels[i]]++] = (int)i;
     }
-    const int64_t chunk = std::min<int64_t>(Q, kRecruitChunk);
+    const int ns = nm > 0 ? nm : 1;   // result slices per chunk
+    unsigned mmask = 0;
+    int slot[kMaxM];   // list entry j's slice on the device = the number of smaller entries
+    for (int j = 0; j < nm; ++j) {
+        mmask |= 1u << (ms[j] - 1);
+        slot[j] = 0;
+        for (int k = 0; k < nm; ++k) slot[j] += ms[k] < ms[j];
+    }
+    if (nm > 0) h->rc.multi_rows = std::max<int64_t>(kQTile, kRecruitChunk / nm / kQTile * kQTile);
+    const int64_t chunk = std::min<int64_t>(Q, nm > 0 ? h->rc.multi_rows : kRecruitChunk);
+    const size_t res = (size_t)chunk * (size_t)ns;   // result rows of a chunk
     const int halves = Q > chunk ? 2 : 1;   // (a plan's first cut is shorter than Q whenever it has a second)
     HIPCHK(h->rc.ptr.ensure((size_t)B + 1));
     HIPCHK(h->rc.memb.ensure(n_memb));
@@ -2554,14 +2579,14 @@ int recruit_run(chb_ctx *h, const int64_t *labels, int64_t B, int m, const doubl
             HIPCHK(h->rc.qid[i].ensure((size_t)chunk));
             HIPCHK(h->rc.hqid[i].ensure((size_t)chunk));
         }
-        HIPCHK(h->rc.dist[i].ensure((size_t)chunk * (size_t)B));
-        if (dist_out) HIPCHK(h->rc.hdist[i].ensure((size_t)chunk * (size_t)B));
-        HIPCHK(h->rc.bin[i].ensure((size_t)chunk));
-        HIPCHK(h->rc.hbin[i].ensure((size_t)chunk));
-        HIPCHK(h->rc.min[i].ensure((size_t)chunk));
-        HIPCHK(h->rc.hmin[i].ensure((size_t)chunk));
-        HIPCHK(h->rc.margin[i].ensure((size_t)chunk));
-        HIPCHK(h->rc.hmargin[i].ensure((size_t)chunk));
+        HIPCHK(h->rc.dist[i].ensure(res * (size_t)B));
+        if (dist_out) HIPCHK(h->rc.hdist[i].ensure(res * (size_t)B));
+        HIPCHK(h->rc.bin[i].ensure(res));
+        HIPCHK(h->rc.hbin[i].ensure(res));
+        HIPCHK(h->rc.min[i].ensure(res));
+        HIPCHK(h->rc.hmin[i].ensure(res));
+        HIPCHK(h->rc.margin[i].ensure(res));
+        HIPCHK(h->rc.hmargin[i].ensure(res));
         if (rp) {   // a chunk holds at most one run per label
             HIPCHK(h->rc.seg[i].ensure((size_t)std::min<int64_t>(B, chunk) + 1));
             HIPCHK(h->rc.hseg[i].ensure((size_t)std::min<int64_t>(B, chunk) + 1));
@@ -2586,8 +2611,9 @@ int recruit_run(chb_ctx *h, const int64_t *labels, int64_t B, int m, const doubl
     HIPCHK(hipMemcpyAsync(h->rc.memb.p, h->rc.hmemb.p, sizeof(int) * n_memb, hipMemcpyHostToDevice, s));
     RecruitArgs a{};
     a.X = h->X.p; a.D = h->D; a.Dp = Dp; a.bin_ptr = h->rc.ptr.p; a.memb_id = h->rc.memb.p;
-    a.B = (int)B; a.m = m; a.metric = h->metric;
-    const hipError_t e = recruit_chunks(h, a, Y, row_idx, Q, chunk, bin_out, dist_out, min_dist_out, margin_out, rp);
+    a.B = (int)B; a.m = m; a.metric = h->metric; a.mmask = mmask;
+    const hipError_t e = recruit_chunks(h, a, Y, row_idx, Q, chunk, bin_out, dist_out, min_dist_out, margin_out, rp,
+                                        nm > 0 ? slot : nullptr, ns);
     if (e != hipSuccess) {   // nothing of this call stays in flight behind the error
         (void)hipStreamSynchronize(h->rc.copy);
         (void)hipStreamSynchronize(s);
@@ -2632,6 +2658,66 @@ int chb_audit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const in
     for (int64_t q = 0; row_idx && q < Q; ++q)
         if (row_idx[q] < 0 || row_idx[q] >= h->N) return fail(CHB_EINVAL, "row_idx entry outside [0, N)");
     return recruit_run(h, labels, B, m, nullptr, row_idx, Q, bin_out, dist_out, min_dist_out, margin_out);
+}
+
+namespace {
+
+// the list of a chb_*_rows_multi call: 1 .. 16 distinct entries in 1 .. 16; *m_max = the largest
+int check_m_list(const char *who, const int *ms, int nm, int *m_max)
+{
+    if (!ms) return fail(CHB_EINVAL, "ms is null");
+    if (nm < 1 || nm > kMaxM) return fail(CHB_EINVAL, "nm must be 1 .. 16");
+    for (int j = 0; j < nm; ++j)
+        if (ms[j] < 1) return fail(CHB_EINVAL, "an entry of ms is < 1");
+    for (int j = 0; j < nm; ++j)
+        if (ms[j] > kMaxM) return fail(CHB_EUNSUPPORTED, std::string(who) + " supports at most 16 neighbours");
+    unsigned seen = 0;
+    for (int j = 0; j < nm; ++j) {
+        if (seen & (1u << (ms[j] - 1))) return fail(CHB_EINVAL, "ms holds a value twice");
+        seen |= 1u << (ms[j] - 1);
+    }
+    *m_max = 32 - __builtin_clz(seen);
+    return CHB_OK;
+}
+
+}  // namespace
+
+int chb_recruit_rows_multi(chb_ctx *h, const int64_t *labels, int64_t B, const int *ms, int nm, const double *Y, int64_t Q,
+                           int64_t D, int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
+{
+    if (!h) return fail(CHB_EINVAL, "null context");
+    if (Q < 0 || B < 1) return fail(CHB_EINVAL, "Q < 0 or B < 1");
+    int m_max = 0;
+    { const int rc = check_m_list("chb_recruit_rows_multi", ms, nm, &m_max); if (rc) return rc; }
+    if (Q > 0 && (!labels || !Y)) return fail(CHB_EINVAL, "null argument");
+    if (!bin_out && !dist_out) return fail(CHB_EINVAL, "bin_out and dist_out are both null");
+    if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
+    if (D != h->D) return fail(CHB_EINVAL, "the rows must have the resident samples' number of columns");
+    if (B > kRecruitMaxBins) return fail(CHB_EUNSUPPORTED, "chb_recruit_rows_multi supports at most 8192 bins");
+    if (h->batch.open || (h->fit_open && h->stepwise))
+        return fail(CHB_ESTATE, "a stepwise fit is open on this context (chb_fit_begin): chb_set_samples ends it");
+    if (Q == 0) return CHB_OK;
+    return recruit_run(h, labels, B, m_max, Y, nullptr, Q, bin_out, dist_out, min_dist_out, margin_out, nullptr, ms, nm);
+}
+
+int chb_audit_rows_multi(chb_ctx *h, const int64_t *labels, int64_t B, const int *ms, int nm, const int64_t *row_idx,
+                         int64_t Q, int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
+{
+    if (!h) return fail(CHB_EINVAL, "null context");
+    if (Q < 0 || B < 1) return fail(CHB_EINVAL, "Q < 0 or B < 1");
+    int m_max = 0;
+    { const int rc = check_m_list("chb_audit_rows_multi", ms, nm, &m_max); if (rc) return rc; }
+    if (Q > 0 && !labels) return fail(CHB_EINVAL, "null argument");
+    if (!bin_out && !dist_out) return fail(CHB_EINVAL, "bin_out and dist_out are both null");
+    if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
+    if (B > kRecruitMaxBins) return fail(CHB_EUNSUPPORTED, "chb_audit_rows_multi supports at most 8192 bins");
+    if (h->batch.open || (h->fit_open && h->stepwise))
+        return fail(CHB_ESTATE, "a stepwise fit is open on this context (chb_fit_begin): chb_set_samples ends it");
+    if (Q == 0) return CHB_OK;
+    if (!row_idx && Q != h->N) return fail(CHB_EINVAL, "row_idx is null (all rows): Q must be the number of resident samples");
+    for (int64_t q = 0; row_idx && q < Q; ++q)
+        if (row_idx[q] < 0 || row_idx[q] >= h->N) return fail(CHB_EINVAL, "row_idx entry outside [0, N)");
+    return recruit_run(h, labels, B, m_max, nullptr, row_idx, Q, bin_out, dist_out, min_dist_out, margin_out, nullptr, ms, nm);
 }
 
 int chb_bin_report(chb_ctx *h, const int64_t *labels, int64_t B, int m, const int64_t *row_idx, int64_t Q,
@@ -3071,6 +3157,7 @@ static const struct { const char *name; int64_t (*get)(const chb_ctx *); } kHost
     CTR("tile_skip_state", h->seat.state), CTR("tile_skipped", h->seat.skipped), CTR("tile_seen", h->seat.seen),
     CTR("tile_unloaded", h->seat.unloaded), CTR("last_batch_k", h->batch.K),
     CTR("recruit_chunk", kRecruitChunk),   // rows per launch of chb_recruit_rows
+    CTR("recruit_multi_rows", h->rc.multi_rows),   // ... of the last chb_audit_rows_multi / chb_recruit_rows_multi
     // chb_kmer_profiles / chb_set_samples_from_sequences: a chunk's limits, the chunks of the last call
     CTR("kmer_chunk_bytes", kKmerChunkBytes), CTR("kmer_chunk_rows", kKmerChunkRows), CTR("kmer_chunks", h->kmer_chunks),
     CTR("prefilter_enabled", (h->sw.use_prefilter && h->shadow_ok) ? 1 : 0),

@@ -353,7 +353,11 @@ struct RecruitArgs {
     const int *bin_ptr;    // [B+1] CSR over the labelled samples ...
     const int *memb_id;    // ... their sample indices, grouped by bin
     int B, m, metric;
-    double *dist;          // [nq][B]
+    // a list of m served from one selection pass (chb_*_rows_multi): bit m' - 1 set for every m' of the list, m above is then
+    // the largest of them and dist holds one [nq][B] slice per list entry, in ASCENDING order of m' (the host puts the
+    // slices in the caller's order when it unpacks them).  0: the single-m kernels
+    unsigned mmask;
+    double *dist;          // [nq][B]; with a list of m: [popcount(mmask)][nq][B]
 };
 constexpr int kRecruitChunk = 16384;   // rows of Y uploaded (recruit) or positions of row_idx (audit) scored per launch
 constexpr int kRecruitMaxBins = 8192;

@@ -61,7 +61,16 @@ union RecruitLds {
 // kResident (chb_audit_rows): position q of the chunk is the resident sample a.qid[q] -- its row is read from X, nothing
 // is uploaded -- and that sample alone is withheld from its own lists (leave-one-out: algorithm.py:50).  Everything else,
 // the arithmetic included, is the same code; the `false` instantiation is chb_recruit_rows' kernel unchanged.
-template <bool kResident>
+//
+// kMulti (chb_audit_rows_multi / chb_recruit_rows_multi): a list of m (the bits of a.mmask) served from one selection
+// pass, one [nq][B] slice of dist per entry in ascending order.  a.m is the list's largest entry, so the lists hold the min(members, a.m) nearest in (distance, index)
+// order and the m' nearest of any smaller m' are their first m' entries; entry (r, c) of the Gram tile is computed from
+// vertices r and c alone, so the m' x m' problem is the tile's leading block.  Per row: phase 1 once, every lane keeps
+// its plain row of the tile in registers (the selection state is dead by then), and per list entry the tile is written
+// back with everything outside the leading block zeroed -- what a launch with that m alone hands to solve16, where a
+// missing vertex reads the query row -- because solve16 overwrites the tile with the lifted, rescaled Gram.  The `false`
+// instantiations are the single-m kernels unchanged: everything of the list sits behind `if constexpr (kMulti)`.
+template <bool kResident, bool kMulti>
 __global__ __launch_bounds__(256, 2) void recruit_kernel(RecruitArgs a, int nqt, int total)
 {
     __shared__ __attribute__((aligned(16))) RecruitLds lds;
@@ -215,6 +224,39 @@ __global__ __launch_bounds__(256, 2) void recruit_kernel(RecruitArgs a, int nqt,
         __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wavefront's LDS writes have landed
         // phase 2: one problem per 16-lane group
         const int qpos = pos0 + 4 * ty + i;
+        if constexpr (kMulti) {
+            // my plain row of the group's tile (rows and columns at or past n are zero already)
+            double *Qg = &lds.so.Qt[w][kq][0][0];
+            double gr[16];
+#pragma unroll
+            for (int k = 0; k < 16; k += 2) {
+                const double2 t = *reinterpret_cast<const double2 *>(Qg + row * kQ16Ld + k);
+                gr[k] = t.x; gr[k + 1] = t.y;
+            }
+            int nlast = -1;       // the n my group solved last, and its distance: a bin with no more members than two
+            double dist = kInf;   // list entries asks for the same problem twice
+            unsigned left = a.mmask;
+#pragma unroll 1
+            for (int j = 0; left; ++j) {
+                const int nj = min(n, __ffs(left));   // (ascending: once nj has reached n it stays there)
+                left &= left - 1;
+                if (n > 0 && nj != nlast) {
+                    // the leading nj x nj block of the tile, zero around it
+#pragma unroll
+                    for (int k = 0; k < 16; k += 2)
+                        *reinterpret_cast<double2 *>(Qg + row * kQ16Ld + k) =
+                            double2{(row < nj && k < nj) ? gr[k] : 0.0, (row < nj && k + 1 < nj) ? gr[k + 1] : 0.0};
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_s_waitcnt(0xC07F);
+                    double alpha = 0.0;
+                    const double val = solve16(Qg, &lds.so.sv[w][kq][0], nj, a.metric, lane, alpha);
+                    dist = sqrt(fmax(val, 0.0));
+                    nlast = nj;
+                    __builtin_amdgcn_wave_barrier();   // the tile is rewritten for the next list entry
+                }
+                if (tx == 0 && qpos < a.nq) a.dist[((size_t)j * a.nq + qpos) * a.B + c] = dist;
+            }
+        } else {
         double dist = kInf;
         if (n > 0) {
             double alpha = 0.0;
@@ -222,6 +264,7 @@ __global__ __launch_bounds__(256, 2) void recruit_kernel(RecruitArgs a, int nqt,
             dist = sqrt(fmax(val, 0.0));
         }
         if (tx == 0 && qpos < a.nq) a.dist[(size_t)qpos * a.B + c] = dist;
+        }
         __builtin_amdgcn_wave_barrier();   // the tiles are rewritten by the next row's phase 1
         nn[0] = nn[1]; nn[1] = nn[2]; nn[2] = nn[3];
         idv[0] = idv[1]; idv[1] = idv[2]; idv[2] = idv[3];
@@ -363,8 +406,13 @@ void launch_recruit(const RecruitArgs &a, hipStream_t s)
     const int nqt = (a.nq + kQTile - 1) / kQTile;
     const int total = nqt * a.B;
     const int grid = ((total + 7) / 8) * 8;
-    if (a.qid) hipLaunchKernelGGL(recruit_kernel<true>, dim3(grid), dim3(256), 0, s, a, nqt, total);
-    else hipLaunchKernelGGL(recruit_kernel<false>, dim3(grid), dim3(256), 0, s, a, nqt, total);
+    if (a.mmask) {   // a list of m: one slice of dist per entry
+        if (a.qid) hipLaunchKernelGGL((recruit_kernel<true, true>), dim3(grid), dim3(256), 0, s, a, nqt, total);
+        else hipLaunchKernelGGL((recruit_kernel<false, true>), dim3(grid), dim3(256), 0, s, a, nqt, total);
+        return;
+    }
+    if (a.qid) hipLaunchKernelGGL((recruit_kernel<true, false>), dim3(grid), dim3(256), 0, s, a, nqt, total);
+    else hipLaunchKernelGGL((recruit_kernel<false, false>), dim3(grid), dim3(256), 0, s, a, nqt, total);
 }
 
 void launch_recruit_reduce(const double *dist, int nq, int B, int *bin, double *mind, double *margin, hipStream_t s)

@@ -148,6 +148,35 @@ int chb_recruit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const 
 int chb_audit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const int64_t *row_idx, int64_t Q,
                    int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out);
 
+/* Neighbour sweep: chb_audit_rows / chb_recruit_rows for a LIST of m in one pass -- does a finished labelling hold up at
+ * other numbers of neighbours?  The calls are defined by the single-m calls: for every j in [0, nm), slice j of each
+ * output -- bin_out + j*Q, min_dist_out + j*Q, margin_out + j*Q, dist_out + j*Q*B -- is bit for bit what chb_audit_rows /
+ * chb_recruit_rows returns for m = ms[j] on the same other arguments (+inf included).  The outputs are m-major and in the
+ * order of ms[], which need not be sorted.
+ * How: the members of a bin are ordered by the total order (distance, sample index), so the m' nearest are the first m'
+ * entries of the list of the max(ms) nearest, and entry (r, c) of the Gram tile of the shifted vertices depends on vertices
+ * r and c alone, so the m' x m' problem is the leading block of the tile of the largest m.  One selection stream (every row
+ * against every member of every bin: the dominant cost) and one Gram tile per (row, bin) serve the whole list; only the
+ * 16-lane solves repeat, each on exactly the tile the single-m kernel would have formed.
+ *   - ms: nm distinct values, 1 <= nm <= 16, each in 1 .. 16.  NULL ms, nm outside 1 .. 16, an entry < 1 or a repeated
+ *     entry is CHB_EINVAL; an entry > 16 is CHB_EUNSUPPORTED;
+ *   - every other rule is the single-m call's: dist_out, min_dist_out, margin_out may each be NULL, bin_out may be NULL if
+ *     dist_out is not; row_idx == NULL means all rows and Q must then be N; every row_idx[q] must lie in [0, N); B <= 8192
+ *     (CHB_EUNSUPPORTED beyond); D must be the resident samples' D; CHB_ESTATE without resident samples or while a
+ *     stepwise fit is open (the fit stays usable); Q = 0 is a no-op; every check runs on the host before anything is
+ *     enqueued; the call uses no state of a fit and leaves every counter (but "recruit_multi_rows"), memo and switch of
+ *     the context as it found it; with a communicator each rank scores what it is given, there is no collective;
+ *   - chunks: max(64, 16384 / nm rounded down to a multiple of 64) rows per launch (chb_counter "recruit_multi_rows": the
+ *     figure of the last such call), through the buffers and the two streams of the single-m calls -- the nm result slices
+ *     of a chunk never need more device or pinned memory than the results of a single-m chunk of 16384 rows;
+ *   - profile names "audit_multi" / "recruit_multi", work units = (row, bin, m) triples. */
+int chb_audit_rows_multi(chb_ctx *h, const int64_t *labels, int64_t B, const int *ms, int nm,
+                         const int64_t *row_idx, int64_t Q,
+                         int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out);
+int chb_recruit_rows_multi(chb_ctx *h, const int64_t *labels, int64_t B, const int *ms, int nm,
+                           const double *Y, int64_t Q, int64_t D,
+                           int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out);
+
 /* Bin report: what chb_audit_rows says about a labelling, summed up per (own bin, other bin) pair on the device -- which
  * bins bleed into each other and which are cleanly apart -- without a per-row value crossing the host boundary.
  * The call is defined by chb_audit_rows on the same arguments: for every position q whose own label
@@ -340,7 +369,9 @@ int chb_profile_reset(chb_ctx *h);
  * "pairwise" | "kmer_count" | "kmer_multi" (chb_kmer_profiles / chb_set_samples_from_sequences: the counting and the
  * finalise launch of one chunk; work units = bases) | "recruit" (chb_recruit_rows: selection + hull kernel and the row reduction of one chunk; work
  * units = (row, bin) pairs) | "audit" (chb_audit_rows: the same pair of launches for one chunk of resident rows; work units
- * = (row, bin) pairs; chb_bin_report books its two audit launches here as well) | "bin_report" (chb_bin_report: the launch
+ * = (row, bin) pairs; chb_bin_report books its two audit launches here as well) | "audit_multi" / "recruit_multi"
+ * (chb_audit_rows_multi / chb_recruit_rows_multi: the same pair of launches for one chunk and a list of m; work units =
+ * (row, bin, m) triples) | "bin_report" (chb_bin_report: the launch
  * that folds one chunk's distances and bins into the B x B tables; work units = (row, bin) pairs).  For m <= 16 "hull_qp" is the fused selection + hull-distance kernel and
  * "slow_path" the exact path for what it leaves over; "rescore*" then only appear for m > 16 or CHB_FUSED=0. */
 int chb_profile_get(chb_ctx *h, const char *kernel, double *total_ms, int64_t *launches,
@@ -366,6 +397,8 @@ int chb_fit_stats(chb_ctx *h, int64_t *out4);
  * from the pools), "pool_state" (0 undecided = on, 1 kept on, -1 turned off because the shortlists came out long),
  * "pool_candidates" / "pool_pairs" (sampled shortlist lengths behind that decision), "exchanges" (framed all-gathers of the last fit under an exchange: one per batch for the
  * label guess, one per round), "recruit_chunk" (rows per launch of chb_recruit_rows, chb_audit_rows and -- at most -- chb_bin_report: a constant),
+ * "recruit_multi_rows" (rows per launch of the last chb_audit_rows_multi / chb_recruit_rows_multi call: 16384 / nm rounded
+ * down to a multiple of 64; 0 before the first),
  * "kmer_chunk_bytes" / "kmer_chunk_rows" (the most bases / contigs of one sequence chunk of chb_kmer_profiles and
  * chb_set_samples_from_sequences: constants), "kmer_chunks" (chunks of the last such call) */
 int chb_counter(chb_ctx *h, const char *name, int64_t *out);
