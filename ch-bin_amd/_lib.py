@@ -201,112 +201,77 @@ class Context:
                                          dist.ctypes.data, cnt))
         return idx, dist, cnt
 
+    def _labels(self, labels):
+        labels = np.ascontiguousarray(labels, dtype=np.int64)
+        if labels.shape != (self.N,):
+            raise ValueError("labels must have one entry per resident sample")
+        return labels
+
+    def _row_indices(self, rows):
+        """(row_idx argument, Q, the array behind it) of rows=None (every resident row in order) or a 1-D list of indices"""
+        if rows is None:
+            return None, self.N, None
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        if rows.ndim != 1:
+            raise ValueError("rows must be a 1-D array of sample indices")
+        return rows.ctypes.data, rows.shape[0], rows
+
+    def _score_rows(self, name, labels, B, want_dist, m=None, ms=None, rows=None, Y=None):
+        """The four row-scoring calls: chb_<name>_rows for one m, of the new rows Y or the resident rows `rows`, or with a
+        list `ms` its _multi form, whose outputs carry a leading axis of len(ms)."""
+        if ms is not None:
+            ms = np.ascontiguousarray(ms, dtype=np.intc)
+            if ms.ndim != 1:
+                raise ValueError("ms must be a 1-D list of neighbour counts")
+        if Y is not None:
+            Y = np.ascontiguousarray(Y, dtype=np.float64)
+            if Y.ndim != 2:
+                raise ValueError("rows must be a 2-D array")
+        labels = self._labels(labels)
+        if Y is not None:
+            source = (Y.ctypes.data, *Y.shape)
+        else:
+            *source, rows = self._row_indices(rows)
+        lead, Q = () if ms is None else ms.shape, source[1]
+        bins = np.empty(lead + (Q,), dtype=np.int64)
+        dist = np.empty(lead + (Q, int(B)), dtype=np.float64) if want_dist else None
+        mind = np.empty(lead + (Q,), dtype=np.float64)
+        margin = np.empty(lead + (Q,), dtype=np.float64)
+        fn = getattr(self._lib, f"chb_{name}_rows" if ms is None else f"chb_{name}_rows_multi")
+        neighbours = (int(m),) if ms is None else (ms.ctypes.data, ms.shape[0])
+        check(fn(self._h, labels.ctypes.data, int(B), *neighbours, *source,
+                 bins.ctypes.data, None if dist is None else dist.ctypes.data, mind.ctypes.data, margin.ctypes.data))
+        return bins, dist, mind, margin
+
     def recruit_rows(self, labels, B, m, Y, want_dist=True):
         """chb_recruit_rows: hull distance of the NEW rows Y (not samples) to every bin of the frozen `labels`.
         Returns (bins [Q], dist [Q, B] or None, min_dist [Q], margin [Q])."""
-        labels = np.ascontiguousarray(labels, dtype=np.int64)
-        Y = np.ascontiguousarray(Y, dtype=np.float64)
-        if Y.ndim != 2:
-            raise ValueError("rows must be a 2-D array")
-        if labels.shape != (self.N,):
-            raise ValueError("labels must have one entry per resident sample")
-        Q, D = Y.shape
-        bins = np.empty(Q, dtype=np.int64)
-        dist = np.empty((Q, int(B)), dtype=np.float64) if want_dist else None
-        mind = np.empty(Q, dtype=np.float64)
-        margin = np.empty(Q, dtype=np.float64)
-        check(self._lib.chb_recruit_rows(self._h, labels.ctypes.data, int(B), int(m), Y.ctypes.data, Q, D,
-                                         bins.ctypes.data, None if dist is None else dist.ctypes.data,
-                                         mind.ctypes.data, margin.ctypes.data))
-        return bins, dist, mind, margin
+        return self._score_rows("recruit", labels, B, want_dist, m=m, Y=Y)
 
     def audit_rows(self, labels, B, m, rows=None, want_dist=True):
         """chb_audit_rows: leave-one-out hull distance of the RESIDENT rows `rows` (sample indices, repeats allowed; None:
         every row in order) to every bin of the frozen `labels`; a row is withheld from its own bin's candidates.
         Returns (bins [Q], dist [Q, B] or None, min_dist [Q], margin [Q])."""
-        labels = np.ascontiguousarray(labels, dtype=np.int64)
-        if labels.shape != (self.N,):
-            raise ValueError("labels must have one entry per resident sample")
-        if rows is not None:
-            rows = np.ascontiguousarray(rows, dtype=np.int64)
-            if rows.ndim != 1:
-                raise ValueError("rows must be a 1-D array of sample indices")
-        Q = self.N if rows is None else rows.shape[0]
-        bins = np.empty(Q, dtype=np.int64)
-        dist = np.empty((Q, int(B)), dtype=np.float64) if want_dist else None
-        mind = np.empty(Q, dtype=np.float64)
-        margin = np.empty(Q, dtype=np.float64)
-        check(self._lib.chb_audit_rows(self._h, labels.ctypes.data, int(B), int(m),
-                                       None if rows is None else rows.ctypes.data, Q,
-                                       bins.ctypes.data, None if dist is None else dist.ctypes.data,
-                                       mind.ctypes.data, margin.ctypes.data))
-        return bins, dist, mind, margin
-
-    @staticmethod
-    def _m_list(ms):
-        ms = np.ascontiguousarray(ms, dtype=np.intc)
-        if ms.ndim != 1:
-            raise ValueError("ms must be a 1-D list of neighbour counts")
-        return ms
+        return self._score_rows("audit", labels, B, want_dist, m=m, rows=rows)
 
     def audit_rows_multi(self, labels, B, ms, rows=None, want_dist=True):
         """chb_audit_rows_multi: audit_rows for every m of the list `ms` (distinct values in 1 .. 16, at most 16 of them,
         any order) from one selection pass; slice j of every result is bit for bit audit_rows(labels, B, ms[j], rows).
         Returns (bins [nm, Q], dist [nm, Q, B] or None, min_dist [nm, Q], margin [nm, Q])."""
-        labels = np.ascontiguousarray(labels, dtype=np.int64)
-        ms = self._m_list(ms)
-        if labels.shape != (self.N,):
-            raise ValueError("labels must have one entry per resident sample")
-        if rows is not None:
-            rows = np.ascontiguousarray(rows, dtype=np.int64)
-            if rows.ndim != 1:
-                raise ValueError("rows must be a 1-D array of sample indices")
-        Q = self.N if rows is None else rows.shape[0]
-        nm = ms.shape[0]
-        bins = np.empty((nm, Q), dtype=np.int64)
-        dist = np.empty((nm, Q, int(B)), dtype=np.float64) if want_dist else None
-        mind = np.empty((nm, Q), dtype=np.float64)
-        margin = np.empty((nm, Q), dtype=np.float64)
-        check(self._lib.chb_audit_rows_multi(self._h, labels.ctypes.data, int(B), ms.ctypes.data, nm,
-                                             None if rows is None else rows.ctypes.data, Q,
-                                             bins.ctypes.data, None if dist is None else dist.ctypes.data,
-                                             mind.ctypes.data, margin.ctypes.data))
-        return bins, dist, mind, margin
+        return self._score_rows("audit", labels, B, want_dist, ms=ms, rows=rows)
 
     def recruit_rows_multi(self, labels, B, ms, Y, want_dist=True):
         """chb_recruit_rows_multi: recruit_rows for every m of the list `ms` from one selection pass; slice j of every
         result is bit for bit recruit_rows(labels, B, ms[j], Y).
         Returns (bins [nm, Q], dist [nm, Q, B] or None, min_dist [nm, Q], margin [nm, Q])."""
-        labels = np.ascontiguousarray(labels, dtype=np.int64)
-        ms = self._m_list(ms)
-        Y = np.ascontiguousarray(Y, dtype=np.float64)
-        if Y.ndim != 2:
-            raise ValueError("rows must be a 2-D array")
-        if labels.shape != (self.N,):
-            raise ValueError("labels must have one entry per resident sample")
-        Q, D = Y.shape
-        nm = ms.shape[0]
-        bins = np.empty((nm, Q), dtype=np.int64)
-        dist = np.empty((nm, Q, int(B)), dtype=np.float64) if want_dist else None
-        mind = np.empty((nm, Q), dtype=np.float64)
-        margin = np.empty((nm, Q), dtype=np.float64)
-        check(self._lib.chb_recruit_rows_multi(self._h, labels.ctypes.data, int(B), ms.ctypes.data, nm, Y.ctypes.data, Q, D,
-                                               bins.ctypes.data, None if dist is None else dist.ctypes.data,
-                                               mind.ctypes.data, margin.ctypes.data))
-        return bins, dist, mind, margin
+        return self._score_rows("recruit", labels, B, want_dist, ms=ms, Y=Y)
 
     def bin_report(self, labels, B, m, rows=None):
         """chb_bin_report: chb_audit_rows' answer for the RESIDENT rows `rows` (None: every row in order) summed up on the
         device per (own bin a, bin b) pair; rows whose own label lies outside [0, B) are not scored.
         Returns (confusion [B, B], unplaced [B], dcnt [B, B], dmin [B, B], dsum [B, B], n_skipped)."""
-        labels = np.ascontiguousarray(labels, dtype=np.int64)
-        if labels.shape != (self.N,):
-            raise ValueError("labels must have one entry per resident sample")
-        if rows is not None:
-            rows = np.ascontiguousarray(rows, dtype=np.int64)
-            if rows.ndim != 1:
-                raise ValueError("rows must be a 1-D array of sample indices")
-        Q = self.N if rows is None else rows.shape[0]
+        labels = self._labels(labels)
+        row_idx, Q, rows = self._row_indices(rows)
         B = int(B)
         nb = max(B, 0) if B <= 8192 else 0   # (beyond the limit the call is refused before it writes anything)
         confusion = np.empty((nb, nb), dtype=np.int64)
@@ -315,10 +280,9 @@ class Context:
         dmin = np.empty((nb, nb), dtype=np.float64)
         dsum = np.empty((nb, nb), dtype=np.float64)
         skipped = C.c_int64(0)
-        check(self._lib.chb_bin_report(self._h, labels.ctypes.data, B, int(m),
-                                       None if rows is None else rows.ctypes.data, Q,
-                                       confusion.ctypes.data, unplaced.ctypes.data, dcnt.ctypes.data, dmin.ctypes.data,
-                                       dsum.ctypes.data, C.addressof(skipped)))
+        check(self._lib.chb_bin_report(self._h, labels.ctypes.data, B, int(m), row_idx, Q, confusion.ctypes.data,
+                                       unplaced.ctypes.data, dcnt.ctypes.data, dmin.ctypes.data, dsum.ctypes.data,
+                                       C.addressof(skipped)))
         return confusion, unplaced, dcnt, dmin, dsum, int(skipped.value)
 
     def find_nearest_from_row(self, c, labels, row, m):

@@ -101,6 +101,9 @@ RcclApi *rccl()
             return fail(CHB_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));      \
     } while (0)
 
+// (in a function that returns the hipError_t itself)
+#define HIPTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
+
 struct ProfEntry {
     double ms = 0.0;
     int64_t launches = 0;
@@ -250,26 +253,32 @@ struct Segments {
     int64_t stat_batches = 0;   // batches of the last fit that ran the segment launches
 };
 
-// chb_recruit_rows: a chunk of the new rows (padded like X), its distances and row reductions, the call's CSR over the
-// labels -- the call's own buffers, nothing of a fit.  Two of each per-chunk buffer, on the device and pinned on the
-// host: while the kernels of chunk k run on the context's stream, copy brings chunk k + 1 up and chunk k - 1 down
-// (up / done / down: upload, kernels, download of the chunk in that half are through).  chb_audit_rows runs through the
-// same buffers: what it sends up per chunk is qid, the chunk's sample indices, in place of Y.  The calls for a list of m
-// (chb_*_rows_multi) cut their chunks shorter by the list's length, so that the list's result slices of a chunk fit the
-// result buffers of a single-m chunk.  chb_bin_report is an audit
-// whose chunks are cut from the positions in label order: per chunk seg (each label's run, BinReportArgs) goes up as
-// well, nothing comes down, and the B x B tables rep_* (zeroed at the call's start) collect what the chunks' rows say.
-struct Recruit {
-    DevBuf<double> Y[2], dist[2], min[2], margin[2];
-    DevBuf<int> bin[2], qid[2], ptr, memb;
-    PinBuf<double> hY[2], hdist[2], hmin[2], hmargin[2];
-    PinBuf<int> hbin[2], hqid[2], hptr, hmemb;
-    DevBuf<int2> seg[2];
-    PinBuf<int2> hseg[2];
+// One half of the row-scoring calls' double buffer: a chunk of the new rows (padded like X) or of sample indices (qid), its
+// distances and row reductions, on the device and pinned on the host (h*); chb_bin_report's chunks also carry seg, each label's
+// run (BinReportArgs), nseg of them.  up / done / down: the upload, the kernels, the download of the chunk in this half are through.
+struct ChunkHalf {
+    DevBuf<double> Y, dist, min, margin;
+    DevBuf<int> bin, qid;
+    DevBuf<int2> seg;
+    PinBuf<double> hY, hdist, hmin, hmargin;
+    PinBuf<int> hbin, hqid;
+    PinBuf<int2> hseg;
+    hipEvent_t up = nullptr, done = nullptr, down = nullptr;
+    int nseg = 0;
+    void destroy_events() { for (hipEvent_t ev : {up, done, down}) if (ev) (void)hipEventDestroy(ev); }
+};
+
+// chb_recruit_rows, chb_audit_rows, chb_*_rows_multi, chb_bin_report (ScoreRun): the calls' own buffers, nothing of a fit.
+// While the kernels of chunk k run on the context's stream, copy brings chunk k + 1 up into the other half and chunk
+// k - 1 down.  Not per half: the call's CSR over the labels (ptr, memb) and chb_bin_report's B x B tables rep_* (zeroed at
+// the call's start), which collect what the chunks' rows say.
+struct RowScoring {
+    ChunkHalf half[2];
+    DevBuf<int> ptr, memb;
+    PinBuf<int> hptr, hmemb;
     DevBuf<long long> rep_conf, rep_unplaced, rep_cnt;
     DevBuf<double> rep_min, rep_sum;
     hipStream_t copy = nullptr;
-    hipEvent_t up[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr}, down[2] = {nullptr, nullptr};
     int64_t multi_rows = 0;   // rows per launch of the last chb_audit_rows_multi / chb_recruit_rows_multi
 };
 
@@ -317,7 +326,7 @@ struct chb_ctx {
     ThresholdPools pool;
     Seating seat;
     Segments seg;
-    Recruit rc;
+    RowScoring score;
     Exchange xchg;
     Profile prof;
     BatchState batch;
@@ -1866,13 +1875,13 @@ int chb_destroy(chb_ctx *h)
     if (!h) return CHB_OK;
     (void)hipSetDevice(h->dev);
     (void)hipStreamSynchronize(h->stream);
-    if (h->rc.copy) (void)hipStreamSynchronize(h->rc.copy);
+    if (h->score.copy) (void)hipStreamSynchronize(h->score.copy);
     drain_profile(h);
     if (h->xchg.comm && rccl()) { (void)rccl()->CommDestroy(h->xchg.comm); h->xchg.comm = nullptr; }
     // the handles without an owner; the buffers (DevBuf / PinBuf, PackBufs) free themselves when `delete h` destroys them
-    hipEvent_t ev[] = {h->rc.up[0], h->rc.up[1], h->rc.done[0], h->rc.done[1], h->rc.down[0], h->rc.down[1], h->fc_event[0], h->fc_event[1]};
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    if (h->rc.copy) (void)hipStreamDestroy(h->rc.copy);
+    for (ChunkHalf &half : h->score.half) half.destroy_events();
+    for (hipEvent_t e : h->fc_event) if (e) (void)hipEventDestroy(e);
+    if (h->score.copy) (void)hipStreamDestroy(h->score.copy);
     if (h->fc_host) (void)hipHostFree(h->fc_host);
     (void)hipStreamDestroy(h->stream);
     delete h;
@@ -2378,22 +2387,43 @@ int chb_hull_distance_points(chb_ctx *h, const double *x, const double *pts, int
     return hull_indexed(h, h->xpts.p, (int)D, Dp, m + 1, &q, 1, idx.data(), m, dist, alpha);
 }
 
+// ======== row scoring (chb_recruit_rows, chb_audit_rows, chb_*_rows_multi, chb_bin_report): the entry point checks its
+// arguments (score_check_args) and fills a ScoreRequest, a ScoreRun carries it through its stages
 namespace {
 
 constexpr int kRecruitPiece = 2048;   // rows per host-to-device copy of a chunk
 
-// chb_bin_report's part of a recruit_run call: the scored positions (those whose own label lies in [0, B)) in label
-// order -- a stable counting sort, so a label's positions keep the order of row_idx -- and the chunks cut from that
-// order: at most kRecruitChunk positions each, cut back to the last kReportBlock-row block boundary of the label a cut
-// would split, so that no summation block of dsum (BinReportArgs) lies in two chunks.
+// chb_bin_report's five tables as the caller wants them (any may be null)
+struct ReportOut { int64_t *confusion, *unplaced, *dcnt; double *dmin, *dsum; };
+
+// chb_bin_report's part of a ScoreRun: the scored positions (those whose own label lies in [0, B)) in label order -- a
+// stable counting sort, so a label's positions keep the order of row_idx -- and the chunks cut from that order: at most
+// kRecruitChunk positions each, cut back to the last kReportBlock-row block boundary of the label a cut would split, so
+// that no summation block of dsum (BinReportArgs) lies in two chunks.
 struct ReportPlan {
+    int64_t B = 0;
     std::vector<int> ord;            // [Qv] sample index of every scored position, grouped by label
     std::vector<int64_t> lab_ptr;    // [B + 1] label a's run is ord[lab_ptr[a] .. lab_ptr[a + 1])
     std::vector<int64_t> cut;        // chunk k is ord[cut[k] .. cut[k + 1])
-    BinReportArgs tables{};          // the context's tables (conf, unplaced, cnt, dmin, dsum)
-    void cut_chunks()
+    // the plan of the positions row_idx[0 .. Q) (nullptr: position = sample); returns Qv, the others are only counted
+    int64_t build(const int64_t *labels, int64_t B_, const int64_t *row_idx, int64_t Q)
     {
-        const int64_t Qv = (int64_t)ord.size();
+        B = B_;
+        lab_ptr.assign((size_t)B + 1, 0);
+        auto own = [&](int64_t q) { return labels[row_idx ? row_idx[q] : q]; };
+        int64_t Qv = 0;
+        for (int64_t q = 0; q < Q; ++q) {
+            const int64_t l = own(q);
+            if (l >= 0 && l < B) { ++lab_ptr[(size_t)l + 1]; ++Qv; }
+        }
+        if (Qv == 0) return 0;
+        for (int64_t c = 0; c < B; ++c) lab_ptr[(size_t)c + 1] += lab_ptr[(size_t)c];
+        ord.resize((size_t)Qv);
+        std::vector<int64_t> cur(lab_ptr.begin(), lab_ptr.end() - 1);
+        for (int64_t q = 0; q < Q; ++q) {
+            const int64_t l = own(q);
+            if (l >= 0 && l < B) ord[(size_t)cur[(size_t)l]++] = (int)(row_idx ? row_idx[q] : q);
+        }
         cut.assign(1, 0);
         while (cut.back() < Qv) {
             int64_t c1 = std::min<int64_t>(Qv, cut.back() + kRecruitChunk);
@@ -2403,223 +2433,334 @@ struct ReportPlan {
             }
             cut.push_back(c1);
         }
+        return Qv;
+    }
+    // nothing to score: the tables of a call without rows
+    void empty_tables(const ReportOut &o) const
+    {
+        const size_t BB = (size_t)B * (size_t)B;
+        if (o.confusion) std::fill(o.confusion, o.confusion + BB, (int64_t)0);
+        if (o.unplaced) std::fill(o.unplaced, o.unplaced + B, (int64_t)0);
+        if (o.dcnt) std::fill(o.dcnt, o.dcnt + BB, (int64_t)0);
+        if (o.dmin) std::fill(o.dmin, o.dmin + BB, std::numeric_limits<double>::infinity());
+        if (o.dsum) std::fill(o.dsum, o.dsum + BB, 0.0);
+    }
+    // the context's tables, behind the last chunk
+    int copy_tables(chb_ctx *h, const ReportOut &o) const
+    {
+        const RowScoring &sc = h->score;
+        hipStream_t s = h->stream;
+        const size_t BB = (size_t)B * (size_t)B;
+        static_assert(sizeof(long long) == sizeof(int64_t), "the tables are copied out as they are");
+        if (o.confusion) HIPCHK(hipMemcpyAsync(o.confusion, sc.rep_conf.p, sizeof(int64_t) * BB, hipMemcpyDeviceToHost, s));
+        if (o.unplaced) HIPCHK(hipMemcpyAsync(o.unplaced, sc.rep_unplaced.p, sizeof(int64_t) * (size_t)B, hipMemcpyDeviceToHost, s));
+        if (o.dcnt) HIPCHK(hipMemcpyAsync(o.dcnt, sc.rep_cnt.p, sizeof(int64_t) * BB, hipMemcpyDeviceToHost, s));
+        if (o.dmin) HIPCHK(hipMemcpyAsync(o.dmin, sc.rep_min.p, sizeof(double) * BB, hipMemcpyDeviceToHost, s));
+        if (o.dsum) HIPCHK(hipMemcpyAsync(o.dsum, sc.rep_sum.p, sizeof(double) * BB, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return CHB_OK;
     }
 };
 
-// The chunks of one chb_recruit_rows or chb_audit_rows call, pipelined: the rows of chunk k are packed (zero-padded to
-// Dp) into pinned memory and copied up on rc_copy piece by piece, so the copy of a piece runs under the packing of the
-// next; the kernels run on the context's stream; the results come down on rc_copy into pinned memory and are unpacked by
-// the host.  The order of a step -- kernels of k, upload of k + 1, download of k, unpack of k - 1 -- keeps rc_copy from
-// queueing an upload behind a download that waits for kernels.  Everything asynchronous reads and writes context-owned
-// memory.  Y == nullptr is the audit: no row goes up, only the chunk's sample indices as int32 (row_idx, already checked
-// against N; nullptr: position = sample), and the kernel reads the rows from the resident matrix.  With a plan (rp:
-// chb_bin_report) the positions are the plan's, chunk k is the plan's cut k, each label's run in the chunk goes up beside
-// the indices and bin_report_kernel folds the chunk into the plan's tables behind the two audit kernels.  Outputs that
-// have no destination are neither downloaded nor unpacked.  With a list of m (a.mmask; slot: list entry j's slice on the
-// device, where the slices lie in ascending order of m) a chunk's results are ns slices of nq rows each, reduced by one
-// launch over ns * nq rows, and unpacking puts slice slot[j] of the chunk at out + j * Q + t0.
-hipError_t recruit_chunks(chb_ctx *h, RecruitArgs a, const double *Y, const int64_t *row_idx, int64_t Q, int64_t chunk,
-                          int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out, const ReportPlan *rp,
-                          const int *slot = nullptr, int ns = 1)
+// What a row-scoring call asks for, filled by its entry point
+struct ScoreRequest {
+    const int64_t *labels; int64_t B;
+    // the source, one of three: the new rows Y (recruit); the resident rows row_idx, nullptr meaning all rows (audit);
+    // a plan's positions (chb_bin_report: an audit whose chunks are the plan's cuts)
+    const double *Y; const int64_t *row_idx; const ReportPlan *plan;
+    int64_t Q;
+    int m; const int *ms; int nm;   // neighbours; nm > 0: the list of a chb_*_rows_multi call, m its largest entry
+    int64_t *bin_out; double *dist_out, *min_dist_out, *margin_out;   // (without a destination: neither downloaded nor unpacked)
+};
+
+// The argument checks of the five entry points, for all of them in this order: null context; ranges and a malformed list
+// (CHB_EINVAL); null arguments; outputs; no samples; D; more than 16 neighbours (CHB_EUNSUPPORTED); more than 8192 bins;
+// an open stepwise fit; Q == 0 (CHB_OK: nothing further is read); the row_idx rules.
+// D: the rows' number of columns in the calls that take Y, nullptr in the others.  list: the call takes ms / nm, whose
+// largest entry becomes rq.m.  no_output: the refusal's text when every output that counts for the call is null, else nullptr.
+int score_check_args(chb_ctx *h, const char *who, ScoreRequest &rq, const int64_t *D, bool list, const char *no_output)
 {
-#define RCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
-    hipStream_t s = h->stream, c = h->rc.copy;
-    const bool audit = !Y;
-    const bool any_out = bin_out || dist_out || min_dist_out || margin_out;
-    const int64_t D = a.D, Dp = a.Dp, B = a.B;
-    const int64_t n = rp ? (int64_t)rp->cut.size() - 1 : (Q + chunk - 1) / chunk;
-    auto start = [&](int64_t k) { return rp ? rp->cut[(size_t)k] : k * chunk; };
-    auto rows = [&](int64_t k) { return (int)(std::min<int64_t>(start(k + 1), Q) - start(k)); };
-    int nseg[2] = {0, 0};   // runs of the chunk in each half
-    auto upload = [&](int64_t k) -> hipError_t {
-        const int b = (int)(k & 1), nq = rows(k);
-        RCHK(hipEventSynchronize(h->rc.up[b]));          // the pinned half: its last upload (chunk k - 2) has left it
-        RCHK(hipStreamWaitEvent(c, h->rc.done[b], 0));   // the device half: the kernels of chunk k - 2 have read it
-        if (audit) {   // the chunk's sample indices and nothing else
-            int *ids = h->rc.hqid[b].p;
-            const int64_t t0 = start(k);
-            if (rp) {
-                memcpy(ids, rp->ord.data() + t0, sizeof(int) * nq);
-                int2 *sg = h->rc.hseg[b].p;
-                int ns = 0;
-                size_t l = (size_t)(std::upper_bound(rp->lab_ptr.begin(), rp->lab_ptr.end(), t0) - rp->lab_ptr.begin()) - 1;
-                for (; l < (size_t)B && rp->lab_ptr[l] < t0 + nq; ++l)
-                    if (rp->lab_ptr[l + 1] > rp->lab_ptr[l]) sg[ns++] = make_int2((int)l, (int)(std::max(rp->lab_ptr[l], t0) - t0));
-                sg[ns] = make_int2(-1, nq);
-                nseg[b] = ns;
-                RCHK(hipMemcpyAsync(h->rc.seg[b].p, sg, sizeof(int2) * ((size_t)ns + 1), hipMemcpyHostToDevice, c));
-            } else {
-                for (int i = 0; i < nq; ++i) ids[i] = (int)(row_idx ? row_idx[t0 + i] : t0 + i);
-            }
-            RCHK(hipMemcpyAsync(h->rc.qid[b].p, ids, sizeof(int) * nq, hipMemcpyHostToDevice, c));
-            return hipEventRecord(h->rc.up[b], c);
+    if (!h) return fail(CHB_EINVAL, "null context");
+    if (list) {
+        if (rq.Q < 0 || rq.B < 1) return fail(CHB_EINVAL, "Q < 0 or B < 1");
+        if (!rq.ms) return fail(CHB_EINVAL, "ms is null");
+        if (rq.nm < 1 || rq.nm > kMaxM) return fail(CHB_EINVAL, "nm must be 1 .. 16");
+        unsigned seen = 0;   // 1 .. 16 distinct entries in 1 .. 16 (an entry above 16 is refused below and sets no bit here)
+        rq.m = 0;
+        for (int j = 0; j < rq.nm; ++j) {
+            if (rq.ms[j] < 1) return fail(CHB_EINVAL, "an entry of ms is < 1");
+            const unsigned bit = rq.ms[j] <= kMaxM ? 1u << (rq.ms[j] - 1) : 0;
+            if (seen & bit) return fail(CHB_EINVAL, "ms holds a value twice");
+            seen |= bit;
+            rq.m = std::max(rq.m, rq.ms[j]);
         }
+    } else if (rq.Q < 0 || rq.B < 1 || rq.m < 1) {
+        return fail(CHB_EINVAL, "Q < 0, B < 1 or m < 1");
+    }
+    if (rq.Q > 0 && (!rq.labels || (D && !rq.Y))) return fail(CHB_EINVAL, "null argument");
+    if (no_output) return fail(CHB_EINVAL, no_output);
+    if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
+    if (D && *D != h->D) return fail(CHB_EINVAL, "the rows must have the resident samples' number of columns");
+    if (rq.m > kMaxM) return fail(CHB_EUNSUPPORTED, std::string(who) + " supports at most 16 neighbours");
+    if (rq.B > kRecruitMaxBins) return fail(CHB_EUNSUPPORTED, std::string(who) + " supports at most 8192 bins");
+    if (h->batch.open || (h->fit_open && h->stepwise))
+        return fail(CHB_ESTATE, "a stepwise fit is open on this context (chb_fit_begin): chb_set_samples ends it");
+    if (rq.Q == 0 || D) return CHB_OK;   // (the calls that take Y have no row_idx)
+    if (!rq.row_idx && rq.Q != h->N) return fail(CHB_EINVAL, "row_idx is null (all rows): Q must be the number of resident samples");
+    for (int64_t q = 0; rq.row_idx && q < rq.Q; ++q)
+        if (rq.row_idx[q] < 0 || rq.row_idx[q] >= h->N) return fail(CHB_EINVAL, "row_idx entry outside [0, N)");
+    return CHB_OK;
+}
+
+// One row-scoring call behind its checks: its stages in call order, then the steps of its pipeline.  The chunks go through
+// the two halves of the context's RowScoring: chunk k is staged in pinned memory and copied up on the copy stream, the
+// kernels run on the context's stream, the results come down on the copy stream into pinned memory and are unpacked by
+// the host.  Everything asynchronous reads and writes context-owned memory.
+struct ScoreRun {
+    chb_ctx *h;
+    const ScoreRequest rq;
+    RowScoring &sc = h->score;
+    hipStream_t s = h->stream;
+    const bool audit = !rq.Y /* the rows are resident */, any_out = rq.bin_out || rq.dist_out || rq.min_dist_out || rq.margin_out;
+    const int ns = rq.nm > 0 ? rq.nm : 1;   // result slices per chunk
+    int slot[kMaxM] = {0};                  // list entry j's slice on the device = the number of smaller entries
+    size_t n_memb = 0;
+    int64_t chunk = 0, n = 0;               // rows per chunk (a plan: its cuts), chunks
+    RecruitArgs a{};
+    int64_t start(int64_t k) const { return rq.plan ? rq.plan->cut[(size_t)k] : k * chunk; }
+    int rows(int64_t k) const { return (int)(std::min<int64_t>(start(k + 1), rq.Q) - start(k)); }
+    ChunkHalf &half(int64_t k) { return sc.half[k & 1]; }
+    // the copy stream and the halves' events: created by the context's first row-scoring call
+    int ensure_copy_stream()
+    {
+        if (sc.copy) return CHB_OK;
+        HIPCHK(hipStreamCreateWithFlags(&sc.copy, hipStreamNonBlocking));
+        for (ChunkHalf &b : sc.half)
+            for (hipEvent_t *ev : {&b.up, &b.done, &b.down}) HIPCHK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+        return CHB_OK;
+    }
+    // CSR over the labels (host counting sort into pinned memory; members of a bin in index order -- the selection does
+    // not depend on it)
+    int label_csr()
+    {
+        const int64_t N = h->N, B = rq.B, *labels = rq.labels;
+        HIPCHK(sc.hptr.ensure((size_t)B + 1));
+        int *ptr = sc.hptr.p;
+        std::fill(ptr, ptr + B + 1, 0);
+        for (int64_t i = 0; i < N; ++i)
+            if (labels[i] >= 0 && labels[i] < B) ++ptr[labels[i] + 1];
+        for (int64_t c = 0; c < B; ++c) ptr[c + 1] += ptr[c];
+        n_memb = (size_t)std::max(ptr[B], 1);
+        HIPCHK(sc.hmemb.ensure(n_memb));
+        std::vector<int> cur(ptr, ptr + B);
+        for (int64_t i = 0; i < N; ++i)
+            if (labels[i] >= 0 && labels[i] < B) sc.hmemb.p[cur[(size_t)labels[i]]++] = (int)i;
+        return CHB_OK;
+    }
+    // a list of m: its mask for the kernel, and where the unpack step finds entry j's slice
+    void list_slots()
+    {
+        for (int j = 0; j < rq.nm; ++j) {
+            a.mmask |= 1u << (rq.ms[j] - 1);
+            for (int k = 0; k < rq.nm; ++k) slot[j] += rq.ms[k] < rq.ms[j];
+        }
+    }
+    // chunk length and buffers.  A list's chunks are kRecruitChunk / nm rows, rounded down to whole 64-row tiles, so the
+    // nm result slices of a chunk fill no more than a single-m chunk's buffers.
+    int size_buffers()
+    {
+        const int64_t B = rq.B;
+        if (rq.nm > 0) sc.multi_rows = std::max<int64_t>(kQTile, kRecruitChunk / rq.nm / kQTile * kQTile);
+        chunk = std::min<int64_t>(rq.Q, rq.nm > 0 ? sc.multi_rows : kRecruitChunk);
+        n = rq.plan ? (int64_t)rq.plan->cut.size() - 1 : (rq.Q + chunk - 1) / chunk;
+        const size_t res = (size_t)chunk * (size_t)ns;   // result rows of a chunk
+        const int halves = rq.Q > chunk ? 2 : 1;   // (a plan's first cut is shorter than Q whenever it has a second)
+        HIPCHK(sc.ptr.ensure((size_t)B + 1));
+        HIPCHK(sc.memb.ensure(n_memb));
+        for (int i = 0; i < halves; ++i) {
+            ChunkHalf &b = sc.half[i];
+            HIPCHK(rq.Y ? b.Y.ensure((size_t)chunk * h->Dp) : b.qid.ensure((size_t)chunk));
+            HIPCHK(rq.Y ? b.hY.ensure((size_t)chunk * h->Dp) : b.hqid.ensure((size_t)chunk));
+            HIPCHK(b.dist.ensure(res * (size_t)B));
+            if (rq.dist_out) HIPCHK(b.hdist.ensure(res * (size_t)B));
+            HIPCHK(b.bin.ensure(res));
+            HIPCHK(b.hbin.ensure(res));
+            HIPCHK(b.min.ensure(res));
+            HIPCHK(b.hmin.ensure(res));
+            HIPCHK(b.margin.ensure(res));
+            HIPCHK(b.hmargin.ensure(res));
+            if (rq.plan) {   // a chunk holds at most one run per label
+                HIPCHK(b.seg.ensure((size_t)std::min<int64_t>(B, chunk) + 1));
+                HIPCHK(b.hseg.ensure((size_t)std::min<int64_t>(B, chunk) + 1));
+            }
+        }
+        return CHB_OK;
+    }
+    // chb_bin_report: the context's tables, zeroed (dmin: +inf) on the stream
+    int reset_report_tables()
+    {
+        if (!rq.plan) return CHB_OK;
+        const size_t B = (size_t)rq.B, BB = B * B;
+        HIPCHK(sc.rep_conf.ensure(BB));
+        HIPCHK(sc.rep_unplaced.ensure(B));
+        HIPCHK(sc.rep_cnt.ensure(BB));
+        HIPCHK(sc.rep_min.ensure(BB));
+        HIPCHK(sc.rep_sum.ensure(BB));
+        HIPCHK(hipMemsetAsync(sc.rep_conf.p, 0, sizeof(long long) * BB, s));
+        HIPCHK(hipMemsetAsync(sc.rep_unplaced.p, 0, sizeof(long long) * B, s));
+        HIPCHK(hipMemsetAsync(sc.rep_cnt.p, 0, sizeof(long long) * BB, s));
+        HIPCHK(hipMemsetAsync(sc.rep_sum.p, 0, sizeof(double) * BB, s));
+        launch_fill_f64(sc.rep_min.p, std::numeric_limits<double>::infinity(), BB, s);
+        return CHB_OK;
+    }
+    // what every chunk's launch shares, and the CSR it points at on its way up
+    int kernel_args()
+    {
+        HIPCHK(hipMemcpyAsync(sc.ptr.p, sc.hptr.p, sizeof(int) * ((size_t)rq.B + 1), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(sc.memb.p, sc.hmemb.p, sizeof(int) * n_memb, hipMemcpyHostToDevice, s));
+        a.X = h->X.p; a.D = h->D; a.Dp = h->Dp; a.bin_ptr = sc.ptr.p; a.memb_id = sc.memb.p;
+        a.B = (int)rq.B; a.m = rq.m; a.metric = h->metric;
+        return CHB_OK;
+    }
+    // The order of a step -- kernels of k, upload of k + 1, download of k, unpack of k - 1 -- keeps the copy stream from
+    // queueing an upload behind a download that waits for kernels.
+    hipError_t pipeline()
+    {
+        HIPTRY(upload(0));
+        for (int64_t k = 0; k < n; ++k) {
+            HIPTRY(launch(k));
+            if (k + 1 < n) HIPTRY(upload(k + 1));
+            if (!any_out) continue;
+            HIPTRY(download(k));
+            if (k > 0) HIPTRY(unpack(k - 1));
+        }
+        return any_out ? unpack(n - 1) : hipSuccess;
+    }
+    int run()
+    {
+        HIPCHK(hipSetDevice(h->dev));
+        int rc;
+        if ((rc = ensure_copy_stream()) || (rc = label_csr())) return rc;
+        list_slots();
+        if ((rc = size_buffers()) || (rc = reset_report_tables()) || (rc = kernel_args())) return rc;
+        const hipError_t e = pipeline();
+        if (e != hipSuccess) {   // nothing of this call stays in flight behind the error
+            (void)hipStreamSynchronize(sc.copy);
+            (void)hipStreamSynchronize(s);
+            return fail(CHB_EHIP, hipGetErrorString(e));
+        }
+        return CHB_OK;
+    }
+    // ---- the pipeline's steps for chunk k
+    hipError_t upload(int64_t k)
+    {
+        ChunkHalf &b = half(k);
+        HIPTRY(hipEventSynchronize(b.up));                // the pinned half: its last upload (chunk k - 2) has left it
+        HIPTRY(hipStreamWaitEvent(sc.copy, b.done, 0));   // the device half: the kernels of chunk k - 2 have read it
+        HIPTRY(rq.Y ? upload_rows(b, k) : rq.plan ? upload_plan(b, k) : upload_indices(b, k));
+        return hipEventRecord(b.up, sc.copy);
+    }
+    // packed rows (zero-padded to Dp) in kRecruitPiece pieces, so the copy of a piece runs under the packing of the next
+    hipError_t upload_rows(ChunkHalf &b, int64_t k)
+    {
+        const int64_t D = h->D, Dp = h->Dp;
+        const int nq = rows(k);
         for (int r0 = 0; r0 < nq; r0 += kRecruitPiece) {
             const int nr = std::min(kRecruitPiece, nq - r0);
-            double *dst = h->rc.hY[b].p + (size_t)r0 * Dp;
-            const double *src = Y + (start(k) + r0) * D;
+            double *dst = b.hY.p + (size_t)r0 * Dp;
+            const double *src = rq.Y + (start(k) + r0) * D;
             for (int r = 0; r < nr; ++r, dst += Dp, src += D) {
                 memcpy(dst, src, sizeof(double) * D);
                 for (int64_t j = D; j < Dp; ++j) dst[j] = 0.0;
             }
-            RCHK(hipMemcpyAsync(h->rc.Y[b].p + (size_t)r0 * Dp, h->rc.hY[b].p + (size_t)r0 * Dp, sizeof(double) * (size_t)nr * Dp,
-                                hipMemcpyHostToDevice, c));
-        }
-        return hipEventRecord(h->rc.up[b], c);
-    };
-    auto download = [&](int64_t k) -> hipError_t {
-        const int b = (int)(k & 1), nq = rows(k);
-        RCHK(hipStreamWaitEvent(c, h->rc.done[b], 0));
-        const size_t nr = (size_t)nq * (size_t)ns;
-        if (dist_out)
-            RCHK(hipMemcpyAsync(h->rc.hdist[b].p, h->rc.dist[b].p, sizeof(double) * nr * (size_t)B, hipMemcpyDeviceToHost, c));
-        if (min_dist_out) RCHK(hipMemcpyAsync(h->rc.hmin[b].p, h->rc.min[b].p, sizeof(double) * nr, hipMemcpyDeviceToHost, c));
-        if (margin_out) RCHK(hipMemcpyAsync(h->rc.hmargin[b].p, h->rc.margin[b].p, sizeof(double) * nr, hipMemcpyDeviceToHost, c));
-        if (bin_out) RCHK(hipMemcpyAsync(h->rc.hbin[b].p, h->rc.bin[b].p, sizeof(int) * nr, hipMemcpyDeviceToHost, c));
-        return hipEventRecord(h->rc.down[b], c);
-    };
-    auto unpack = [&](int64_t k) -> hipError_t {
-        const int b = (int)(k & 1), nq = rows(k);
-        const int64_t t0 = start(k);
-        RCHK(hipEventSynchronize(h->rc.down[b]));
-        for (int j = 0; j < ns; ++j) {
-            const size_t from = (size_t)(slot ? slot[j] : 0) * (size_t)nq;
-            const int64_t to = (int64_t)j * Q + t0;
-            if (dist_out) memcpy(dist_out + to * B, h->rc.hdist[b].p + from * (size_t)B, sizeof(double) * (size_t)nq * (size_t)B);
-            if (min_dist_out) memcpy(min_dist_out + to, h->rc.hmin[b].p + from, sizeof(double) * nq);
-            if (margin_out) memcpy(margin_out + to, h->rc.hmargin[b].p + from, sizeof(double) * nq);
-            if (bin_out)
-                for (int i = 0; i < nq; ++i) bin_out[to + i] = h->rc.hbin[b].p[from + i];
+            HIPTRY(hipMemcpyAsync(b.Y.p + (size_t)r0 * Dp, b.hY.p + (size_t)r0 * Dp, sizeof(double) * (size_t)nr * Dp,
+                                  hipMemcpyHostToDevice, sc.copy));
         }
         return hipSuccess;
-    };
-    RCHK(upload(0));
-    for (int64_t k = 0; k < n; ++k) {
-        const int b = (int)(k & 1), nq = rows(k);
-        RCHK(hipStreamWaitEvent(s, h->rc.up[b], 0));
-        if (any_out) RCHK(hipStreamWaitEvent(s, h->rc.down[b], 0));   // (chunk k - 2 has been copied out of this half's results)
-        a.Y = audit ? nullptr : h->rc.Y[b].p; a.qid = audit ? h->rc.qid[b].p : nullptr; a.dist = h->rc.dist[b].p; a.nq = nq;
+    }
+    // the chunk's sample indices and nothing else: the kernel reads the rows from the resident matrix
+    hipError_t upload_indices(ChunkHalf &b, int64_t k)
+    {
+        const int nq = rows(k);
+        const int64_t t0 = start(k);
+        for (int i = 0; i < nq; ++i) b.hqid.p[i] = (int)(rq.row_idx ? rq.row_idx[t0 + i] : t0 + i);
+        return hipMemcpyAsync(b.qid.p, b.hqid.p, sizeof(int) * nq, hipMemcpyHostToDevice, sc.copy);
+    }
+    // a plan's indices and the chunk's label runs, for bin_report_kernel behind the two audit kernels
+    hipError_t upload_plan(ChunkHalf &b, int64_t k)
+    {
+        const std::vector<int64_t> &lab_ptr = rq.plan->lab_ptr;
+        const int nq = rows(k);
+        const int64_t t0 = start(k);
+        memcpy(b.hqid.p, rq.plan->ord.data() + t0, sizeof(int) * nq);
+        int2 *sg = b.hseg.p;   // {label, first position in the chunk} per run, closed by {-1, nq}
+        b.nseg = 0;
+        size_t l = (size_t)(std::upper_bound(lab_ptr.begin(), lab_ptr.end(), t0) - lab_ptr.begin()) - 1;
+        for (; l < (size_t)rq.B && lab_ptr[l] < t0 + nq; ++l)
+            if (lab_ptr[l + 1] > lab_ptr[l]) sg[b.nseg++] = make_int2((int)l, (int)(std::max(lab_ptr[l], t0) - t0));
+        sg[b.nseg] = make_int2(-1, nq);
+        HIPTRY(hipMemcpyAsync(b.seg.p, b.hseg.p, sizeof(int2) * ((size_t)b.nseg + 1), hipMemcpyHostToDevice, sc.copy));
+        return hipMemcpyAsync(b.qid.p, b.hqid.p, sizeof(int) * nq, hipMemcpyHostToDevice, sc.copy);
+    }
+    hipError_t launch(int64_t k)
+    {
+        ChunkHalf &b = half(k);
+        const int nq = rows(k);
+        HIPTRY(hipStreamWaitEvent(s, b.up, 0));
+        if (any_out) HIPTRY(hipStreamWaitEvent(s, b.down, 0));   // (chunk k - 2 has been copied out of this half's results)
+        a.Y = audit ? nullptr : b.Y.p; a.qid = audit ? b.qid.p : nullptr; a.dist = b.dist.p; a.nq = nq;
         {
             Timed t(h, a.mmask ? (audit ? "audit_multi" : "recruit_multi") : (audit ? "audit" : "recruit"),
-                    (double)nq * (double)B * (double)ns);
+                    (double)nq * (double)rq.B * (double)ns);
             launch_recruit(a, s);
-            launch_recruit_reduce(h->rc.dist[b].p, nq * ns, (int)B, h->rc.bin[b].p, h->rc.min[b].p, h->rc.margin[b].p, s);
+            launch_recruit_reduce(b.dist.p, nq * ns, (int)rq.B, b.bin.p, b.min.p, b.margin.p, s);
         }
-        if (rp) {
-            BinReportArgs r = rp->tables;
-            r.dist = h->rc.dist[b].p; r.bin = h->rc.bin[b].p; r.seg = h->rc.seg[b].p; r.nseg = nseg[b]; r.B = (int)B;
-            Timed t(h, "bin_report", (double)nq * (double)B);
+        if (rq.plan) {
+            const BinReportArgs r{b.dist.p, b.bin.p, b.seg.p, b.nseg, (int)rq.B,
+                                  sc.rep_conf.p, sc.rep_unplaced.p, sc.rep_cnt.p, sc.rep_min.p, sc.rep_sum.p};
+            Timed t(h, "bin_report", (double)nq * (double)rq.B);
             launch_bin_report(r, s);
         }
-        RCHK(hipGetLastError());
-        RCHK(hipEventRecord(h->rc.done[b], s));
-        if (k + 1 < n) RCHK(upload(k + 1));
-        if (!any_out) continue;
-        RCHK(download(k));
-        if (k > 0) RCHK(unpack(k - 1));
+        HIPTRY(hipGetLastError());
+        return hipEventRecord(b.done, s);
     }
-    return any_out ? unpack(n - 1) : hipSuccess;
-#undef RCHK
-}
-
-// What chb_recruit_rows and chb_audit_rows do once their arguments are checked: the CSR over the labels, the context's
-// chunk buffers, the pipelined chunks.  Y: the new rows (recruit), or nullptr for the resident rows row_idx (audit).
-// ms / nm: the checked list of a chb_*_rows_multi call (m is then its largest entry): the chunks are kRecruitChunk / nm
-// rows, rounded down to whole 64-row tiles, so nm result slices of a chunk fill no more than a single-m chunk's buffers.
-int recruit_run(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, const int64_t *row_idx, int64_t Q,
-                int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out, ReportPlan *rp = nullptr,
-                const int *ms = nullptr, int nm = 0)
-{
-    HIPCHK(hipSetDevice(h->dev));
-    hipStream_t s = h->stream;
-    const int64_t N = h->N;
-    const int Dp = h->Dp;
-    if (!h->rc.copy) {
-        HIPCHK(hipStreamCreateWithFlags(&h->rc.copy, hipStreamNonBlocking));
-        for (int i = 0; i < 2; ++i) {
-            HIPCHK(hipEventCreateWithFlags(&h->rc.up[i], hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&h->rc.done[i], hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&h->rc.down[i], hipEventDisableTiming));
-        }
-    }
-    // CSR over the labels (host counting sort into pinned memory; members of a bin in index order -- the selection does
-    // not depend on it)
-    HIPCHK(h->rc.hptr.ensure((size_t)B + 1));
-    int *ptr = h->rc.hptr.p;
-    std::fill(ptr, ptr + B + 1, 0);
-    for (int64_t i = 0; i < N; ++i)
-        if (labels[i] >= 0 && labels[i] < B) ++ptr[labels[i] + 1];
-    for (int64_t c = 0; c < B; ++c) ptr[c + 1] += ptr[c];
-    const size_t n_memb = (size_t)std::max(ptr[B], 1);
-    HIPCHK(h->rc.hmemb.ensure(n_memb));
+    hipError_t download(int64_t k)
     {
-        std::vector<int> cur(ptr, ptr + B);
-        for (int64_t i = 0; i < N; ++i)
-            if (labels[i] >= 0 && labels[i] < B) h->rc.hmemb.p[cur[(size_t)labels[i]]++] = (int)i;
+        ChunkHalf &b = half(k);
+        hipStream_t c = sc.copy;
+        const size_t nr = (size_t)rows(k) * (size_t)ns, B = (size_t)rq.B;
+        HIPTRY(hipStreamWaitEvent(c, b.done, 0));
+        if (rq.dist_out) HIPTRY(hipMemcpyAsync(b.hdist.p, b.dist.p, sizeof(double) * nr * B, hipMemcpyDeviceToHost, c));
+        if (rq.min_dist_out) HIPTRY(hipMemcpyAsync(b.hmin.p, b.min.p, sizeof(double) * nr, hipMemcpyDeviceToHost, c));
+        if (rq.margin_out) HIPTRY(hipMemcpyAsync(b.hmargin.p, b.margin.p, sizeof(double) * nr, hipMemcpyDeviceToHost, c));
+        if (rq.bin_out) HIPTRY(hipMemcpyAsync(b.hbin.p, b.bin.p, sizeof(int) * nr, hipMemcpyDeviceToHost, c));
+        return hipEventRecord(b.down, c);
     }
-    const int ns = nm > 0 ? nm : 1;   // result slices per chunk
-    unsigned mmask = 0;
-    int slot[kMaxM];   // list entry j's slice on the device = the number of smaller entries
-    for (int j = 0; j < nm; ++j) {
-        mmask |= 1u << (ms[j] - 1);
-        slot[j] = 0;
-        for (int k = 0; k < nm; ++k) slot[j] += ms[k] < ms[j];
-    }
-    if (nm > 0) h->rc.multi_rows = std::max<int64_t>(kQTile, kRecruitChunk / nm / kQTile * kQTile);
-    const int64_t chunk = std::min<int64_t>(Q, nm > 0 ? h->rc.multi_rows : kRecruitChunk);
-    const size_t res = (size_t)chunk * (size_t)ns;   // result rows of a chunk
-    const int halves = Q > chunk ? 2 : 1;   // (a plan's first cut is shorter than Q whenever it has a second)
-    HIPCHK(h->rc.ptr.ensure((size_t)B + 1));
-    HIPCHK(h->rc.memb.ensure(n_memb));
-    for (int i = 0; i < halves; ++i) {
-        if (Y) {
-            HIPCHK(h->rc.Y[i].ensure((size_t)chunk * Dp));
-            HIPCHK(h->rc.hY[i].ensure((size_t)chunk * Dp));
-        } else {
-            HIPCHK(h->rc.qid[i].ensure((size_t)chunk));
-            HIPCHK(h->rc.hqid[i].ensure((size_t)chunk));
+    // (a list of m: ns slices of nq rows each, on the device in ascending order of m; slice slot[j] goes to out + j * Q + t0)
+    hipError_t unpack(int64_t k)
+    {
+        ChunkHalf &b = half(k);
+        const int nq = rows(k);
+        const int64_t t0 = start(k), B = rq.B;
+        HIPTRY(hipEventSynchronize(b.down));
+        for (int j = 0; j < ns; ++j) {
+            const size_t from = (size_t)slot[j] * (size_t)nq;
+            const int64_t to = (int64_t)j * rq.Q + t0;
+            if (rq.dist_out) memcpy(rq.dist_out + to * B, b.hdist.p + from * (size_t)B, sizeof(double) * (size_t)nq * (size_t)B);
+            if (rq.min_dist_out) memcpy(rq.min_dist_out + to, b.hmin.p + from, sizeof(double) * nq);
+            if (rq.margin_out) memcpy(rq.margin_out + to, b.hmargin.p + from, sizeof(double) * nq);
+            if (rq.bin_out)
+                for (int i = 0; i < nq; ++i) rq.bin_out[to + i] = b.hbin.p[from + i];
         }
-        HIPCHK(h->rc.dist[i].ensure(res * (size_t)B));
-        if (dist_out) HIPCHK(h->rc.hdist[i].ensure(res * (size_t)B));
-        HIPCHK(h->rc.bin[i].ensure(res));
-        HIPCHK(h->rc.hbin[i].ensure(res));
-        HIPCHK(h->rc.min[i].ensure(res));
-        HIPCHK(h->rc.hmin[i].ensure(res));
-        HIPCHK(h->rc.margin[i].ensure(res));
-        HIPCHK(h->rc.hmargin[i].ensure(res));
-        if (rp) {   // a chunk holds at most one run per label
-            HIPCHK(h->rc.seg[i].ensure((size_t)std::min<int64_t>(B, chunk) + 1));
-            HIPCHK(h->rc.hseg[i].ensure((size_t)std::min<int64_t>(B, chunk) + 1));
-        }
+        return hipSuccess;
     }
-    if (rp) {
-        const size_t BB = (size_t)B * (size_t)B;
-        HIPCHK(h->rc.rep_conf.ensure(BB));
-        HIPCHK(h->rc.rep_unplaced.ensure((size_t)B));
-        HIPCHK(h->rc.rep_cnt.ensure(BB));
-        HIPCHK(h->rc.rep_min.ensure(BB));
-        HIPCHK(h->rc.rep_sum.ensure(BB));
-        HIPCHK(hipMemsetAsync(h->rc.rep_conf.p, 0, sizeof(long long) * BB, s));
-        HIPCHK(hipMemsetAsync(h->rc.rep_unplaced.p, 0, sizeof(long long) * (size_t)B, s));
-        HIPCHK(hipMemsetAsync(h->rc.rep_cnt.p, 0, sizeof(long long) * BB, s));
-        HIPCHK(hipMemsetAsync(h->rc.rep_sum.p, 0, sizeof(double) * BB, s));
-        launch_fill_f64(h->rc.rep_min.p, std::numeric_limits<double>::infinity(), BB, s);
-        rp->tables.conf = h->rc.rep_conf.p; rp->tables.unplaced = h->rc.rep_unplaced.p; rp->tables.cnt = h->rc.rep_cnt.p;
-        rp->tables.dmin = h->rc.rep_min.p; rp->tables.dsum = h->rc.rep_sum.p;
-    }
-    HIPCHK(hipMemcpyAsync(h->rc.ptr.p, ptr, sizeof(int) * ((size_t)B + 1), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->rc.memb.p, h->rc.hmemb.p, sizeof(int) * n_memb, hipMemcpyHostToDevice, s));
-    RecruitArgs a{};
-    a.X = h->X.p; a.D = h->D; a.Dp = Dp; a.bin_ptr = h->rc.ptr.p; a.memb_id = h->rc.memb.p;
-    a.B = (int)B; a.m = m; a.metric = h->metric; a.mmask = mmask;
-    const hipError_t e = recruit_chunks(h, a, Y, row_idx, Q, chunk, bin_out, dist_out, min_dist_out, margin_out, rp,
-                                        nm > 0 ? slot : nullptr, ns);
-    if (e != hipSuccess) {   // nothing of this call stays in flight behind the error
-        (void)hipStreamSynchronize(h->rc.copy);
-        (void)hipStreamSynchronize(s);
-        return fail(CHB_EHIP, hipGetErrorString(e));
-    }
-    return CHB_OK;
+};
+
+// the four calls that return rows: the request goes through the checks and, unless Q == 0, through a ScoreRun
+int score_rows(chb_ctx *h, const char *who, ScoreRequest &rq, const int64_t *D, bool list)
+{
+    const int rc = score_check_args(h, who, rq, D, list, rq.bin_out || rq.dist_out ? nullptr : "bin_out and dist_out are both null");
+    return rc != CHB_OK || rq.Q == 0 ? rc : ScoreRun{h, rq}.run();
 }
 
 }  // namespace
@@ -2627,154 +2768,46 @@ int recruit_run(chb_ctx *h, const int64_t *labels, int64_t B, int m, const doubl
 int chb_recruit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
                      int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
 {
-    if (!h) return fail(CHB_EINVAL, "null context");
-    if (Q < 0 || B < 1 || m < 1) return fail(CHB_EINVAL, "Q < 0, B < 1 or m < 1");
-    if (Q > 0 && (!labels || !Y)) return fail(CHB_EINVAL, "null argument");
-    if (!bin_out && !dist_out) return fail(CHB_EINVAL, "bin_out and dist_out are both null");
-    if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
-    if (D != h->D) return fail(CHB_EINVAL, "the rows must have the resident samples' number of columns");
-    if (m > kMaxM) return fail(CHB_EUNSUPPORTED, "chb_recruit_rows supports at most 16 neighbours");
-    if (B > kRecruitMaxBins) return fail(CHB_EUNSUPPORTED, "chb_recruit_rows supports at most 8192 bins");
-    if (h->batch.open || (h->fit_open && h->stepwise))
-        return fail(CHB_ESTATE, "a stepwise fit is open on this context (chb_fit_begin): chb_set_samples ends it");
-    if (Q == 0) return CHB_OK;
-    return recruit_run(h, labels, B, m, Y, nullptr, Q, bin_out, dist_out, min_dist_out, margin_out);
+    ScoreRequest rq{labels, B, Y, nullptr, nullptr, Q, m, nullptr, 0, bin_out, dist_out, min_dist_out, margin_out};
+    return score_rows(h, "chb_recruit_rows", rq, &D, false);
 }
 
 int chb_audit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const int64_t *row_idx, int64_t Q,
                    int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
 {
-    if (!h) return fail(CHB_EINVAL, "null context");
-    if (Q < 0 || B < 1 || m < 1) return fail(CHB_EINVAL, "Q < 0, B < 1 or m < 1");
-    if (Q > 0 && !labels) return fail(CHB_EINVAL, "null argument");
-    if (!bin_out && !dist_out) return fail(CHB_EINVAL, "bin_out and dist_out are both null");
-    if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
-    if (m > kMaxM) return fail(CHB_EUNSUPPORTED, "chb_audit_rows supports at most 16 neighbours");
-    if (B > kRecruitMaxBins) return fail(CHB_EUNSUPPORTED, "chb_audit_rows supports at most 8192 bins");
-    if (h->batch.open || (h->fit_open && h->stepwise))
-        return fail(CHB_ESTATE, "a stepwise fit is open on this context (chb_fit_begin): chb_set_samples ends it");
-    if (Q == 0) return CHB_OK;
-    if (!row_idx && Q != h->N) return fail(CHB_EINVAL, "row_idx is null (all rows): Q must be the number of resident samples");
-    for (int64_t q = 0; row_idx && q < Q; ++q)
-        if (row_idx[q] < 0 || row_idx[q] >= h->N) return fail(CHB_EINVAL, "row_idx entry outside [0, N)");
-    return recruit_run(h, labels, B, m, nullptr, row_idx, Q, bin_out, dist_out, min_dist_out, margin_out);
+    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, m, nullptr, 0, bin_out, dist_out, min_dist_out, margin_out};
+    return score_rows(h, "chb_audit_rows", rq, nullptr, false);
 }
-
-namespace {
-
-// the list of a chb_*_rows_multi call: 1 .. 16 distinct entries in 1 .. 16; *m_max = the largest
-int check_m_list(const char *who, const int *ms, int nm, int *m_max)
-{
-    if (!ms) return fail(CHB_EINVAL, "ms is null");
-    if (nm < 1 || nm > kMaxM) return fail(CHB_EINVAL, "nm must be 1 .. 16");
-    for (int j = 0; j < nm; ++j)
-        if (ms[j] < 1) return fail(CHB_EINVAL, "an entry of ms is < 1");
-    for (int j = 0; j < nm; ++j)
-        if (ms[j] > kMaxM) return fail(CHB_EUNSUPPORTED, std::string(who) + " supports at most 16 neighbours");
-    unsigned seen = 0;
-    for (int j = 0; j < nm; ++j) {
-        if (seen & (1u << (ms[j] - 1))) return fail(CHB_EINVAL, "ms holds a value twice");
-        seen |= 1u << (ms[j] - 1);
-    }
-    *m_max = 32 - __builtin_clz(seen);
-    return CHB_OK;
-}
-
-}  // namespace
 
 int chb_recruit_rows_multi(chb_ctx *h, const int64_t *labels, int64_t B, const int *ms, int nm, const double *Y, int64_t Q,
                            int64_t D, int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
 {
-    if (!h) return fail(CHB_EINVAL, "null context");
-    if (Q < 0 || B < 1) return fail(CHB_EINVAL, "Q < 0 or B < 1");
-    int m_max = 0;
-    { const int rc = check_m_list("chb_recruit_rows_multi", ms, nm, &m_max); if (rc) return rc; }
-    if (Q > 0 && (!labels || !Y)) return fail(CHB_EINVAL, "null argument");
-    if (!bin_out && !dist_out) return fail(CHB_EINVAL, "bin_out and dist_out are both null");
-    if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
-    if (D != h->D) return fail(CHB_EINVAL, "the rows must have the resident samples' number of columns");
-    if (B > kRecruitMaxBins) return fail(CHB_EUNSUPPORTED, "chb_recruit_rows_multi supports at most 8192 bins");
-    if (h->batch.open || (h->fit_open && h->stepwise))
-        return fail(CHB_ESTATE, "a stepwise fit is open on this context (chb_fit_begin): chb_set_samples ends it");
-    if (Q == 0) return CHB_OK;
-    return recruit_run(h, labels, B, m_max, Y, nullptr, Q, bin_out, dist_out, min_dist_out, margin_out, nullptr, ms, nm);
+    ScoreRequest rq{labels, B, Y, nullptr, nullptr, Q, 0, ms, nm, bin_out, dist_out, min_dist_out, margin_out};
+    return score_rows(h, "chb_recruit_rows_multi", rq, &D, true);
 }
 
 int chb_audit_rows_multi(chb_ctx *h, const int64_t *labels, int64_t B, const int *ms, int nm, const int64_t *row_idx,
                          int64_t Q, int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
 {
-    if (!h) return fail(CHB_EINVAL, "null context");
-    if (Q < 0 || B < 1) return fail(CHB_EINVAL, "Q < 0 or B < 1");
-    int m_max = 0;
-    { const int rc = check_m_list("chb_audit_rows_multi", ms, nm, &m_max); if (rc) return rc; }
-    if (Q > 0 && !labels) return fail(CHB_EINVAL, "null argument");
-    if (!bin_out && !dist_out) return fail(CHB_EINVAL, "bin_out and dist_out are both null");
-    if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
-    if (B > kRecruitMaxBins) return fail(CHB_EUNSUPPORTED, "chb_audit_rows_multi supports at most 8192 bins");
-    if (h->batch.open || (h->fit_open && h->stepwise))
-        return fail(CHB_ESTATE, "a stepwise fit is open on this context (chb_fit_begin): chb_set_samples ends it");
-    if (Q == 0) return CHB_OK;
-    if (!row_idx && Q != h->N) return fail(CHB_EINVAL, "row_idx is null (all rows): Q must be the number of resident samples");
-    for (int64_t q = 0; row_idx && q < Q; ++q)
-        if (row_idx[q] < 0 || row_idx[q] >= h->N) return fail(CHB_EINVAL, "row_idx entry outside [0, N)");
-    return recruit_run(h, labels, B, m_max, nullptr, row_idx, Q, bin_out, dist_out, min_dist_out, margin_out, nullptr, ms, nm);
+    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, 0, ms, nm, bin_out, dist_out, min_dist_out, margin_out};
+    return score_rows(h, "chb_audit_rows_multi", rq, nullptr, true);
 }
 
 int chb_bin_report(chb_ctx *h, const int64_t *labels, int64_t B, int m, const int64_t *row_idx, int64_t Q,
                    int64_t *confusion, int64_t *unplaced, int64_t *dcnt, double *dmin, double *dsum, int64_t *n_skipped)
 {
-    if (!h) return fail(CHB_EINVAL, "null context");
-    if (Q < 0 || B < 1 || m < 1) return fail(CHB_EINVAL, "Q < 0, B < 1 or m < 1");
-    if (Q > 0 && !labels) return fail(CHB_EINVAL, "null argument");
-    if (!confusion && !unplaced && !dcnt && !dmin && !dsum && !n_skipped) return fail(CHB_EINVAL, "every output is null");
-    if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
-    if (m > kMaxM) return fail(CHB_EUNSUPPORTED, "chb_bin_report supports at most 16 neighbours");
-    if (B > kRecruitMaxBins) return fail(CHB_EUNSUPPORTED, "chb_bin_report supports at most 8192 bins");
-    if (h->batch.open || (h->fit_open && h->stepwise))
-        return fail(CHB_ESTATE, "a stepwise fit is open on this context (chb_fit_begin): chb_set_samples ends it");
-    if (Q > 0 && !row_idx && Q != h->N) return fail(CHB_EINVAL, "row_idx is null (all rows): Q must be the number of resident samples");
-    for (int64_t q = 0; row_idx && q < Q; ++q)
-        if (row_idx[q] < 0 || row_idx[q] >= h->N) return fail(CHB_EINVAL, "row_idx entry outside [0, N)");
-    // the scored positions in label order (stable counting sort); the others are only counted
-    const size_t BB = (size_t)B * (size_t)B;
-    ReportPlan rp;
-    rp.lab_ptr.assign((size_t)B + 1, 0);
-    auto own = [&](int64_t q) { return labels[row_idx ? row_idx[q] : q]; };
-    int64_t Qv = 0;
-    for (int64_t q = 0; q < Q; ++q) {
-        const int64_t l = own(q);
-        if (l >= 0 && l < B) { ++rp.lab_ptr[(size_t)l + 1]; ++Qv; }
-    }
-    if (n_skipped) *n_skipped = Q - Qv;
-    if (Qv == 0) {   // nothing to score: the tables of a call without rows
-        if (confusion) std::fill(confusion, confusion + BB, (int64_t)0);
-        if (unplaced) std::fill(unplaced, unplaced + B, (int64_t)0);
-        if (dcnt) std::fill(dcnt, dcnt + BB, (int64_t)0);
-        if (dmin) std::fill(dmin, dmin + BB, std::numeric_limits<double>::infinity());
-        if (dsum) std::fill(dsum, dsum + BB, 0.0);
-        return CHB_OK;
-    }
-    for (int64_t c = 0; c < B; ++c) rp.lab_ptr[(size_t)c + 1] += rp.lab_ptr[(size_t)c];
-    rp.ord.resize((size_t)Qv);
-    {
-        std::vector<int64_t> cur(rp.lab_ptr.begin(), rp.lab_ptr.end() - 1);
-        for (int64_t q = 0; q < Q; ++q) {
-            const int64_t l = own(q);
-            if (l >= 0 && l < B) rp.ord[(size_t)cur[(size_t)l]++] = (int)(row_idx ? row_idx[q] : q);
-        }
-    }
-    rp.cut_chunks();
-    const int rc = recruit_run(h, labels, B, m, nullptr, nullptr, Qv, nullptr, nullptr, nullptr, nullptr, &rp);
+    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, m, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
+    const bool any = confusion || unplaced || dcnt || dmin || dsum || n_skipped;
+    int rc = score_check_args(h, "chb_bin_report", rq, nullptr, false, any ? nullptr : "every output is null");
     if (rc != CHB_OK) return rc;
-    hipStream_t s = h->stream;
-    static_assert(sizeof(long long) == sizeof(int64_t), "the tables are copied out as they are");
-    if (confusion) HIPCHK(hipMemcpyAsync(confusion, h->rc.rep_conf.p, sizeof(int64_t) * BB, hipMemcpyDeviceToHost, s));
-    if (unplaced) HIPCHK(hipMemcpyAsync(unplaced, h->rc.rep_unplaced.p, sizeof(int64_t) * (size_t)B, hipMemcpyDeviceToHost, s));
-    if (dcnt) HIPCHK(hipMemcpyAsync(dcnt, h->rc.rep_cnt.p, sizeof(int64_t) * BB, hipMemcpyDeviceToHost, s));
-    if (dmin) HIPCHK(hipMemcpyAsync(dmin, h->rc.rep_min.p, sizeof(double) * BB, hipMemcpyDeviceToHost, s));
-    if (dsum) HIPCHK(hipMemcpyAsync(dsum, h->rc.rep_sum.p, sizeof(double) * BB, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return CHB_OK;
+    const ReportOut out{confusion, unplaced, dcnt, dmin, dsum};
+    ReportPlan plan;
+    const int64_t Qv = plan.build(labels, B, row_idx, Q);
+    if (n_skipped) *n_skipped = Q - Qv;
+    if (Qv == 0) { plan.empty_tables(out); return CHB_OK; }
+    rq.row_idx = nullptr; rq.plan = &plan; rq.Q = Qv;   // the plan's positions, already in label order
+    rc = ScoreRun{h, rq}.run();
+    return rc != CHB_OK ? rc : plan.copy_tables(h, out);
 }
 
 int chb_find_nearest_from_row(chb_ctx *h, int64_t c, const int64_t *labels, const double *row,
@@ -3157,7 +3190,7 @@ static const struct { const char *name; int64_t (*get)(const chb_ctx *); } kHost
     CTR("tile_skip_state", h->seat.state), CTR("tile_skipped", h->seat.skipped), CTR("tile_seen", h->seat.seen),
     CTR("tile_unloaded", h->seat.unloaded), CTR("last_batch_k", h->batch.K),
     CTR("recruit_chunk", kRecruitChunk),   // rows per launch of chb_recruit_rows
-    CTR("recruit_multi_rows", h->rc.multi_rows),   // ... of the last chb_audit_rows_multi / chb_recruit_rows_multi
+    CTR("recruit_multi_rows", h->score.multi_rows),   // ... of the last chb_audit_rows_multi / chb_recruit_rows_multi
     // chb_kmer_profiles / chb_set_samples_from_sequences: a chunk's limits, the chunks of the last call
     CTR("kmer_chunk_bytes", kKmerChunkBytes), CTR("kmer_chunk_rows", kKmerChunkRows), CTR("kmer_chunks", h->kmer_chunks),
     CTR("prefilter_enabled", (h->sw.use_prefilter && h->shadow_ok) ? 1 : 0),
