@@ -50,6 +50,10 @@ SIGNATURES = {
                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "chb_bin_report": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "chb_audit_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                  C.c_void_p]),
+    "chb_recruit_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "chb_find_nearest_from_row": (C.c_int, [C.c_void_p, C.c_int64, _i64p, _f64p, C.c_int64, C.c_int,
                                             _i64p, C.POINTER(C.c_int32)]),
     "chb_hull_distance_batch": (C.c_int, [C.c_void_p, _i64p, C.c_int64, _i64p, C.c_int, _f64p,
@@ -284,6 +288,40 @@ class Context:
                                        unplaced.ctypes.data, dcnt.ctypes.data, dmin.ctypes.data, dsum.ctypes.data,
                                        C.addressof(skipped)))
         return confusion, unplaced, dcnt, dmin, dsum, int(skipped.value)
+
+    @staticmethod
+    def _pair_lists(rows, bins, rows_name):
+        """The two int64 lists of a pair call, one entry per pair."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        bins = np.ascontiguousarray(bins, dtype=np.int64)
+        if rows.ndim != 1 or bins.ndim != 1:
+            raise ValueError(f"{rows_name} and bins must be 1-D arrays")
+        if rows.shape != bins.shape:
+            raise ValueError(f"{rows_name} and bins must have one entry per pair: {rows.shape[0]} and {bins.shape[0]}")
+        return rows, bins
+
+    def audit_pairs(self, labels, B, m, rows, bins):
+        """chb_audit_pairs: dist [P], entry p bit for bit audit_rows(labels, B, m, rows)[1][p, bins[p]] -- the leave-one-out
+        hull distance of the RESIDENT row rows[p] to bin bins[p] -- at the cost of the listed pairs only."""
+        rows, bins = self._pair_lists(rows, bins, "rows")
+        labels = self._labels(labels)
+        dist = np.empty(rows.shape[0], dtype=np.float64)
+        check(self._lib.chb_audit_pairs(self._h, labels.ctypes.data, int(B), int(m), rows.ctypes.data, bins.ctypes.data,
+                                        rows.shape[0], dist.ctypes.data))
+        return dist
+
+    def recruit_pairs(self, labels, B, m, Y, row_of, bins):
+        """chb_recruit_pairs: dist [P], entry p bit for bit recruit_rows(labels, B, m, Y)[1][row_of[p], bins[p]] -- the hull
+        distance of the NEW row Y[row_of[p]] to bin bins[p]."""
+        row_of, bins = self._pair_lists(row_of, bins, "row_of")
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim != 2:
+            raise ValueError("rows must be a 2-D array")
+        labels = self._labels(labels)
+        dist = np.empty(row_of.shape[0], dtype=np.float64)
+        check(self._lib.chb_recruit_pairs(self._h, labels.ctypes.data, int(B), int(m), Y.ctypes.data, *Y.shape,
+                                          row_of.ctypes.data, bins.ctypes.data, row_of.shape[0], dist.ctypes.data))
+        return dist
 
     def find_nearest_from_row(self, c, labels, row, m):
         labels = np.ascontiguousarray(labels, dtype=np.int64)

@@ -1,6 +1,17 @@
 """Host-side mirror of the reference package `ch_bin.core.clustering` (same function names,
 argument meaning and error behaviour) on top of libchbin_hip.so."""
-from .algorithm import BinReport, NeighborSweep, audit, bin_report, fit_cluster, neighbor_sweep, recruit  # noqa: F401
+from .algorithm import (  # noqa: F401
+    BinReport,
+    NeighborSweep,
+    audit,
+    audit_pairs,
+    bin_report,
+    cohesion,
+    fit_cluster,
+    neighbor_sweep,
+    recruit,
+    recruit_pairs,
+)
 from .distance_matrix import (  # noqa: F401
     create_distance_matrix,
     create_in_mem_distance_matrix,

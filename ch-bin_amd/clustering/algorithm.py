@@ -250,3 +250,91 @@ def neighbor_sweep(
                                                         want_dist=return_distances)
     scored = np.arange(samples.shape[0], dtype=np.int64) if rows is None else np.ascontiguousarray(rows, dtype=np.int64)
     return NeighborSweep(neighbors, scored, labels[scored], bins, mind, margin, int(num_clusters), dist)
+
+
+def audit_pairs(
+    samples: np.ndarray,
+    labels: np.ndarray,
+    rows: np.ndarray,
+    bins: np.ndarray,
+    num_clusters: int,
+    num_neighbors: int = 15,
+    metric: str = "convex",
+    qp_solver: str = "quadprog",
+) -> np.ndarray:
+    """`audit`'s leave-one-out hull distances for a list of (row, bin) pairs instead of every bin of every row (no
+    counterpart in the reference): entry p is bit for bit `audit(..., rows=rows, return_distances=True)[3][p, bins[p]]`,
+    and only the members of the listed bins are streamed -- 64 pairs of a bin share one pass over it.  Pairs may repeat
+    and come in any order.  Nothing changes.
+
+    Returns distances [len(rows)]."""
+    if metric not in ("convex", "affine", "affine-qp"):
+        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
+    check_solver(qp_solver)                                              # solve_qp.py:132
+
+    samples = np.ascontiguousarray(samples, dtype=np.float64)
+    ctx = default_context()
+    ctx.set_samples_cached(samples)
+    with ctx.using_metric(metric):
+        return ctx.audit_pairs(labels, int(num_clusters), int(num_neighbors), rows, bins)
+
+
+def recruit_pairs(
+    samples: np.ndarray,
+    labels: np.ndarray,
+    new_rows: np.ndarray,
+    row_of: np.ndarray,
+    bins: np.ndarray,
+    num_clusters: int,
+    num_neighbors: int = 15,
+    metric: str = "convex",
+    qp_solver: str = "quadprog",
+) -> np.ndarray:
+    """`audit_pairs` for rows that are NOT samples: entry p is bit for bit
+    `recruit(..., new_rows, return_distances=True)[1][row_of[p], bins[p]]`, the hull distance of new_rows[row_of[p]] to
+    bin bins[p].  Nothing changes.
+
+    Returns distances [len(row_of)]."""
+    if metric not in ("convex", "affine", "affine-qp"):
+        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
+    check_solver(qp_solver)                                              # solve_qp.py:132
+
+    samples = np.ascontiguousarray(samples, dtype=np.float64)
+    new_rows = np.ascontiguousarray(new_rows, dtype=np.float64)
+    ctx = default_context()
+    ctx.set_samples_cached(samples)
+    with ctx.using_metric(metric):
+        return ctx.recruit_pairs(labels, int(num_clusters), int(num_neighbors), new_rows, row_of, bins)
+
+
+def cohesion(
+    samples: np.ndarray,
+    labels: np.ndarray,
+    num_clusters: int,
+    num_neighbors: int = 15,
+    metric: str = "convex",
+    qp_solver: str = "quadprog",
+    rows: np.ndarray = None,
+) -> np.ndarray:
+    """How well every contig sits in its OWN bin (no counterpart in the reference): for every sample in `rows` (indices
+    into `samples`; None: all of them) the leave-one-out hull distance to the bin its label names -- by definition
+    `audit(..., rows=rows, return_distances=True)[3][i, labels[rows[i]]]`, at about 1 / num_clusters of that call's cost,
+    since only a row's own bin is streamed for it.  NaN where the row's label lies outside [0, num_clusters): such rows
+    are not scored.  +inf where the row is its bin's only member.  Nothing changes.
+
+    Returns distances [len(rows)]."""
+    if metric not in ("convex", "affine", "affine-qp"):
+        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
+    check_solver(qp_solver)                                              # solve_qp.py:132
+
+    samples = np.ascontiguousarray(samples, dtype=np.float64)
+    labels = np.ascontiguousarray(labels, dtype=np.int64)
+    rows = np.arange(samples.shape[0], dtype=np.int64) if rows is None else np.ascontiguousarray(rows, dtype=np.int64)
+    own = labels[rows]
+    scored = (own >= 0) & (own < int(num_clusters))
+    out = np.full(rows.shape[0], np.nan)
+    ctx = default_context()
+    ctx.set_samples_cached(samples)
+    with ctx.using_metric(metric):
+        out[scored] = ctx.audit_pairs(labels, int(num_clusters), int(num_neighbors), rows[scored], own[scored])
+    return out

@@ -26,6 +26,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <map>
 #include <string>
@@ -255,20 +256,23 @@ struct Segments {
 
 // One half of the row-scoring calls' double buffer: a chunk of the new rows (padded like X) or of sample indices (qid), its
 // distances and row reductions, on the device and pinned on the host (h*); chb_bin_report's chunks also carry seg, each label's
-// run (BinReportArgs), nseg of them.  up / done / down: the upload, the kernels, the download of the chunk in this half are through.
+// run (BinReportArgs), nseg of them; the pair calls' chunks carry tile, the chunk's tile table (RecruitPairArgs), ntile rows.
+// up / done / down: the upload, the kernels, the download of the chunk in this half are through.
 struct ChunkHalf {
     DevBuf<double> Y, dist, min, margin;
     DevBuf<int> bin, qid;
     DevBuf<int2> seg;
+    DevBuf<int4> tile;
     PinBuf<double> hY, hdist, hmin, hmargin;
     PinBuf<int> hbin, hqid;
     PinBuf<int2> hseg;
+    PinBuf<int4> htile;
     hipEvent_t up = nullptr, done = nullptr, down = nullptr;
-    int nseg = 0;
+    int nseg = 0, ntile = 0;
     void destroy_events() { for (hipEvent_t ev : {up, done, down}) if (ev) (void)hipEventDestroy(ev); }
 };
 
-// chb_recruit_rows, chb_audit_rows, chb_*_rows_multi, chb_bin_report (ScoreRun): the calls' own buffers, nothing of a fit.
+// chb_recruit_rows, chb_audit_rows, chb_*_rows_multi, chb_bin_report, chb_*_pairs (ScoreRun): the calls' own buffers, nothing of a fit.
 // While the kernels of chunk k run on the context's stream, copy brings chunk k + 1 up into the other half and chunk
 // k - 1 down.  Not per half: the call's CSR over the labels (ptr, memb) and chb_bin_report's B x B tables rep_* (zeroed at
 // the call's start), which collect what the chunks' rows say.
@@ -280,6 +284,7 @@ struct RowScoring {
     DevBuf<double> rep_min, rep_sum;
     hipStream_t copy = nullptr;
     int64_t multi_rows = 0;   // rows per launch of the last chb_audit_rows_multi / chb_recruit_rows_multi
+    int64_t pair_tiles = 0;   // tiles (work items) of the last chb_audit_pairs / chb_recruit_pairs
 };
 
 // Multi-GPU: one context per process per GPU, RCCL communicator over all ranks
@@ -2387,7 +2392,7 @@ int chb_hull_distance_points(chb_ctx *h, const double *x, const double *pts, int
     return hull_indexed(h, h->xpts.p, (int)D, Dp, m + 1, &q, 1, idx.data(), m, dist, alpha);
 }
 
-// ======== row scoring (chb_recruit_rows, chb_audit_rows, chb_*_rows_multi, chb_bin_report): the entry point checks its
+// ======== row scoring (chb_recruit_rows, chb_audit_rows, chb_*_rows_multi, chb_bin_report, chb_*_pairs): the entry point checks its
 // arguments (score_check_args) and fills a ScoreRequest, a ScoreRun carries it through its stages
 namespace {
 
@@ -2462,18 +2467,60 @@ struct ReportPlan {
     }
 };
 
+// chb_audit_pairs / chb_recruit_pairs' part of a ScoreRun: the P pairs in bin order -- a stable counting sort, so a bin's
+// pairs keep the caller's order --, every bin's run cut into tiles of at most kQTile positions (a tile is a work item of
+// the kernel: RecruitPairArgs), and the chunks: runs of whole tiles with at most kRecruitChunk positions.
+struct PairPlan {
+    const int64_t *row = nullptr;      // [P] the row of input pair p: a sample (row_idx) or a row of Y (row_of)
+    std::vector<int64_t> ord;          // [P] the input pair at every position
+    std::vector<int4> tile;            // {bin, first position in its chunk, positions, 0}
+    std::vector<int64_t> cut, tcut;    // chunk k is the positions cut[k] .. cut[k + 1), the tiles tcut[k] .. tcut[k + 1)
+    int64_t max_rows = 0, max_tiles = 0;   // of any chunk
+    void build(const int64_t *row_, const int64_t *bin_idx, int64_t P, int64_t B)
+    {
+        row = row_;
+        std::vector<int64_t> ptr((size_t)B + 1, 0);
+        for (int64_t p = 0; p < P; ++p) ++ptr[(size_t)bin_idx[p] + 1];
+        for (int64_t c = 0; c < B; ++c) ptr[(size_t)c + 1] += ptr[(size_t)c];
+        ord.resize((size_t)P);
+        std::vector<int64_t> cur(ptr.begin(), ptr.end() - 1);
+        for (int64_t p = 0; p < P; ++p) ord[(size_t)cur[(size_t)bin_idx[p]]++] = p;
+        cut.assign(1, 0);
+        tcut.assign(1, 0);
+        int64_t filled = 0;   // positions of the chunk being filled
+        auto close = [&](int64_t pos) {
+            max_rows = std::max(max_rows, pos - cut.back());
+            max_tiles = std::max(max_tiles, (int64_t)tile.size() - tcut.back());
+            cut.push_back(pos);
+            tcut.push_back((int64_t)tile.size());
+            filled = 0;
+        };
+        for (int64_t c = 0; c < B; ++c)
+            for (int64_t t0 = ptr[(size_t)c]; t0 < ptr[(size_t)c + 1]; t0 += kQTile) {
+                const int64_t cnt = std::min<int64_t>(kQTile, ptr[(size_t)c + 1] - t0);
+                if (filled + cnt > kRecruitChunk) close(t0);
+                tile.push_back(make_int4((int)c, (int)filled, (int)cnt, 0));
+                filled += cnt;
+            }
+        close(P);
+    }
+};
+
 // What a row-scoring call asks for, filled by its entry point
 struct ScoreRequest {
     const int64_t *labels; int64_t B;
-    // the source, one of three: the new rows Y (recruit); the resident rows row_idx, nullptr meaning all rows (audit);
-    // a plan's positions (chb_bin_report: an audit whose chunks are the plan's cuts)
+    // the source, one of four: the new rows Y (recruit); the resident rows row_idx, nullptr meaning all rows (audit);
+    // a plan's positions (chb_bin_report: an audit whose chunks are the plan's cuts); a pair plan's positions (below)
     const double *Y; const int64_t *row_idx; const ReportPlan *plan;
     int64_t Q;
     int m; const int *ms; int nm;   // neighbours; nm > 0: the list of a chb_*_rows_multi call, m its largest entry
     int64_t *bin_out; double *dist_out, *min_dist_out, *margin_out;   // (without a destination: neither downloaded nor unpacked)
+    // chb_*_pairs: Q pairs (row, bin) in place of the grid, the rows resident or (Y set) rows of Y; dist_out is [Q], one
+    // double per pair in the caller's order, and there is no row reduction
+    const PairPlan *pairs = nullptr;
 };
 
-// The argument checks of the five entry points, for all of them in this order: null context; ranges and a malformed list
+// The argument checks of the entry points, for all of them in this order: null context; ranges and a malformed list
 // (CHB_EINVAL); null arguments; outputs; no samples; D; more than 16 neighbours (CHB_EUNSUPPORTED); more than 8192 bins;
 // an open stepwise fit; Q == 0 (CHB_OK: nothing further is read); the row_idx rules.
 // D: the rows' number of columns in the calls that take Y, nullptr in the others.  list: the call takes ms / nm, whose
@@ -2523,11 +2570,12 @@ struct ScoreRun {
     hipStream_t s = h->stream;
     const bool audit = !rq.Y /* the rows are resident */, any_out = rq.bin_out || rq.dist_out || rq.min_dist_out || rq.margin_out;
     const int ns = rq.nm > 0 ? rq.nm : 1;   // result slices per chunk
+    const size_t width = rq.pairs ? 1 : (size_t)rq.B;   // distances per result row
     int slot[kMaxM] = {0};                  // list entry j's slice on the device = the number of smaller entries
     size_t n_memb = 0;
     int64_t chunk = 0, n = 0;               // rows per chunk (a plan: its cuts), chunks
-    RecruitArgs a{};
-    int64_t start(int64_t k) const { return rq.plan ? rq.plan->cut[(size_t)k] : k * chunk; }
+    RecruitPairArgs a{};
+    int64_t start(int64_t k) const { return rq.pairs ? rq.pairs->cut[(size_t)k] : rq.plan ? rq.plan->cut[(size_t)k] : k * chunk; }
     int rows(int64_t k) const { return (int)(std::min<int64_t>(start(k + 1), rq.Q) - start(k)); }
     ChunkHalf &half(int64_t k) { return sc.half[k & 1]; }
     // the copy stream and the halves' events: created by the context's first row-scoring call
@@ -2571,18 +2619,23 @@ struct ScoreRun {
     {
         const int64_t B = rq.B;
         if (rq.nm > 0) sc.multi_rows = std::max<int64_t>(kQTile, kRecruitChunk / rq.nm / kQTile * kQTile);
-        chunk = std::min<int64_t>(rq.Q, rq.nm > 0 ? sc.multi_rows : kRecruitChunk);
-        n = rq.plan ? (int64_t)rq.plan->cut.size() - 1 : (rq.Q + chunk - 1) / chunk;
+        chunk = rq.pairs ? rq.pairs->max_rows : std::min<int64_t>(rq.Q, rq.nm > 0 ? sc.multi_rows : kRecruitChunk);
+        n = rq.pairs ? (int64_t)rq.pairs->cut.size() - 1 : rq.plan ? (int64_t)rq.plan->cut.size() - 1 : (rq.Q + chunk - 1) / chunk;
         const size_t res = (size_t)chunk * (size_t)ns;   // result rows of a chunk
-        const int halves = rq.Q > chunk ? 2 : 1;   // (a plan's first cut is shorter than Q whenever it has a second)
+        const int halves = rq.Q > chunk ? 2 : 1;   // (a plan's longest chunk is shorter than Q whenever it has a second)
         HIPCHK(sc.ptr.ensure((size_t)B + 1));
         HIPCHK(sc.memb.ensure(n_memb));
         for (int i = 0; i < halves; ++i) {
             ChunkHalf &b = sc.half[i];
             HIPCHK(rq.Y ? b.Y.ensure((size_t)chunk * h->Dp) : b.qid.ensure((size_t)chunk));
             HIPCHK(rq.Y ? b.hY.ensure((size_t)chunk * h->Dp) : b.hqid.ensure((size_t)chunk));
-            HIPCHK(b.dist.ensure(res * (size_t)B));
-            if (rq.dist_out) HIPCHK(b.hdist.ensure(res * (size_t)B));
+            HIPCHK(b.dist.ensure(res * width));
+            if (rq.dist_out) HIPCHK(b.hdist.ensure(res * width));
+            if (rq.pairs) {   // the tile table, and no row reduction
+                HIPCHK(b.tile.ensure((size_t)rq.pairs->max_tiles));
+                HIPCHK(b.htile.ensure((size_t)rq.pairs->max_tiles));
+                continue;
+            }
             HIPCHK(b.bin.ensure(res));
             HIPCHK(b.hbin.ensure(res));
             HIPCHK(b.min.ensure(res));
@@ -2657,26 +2710,44 @@ struct ScoreRun {
         ChunkHalf &b = half(k);
         HIPTRY(hipEventSynchronize(b.up));                // the pinned half: its last upload (chunk k - 2) has left it
         HIPTRY(hipStreamWaitEvent(sc.copy, b.done, 0));   // the device half: the kernels of chunk k - 2 have read it
-        HIPTRY(rq.Y ? upload_rows(b, k) : rq.plan ? upload_plan(b, k) : upload_indices(b, k));
+        HIPTRY(rq.pairs ? upload_pairs(b, k) : rq.Y ? upload_rows(b, k) : rq.plan ? upload_plan(b, k) : upload_indices(b, k));
         return hipEventRecord(b.up, sc.copy);
     }
-    // packed rows (zero-padded to Dp) in kRecruitPiece pieces, so the copy of a piece runs under the packing of the next
-    hipError_t upload_rows(ChunkHalf &b, int64_t k)
+    // packed rows (zero-padded to Dp) in kRecruitPiece pieces, so the copy of a piece runs under the packing of the next;
+    // position r of the chunk is row y_of(r) of Y
+    hipError_t upload_packed(ChunkHalf &b, int nq, const std::function<int64_t(int)> &y_of)
     {
         const int64_t D = h->D, Dp = h->Dp;
-        const int nq = rows(k);
         for (int r0 = 0; r0 < nq; r0 += kRecruitPiece) {
             const int nr = std::min(kRecruitPiece, nq - r0);
             double *dst = b.hY.p + (size_t)r0 * Dp;
-            const double *src = rq.Y + (start(k) + r0) * D;
-            for (int r = 0; r < nr; ++r, dst += Dp, src += D) {
-                memcpy(dst, src, sizeof(double) * D);
+            for (int r = 0; r < nr; ++r, dst += Dp) {
+                memcpy(dst, rq.Y + y_of(r0 + r) * D, sizeof(double) * D);
                 for (int64_t j = D; j < Dp; ++j) dst[j] = 0.0;
             }
             HIPTRY(hipMemcpyAsync(b.Y.p + (size_t)r0 * Dp, b.hY.p + (size_t)r0 * Dp, sizeof(double) * (size_t)nr * Dp,
                                   hipMemcpyHostToDevice, sc.copy));
         }
         return hipSuccess;
+    }
+    hipError_t upload_rows(ChunkHalf &b, int64_t k)
+    {
+        const int64_t t0 = start(k);
+        return upload_packed(b, rows(k), [t0](int r) { return t0 + r; });
+    }
+    // a pair plan's chunk: its tile table and, in position order, the pairs' sample indices or their rows of Y (a row
+    // named by two pairs is packed twice)
+    hipError_t upload_pairs(ChunkHalf &b, int64_t k)
+    {
+        const PairPlan &pl = *rq.pairs;
+        const int nq = rows(k);
+        const int64_t *ord = pl.ord.data() + start(k), t0 = pl.tcut[(size_t)k];
+        b.ntile = (int)(pl.tcut[(size_t)k + 1] - t0);
+        memcpy(b.htile.p, pl.tile.data() + t0, sizeof(int4) * (size_t)b.ntile);
+        HIPTRY(hipMemcpyAsync(b.tile.p, b.htile.p, sizeof(int4) * (size_t)b.ntile, hipMemcpyHostToDevice, sc.copy));
+        if (!audit) return upload_packed(b, nq, [&pl, ord](int r) { return pl.row[ord[r]]; });
+        for (int i = 0; i < nq; ++i) b.hqid.p[i] = (int)pl.row[ord[i]];
+        return hipMemcpyAsync(b.qid.p, b.hqid.p, sizeof(int) * nq, hipMemcpyHostToDevice, sc.copy);
     }
     // the chunk's sample indices and nothing else: the kernel reads the rows from the resident matrix
     hipError_t upload_indices(ChunkHalf &b, int64_t k)
@@ -2709,7 +2780,11 @@ struct ScoreRun {
         HIPTRY(hipStreamWaitEvent(s, b.up, 0));
         if (any_out) HIPTRY(hipStreamWaitEvent(s, b.down, 0));   // (chunk k - 2 has been copied out of this half's results)
         a.Y = audit ? nullptr : b.Y.p; a.qid = audit ? b.qid.p : nullptr; a.dist = b.dist.p; a.nq = nq;
-        {
+        if (rq.pairs) {   // one launch: the tiles' kernel, no row reduction behind it
+            a.tile = b.tile.p; a.ntile = b.ntile;
+            Timed t(h, audit ? "audit_pairs" : "recruit_pairs", (double)nq);
+            launch_recruit_pairs(a, s);
+        } else {
             Timed t(h, a.mmask ? (audit ? "audit_multi" : "recruit_multi") : (audit ? "audit" : "recruit"),
                     (double)nq * (double)rq.B * (double)ns);
             launch_recruit(a, s);
@@ -2728,21 +2803,27 @@ struct ScoreRun {
     {
         ChunkHalf &b = half(k);
         hipStream_t c = sc.copy;
-        const size_t nr = (size_t)rows(k) * (size_t)ns, B = (size_t)rq.B;
+        const size_t nr = (size_t)rows(k) * (size_t)ns;
         HIPTRY(hipStreamWaitEvent(c, b.done, 0));
-        if (rq.dist_out) HIPTRY(hipMemcpyAsync(b.hdist.p, b.dist.p, sizeof(double) * nr * B, hipMemcpyDeviceToHost, c));
+        if (rq.dist_out) HIPTRY(hipMemcpyAsync(b.hdist.p, b.dist.p, sizeof(double) * nr * width, hipMemcpyDeviceToHost, c));
         if (rq.min_dist_out) HIPTRY(hipMemcpyAsync(b.hmin.p, b.min.p, sizeof(double) * nr, hipMemcpyDeviceToHost, c));
         if (rq.margin_out) HIPTRY(hipMemcpyAsync(b.hmargin.p, b.margin.p, sizeof(double) * nr, hipMemcpyDeviceToHost, c));
         if (rq.bin_out) HIPTRY(hipMemcpyAsync(b.hbin.p, b.bin.p, sizeof(int) * nr, hipMemcpyDeviceToHost, c));
         return hipEventRecord(b.down, c);
     }
-    // (a list of m: ns slices of nq rows each, on the device in ascending order of m; slice slot[j] goes to out + j * Q + t0)
+    // (a list of m: ns slices of nq rows each, on the device in ascending order of m; slice slot[j] goes to out + j * Q + t0;
+    // pairs: the position's double goes to the place of its pair in the caller's order)
     hipError_t unpack(int64_t k)
     {
         ChunkHalf &b = half(k);
         const int nq = rows(k);
         const int64_t t0 = start(k), B = rq.B;
         HIPTRY(hipEventSynchronize(b.down));
+        if (rq.pairs) {
+            const int64_t *ord = rq.pairs->ord.data() + t0;
+            for (int i = 0; i < nq; ++i) rq.dist_out[ord[i]] = b.hdist.p[i];
+            return hipSuccess;
+        }
         for (int j = 0; j < ns; ++j) {
             const size_t from = (size_t)slot[j] * (size_t)nq;
             const int64_t to = (int64_t)j * rq.Q + t0;
@@ -2808,6 +2889,50 @@ int chb_bin_report(chb_ctx *h, const int64_t *labels, int64_t B, int m, const in
     rq.row_idx = nullptr; rq.plan = &plan; rq.Q = Qv;   // the plan's positions, already in label order
     rc = ScoreRun{h, rq}.run();
     return rc != CHB_OK ? rc : plan.copy_tables(h, out);
+}
+
+namespace {
+
+// the two pair calls behind score_check_args and their own checks of the rows: the bins' range, the plan, the run
+int score_pairs(chb_ctx *h, ScoreRequest &rq, const int64_t *row, const int64_t *bin_idx)
+{
+    for (int64_t p = 0; p < rq.Q; ++p)
+        if (bin_idx[p] < 0 || bin_idx[p] >= rq.B) return fail(CHB_EINVAL, "bin_idx entry outside [0, B)");
+    PairPlan plan;
+    plan.build(row, bin_idx, rq.Q, rq.B);
+    h->score.pair_tiles = (int64_t)plan.tile.size();
+    rq.row_idx = nullptr; rq.pairs = &plan;
+    return ScoreRun{h, rq}.run();
+}
+
+const char *pairs_missing(int64_t P, const void *row, const void *bin_idx, const void *dist_out, const char *text)
+{
+    return P > 0 && (!row || !bin_idx || !dist_out) ? text : nullptr;
+}
+
+}  // namespace
+
+int chb_audit_pairs(chb_ctx *h, const int64_t *labels, int64_t B, int m, const int64_t *row_idx, const int64_t *bin_idx,
+                    int64_t P, double *dist_out)
+{
+    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, P, m, nullptr, 0, nullptr, dist_out, nullptr, nullptr};
+    // (row_idx is not "all rows" here: its range is checked like chb_audit_rows' list)
+    const int rc = score_check_args(h, "chb_audit_pairs", rq, nullptr, false,
+                                    pairs_missing(P, row_idx, bin_idx, dist_out, "row_idx, bin_idx or dist_out is null"));
+    return rc != CHB_OK || P == 0 ? rc : score_pairs(h, rq, row_idx, bin_idx);
+}
+
+int chb_recruit_pairs(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
+                      const int64_t *row_of, const int64_t *bin_idx, int64_t P, double *dist_out)
+{
+    ScoreRequest rq{labels, B, Y, nullptr, nullptr, P, m, nullptr, 0, nullptr, dist_out, nullptr, nullptr};
+    const int rc = score_check_args(h, "chb_recruit_pairs", rq, &D, false,
+                                    pairs_missing(P, row_of, bin_idx, dist_out, "row_of, bin_idx or dist_out is null"));
+    if (rc != CHB_OK) return rc;
+    if (Q < 0) return fail(CHB_EINVAL, "Q < 0");
+    for (int64_t p = 0; p < P; ++p)
+        if (row_of[p] < 0 || row_of[p] >= Q) return fail(CHB_EINVAL, "row_of entry outside [0, Q)");
+    return P == 0 ? CHB_OK : score_pairs(h, rq, row_of, bin_idx);
 }
 
 int chb_find_nearest_from_row(chb_ctx *h, int64_t c, const int64_t *labels, const double *row,
@@ -3191,6 +3316,7 @@ static const struct { const char *name; int64_t (*get)(const chb_ctx *); } kHost
     CTR("tile_unloaded", h->seat.unloaded), CTR("last_batch_k", h->batch.K),
     CTR("recruit_chunk", kRecruitChunk),   // rows per launch of chb_recruit_rows
     CTR("recruit_multi_rows", h->score.multi_rows),   // ... of the last chb_audit_rows_multi / chb_recruit_rows_multi
+    CTR("pair_tiles", h->score.pair_tiles),   // work items of the last chb_audit_pairs / chb_recruit_pairs
     // chb_kmer_profiles / chb_set_samples_from_sequences: a chunk's limits, the chunks of the last call
     CTR("kmer_chunk_bytes", kKmerChunkBytes), CTR("kmer_chunk_rows", kKmerChunkRows), CTR("kmer_chunks", h->kmer_chunks),
     CTR("prefilter_enabled", (h->sw.use_prefilter && h->shadow_ok) ? 1 : 0),

@@ -359,9 +359,18 @@ struct RecruitArgs {
     unsigned mmask;
     double *dist;          // [nq][B]; with a list of m: [popcount(mmask)][nq][B]
 };
+// a list of (row, bin) pairs in place of the dense grid (chb_audit_pairs / chb_recruit_pairs): the chunk's nq positions are
+// grouped by bin and every bin's run is cut into tiles of at most kQTile positions; tile[t] = {bin, first position in the
+// chunk, positions, 0}.  Y / qid name the pairs' rows in position order, dist holds one double per position, mmask is 0.
+// (Its own struct: the dense kernels keep the kernel arguments they have.)
+struct RecruitPairArgs : RecruitArgs {
+    const int4 *tile;      // [ntile]
+    int ntile;
+};
 constexpr int kRecruitChunk = 16384;   // rows of Y uploaded (recruit) or positions of row_idx (audit) scored per launch
 constexpr int kRecruitMaxBins = 8192;
 void launch_recruit(const RecruitArgs &a, hipStream_t s);   // (a.qid set: the audit instantiation)
+void launch_recruit_pairs(const RecruitPairArgs &a, hipStream_t s);
 // bin[q] = strict-'>' argmin over dist[q][0 .. B) (-1: all +inf), mind[q] its distance, margin[q] = runner-up minus it (+inf
 // without a finite runner-up)
 void launch_recruit_reduce(const double *dist, int nq, int B, int *bin, double *mind, double *margin, hipStream_t s);

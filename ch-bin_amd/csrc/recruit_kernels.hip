@@ -26,6 +26,10 @@
 // chb_audit_rows runs the same kernel body on RESIDENT rows (template parameter kResident): the rows to score are samples
 // named by index, and a row is withheld from its own bin's candidates -- the leave-one-out step of algorithm.py:49-58.
 //
+// chb_audit_pairs / chb_recruit_pairs run the same kernel body on a LIST of (row, bin) pairs (template parameter kPairs):
+// the work items come from a tile table the host cut from the pairs in bin order, and a pair's one distance is stored at
+// its position; there is no reduction kernel behind it.
+//
 // chb_bin_report runs the audit's two kernels on positions grouped by their own label and a third, bin_report_kernel
 // (below), that folds each chunk's distances and bins into B x B tables keyed (own label, bin).
 #include "chb_internal.h"
@@ -33,6 +37,8 @@
 
 #include <limits.h>
 #include <math.h>
+
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -70,9 +76,19 @@ union RecruitLds {
 // back with everything outside the leading block zeroed -- what a launch with that m alone hands to solve16, where a
 // missing vertex reads the query row -- because solve16 overwrites the tile with the lifted, rescaled Gram.  The `false`
 // instantiations are the single-m kernels unchanged: everything of the list sits behind `if constexpr (kMulti)`.
-template <bool kResident, bool kMulti>
-__global__ __launch_bounds__(256, 2) void recruit_kernel(RecruitArgs a, int nqt, int total)
+//
+// kPairs (chb_audit_pairs / chb_recruit_pairs): a list of (row, bin) pairs in place of the dense grid.  The host has put
+// the pairs in bin order and cut every bin's run into tiles of at most kQTile positions; work item W is row W of the
+// chunk's tile table a.tile = {bin, first position in the chunk, positions}, rows of the tile at or past `positions`
+// score nothing, and the one double of a position goes to a.dist[position].  Nothing else differs from the single-m
+// kernel -- the staged rows of a short tile's tail are the next tile's (or the chunk's last), read and never offered --
+// so a pair's distance has the bits of the dense call's entry.  The `false` instantiations are unchanged: the three
+// places sit behind `if constexpr (kPairs)`.  There is no list of m for pairs.
+template <bool kResident, bool kMulti, bool kPairs>
+__global__ __launch_bounds__(256, 2) void recruit_kernel(std::conditional_t<kPairs, RecruitPairArgs, RecruitArgs> a,
+                                                         int nqt, int total)
 {
+    static_assert(!(kMulti && kPairs), "pairs are scored for a single m");
     __shared__ __attribute__((aligned(16))) RecruitLds lds;
 
     // XCD-aware order: blocks b and b+8 share an XCD (and its L2), so hand each XCD a contiguous range of work
@@ -80,7 +96,13 @@ __global__ __launch_bounds__(256, 2) void recruit_kernel(RecruitArgs a, int nqt,
     const int per = (total + 7) >> 3;
     const int W = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
     if (W >= total) return;
-    const int c = W / nqt, qt = W - c * nqt;
+    int c, qt, nrow = kQTile;   // the bin; the tile of 64 positions or (pairs) its first position, and how many of its rows count
+    if constexpr (kPairs) {
+        const int4 t = a.tile[W];
+        c = t.x; qt = t.y; nrow = t.z;
+    } else {
+        c = W / nqt; qt = W - c * nqt;
+    }
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int tx = tid & 15, ty = tid >> 4;
@@ -88,7 +110,7 @@ __global__ __launch_bounds__(256, 2) void recruit_kernel(RecruitArgs a, int nqt,
     const int srow = tid >> 2, skp = tid & 3;
 
     const int mb = a.bin_ptr[c], nmem = a.bin_ptr[c + 1] - mb;
-    const int pos0 = qt * kQTile;
+    const int pos0 = kPairs ? qt : qt * kQTile;
     const int m = a.m;
 
     // list state of my 4 rows: this lane holds entry #tx
@@ -178,7 +200,9 @@ __global__ __launch_bounds__(256, 2) void recruit_kernel(RecruitArgs a, int nqt,
             for (int j = 0; j < 4; ++j) mid[j] = lds.st.mid[ct & 1][(j < 2) ? 2 * tx + j : 32 + 2 * tx + (j - 2)];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const bool qvalid = pos0 + 4 * ty + i < a.nq;
+                bool qvalid;
+                if constexpr (kPairs) qvalid = 4 * ty + i < nrow;
+                else qvalid = pos0 + 4 * ty + i < a.nq;
                 double s[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -263,7 +287,11 @@ __global__ __launch_bounds__(256, 2) void recruit_kernel(RecruitArgs a, int nqt,
             const double val = solve16(&lds.so.Qt[w][kq][0][0], &lds.so.sv[w][kq][0], n, a.metric, lane, alpha);
             dist = sqrt(fmax(val, 0.0));
         }
+        if constexpr (kPairs) {
+            if (tx == 0 && 4 * ty + i < nrow) a.dist[qpos] = dist;
+        } else {
         if (tx == 0 && qpos < a.nq) a.dist[(size_t)qpos * a.B + c] = dist;
+        }
         }
         __builtin_amdgcn_wave_barrier();   // the tiles are rewritten by the next row's phase 1
         nn[0] = nn[1]; nn[1] = nn[2]; nn[2] = nn[3];
@@ -407,12 +435,21 @@ void launch_recruit(const RecruitArgs &a, hipStream_t s)
     const int total = nqt * a.B;
     const int grid = ((total + 7) / 8) * 8;
     if (a.mmask) {   // a list of m: one slice of dist per entry
-        if (a.qid) hipLaunchKernelGGL((recruit_kernel<true, true>), dim3(grid), dim3(256), 0, s, a, nqt, total);
-        else hipLaunchKernelGGL((recruit_kernel<false, true>), dim3(grid), dim3(256), 0, s, a, nqt, total);
+        if (a.qid) hipLaunchKernelGGL((recruit_kernel<true, true, false>), dim3(grid), dim3(256), 0, s, a, nqt, total);
+        else hipLaunchKernelGGL((recruit_kernel<false, true, false>), dim3(grid), dim3(256), 0, s, a, nqt, total);
         return;
     }
-    if (a.qid) hipLaunchKernelGGL((recruit_kernel<true, false>), dim3(grid), dim3(256), 0, s, a, nqt, total);
-    else hipLaunchKernelGGL((recruit_kernel<false, false>), dim3(grid), dim3(256), 0, s, a, nqt, total);
+    if (a.qid) hipLaunchKernelGGL((recruit_kernel<true, false, false>), dim3(grid), dim3(256), 0, s, a, nqt, total);
+    else hipLaunchKernelGGL((recruit_kernel<false, false, false>), dim3(grid), dim3(256), 0, s, a, nqt, total);
+}
+
+// one work item per row of the tile table
+void launch_recruit_pairs(const RecruitPairArgs &a, hipStream_t s)
+{
+    if (a.nq <= 0 || a.ntile <= 0) return;
+    const int grid = ((a.ntile + 7) / 8) * 8;
+    if (a.qid) hipLaunchKernelGGL((recruit_kernel<true, false, true>), dim3(grid), dim3(256), 0, s, a, 0, a.ntile);
+    else hipLaunchKernelGGL((recruit_kernel<false, false, true>), dim3(grid), dim3(256), 0, s, a, 0, a.ntile);
 }
 
 void launch_recruit_reduce(const double *dist, int nq, int B, int *bin, double *mind, double *margin, hipStream_t s)

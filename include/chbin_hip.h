@@ -209,6 +209,35 @@ int chb_bin_report(chb_ctx *h, const int64_t *labels, int64_t B, int m, const in
                    int64_t *confusion, int64_t *unplaced, int64_t *dcnt, double *dmin, double *dsum,
                    int64_t *n_skipped);
 
+/* Pair scoring: the hull distance of a LIST of (row, bin) pairs instead of every row against every bin -- each contig
+ * against its own bin, the rows of two confused bins against those two, a second look at a few rows.  Both calls are
+ * defined by the dense ones: dist_out[p] of chb_audit_pairs is bit for bit entry [bin_idx[p]] of the dist_out row that
+ * chb_audit_rows returns for sample row_idx[p] on the same labels, B, m and metric (+inf included), dist_out[p] of
+ * chb_recruit_pairs the same entry of chb_recruit_rows' row for Y[row_of[p]] (Y: Q rows of D columns).  Leave-one-out is
+ * the audit's rule: only the sample's own index is withheld, whatever bin the pair names, and a twin with the same
+ * coordinates stays a candidate.  Pairs may repeat and come in any order; dist_out (P doubles) is in the caller's order.
+ * P = 0 (for chb_recruit_pairs also together with Q = 0) is a no-op and CHB_OK.
+ *   - CHB_EINVAL: a null context; P < 0, Q < 0, B < 1 or m < 1; with P > 0 a null labels, bin_idx, row_idx / row_of, Y or
+ *     dist_out; a bin_idx entry outside [0, B), a row_idx entry outside [0, N), a row_of entry outside [0, Q); D other
+ *     than the resident samples'.  CHB_EUNSUPPORTED: m > 16, B > 8192.  CHB_ESTATE: no resident samples, or a stepwise fit
+ *     is open (the fit stays usable).  Every check runs on the host before anything is enqueued, in the order of the
+ *     dense calls' checks where they overlap;
+ *   - the cost is the members streamed: the pairs are put in bin order by a stable counting sort on the host, each bin's
+ *     run is cut into tiles of at most 64 pairs, and a tile streams its bin's members once -- P pairs of one bin cost
+ *     ceil(P / 64) passes over that bin and nothing over any other.  chb_counter "pair_tiles": the tiles of the last call;
+ *   - chunks: runs of whole tiles with at most 16384 pairs (chb_counter "recruit_chunk"); per chunk the int32 tile table
+ *     {bin, first pair, pairs} and the int32 sample indices (chb_audit_pairs) or the pairs' rows of Y (chb_recruit_pairs:
+ *     a row named by two pairs travels twice) go up and one double per pair comes down, through the dense calls' pinned
+ *     double buffer and second stream.  There is no Q x B table anywhere and no row reduction;
+ *   - like the dense calls they use no state of a fit and leave every counter (but "pair_tiles"), memo and switch of the
+ *     context as they found it; one GPU: with a communicator (world > 1) there is no collective;
+ *   - profile names "audit_pairs" / "recruit_pairs": one launch per chunk, work units = pairs. */
+int chb_audit_pairs(chb_ctx *h, const int64_t *labels, int64_t B, int m,
+                    const int64_t *row_idx, const int64_t *bin_idx, int64_t P, double *dist_out);
+int chb_recruit_pairs(chb_ctx *h, const int64_t *labels, int64_t B, int m,
+                      const double *Y, int64_t Q, int64_t D,
+                      const int64_t *row_of, const int64_t *bin_idx, int64_t P, double *dist_out);
+
 /* distance_matrix.py:47-62 find_nearest_from_cluster with the reference's exact signature: the
  * caller supplies one row of a distance matrix (any provenance) and the current labels; selects
  * among {p : labels[p] == c} the (up to) m smallest by (row[p], p).  out_idx[m] (-1 padded). */
@@ -371,7 +400,8 @@ int chb_profile_reset(chb_ctx *h);
  * units = (row, bin) pairs) | "audit" (chb_audit_rows: the same pair of launches for one chunk of resident rows; work units
  * = (row, bin) pairs; chb_bin_report books its two audit launches here as well) | "audit_multi" / "recruit_multi"
  * (chb_audit_rows_multi / chb_recruit_rows_multi: the same pair of launches for one chunk and a list of m; work units =
- * (row, bin, m) triples) | "bin_report" (chb_bin_report: the launch
+ * (row, bin, m) triples) | "audit_pairs" / "recruit_pairs" (chb_audit_pairs / chb_recruit_pairs: the one launch of a chunk;
+ * work units = pairs) | "bin_report" (chb_bin_report: the launch
  * that folds one chunk's distances and bins into the B x B tables; work units = (row, bin) pairs).  For m <= 16 "hull_qp" is the fused selection + hull-distance kernel and
  * "slow_path" the exact path for what it leaves over; "rescore*" then only appear for m > 16 or CHB_FUSED=0. */
 int chb_profile_get(chb_ctx *h, const char *kernel, double *total_ms, int64_t *launches,
@@ -398,7 +428,8 @@ int chb_fit_stats(chb_ctx *h, int64_t *out4);
  * "pool_candidates" / "pool_pairs" (sampled shortlist lengths behind that decision), "exchanges" (framed all-gathers of the last fit under an exchange: one per batch for the
  * label guess, one per round), "recruit_chunk" (rows per launch of chb_recruit_rows, chb_audit_rows and -- at most -- chb_bin_report: a constant),
  * "recruit_multi_rows" (rows per launch of the last chb_audit_rows_multi / chb_recruit_rows_multi call: 16384 / nm rounded
- * down to a multiple of 64; 0 before the first),
+ * down to a multiple of 64; 0 before the first), "pair_tiles" (tiles of at most 64 pairs of one bin -- the kernel's work
+ * items -- of the last chb_audit_pairs / chb_recruit_pairs call that had pairs; 0 before the first),
  * "kmer_chunk_bytes" / "kmer_chunk_rows" (the most bases / contigs of one sequence chunk of chb_kmer_profiles and
  * chb_set_samples_from_sequences: constants), "kmer_chunks" (chunks of the last such call) */
 int chb_counter(chb_ctx *h, const char *name, int64_t *out);
