@@ -187,7 +187,7 @@ struct Switches {
 
 // The persistent base pack (prefilter_kernels.hip): the member pack kept across the batches of a fit
 struct PersistentPack {
-    DevBuf<int> start, cap, fill, live, nt, memb, row, ctl, ovf, dest;
+    DevBuf<int> start, cap, fill, live, nt, fill0, start0, memb, row, ctl, ovf, dest;
     int arena_rows = 0;
     int64_t mark = 0;       // rows handed out from which on the host asks for a rebuild (pack_state_build)
     bool fit = false;       // inside chb_fit_cluster (the stepwise entry points and chb_topm_per_bin always rebuild)
@@ -195,7 +195,7 @@ struct PersistentPack {
     bool batch = false;     // the open batch was started on it
     bool rebuild = false;   // much of the arena is used up: the next batch start outside a look-ahead window rebuilds
     int64_t stat_batches = 0, stat_builds = 0;
-    chb::PackState view() { return chb::PackState{start.p, cap.p, fill.p, live.p, nt.p, memb.p, row.p, ctl.p, ovf.p, dest.p, arena_rows}; }
+    chb::PackState view() { return chb::PackState{start.p, cap.p, fill.p, live.p, nt.p, fill0.p, start0.p, memb.p, row.p, ctl.p, ovf.p, dest.p, arena_rows}; }
     void fit_reset() { valid = false; batch = false; rebuild = false; }
     void fit_scope(bool in) { fit = in; if (in) { stat_batches = 0; stat_builds = 0; } else valid = false; }
 };
@@ -204,10 +204,12 @@ struct PersistentPack {
 // base members of the bin nearest to the home bin's centre; built at a fit's start, maintained by every commit
 struct ThresholdPools {
     DevBuf<unsigned short> Z;
-    DevBuf<int> id, hole, ok;
+    DevBuf<int> id, hole, ok, bad;
     DevBuf<float> key, sn, tsn;
     bool fit = false;      // inside chb_fit_cluster (the stepwise entry points and chb_topm_per_bin never use pools)
     bool valid = false;    // the pools on the device match the labels
+    bool kept = false;     // ... and did when the last fit ended (what the counter pool_bad_slots looks at)
+    bool batch_labelled = true;   // the batch about to be opened may hold labelled samples (the fit loop knows; else: true)
     bool holes = true;     // the open batch may hold labelled samples (their pool slots are holes until the commit)
     int state = 0;         // this fit: 0 undecided = on, 1 kept on, -1 off (its shortlists came out long: overlapping bins;
                            // or tile skipping never loads more than 30 % of the tiles: FitRun::note_verdict has both rules)
@@ -218,7 +220,7 @@ struct ThresholdPools {
     chb::PoolState view() { return chb::PoolState{Z.p, id.p, key.p, sn.p, hole.p, tsn.p, ok.p}; }
     void release() { Z.release(); id.release(); hole.release(); key.release(); sn.release(); tsn.release(); ok.release(); }
     void fit_reset(bool off) { stat_batches = 0; state = off ? -1 : 0; batches = 0; cand = 0; pairs = 0; }
-    void fit_scope(bool in) { fit = in; if (!in) valid = false; }
+    void fit_scope(bool in) { fit = in; kept = !in && valid; batch_labelled = true; if (!in) valid = false; }
 };
 
 // Tile skipping in the base shortlist launch, and the queries' seats it and the pools need
@@ -704,7 +706,7 @@ int pack_state_build(chb_ctx *h)
         h->pp.arena_rows = arena;
     }
     HIPCHK(h->pp.row.ensure((size_t)h->N));
-    DevBuf<int> *pb[] = {&h->pp.start, &h->pp.cap, &h->pp.fill, &h->pp.live, &h->pp.nt};
+    DevBuf<int> *pb[] = {&h->pp.start, &h->pp.cap, &h->pp.fill, &h->pp.live, &h->pp.nt, &h->pp.fill0, &h->pp.start0};
     for (auto *b : pb) HIPCHK(b->ensure(B + 1));
     HIPCHK(h->pp.ctl.ensure_zeroed(4, h->stream));
     HIPCHK(h->pp.ovf.ensure((size_t)std::max(h->Kcap, 1)));
@@ -931,12 +933,17 @@ int settle_batch(chb_ctx *h, BatchPlan &p)
 void open_batch(chb_ctx *h, const BatchPlan &p)
 {
     const SegPlan *seg = p.sp.gflag ? &p.sp : nullptr;
+    // the pools are opened only for a batch that can hold a labelled sample: no other batch makes a hole, and ok[] is kept
+    // right by the build and by every commit (sweep 1 of a fit from seeds -- the benchmark's step -- opens none).  The
+    // second-chance launch's overflow counter, which launch_pool_open resets, is then reset by the pack's batch start
+    const bool open_pools = h->pool.valid && (h->pool.batch_labelled || !p.pp_now);
     if (p.pp_now) {
         // the batch is opened (its members' rows become holes) and tiles per bin / statistics / segment plan written:
         // one launch instead of count + scan + fill + gather
         Timed t(h, "bucket", (double)h->batch.K);
         launch_pack_state_start(h->pp.view(), h->pk.view(), h->D, h->Dz, h->labels.p, h->inb.p, h->batch.bq_cur, h->batch.K, h->lab_old.p,
-                                h->B, seg, h->batch.fc_cur + kSlotMaxTiles, h->nflag.p, h->stream);
+                                h->B, seg, h->batch.fc_cur + kSlotMaxTiles, h->nflag.p, h->pool.valid && !open_pools ? h->nflag2.p : nullptr,
+                                h->stream);
         h->pp.stat_batches += 1;
     } else {
         // (the batch is opened -- labels remembered, members marked -- inside the CSR count's launch)
@@ -945,12 +952,12 @@ void open_batch(chb_ctx *h, const BatchPlan &p)
                            h->pk.pad_ptr.p, h->nflag.p, h->stream, h->batch.bq_cur, h->batch.K, h->lab_old.p, seg, h->batch.fc_cur + kSlotMaxTiles,
                            p.pf_base_path ? h->ms.p : nullptr, p.skip_on ? h->seat.shell_inv.p : nullptr, p.skip_on ? h->seat.nsh : 1);
     }
-    if (h->pool.valid) {
+    if (open_pools) {
         // (the batch's samples are marked: their slots in the pools are holes while it is open)
         Timed t(h, "pool", (double)h->batch.K);
         launch_pool_open(h->pool.view(), h->inb.p, h->D, h->Dz, h->B, h->nflag2.p, h->stream);
     }
-    h->pool.holes = true;
+    h->pool.holes = h->pool.batch_labelled;
 }
 
 // what the base shortlist launch reads besides the CSR: the fit's overflow counter, a rebuilt CSR's pack, the queries' seats
@@ -1213,8 +1220,10 @@ int batch_commit_dev(chb_ctx *h, const int *final_dev)
     if (h->pool.valid) {
         // (labels and shadow rows are final: holes resolved, the batch's arrivals offered to their new bins' pools)
         Timed t(h, "pool", (double)h->batch.K);
+        // (a batch the persistent pack served: its commit has just put every bin's arrivals at the tail of the bin's region)
+        const chb::PackState pack = h->pp.view();
         launch_pool_commit(h->pool.view(), h->Zs.p, h->ms.p, h->qn.p, h->D, h->Dz, h->batch.bq_cur, h->batch.K, final_dev, h->lab_old.p,
-                           h->labels.p, h->B, h->pool.holes, s);
+                           h->labels.p, h->B, h->pool.holes, h->pp.batch ? &pack : nullptr, s);
     }
     HIPCHK(hipGetLastError());
     h->batch.open = false;
@@ -1676,9 +1685,11 @@ struct FitRun {
         h->batch.hint_base_members = (double)((it == 0) ? assigned0 + g.t0 : labelled - g.K);
         h->batch.hint_batch_entries = (double)((it == 0) ? g.K : 2 * g.K);
         h->argmin_in_place = !xchg;
+        // (an all-unlabelled batch makes no holes in the pools: nothing to open, nothing for its commit to look for)
+        h->pool.batch_labelled = sweep_has_labelled;
         int r = batch_begin_dev(h, g.K, g.q_lo, g.q_hi, false);
+        h->pool.batch_labelled = true;
         if (r) return r;
-        h->pool.holes = sweep_has_labelled;   // (an all-unlabelled batch leaves no holes for its commit to look for)
         // starting labels of the rounds: last sweep's label, or for still-unlabelled contigs
         // (sweep 1) the bin whose m-th nearest outside member is closest
         if (h->fused && !h->batch.lists_valid) launch_guess_near(h->tau.p, h->lab_old.p, g.q_lo, g.q_hi, h->B, h->Kcap, h->lab_prev.p, s);
@@ -1922,7 +1933,7 @@ static int samples_upload(chb_ctx *h, const double *X, int64_t N, int64_t D, boo
 // everything that is a function of the resident X alone (global mean, scale, query-side shadow rows)
 static int samples_finish(chb_ctx *h)
 {
-    h->seat.off_key = -1; h->pool.off_key = -1;
+    h->seat.off_key = -1; h->pool.off_key = -1; h->pool.kept = false;
     const int64_t N = h->N, D = h->D;
     const int Dp = h->Dp;
     // the shortlist stage (prefilter_kernels.hip) keeps its query fragments in registers: D <= 157 in the narrow builds,
@@ -3303,6 +3314,20 @@ static int last_batch_cand_cnt(chb_ctx *h, std::vector<int> *cnt)
     return CHB_OK;
 }
 
+// the last fit's threshold pools, as it left them, against what the shortlist kernel relies on (launch_pool_check): slots
+// and pools in breach.  For the tests, while no batch is open; 0 where the context has no pools or the fit dropped them
+static int pool_bad_slots(chb_ctx *h, int64_t *out)
+{
+    *out = 0;
+    if (!(h->pool.valid || h->pool.kept) || !h->pool.Z.p || !h->labels.p || !h->qn.p || !h->Zs.p) return CHB_OK;
+    HIPCHK(hipSetDevice(h->dev));
+    HIPCHK(h->pool.bad.ensure(1));
+    HIPCHK(hipMemsetAsync(h->pool.bad.p, 0, sizeof(int), h->stream));
+    launch_pool_check(h->pool.view(), h->Zs.p, h->qn.p, h->labels.p, (int)h->N, h->Dz, h->B, h->pool.bad.p, h->stream);
+    HIPCHK(hipGetLastError());
+    return read_device_int(h, h->pool.bad.p, out);
+}
+
 // the counters the host keeps
 #define CTR(name, expr) {name, [](const chb_ctx *h) -> int64_t { return expr; }}
 static const struct { const char *name; int64_t (*get)(const chb_ctx *); } kHostCounters[] = {
@@ -3330,6 +3355,9 @@ int chb_counter(chb_ctx *h, const char *name, int64_t *out)
     if (!strcmp(name, "prefilter_overflow")) return read_device_int(h, h->overflow_total_valid ? h->overflow.p : nullptr, out);
     // pairs of the last fit that broke the shortlist stage's contract (0, or the fit failed)
     if (!strcmp(name, "shortlist_short")) return read_device_int(h, h->short_cnt.p, out);
+    if (!strcmp(name, "pool_bad_slots")) return pool_bad_slots(h, out);
+    // regions of the persistent pack that ran full and moved in the last fit (pack_state_fix_kernel)
+    if (!strcmp(name, "pack_region_moves")) return read_device_int(h, h->pp.ctl.p ? h->pp.ctl.p + 3 : nullptr, out);
     // pairs the fused kernel left to the exact path
     if (!strcmp(name, "slow_pairs_last_round")) return read_device_int(h, h->fused ? h->n_slow.p : nullptr, out);
     // "shortlist_le<N>_last_batch": pairs of the last batch with <= N candidates

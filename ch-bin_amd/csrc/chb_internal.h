@@ -152,7 +152,8 @@ struct PoolState {
     float *sn;           // [B * B * 32] ||zh_p|| (rounded up; 0: empty)
     int *hole;           // [B * B * 32] 1: the slot's sample is in the open batch (not a base member right now)
     float *tsn;          // [B * B + 64] largest ||zh|| of the tile's slots (the tile's query-rounding term)
-    int *ok;             // [B * B] usable rows of the tile while the current batch is open (written by every batch open)
+    int *ok;             // [B * B] usable rows of the tile (written by the build, by every batch open, and by a commit for the
+                         // pools it writes back)
 };
 struct ShortlistArgs {
     const unsigned short *Gs;  // [N][Dz] query-side rows
@@ -206,9 +207,12 @@ struct PackState {
     int *fill;     // [B] rows in use (members and holes); the rest of the region is padding
     int *live;     // [B] members (rows in use minus holes)
     int *nt;       // [B] tiles in use, ceil(fill / 32): written at every batch start
+    int *fill0;    // [B] `fill` as the open batch's start found it ...
+    int *start0;   // [B] ... and `start`: rows [start + fill0, start + fill) of a bin whose region has not moved since are
+                   //     the samples that ARRIVED in the bin with the batch's commit (read by launch_pool_commit)
     int *memb;     // [arena rows] sample of each row, -1: hole / padding
     int *row;      // [N] row of each sample, -1: not in the pack
-    int *ctl;      // [4] {rows of the arena handed out, overflowed appends of the commit in flight, error flag, -}
+    int *ctl;      // [4] {rows of the arena handed out, overflowed appends of the commit in flight, error flag, regions moved}
     int *ovf;      // [K] batch positions whose append found its bin's region full (served by the fix kernel)
     int *dest;     // [K] where each committed sample's row goes: 2 * row + (1: a new row of its bin), -1: nowhere / overflowed
     int arena_rows;
@@ -220,9 +224,11 @@ void launch_pack_state_build(const PackState &ps, const MemberPack &P, const uns
 // (grow: rows every region gets at least -- what a bin is expected to hold once the unlabelled contigs are in)
 // batch start: the batch is opened (labels remembered, members marked, their rows turned into holes), the tiles per bin,
 // bin-size statistics and segment plan are written: one launch
+// (zero_me, zero_me2, optional: two ints reset here -- the overflow counters of the base shortlist launch and, where no
+//  launch_pool_open follows, of its second chance)
 void launch_pack_state_start(const PackState &ps, const MemberPack &P, int D, int Dz, const int *labels, int *inb,
                              const int *open_bq, int open_K, int *open_lab_old, int B, const SegPlan *seg, int *stats,
-                             int *zero_me, hipStream_t s);
+                             int *zero_me, int *zero_me2, hipStream_t s);
 // batch commit: launch_sample_shadow's commit form, which also puts every committed sample's row back into the pack (in
 // place when its label is the one it was removed under, else appended to its new bin), then the regions that ran full are
 // moved to larger ones
@@ -235,16 +241,23 @@ void launch_pack_state_commit(const PackState &ps, const MemberPack &P, const do
 void launch_pool_build(const PoolState &ps, const unsigned short *Zs, const void *ms, const void *qn, int D, int Dz,
                        const int *memb_id, const int *bin_ptr, int B, hipStream_t s);
 // batch open (behind the kernel that marks the batch's samples in inb): the slots of batch members become holes,
-// ok[c * B + h] = usable rows
+// ok[c * B + h] = usable rows.  Only a batch that may hold labelled samples needs it: build and commit leave ok[] right
 // (zero_me, optional: one int reset here -- the second-chance launch's overflow counter)
 void launch_pool_open(const PoolState &ps, const int *inb, int D, int Dz, int B, int *zero_me, hipStream_t s);
 // batch commit (behind the kernel that writes the final labels and refreshes the samples' shadow rows): holes whose sample
 // stayed in the bin are usable again, the others are emptied; the batch's ARRIVALS of every bin (final label c, label at
 // the batch's start another one) compete for the pools (c, *), replacing the slot with the largest key
 // (holes: the batch may have held labelled samples -- false in a fit's first sweep, whose batches are all unlabelled)
+// (pack: the persistent pack whose commit has just served this batch -- a bin's arrivals are then read from the tail of its
+//  region instead of being looked for in new_lab / lab_old; nullptr: the batch was not served by the pack)
 void launch_pool_commit(const PoolState &ps, const unsigned short *Zs, const void *ms, const void *qn, int D, int Dz,
                         const int *ids, int n, const int *new_lab, const int *lab_old, const int *labels, int B, bool holes,
-                        hipStream_t s);
+                        const PackState *pack, hipStream_t s);
+// slots that break what the shortlist kernel relies on, plus pools whose ok[] is not their number of usable rows, added to
+// *bad (zeroed by the caller); for the tests, while no batch is open.  A usable slot (id >= 0, no hole) of pool (c, h) must
+// hold a sample labelled c, that sample's shadow row, its key qn[id][h].x, and a norm that the tile's tsn covers
+void launch_pool_check(const PoolState &ps, const unsigned short *Zs, const void *qn, const int *labels, int N, int Dz, int B,
+                       int *bad, hipStream_t s);
 
 // flags64[bin][ceil(nq/64)] (pre-zeroed): set for (query tile of 64, bin) pairs whose shortlist overflowed
 // (and listed once in a.flaglist); bpw_force > 0: bins per workgroup (the developer library's CHB_SL_BPW; not for the

@@ -750,18 +750,27 @@ __global__ __launch_bounds__(256) void pack_state_build_kernel(PackState ps, Mem
 // rebuilt pack), blocks [1, 1 + nopen) open the batch
 __global__ __launch_bounds__(256) void pack_state_start_kernel(PackState ps, MemberPack P, int D, int Dz, const int *labels,
                                                                int *inb, const int *bq, int K, int *lab_old, int B,
-                                                               SegPlan seg, int *stats, int *zero_me, Gate gate)
+                                                               SegPlan seg, int *stats, int *zero_me, int *zero_me2, Gate gate)
 {
     CHB_GATE(gate);
     const int b = blockIdx.x;
     if (b == 0) {
         __shared__ int s_max, s_tot, s_ng, s_ni;
-        if (threadIdx.x == 0) { s_max = 0; s_tot = 0; s_ng = 0; s_ni = 0; ps.ctl[1] = 0; if (zero_me != nullptr) *zero_me = 0; }
+        if (threadIdx.x == 0) {
+            s_max = 0; s_tot = 0; s_ng = 0; s_ni = 0; ps.ctl[1] = 0;
+            if (zero_me != nullptr) *zero_me = 0;
+            if (zero_me2 != nullptr) *zero_me2 = 0;
+        }
         __syncthreads();
         int loc_tot = 0, loc_max = 0;
         for (int c = threadIdx.x; c < B; c += 256) {
-            const int nt = (ps.fill[c] + 31) / 32;
+            const int fill = ps.fill[c];
+            const int nt = (fill + 31) / 32;
             ps.nt[c] = nt;
+            // where the bin's region ends now: what the commit appends behind it are the batch's arrivals (pool_update_kernel).
+            // (One snapshot is enough: on the stream a commit precedes the next start, and a start that its gate turns off
+            //  leaves the open batch's snapshot as it is.)
+            ps.fill0[c] = fill; ps.start0[c] = ps.start[c];
             loc_tot += nt; loc_max = max(loc_max, nt);
         }
         atomicAdd(&s_tot, loc_tot); atomicMax(&s_max, loc_max);
@@ -931,6 +940,7 @@ __global__ __launch_bounds__(256) void pack_state_fix_kernel(PackState ps, Membe
         int st = atomicAdd(&ps.ctl[0], nc);
         if (st + nc > ps.arena_rows) { ps.ctl[2] = 1; st = -1; }   // (the host sizes the arena so that this cannot happen)
         s_new = st; s_ncap = nc; s_cnt = 0;
+        atomicAdd(&ps.ctl[3], 1);   // (statistics: regions moved in this fit)
     }
     __syncthreads();
     const int nst = s_new;
@@ -1050,47 +1060,71 @@ __device__ __forceinline__ void pool_worst(float key, int lane, float &wkey, int
 // (Tried in round 5: one block per bin with one HOME per lane, so that a candidate's keys are one coalesced load of its qn
 //  row -- 64 .. 200 blocks of long serial loops instead of B x B short wavefronts: 11.9 against 0.58 ms per sweep at
 //  100k x 136 x 64.  The parallel form stays.)
-template <bool BUILD>
-__global__ __launch_bounds__(256) void pool_update_kernel(PoolState ps, const unsigned short *Zs, const float4 *ms,
+// TAILS (commit of a batch that the persistent pack served): the arrivals of bin c are not looked for in new_lab / lab_old --
+// 16 blocks per bin each scanning the whole batch -- but read where the pack's commit has just put them: every sample that
+// arrives in c gets a fresh row behind the rows the bin had at the batch's start, so they are ps.memb[start + fill0 ..
+// start + fill) (fill0 / start0: pack_state_start_kernel's snapshot; a sample restored in place is no arrival, and is not
+// offered in the scan form either).  A bin whose region pack_state_fix_kernel moved in this commit (start != start0: rows
+// squeezed together, and its overflowed appends were never in the tail) offers NOTHING this batch: a pool is valid with any
+// base members of its bin in it, a missed offer only leaves a threshold as loose as it was.
+// A pool is a chain of dependent memory round trips and little else, so loads are issued together wherever their addresses
+// are known: the slot state with the keys of the first 128 candidates (two per lane, their ids read once per wavefront), and
+// the rows of ALL slots that changed hands -- three rows per wave instruction at 18 or 20 pieces per row -- before the first
+// of them is stored.
+constexpr int kPoolCopyIt = 11;   // wave instructions of row pieces in flight: 3 rows each = all 32 slots of a pool (Dz <= 160)
+template <bool BUILD, bool TAILS>
+__global__ __launch_bounds__(256) void pool_update_kernel(PoolState ps, PackState pk, const unsigned short *Zs, const float4 *ms,
                                                           const float2 *qn, int D, int Dz, int B, int hb,
                                                           const int *memb_id, const int *bin_ptr,   // BUILD
                                                           const int *ids, int n, const int *new_lab, const int *lab_old,
                                                           const int *labels, int holes, Gate gate)
 {
     CHB_GATE(gate);
-    __shared__ int s_ids[kPoolWin];
+    static_assert(!(BUILD && TAILS), "the build takes its candidates from the CSR");
+    __shared__ int s_ids[TAILS ? 1 : kPoolWin];
     __shared__ int s_n;
     const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int h_begin = blockIdx.y * hb, h_end = min(B, h_begin + hb);
     const int cpr = Dz >> 3;
     const int src_n = BUILD ? bin_ptr[c + 1] - bin_ptr[c] : n;
-    const int nwin = max(1, (src_n + kPoolWin - 1) / kPoolWin);
+    const int nwin = TAILS ? 1 : max(1, (src_n + kPoolWin - 1) / kPoolWin);
     for (int win = 0; win < nwin; ++win) {
-        __syncthreads();
-        if (tid == 0) s_n = 0;
-        __syncthreads();
-        const int w0 = win * kPoolWin, w1 = min(src_n, w0 + kPoolWin);
-        if (BUILD) {
-            for (int i = w0 + tid; i < w1; i += 256) s_ids[i - w0] = memb_id[bin_ptr[c] + i];
-            if (tid == 0) s_n = w1 - w0;
+        int ncand = 0;
+        const int *tail = nullptr;
+        if (TAILS) {
+            const int st = pk.start[c], f0 = pk.fill0[c];
+            if (st == pk.start0[c]) ncand = max(0, min(pk.fill[c], pk.cap[c]) - f0);   // (moved: nothing offered)
+            tail = pk.memb + st + f0;
         } else {
-            // (four positions per load: the scan of the batch's labels is every block's first ~K / 256 dependent loads)
-            for (int i = w0 + 4 * tid; i < w1; i += 1024) {
-                if (i + 4 <= w1) {
-                    const int4 nl = *reinterpret_cast<const int4 *>(new_lab + i), lo = *reinterpret_cast<const int4 *>(lab_old + i);
-                    if (nl.x == c && lo.x != c) s_ids[atomicAdd(&s_n, 1)] = ids[i];
-                    if (nl.y == c && lo.y != c) s_ids[atomicAdd(&s_n, 1)] = ids[i + 1];
-                    if (nl.z == c && lo.z != c) s_ids[atomicAdd(&s_n, 1)] = ids[i + 2];
-                    if (nl.w == c && lo.w != c) s_ids[atomicAdd(&s_n, 1)] = ids[i + 3];
-                } else {
-                    for (int k = i; k < w1; ++k)
-                        if (new_lab[k] == c && lab_old[k] != c) s_ids[atomicAdd(&s_n, 1)] = ids[k];
+            __syncthreads();
+            if (tid == 0) s_n = 0;
+            __syncthreads();
+            const int w0 = win * kPoolWin, w1 = min(src_n, w0 + kPoolWin);
+            if (BUILD) {
+                for (int i = w0 + tid; i < w1; i += 256) s_ids[i - w0] = memb_id[bin_ptr[c] + i];
+                if (tid == 0) s_n = w1 - w0;
+            } else {
+                // (four positions per load: the scan of the batch's labels is every block's first ~K / 256 dependent loads)
+                for (int i = w0 + 4 * tid; i < w1; i += 1024) {
+                    if (i + 4 <= w1) {
+                        const int4 nl = *reinterpret_cast<const int4 *>(new_lab + i), lo = *reinterpret_cast<const int4 *>(lab_old + i);
+                        if (nl.x == c && lo.x != c) s_ids[atomicAdd(&s_n, 1)] = ids[i];
+                        if (nl.y == c && lo.y != c) s_ids[atomicAdd(&s_n, 1)] = ids[i + 1];
+                        if (nl.z == c && lo.z != c) s_ids[atomicAdd(&s_n, 1)] = ids[i + 2];
+                        if (nl.w == c && lo.w != c) s_ids[atomicAdd(&s_n, 1)] = ids[i + 3];
+                    } else {
+                        for (int k = i; k < w1; ++k)
+                            if (new_lab[k] == c && lab_old[k] != c) s_ids[atomicAdd(&s_n, 1)] = ids[k];
+                    }
                 }
             }
+            __syncthreads();
+            ncand = s_n;
         }
-        __syncthreads();
-        const int ncand = s_n;
         if (!BUILD && ncand == 0 && !(win == 0 && holes)) continue;   // (nothing arrives in this bin, no hole to look for)
+        auto cand_at = [&](int i) -> int { return i >= ncand ? -1 : TAILS ? tail[i] : s_ids[i]; };
+        // (the ids of the first 128 candidates are the same for every pool of the bin: read once per wavefront)
+        const int first0 = cand_at(lane), first1 = cand_at(64 + lane);
         for (int h = h_begin + w; h < h_end; h += 4) {
             const size_t slot = ((size_t)c * B + h) * kPoolRows + (size_t)(lane & 31);
             float key = INFINITY, sn = 0.f;
@@ -1103,6 +1137,9 @@ __global__ __launch_bounds__(256) void pool_update_kernel(PoolState ps, const un
                 key = ps.key[slot]; id = ps.id[slot]; sn = ps.sn[slot];
                 if (holes) hole = ps.hole[slot];
             }
+            // (the keys of the first 128 candidates: in flight together with the slot state)
+            float ck0 = first0 >= 0 ? qn[(size_t)first0 * B + h].x : INFINITY;
+            float ck1 = first1 >= 0 ? qn[(size_t)first1 * B + h].x : INFINITY;
             if (!BUILD && win == 0 && lane < kPoolRows && hole) {
                 if (id >= 0 && labels[id] == c) {
                     ps.Z[slot * Dz + D] = Zs[(size_t)id * Dz + D];   // usable again (the row itself never changed)
@@ -1113,9 +1150,8 @@ __global__ __launch_bounds__(256) void pool_update_kernel(PoolState ps, const un
             }
             float wkey; int wlane;
             pool_worst(key, lane, wkey, wlane);
-            for (int base = 0; base < ncand; base += 64) {
-                const int cid = base + lane < ncand ? s_ids[base + lane] : -1;
-                const float ck = cid >= 0 ? qn[(size_t)cid * B + h].x : INFINITY;
+            // 64 candidates, lowest lane first: each replaces the slot with the largest key if its own is smaller
+            auto offer = [&](int cid, float ck) {
                 unsigned long long mask = __ballot(cid >= 0 && ck < wkey);
                 while (mask) {
                     const int b = __ffsll((long long)mask) - 1;
@@ -1127,24 +1163,57 @@ __global__ __launch_bounds__(256) void pool_update_kernel(PoolState ps, const un
                         pool_worst(key, lane, wkey, wlane);
                     }
                 }
+            };
+            for (int base = 0; base < ncand; base += 128) {
+                int cid0 = first0, cid1 = first1;
+                if (base > 0) {   // (the keys of 128 candidates gathered before any of them is looked at)
+                    cid0 = cand_at(base + lane); cid1 = cand_at(base + 64 + lane);
+                    ck0 = cid0 >= 0 ? qn[(size_t)cid0 * B + h].x : INFINITY;
+                    ck1 = cid1 >= 0 ? qn[(size_t)cid1 * B + h].x : INFINITY;
+                }
+                offer(cid0, ck0);
+                offer(cid1, ck1);
             }
-            // the rows of the slots that changed hands
-            const unsigned long long chm = __ballot((changed & 1) != 0 && lane < kPoolRows);
-            if (changed & 1) sn = sqrtf(ms[id].z) * (1.0f + 2e-6f);
-            for (unsigned long long mm = chm; mm; mm &= mm - 1) {
-                const int r = __ffsll((long long)mm) - 1;
-                const int rid = __shfl(id, r, 64);
-                if (lane < cpr)
-                    *reinterpret_cast<uint4 *>(ps.Z + (((size_t)c * B + h) * kPoolRows + r) * Dz + lane * 8) =
-                        *reinterpret_cast<const uint4 *>(Zs + (size_t)rid * Dz + lane * 8);
+            // the rows of the slots that changed hands: the k-th of them (slot, sample) goes to lane k, then `rpi` rows per wave
+            // instruction, every load issued before the first store (the compiler cannot tell that ps.Z and Zs are apart)
+            const bool mine = (changed & 1) != 0 && lane < kPoolRows;
+            const unsigned long long chm = __ballot(mine);
+            if (chm != 0ull) {
+                const int nch = __popcll(chm);
+                const int to = mine ? __popcll(chm & ((1ull << lane) - 1ull)) : 63;   // (lane 63 holds no slot and is never read)
+                const int slot_of = __builtin_amdgcn_ds_permute(to << 2, lane), id_of = __builtin_amdgcn_ds_permute(to << 2, id);
+                const float z = mine ? ms[id].z : 0.f;
+                const int rpi = max(1, 64 / cpr), g = lane / cpr, piece = lane - g * cpr;   // (pools: Dz <= 160, 20 pieces at most)
+                unsigned short *const pool_rows = ps.Z + ((size_t)c * B + h) * kPoolRows * Dz;
+                for (int k0 = 0; k0 < nch; k0 += kPoolCopyIt * rpi) {
+                    f32x4 buf[kPoolCopyIt];
+                    int dst[kPoolCopyIt];
+#pragma unroll
+                    for (int j = 0; j < kPoolCopyIt; ++j) {
+                        dst[j] = -1; buf[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+                        if (k0 + j * rpi < nch) {
+                            const int k = k0 + j * rpi + g;
+                            const int r = __shfl(slot_of, k & 63, 64), rid = __shfl(id_of, k & 63, 64);
+                            if (g < rpi && k < nch) {
+                                dst[j] = r;
+                                buf[j] = *reinterpret_cast<const f32x4 *>(Zs + (size_t)rid * Dz + piece * 8);
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int j = 0; j < kPoolCopyIt; ++j)
+                        if (dst[j] >= 0) *reinterpret_cast<f32x4 *>(pool_rows + (size_t)dst[j] * Dz + piece * 8) = buf[j];
+                }
+                if (mine) sn = sqrtf(z) * (1.0f + 2e-6f);
             }
             const bool wr = BUILD || __ballot(changed != 0) != 0ull;   // (a pool nothing happened to is not written back)
             if (wr) {
                 float tn = lane < kPoolRows ? sn : 0.f;
 #pragma unroll
                 for (int off = 16; off >= 1; off >>= 1) tn = fmaxf(tn, __shfl_xor(tn, off, 64));
+                const int usable = __popcll(__ballot(lane < kPoolRows && id >= 0 && hole == 0));
                 if (lane < kPoolRows) { ps.key[slot] = key; ps.id[slot] = id; ps.sn[slot] = sn; ps.hole[slot] = hole; }
-                if (lane == 0) ps.tsn[(size_t)c * B + h] = tn;
+                if (lane == 0) { ps.tsn[(size_t)c * B + h] = tn; ps.ok[(size_t)c * B + h] = usable; }
             }
         }
     }
@@ -2592,12 +2661,12 @@ void launch_pack_state_build(const PackState &ps, const MemberPack &P, const uns
 
 void launch_pack_state_start(const PackState &ps, const MemberPack &P, int D, int Dz, const int *labels, int *inb,
                              const int *open_bq, int open_K, int *open_lab_old, int B, const SegPlan *seg, int *stats,
-                             int *zero_me, hipStream_t s)
+                             int *zero_me, int *zero_me2, hipStream_t s)
 {
     if (B <= 0) return;
     const int nopen = (open_K + 255) / 256;
     hipLaunchKernelGGL(pack_state_start_kernel, dim3(1 + nopen), dim3(256), (size_t)B * sizeof(int), s, ps, P, D, Dz, labels,
-                       inb, open_bq, open_K, open_lab_old, B, seg ? *seg : SegPlan{}, stats, zero_me, g_gate);
+                       inb, open_bq, open_K, open_lab_old, B, seg ? *seg : SegPlan{}, stats, zero_me, zero_me2, g_gate);
 }
 
 void launch_pack_state_commit(const PackState &ps, const MemberPack &P, const double *X, int D, int Dp, const int *ids, int n,
@@ -2626,9 +2695,9 @@ void launch_pool_build(const PoolState &ps, const unsigned short *Zs, const void
     if (B <= 0) return;
     int hb = 1;
     const int hy = pool_home_blocks(B, &hb);
-    hipLaunchKernelGGL((pool_update_kernel<true>), dim3(B, hy), dim3(256), 0, s, ps, Zs, reinterpret_cast<const float4 *>(ms),
-                       reinterpret_cast<const float2 *>(qn), D, Dz, B, hb, memb_id, bin_ptr, nullptr, 0, nullptr, nullptr, nullptr, 0,
-                       g_gate);
+    hipLaunchKernelGGL((pool_update_kernel<true, false>), dim3(B, hy), dim3(256), 0, s, ps, PackState{}, Zs,
+                       reinterpret_cast<const float4 *>(ms), reinterpret_cast<const float2 *>(qn), D, Dz, B, hb, memb_id, bin_ptr,
+                       nullptr, 0, nullptr, nullptr, nullptr, 0, g_gate);
 }
 
 void launch_pool_open(const PoolState &ps, const int *inb, int D, int Dz, int B, int *zero_me, hipStream_t s)
@@ -2641,14 +2710,55 @@ void launch_pool_open(const PoolState &ps, const int *inb, int D, int Dz, int B,
 
 void launch_pool_commit(const PoolState &ps, const unsigned short *Zs, const void *ms, const void *qn, int D, int Dz,
                         const int *ids, int n, const int *new_lab, const int *lab_old, const int *labels, int B, bool holes,
-                        hipStream_t s)
+                        const PackState *pack, hipStream_t s)
 {
     if (B <= 0 || n <= 0) return;
     int hb = 1;
     const int hy = pool_home_blocks(B, &hb);
-    hipLaunchKernelGGL((pool_update_kernel<false>), dim3(B, hy), dim3(256), 0, s, ps, Zs, reinterpret_cast<const float4 *>(ms),
-                       reinterpret_cast<const float2 *>(qn), D, Dz, B, hb, nullptr, nullptr, ids, n, new_lab, lab_old, labels,
-                       holes ? 1 : 0, g_gate);
+    if (pack != nullptr)   // (the arrivals from the tails of the pack's regions)
+        hipLaunchKernelGGL((pool_update_kernel<false, true>), dim3(B, hy), dim3(256), 0, s, ps, *pack, Zs,
+                           reinterpret_cast<const float4 *>(ms), reinterpret_cast<const float2 *>(qn), D, Dz, B, hb, nullptr, nullptr,
+                           ids, n, new_lab, lab_old, labels, holes ? 1 : 0, g_gate);
+    else                   // (... or looked for in the batch's labels)
+        hipLaunchKernelGGL((pool_update_kernel<false, false>), dim3(B, hy), dim3(256), 0, s, ps, PackState{}, Zs,
+                           reinterpret_cast<const float4 *>(ms), reinterpret_cast<const float2 *>(qn), D, Dz, B, hb, nullptr, nullptr,
+                           ids, n, new_lab, lab_old, labels, holes ? 1 : 0, g_gate);
+}
+
+// one wavefront per pool, lanes 0 .. 31 = its slots
+static __global__ __launch_bounds__(256) void pool_check_kernel(PoolState ps, const unsigned short *Zs, const float2 *qn, const int *labels,
+                                                         int N, int Dz, int B, int *bad)
+{
+    const long long pool = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pool >= (long long)B * B) return;
+    const int lane = threadIdx.x & 63;
+    const int c = (int)(pool / B), h = (int)(pool - (long long)c * B);
+    const size_t slot = (size_t)pool * kPoolRows + (size_t)(lane & 31);
+    bool usable = false, wrong = false;
+    if (lane < kPoolRows) {
+        const int id = ps.id[slot];
+        usable = id >= 0 && ps.hole[slot] == 0;
+        if (usable && id >= N) wrong = true;
+        else if (usable) {
+            wrong = labels[id] != c || ps.key[slot] != qn[(size_t)id * B + h].x || !(ps.tsn[pool] >= ps.sn[slot]);
+            for (int cc = 0; cc < (Dz >> 3); ++cc) {
+                const uint4 a = *reinterpret_cast<const uint4 *>(ps.Z + slot * Dz + cc * 8);
+                const uint4 b = *reinterpret_cast<const uint4 *>(Zs + (size_t)id * Dz + cc * 8);
+                wrong = wrong || a.x != b.x || a.y != b.y || a.z != b.z || a.w != b.w;
+            }
+        }
+    }
+    const int nbad = __popcll(__ballot(wrong)) + (__popcll(__ballot(usable)) != ps.ok[pool] ? 1 : 0);
+    if (lane == 0 && nbad > 0) atomicAdd(bad, nbad);
+}
+
+void launch_pool_check(const PoolState &ps, const unsigned short *Zs, const void *qn, const int *labels, int N, int Dz, int B,
+                       int *bad, hipStream_t s)
+{
+    const long long npool = (long long)B * B;
+    if (npool > 0)
+        hipLaunchKernelGGL(pool_check_kernel, dim3((unsigned)((npool + 3) / 4)), dim3(256), 0, s, ps, Zs,
+                           reinterpret_cast<const float2 *>(qn), labels, N, Dz, B, bad);
 }
 
 void launch_shortlist_worklist(const ShortlistArgs &a_, int *flags64, hipStream_t s)

@@ -425,7 +425,11 @@ int chb_fit_stats(chb_ctx *h, int64_t *out4);
  * and kept: on one GPU and, since round 4, under the RCCL exchange), "lookahead_failed" (... and discarded because the
  * batch needed further rounds), "pool_batches" (batches of the last fit whose base shortlist launch took its thresholds
  * from the pools), "pool_state" (0 undecided = on, 1 kept on, -1 turned off because the shortlists came out long),
- * "pool_candidates" / "pool_pairs" (sampled shortlist lengths behind that decision), "exchanges" (framed all-gathers of the last fit under an exchange: one per batch for the
+ * "pool_candidates" / "pool_pairs" (sampled shortlist lengths behind that decision), "pool_bad_slots" (for tests, while no
+ * batch is open: slots of the last fit's pools that are not what the shortlist kernel relies on -- a usable slot of pool
+ * (bin, home) holds a sample labelled with the bin, that sample's shadow row and key, under the tile's norm bound -- plus pools
+ * whose count of usable rows is off; 0 without pools), "pack_region_moves" (regions of the persistent pack that ran full and
+ * moved in the last fit), "exchanges" (framed all-gathers of the last fit under an exchange: one per batch for the
  * label guess, one per round), "recruit_chunk" (rows per launch of chb_recruit_rows, chb_audit_rows and -- at most -- chb_bin_report: a constant),
  * "recruit_multi_rows" (rows per launch of the last chb_audit_rows_multi / chb_recruit_rows_multi call: 16384 / nm rounded
  * down to a multiple of 64; 0 before the first), "pair_tiles" (tiles of at most 64 pairs of one bin -- the kernel's work
