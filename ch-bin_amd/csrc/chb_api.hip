@@ -177,6 +177,7 @@ struct Switches {
     bool force_gather = false;    // CHB_FORCE_GATHER=1: run the exchange path even with one rank (tests)
     bool allow_segments = true;   // CHB_SEGMENTS=0: never (A/B tests)
     bool fused_stripe = true;     // CHB_FUSED_STRIPE=0: position-major work order in the fused kernels
+    bool fused_trim = true;       // CHB_FUSED_TRIM=0: the m <= 5 fused kernel gathers every candidate of a wide shortlist
     bool pp_allowed = true;       // CHB_PACK_INCR=0: every batch start rebuilds CSR and pack (the form up to round 3; A/B tests)
     bool pool_allowed = true, pool_force = false;   // CHB_POOL_TAU=0: a bin always streamed twice; =2: pools whatever the size
     bool allow_skip = true;       // CHB_TILE_SKIP=0: never (A/B tests)
@@ -385,6 +386,9 @@ struct chb_ctx {
     // the shortlist stage's contract as checked by the fused kernels (FusedArgs::short_cnt): pairs of this fit whose base
     // shortlist held fewer than min(m, bin size) candidates or a wild index -- any is an internal error of the fit
     DevBuf<int> short_cnt;
+    // the m <= 5 fused kernel's trim (FusedArgs::trim_ctr): pairs trimmed in this fit, their candidates before and after
+    DevBuf<unsigned long long> trim_ctr;
+    DevBuf<TrimArgs> trim_args;   // (written with the global shadows: samples_finish)
     // scratch for the indexed / explicit-point entry points
     DevBuf<int> xq, xhull, xcnt;
     DevBuf<double> xdist, xalpha, xpts;
@@ -451,6 +455,8 @@ struct chb_ctx {
         FusedArgs a{};
         a.X = X.p; a.n_samples = N; a.D = D; a.Dp = Dp; a.bq = batch.bq_cur; a.pos_begin = lo; a.pos_end = hi;
         a.B = B; a.m = m; a.Kcap = Kcap; a.dist = dist.p; a.metric = metric;
+        // (the trim sweeps one 160-column slice of the global shadows at the most)
+        if (sw.fused_trim && shadow_ok && Dz <= 160 && D + 3 <= 160) a.trim = trim_args.p;
         return a;
     }
 };
@@ -671,6 +677,7 @@ int fit_begin_impl(chb_ctx *h, int64_t B, const int64_t *initial, int m, bool sy
     h->fit_open = true; h->batch.open = false; h->Kcap = 0;
     h->overflow_total_valid = false;
     if (h->short_cnt.p) HIPCHK(hipMemsetAsync(h->short_cnt.p, 0, sizeof(int), h->stream));
+    if (h->trim_ctr.p) HIPCHK(hipMemsetAsync(h->trim_ctr.p, 0, 3 * sizeof(unsigned long long), h->stream));
     h->pp.fit_reset();
     if (h->pp.ctl.p) HIPCHK(hipMemsetAsync(h->pp.ctl.p, 0, 4 * sizeof(int), h->stream));
     return CHB_OK;
@@ -772,6 +779,7 @@ void read_switches(chb_ctx *h)
     flag("CHB_FORCE_GATHER", w.force_gather);
     flag("CHB_SEGMENTS", w.allow_segments);
     flag("CHB_FUSED_STRIPE", w.fused_stripe);
+    flag("CHB_FUSED_TRIM", w.fused_trim);
     flag("CHB_PACK_INCR", w.pp_allowed);
     flag("CHB_TILE_SKIP", w.allow_skip);
     if (const char *e = getenv("CHB_POOL_TAU")) { w.pool_allowed = atoi(e) != 0; w.pool_force = atoi(e) == 2; }
@@ -1970,6 +1978,12 @@ static int samples_finish(chb_ctx *h)
         launch_global_shadow(h->X.p, (int)N, (int)D, Dp, h->mu_g.p, S, h->Gs.p, Dz, h->gq.p, h->stream);
         HIPCHK(hipGetLastError());
         h->Dz = Dz;
+        // the m <= 5 fused kernel's view of these rows (FusedArgs::trim)
+        HIPCHK(h->trim_ctr.ensure_zeroed(3, h->stream));
+        HIPCHK(h->trim_args.ensure(1));
+        const TrimArgs ta{h->Gs.p, reinterpret_cast<const float2 *>(h->gq.p), Dz, h->trim_ctr.p};
+        HIPCHK(hipMemcpyAsync(h->trim_args.p, &ta, sizeof(ta), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));   // (ta is a local)
         h->shadow_ok = true;
     }
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -3360,6 +3374,17 @@ int chb_counter(chb_ctx *h, const char *name, int64_t *out)
     if (!strcmp(name, "pack_region_moves")) return read_device_int(h, h->pp.ctl.p ? h->pp.ctl.p + 3 : nullptr, out);
     // pairs the fused kernel left to the exact path
     if (!strcmp(name, "slow_pairs_last_round")) return read_device_int(h, h->fused ? h->n_slow.p : nullptr, out);
+    // the m <= 5 fused kernel's trim in the last fit: pairs it swept, their candidates before and after
+    for (int i = 0; i < 3; ++i)
+        if (!strcmp(name, i == 0 ? "fused_trim_pairs" : i == 1 ? "fused_trim_in" : "fused_trim_kept")) {
+            unsigned long long v = 0;
+            if (h->fused && h->trim_ctr.p) {
+                HIPCHK(hipMemcpyAsync(&v, h->trim_ctr.p + i, sizeof(v), hipMemcpyDeviceToHost, h->stream));
+                HIPCHK(hipStreamSynchronize(h->stream));
+            }
+            *out = (int64_t)v;
+            return CHB_OK;
+        }
     // "shortlist_le<N>_last_batch": pairs of the last batch with <= N candidates
     const bool sum = !strcmp(name, "shortlist_sum_last_batch"), le = !strncmp(name, "shortlist_le", 12);
     if (sum || le || !strcmp(name, "shortlist_max_last_batch")) {

@@ -333,6 +333,17 @@ struct FusedArgs {
     const int *bin_ptr = nullptr;
     const int *bin_size = nullptr;   // (instead of bin_ptr: the members of each bin, [B] -- the persistent base pack's live counts)
     int *short_cnt = nullptr;
+    // the trim of the m <= 5 kernel (qp_kernels.hip, "Trim"), in device memory; nullptr: no trim (CHB_FUSED_TRIM=0, no
+    // valid shadows, or rows of more than one 160-column slice).  Behind a pointer so that the kernel loads these words
+    // where the trim runs: as arguments they would sit in scalar registers from the kernel's start to its end
+    const struct TrimArgs *trim = nullptr;
+};
+// the global fp16 shadow rows of all samples (prefilter_kernels.hip), as the trim reads them
+struct TrimArgs {
+    const unsigned short *Gs;   // [n_samples][Dz]
+    const float2 *gq;           // [n_samples]: {||Gs[p]||^2 rounded up, rho_p rounded up}
+    int Dz;
+    unsigned long long *ctr;    // [3]: pairs trimmed, their candidates before, after (summed over the fit)
 };
 // false: not supported by the fused kernels (caller uses the list-based path): m <= 16, padded rows of at most
 // kFusedMaxDp doubles (the 16-lane kernel stages the query row in LDS)

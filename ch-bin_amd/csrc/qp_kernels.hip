@@ -538,6 +538,68 @@ __device__ __forceinline__ double diag_rows8(const double *X, int Dp, int Dk, in
     return reduce_scatter16(acc, l16);
 }
 
+// Trim.  A pair with more than C candidates costs the kernel a distance sweep over up to 16 fp64 rows (or the exact path,
+// above 16) although only the m nearest of them enter the hull.  Where the fit has global shadow rows (prefilter_kernels.hip;
+// TrimArgs: Gs[p] = fp16((x_p - mu_g) S), gq[p] = {N_p = ||Gs[p]||^2 rounded up, rho_p = ||Gs[p] - (x_p - mu_g) S|| rounded
+// up}) such a pair of up to kTrimMax candidates is cut down BEFORE any fp64 row of a candidate is read.  The triangle
+// inequality alone gives, for query j and candidate p,
+//     sqrt(T) - rho_j - rho_p <= S d(j, p) <= sqrt(T) + rho_j + rho_p,     T = ||Gs[j] - Gs[p]||^2 = N_j + N_p - 2 <Gs[j], Gs[p]>
+// -- no bias pieces, no tile terms, no per-bin bounds.  The dot product comes from v_dot2_f32_f16 (fp16 products are exact in
+// fp32) summed in fp32 and, over the 16 lanes, in fp64; the computed T is within
+//     E = 2 g sqrt(N_j N_p) + 2^-23 (N_j + N_p) + 2^-13 sqrt(D) (sqrt(N_j) + sqrt(N_p)) + D 2^-27
+// of the exact one: g = 2.5e-5 bounds the fp32 summation of up to 161 terms in any order (Cauchy-Schwarz on the sum of the
+// terms' magnitudes; the constant of prefilter_kernels.hip), the second term the stored norms' rounding, the last two a
+// flush of fp16 subnormals to zero, should the instruction do that.  So LB = sqrt(max(T - E, 0)) - rho_j - rho_p and
+// UB = sqrt(T + E) + rho_j + rho_p.  tau_u = the m-th smallest UB among the pair's candidates: m of them are provably within
+// tau_u, so the m-th distance of the union is at most tau_u / S.  Candidate p is dropped only if LB_p > tau_u (1 + kTrimSlack)
+// holds; a NaN or infinite bound anywhere in the pair keeps all of it.
+// Guarantee.  Every candidate within 1e-6 relative of the union's m-th distance survives (the fp64 rounding of the bound
+// arithmetic, ~1e-15 relative, comes out of that slack).  That covers the m nearest, and any (m+1)-th candidate that the
+// kTieRel = 1e-11 test could call a tie of the m-th.  So the selected set, the tie hand-off to the exact path and the hull's
+// vertex set are what they are without the trim; only the slot a Gram entry is summed in can differ (its last bit).
+// A pair keeps its survivors (at most kTrimKeep, in shortlist order) in LDS and is classed by their number; one with more
+// survivors stays as it was.
+constexpr int kTrimMax = 32;     // two candidates per lane of a 16-lane group
+constexpr int kTrimKeep = 8;     // ids per pair in LDS
+constexpr int kNbTrimmed = -1;   // base count of a trimmed pair in the passes: its ids come from the LDS list
+constexpr double kTrimSlack = 1e-6;
+constexpr double kTrimGamma = 2.5e-5;   // fp32 summation of up to 161 terms (kGamma of prefilter_kernels.hip)
+
+// The columns of a lane in a shadow sweep (rows of up to 160 columns): the 8 from 8 * l16 on (one 16-byte load) and the 2
+// from 128 + 2 * l16 on (one 4-byte load; clamped to the row's last pair, which the mask then clears).
+__device__ __forceinline__ int trim_tail_col(int l16) { return 128 + 2 * l16; }
+
+// <Gs[j], Gs[p]> of the first nmax (uniform) of 16 candidates: candidate v of every 16-lane group is the one lane gbase + v
+// holds in `ids` (none: the query's own row is read, the value is not used); qm / qt = the lane's 10 columns of the query's
+// row, the halves from column D on cleared (there the rows carry the shortlist kernels' bias constants).  On return lane l16
+// holds the product of candidate l16.
+__device__ __forceinline__ double shadow_dot16(const unsigned short *Gs, int Dz, int qid, int ids, int nmax, int gbase, int l16,
+                                               const uint4 &qm, unsigned qt)
+{
+    using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
+    auto dot2 = [](unsigned x, unsigned y, float c) {
+        return __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2, x), __builtin_bit_cast(f16x2, y), c, false);
+    };
+    const int tcol = min(trim_tail_col(l16), Dz - 2);
+    double acc[16];
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[v] = 0.0;
+#pragma unroll
+    for (int v0 = 0; v0 < 16; v0 += 4) {
+        if (v0 < nmax) {
+#pragma unroll
+            for (int v = v0; v < v0 + 4; ++v) {
+                const int idv = __shfl(ids, gbase + v, 64);
+                const unsigned short *row = Gs + (size_t)(idv >= 0 ? idv : qid) * Dz;
+                const uint4 u = *reinterpret_cast<const uint4 *>(row + 8 * l16);   // (8 * l16 + 8 <= 128 < Dz)
+                const unsigned ut = *reinterpret_cast<const unsigned *>(row + tcol);
+                acc[v] = (double)dot2(ut, qt, dot2(u.w, qm.w, dot2(u.z, qm.z, dot2(u.y, qm.y, dot2(u.x, qm.x, 0.f)))));
+            }
+        }
+    }
+    return reduce_scatter16(acc, l16);
+}
+
 // Work order of the m <= 5 fused kernel.  STRIPED (a.stripe != 0, B >= 16): consecutive workgroups go round-robin over the
 // 8 XCDs, each with its own L2; workgroup b (XCD b % 8) only takes pairs of the bins c = b % 8 (mod 8), walked position-major
 // over that bin subset (64 consecutive pairs per wavefront = 64 / nbx positions x the XCD's nbx bins).  The candidate rows an
@@ -577,12 +639,16 @@ __global__ __launch_bounds__(64 * WAVES, CHB_FUSED_OCC) void hull_select_qp_kern
     __shared__ int sN[WAVES][64];
     __shared__ int sOrd[WAVES][64];            // problem (lane) of each work position, narrow shortlists first
     __shared__ int sSlowN, sSlowBase;
+    __shared__ int sTrim[WAVES][64][kTrimKeep];   // the survivors of a trimmed pair (see "Trim" above)
+    __shared__ int sTrimN[WAVES][64];             // ... their number; 0: the pair is not trimmed
+    __shared__ int sTrimCtr[3];                   // pairs through the trim, their candidates before and after
 
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int grp = lane >> 4, l16 = lane & 15, gbase = lane & 48;
     const int m = a.m;
     const int Dk = (a.D + 7) & ~7;   // columns swept (the rows are padded to whole 128-byte lines beyond)
     if (threadIdx.x == 0) sSlowN = 0;
+    if (threadIdx.x < 3) sTrimCtr[threadIdx.x] = 0;
     __syncthreads();
     // (striped: the wavefront's place in its XCD's own pair list; nprob is then the length of the longest of the 8 lists)
     const int g0 = ((a.stripe ? (int)(blockIdx.x >> 3) : (int)blockIdx.x) * WAVES + w) * 64;
@@ -623,7 +689,114 @@ __global__ __launch_bounds__(64 * WAVES, CHB_FUSED_OCC) void hull_select_qp_kern
             const unsigned long long shm = __ballot(sh);
             if (shm != 0ull && lane == 0) atomicAdd(a.short_cnt, __popcll(shm));
         }
-        const int n = nb + nu;
+        int n = nb + nu;
+        // ---- trim (see "Trim" above): pairs with C < n <= kTrimMax, 16 lanes per pair, four pairs per pass, before any
+        // fp64 row of a candidate is read; the classes below then see the survivors.  A loop of its own.
+        if (a.trim != nullptr) {
+            const bool tr = changed && n > C && n <= kTrimMax;
+            const unsigned long long tmask = __ballot(tr);
+            const int ntrim = __popcll(tmask);
+            if (ntrim > 0) {
+                sTrimN[w][lane] = 0;
+                if (tr) sOrd[w][__popcll(tmask & ((1ull << lane) - 1ull))] = lane;   // (sOrd: rebuilt below)
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_s_waitcnt(0xC07F);
+                const TrimArgs ta = *a.trim;
+                // (masks by shifts: compares would hold one lane mask each in scalar registers through the loop)
+                auto mask32 = [](int nv) { return (unsigned)((1ull << min(max(16 * nv, 0), 32)) - 1ull); };   // nv columns below D
+                const int nv = a.D - 8 * l16;
+                const uint4 msk{mask32(nv), mask32(nv - 2), mask32(nv - 4), mask32(nv - 6)};
+                const unsigned mskt = mask32(a.D - trim_tail_col(l16));
+                int c_pairs = 0, c_in = 0, c_kept = 0;
+                for (int p0 = 0; p0 < ntrim; p0 += 4) {
+                    const int op = p0 + grp;
+                    const bool has = op < ntrim;
+                    const int pl = has ? sOrd[w][op] : 0;
+                    const int n_s = __shfl(n, pl, 64);
+                    const int n_g = has ? n_s : 0;
+                    const int nb_g = __shfl(nb, pl, 64);
+                    const int qid_g = __shfl(qid, pl, 64);
+                    const size_t slot_g = (size_t)__shfl(c, pl, 64) * a.Kcap + (size_t)__shfl(pos, pl, 64);
+                    // candidates l16 and 16 + l16 of the group's pair
+                    int id0 = -1, id1 = -1;
+                    if (l16 < n_g)
+                        id0 = l16 < nb_g ? a.cand[slot_g * kCandCap + l16] : a.candu[slot_g * kCandCapU + (l16 - nb_g)];
+                    if (16 + l16 < n_g)
+                        id1 = 16 + l16 < nb_g ? a.cand[slot_g * kCandCap + 16 + l16] : a.candu[slot_g * kCandCapU + (16 + l16 - nb_g)];
+                    bool bad = false;   // a wild index: the pair stays as it is (the passes below count it)
+                    if ((unsigned)id0 >= (unsigned)a.n_samples && id0 != -1) { bad = true; id0 = -1; }
+                    if ((unsigned)id1 >= (unsigned)a.n_samples && id1 != -1) { bad = true; id1 = -1; }
+                    int nmax = n_g;
+                    nmax = max(nmax, __shfl_xor(nmax, 16, 64));
+                    nmax = max(nmax, __shfl_xor(nmax, 32, 64));
+                    nmax = __builtin_amdgcn_readfirstlane(nmax);
+                    // the lane's columns of the query's own shadow row, its norm and radius
+                    const unsigned short *qrow = ta.Gs + (size_t)qid_g * ta.Dz;
+                    uint4 qm = *reinterpret_cast<const uint4 *>(qrow + 8 * l16);
+                    qm.x &= msk.x; qm.y &= msk.y; qm.z &= msk.z; qm.w &= msk.w;
+                    const unsigned qt = *reinterpret_cast<const unsigned *>(qrow + min(trim_tail_col(l16), ta.Dz - 2)) & mskt;
+                    const float2 gj = ta.gq[qid_g];
+                    const bool in0 = id0 >= 0, in1 = id1 >= 0;
+                    const float2 g0 = ta.gq[in0 ? id0 : qid_g], g1 = ta.gq[in1 ? id1 : qid_g];
+                    const double dot0 = shadow_dot16(ta.Gs, ta.Dz, qid_g, id0, nmax, gbase, l16, qm, qt);
+                    double dot1 = 0.0;
+                    if (nmax > 16) dot1 = shadow_dot16(ta.Gs, ta.Dz, qid_g, id1, nmax - 16, gbase, l16, qm, qt);
+                    // the bounds (see "Trim")
+                    const double Nj = (double)gj.x, sNj = sqrt(Nj), flush = 0x1p-13 * sqrt((double)a.D);
+                    auto bounds = [&](double dot, float2 gp, double &lo, double &hi) {
+                        const double Np = (double)gp.x, sNp = sqrt(Np), rho = (double)gj.y + (double)gp.y;
+                        const double T = Nj + Np - 2.0 * dot;
+                        const double E = 2.0 * kTrimGamma * sNj * sNp + 0x1p-23 * (Nj + Np) + flush * (sNj + sNp) + 0x1p-27 * (double)a.D;
+                        lo = sqrt(fmax(T - E, 0.0)) - rho;
+                        hi = sqrt(T + E) + rho;
+                    };
+                    double lo0, lo1, hi0, hi1;
+                    bounds(dot0, g0, lo0, hi0);
+                    bounds(dot1, g1, lo1, hi1);
+                    if (!in0) hi0 = kInf;
+                    if (!in1) hi1 = kInf;
+                    bad = bad || (in0 && !(hi0 < kInf)) || (in1 && !(hi1 < kInf));   // NaN or infinite: no bound, keep everything
+                    // tau_u: the upper bound of rank m - 1 by (bound, slot)
+                    int rank0 = 0, rank1 = 0;
+#pragma unroll
+                    for (int u = 0; u < 16; ++u) {
+                        const double hu = __shfl(hi0, gbase + u, 64);
+                        rank0 += (hu < hi0 || (hu == hi0 && u < l16)) ? 1 : 0;
+                        rank1 += hu <= hi1 ? 1 : 0;
+                    }
+                    if (nmax > 16) {
+#pragma unroll
+                        for (int u = 0; u < 16; ++u) {
+                            const double hu = __shfl(hi1, gbase + u, 64);
+                            rank0 += hu < hi0 ? 1 : 0;
+                            rank1 += (hu < hi1 || (hu == hi1 && u < l16)) ? 1 : 0;
+                        }
+                    }
+                    double tau = (in0 && rank0 == m - 1) ? hi0 : (in1 && rank1 == m - 1) ? hi1 : kInf;
+#pragma unroll
+                    for (int off = 1; off < 16; off <<= 1) tau = fmin(tau, __shfl_xor(tau, off, 64));
+                    const double lim = tau * (1.0 + kTrimSlack);
+                    const bool k0 = in0 && !(lo0 > lim), k1 = in1 && !(lo1 > lim);   // (a NaN keeps the candidate)
+                    const unsigned badm = (unsigned)(__ballot(bad) >> gbase) & 0xffffu;
+                    const unsigned b0 = (unsigned)(__ballot(k0) >> gbase) & 0xffffu, b1 = (unsigned)(__ballot(k1) >> gbase) & 0xffffu;
+                    const int nk = badm != 0u ? n_g : __popc(b0) + __popc(b1);
+                    if (has && badm == 0u && nk <= kTrimKeep) {
+                        if (k0) sTrim[w][pl][__popc(b0 & ((1u << l16) - 1u))] = id0;
+                        if (k1) sTrim[w][pl][__popc(b0) + __popc(b1 & ((1u << l16) - 1u))] = id1;
+                        if (l16 == 0) sTrimN[w][pl] = nk;
+                    }
+                    if (has && l16 == 0) { c_pairs += 1; c_in += n_g; c_kept += nk; }
+                }
+                c_pairs += __shfl_xor(c_pairs, 16, 64); c_pairs += __shfl_xor(c_pairs, 32, 64);
+                c_in += __shfl_xor(c_in, 16, 64); c_in += __shfl_xor(c_in, 32, 64);
+                c_kept += __shfl_xor(c_kept, 16, 64); c_kept += __shfl_xor(c_kept, 32, 64);
+                if (lane == 0) { atomicAdd(&sTrimCtr[0], c_pairs); atomicAdd(&sTrimCtr[1], c_in); atomicAdd(&sTrimCtr[2], c_kept); }
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_s_waitcnt(0xC07F);
+                const int nt = sTrimN[w][lane];
+                if (nt > 0) { n = nt; nb = kNbTrimmed; }
+            }
+        }
         // class 0: nothing to compute here.  Classes 1 .. NCLS: ONE sweep over max(n, M) = M + k - 1 candidate
         // rows (full candidate Gram).  Class NCLS + 1 (C < n <= 16): a distance sweep over all candidates,
         // then a second sweep over the m selected rows (just read: they come out of L1 / L2).
@@ -659,7 +832,8 @@ __global__ __launch_bounds__(64 * WAVES, CHB_FUSED_OCC) void hull_select_qp_kern
             const size_t slot_g = (size_t)__shfl(c, pl, 64) * a.Kcap + (size_t)__shfl(pos, pl, 64);
             int idm = -1;
             if (l16 < n_g)
-                idm = l16 < nb_g ? a.cand[slot_g * kCandCap + l16] : a.candu[slot_g * kCandCapU + (l16 - nb_g)];
+                idm = nb_g == kNbTrimmed ? sTrim[w][pl][l16]
+                      : l16 < nb_g ? a.cand[slot_g * kCandCap + l16] : a.candu[slot_g * kCandCapU + (l16 - nb_g)];
             if ((unsigned)idm >= (unsigned)a.n_samples && idm != -1) {   // never a row address from a wild index
                 if (a.short_cnt != nullptr) atomicAdd(a.short_cnt, 1);
                 idm = -1;
@@ -741,7 +915,8 @@ __global__ __launch_bounds__(64 * WAVES, CHB_FUSED_OCC) void hull_select_qp_kern
             const size_t slot_g = (size_t)__shfl(c, pl, 64) * a.Kcap + (size_t)__shfl(pos, pl, 64);
             int idm = -1;
             if (l16 < n_g)
-                idm = l16 < nb_g ? a.cand[slot_g * kCandCap + l16] : a.candu[slot_g * kCandCapU + (l16 - nb_g)];
+                idm = nb_g == kNbTrimmed ? sTrim[w][pl][l16]
+                      : l16 < nb_g ? a.cand[slot_g * kCandCap + l16] : a.candu[slot_g * kCandCapU + (l16 - nb_g)];
             if ((unsigned)idm >= (unsigned)a.n_samples && idm != -1) {   // never a row address from a wild index
                 if (a.short_cnt != nullptr) atomicAdd(a.short_cnt, 1);
                 idm = -1;
@@ -823,6 +998,9 @@ __global__ __launch_bounds__(64 * WAVES, CHB_FUSED_OCC) void hull_select_qp_kern
     if (lane == 0 && nsl > 0) wbase = atomicAdd(&sSlowN, nsl);
     __syncthreads();
     if (threadIdx.x == 0) sSlowBase = sSlowN > 0 ? atomicAdd(a.n_slow, sSlowN) : 0;
+    // (the trim's three counters, by three lanes at once)
+    if (threadIdx.x < 3 && a.trim != nullptr && sTrimCtr[0] > 0)
+        atomicAdd(a.trim->ctr + threadIdx.x, (unsigned long long)sTrimCtr[threadIdx.x]);
     __syncthreads();
     wbase = __shfl(wbase, 0, 64) + sSlowBase;
     if (nsl > 0 && ((sm >> lane) & 1ull)) {

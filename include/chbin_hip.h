@@ -27,6 +27,8 @@
  *       CHB_FORCE_GATHER=1  exchange path of the sharded loop even with one rank
  *       CHB_SEGMENTS=0      bins far larger than the rest are never cut into segments for the shortlist stage
  *       CHB_FUSED_STRIPE=0  position-major work order in the fused kernels (default: striped over the XCDs by bin)
+ *       CHB_FUSED_TRIM=0    the m <= 5 fused kernel gathers every candidate of a shortlist of more than 7 (default: such a
+ *                           shortlist of up to 32 is first cut down by fp16 bounds from the samples' global shadow rows)
  *       CHB_PACK_INCR=0     CSR and member pack of the shortlist stage rebuilt from the labels at every batch start (default:
  *                           kept across the batches of a fit and updated by each commit, where tiles are not skipped)
  *       CHB_POOL_TAU=0      the base shortlist launch always streams a bin twice (threshold sweep + admission sweep); default:
@@ -418,6 +420,8 @@ int chb_fit_stats(chb_ctx *h, int64_t *out4);
  * "tile_skip_state" (tile skipping of the last fit: 0 undecided, 1 kept on, -1 turned off because next to nothing could be
  * skipped), "tile_skipped" / "tile_seen" / "tile_unloaded" (wave-tiles whose compute was skipped / that were met / that
  * were never loaded, as sampled by about 64 workgroups of each base shortlist launch, a batch's launch counted once),
+ * "fused_trim_pairs" / "fused_trim_in" / "fused_trim_kept" ((position, bin) pairs of the last fit whose shortlist the
+ * m <= 5 fused kernel trimmed, rounds of a batch counted each; their candidates before and after),
  * "shortlist_short" ((position, bin) pairs of the last fit whose base shortlist reached the hull kernels with fewer than
  * min(num_neighbors, members of the bin) candidates or with a wild index: always 0, or chb_fit_cluster has returned
  * CHB_ESTATE at the end of that sweep -- the product build checks the shortlist stage's contract in every fused hull
