@@ -54,6 +54,15 @@ SIGNATURES = {
                                   C.c_void_p]),
     "chb_recruit_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
                                     C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    # the leave-group-out forms: the ungrouped call's arguments with `groups` after `labels`
+    "chb_audit_rows_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "chb_audit_rows_multi_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
+                                               C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "chb_audit_pairs_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_int64, C.c_void_p]),
+    "chb_bin_report_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "chb_find_nearest_from_row": (C.c_int, [C.c_void_p, C.c_int64, _i64p, _f64p, C.c_int64, C.c_int,
                                             _i64p, C.POINTER(C.c_int32)]),
     "chb_hull_distance_batch": (C.c_int, [C.c_void_p, _i64p, C.c_int64, _i64p, C.c_int, _f64p,
@@ -220,9 +229,18 @@ class Context:
             raise ValueError("rows must be a 1-D array of sample indices")
         return rows.ctypes.data, rows.shape[0], rows
 
-    def _score_rows(self, name, labels, B, want_dist, m=None, ms=None, rows=None, Y=None):
+    def _groups(self, groups):
+        """The int64 group id per resident sample of a leave-group-out call (negative: no group)."""
+        groups = np.ascontiguousarray(groups, dtype=np.int64)
+        if groups.shape != (self.N,):
+            raise ValueError("groups must have one entry per resident sample")
+        return groups
+
+    def _score_rows(self, name, labels, B, want_dist, m=None, ms=None, rows=None, Y=None, groups=None):
         """The four row-scoring calls: chb_<name>_rows for one m, of the new rows Y or the resident rows `rows`, or with a
-        list `ms` its _multi form, whose outputs carry a leading axis of len(ms)."""
+        list `ms` its _multi form, whose outputs carry a leading axis of len(ms); with `groups` the audit's _grouped form."""
+        if groups is not None and Y is not None:
+            raise ValueError("groups belong to resident samples: rows that are not samples have no siblings to withhold")
         if ms is not None:
             ms = np.ascontiguousarray(ms, dtype=np.intc)
             if ms.ndim != 1:
@@ -241,9 +259,14 @@ class Context:
         dist = np.empty(lead + (Q, int(B)), dtype=np.float64) if want_dist else None
         mind = np.empty(lead + (Q,), dtype=np.float64)
         margin = np.empty(lead + (Q,), dtype=np.float64)
-        fn = getattr(self._lib, f"chb_{name}_rows" if ms is None else f"chb_{name}_rows_multi")
+        fn = f"chb_{name}_rows" if ms is None else f"chb_{name}_rows_multi"
+        grouped = ()
+        if groups is not None:
+            groups = self._groups(groups)
+            fn, grouped = fn + "_grouped", (groups.ctypes.data,)
+        fn = getattr(self._lib, fn)
         neighbours = (int(m),) if ms is None else (ms.ctypes.data, ms.shape[0])
-        check(fn(self._h, labels.ctypes.data, int(B), *neighbours, *source,
+        check(fn(self._h, labels.ctypes.data, *grouped, int(B), *neighbours, *source,
                  bins.ctypes.data, None if dist is None else dist.ctypes.data, mind.ctypes.data, margin.ctypes.data))
         return bins, dist, mind, margin
 
@@ -264,17 +287,32 @@ class Context:
         Returns (bins [nm, Q], dist [nm, Q, B] or None, min_dist [nm, Q], margin [nm, Q])."""
         return self._score_rows("audit", labels, B, want_dist, ms=ms, rows=rows)
 
+    def audit_rows_grouped(self, labels, groups, B, m, rows=None, want_dist=True):
+        """chb_audit_rows_grouped: audit_rows with every sample that shares the scored row's group id withheld as well
+        (leave-group-out; `groups` int64 per resident sample, negative: no group) -- for a row of group g bit for bit
+        audit_rows on `labels` with g's members set to -1.  Returns what audit_rows returns."""
+        return self._score_rows("audit", labels, B, want_dist, m=m, rows=rows, groups=groups)
+
+    def audit_rows_multi_grouped(self, labels, groups, B, ms, rows=None, want_dist=True):
+        """chb_audit_rows_multi_grouped: audit_rows_grouped for every m of the list `ms` from one selection pass."""
+        return self._score_rows("audit", labels, B, want_dist, ms=ms, rows=rows, groups=groups)
+
     def recruit_rows_multi(self, labels, B, ms, Y, want_dist=True):
         """chb_recruit_rows_multi: recruit_rows for every m of the list `ms` from one selection pass; slice j of every
         result is bit for bit recruit_rows(labels, B, ms[j], Y).
         Returns (bins [nm, Q], dist [nm, Q, B] or None, min_dist [nm, Q], margin [nm, Q])."""
         return self._score_rows("recruit", labels, B, want_dist, ms=ms, Y=Y)
 
-    def bin_report(self, labels, B, m, rows=None):
+    def bin_report(self, labels, B, m, rows=None, groups=None):
         """chb_bin_report: chb_audit_rows' answer for the RESIDENT rows `rows` (None: every row in order) summed up on the
-        device per (own bin a, bin b) pair; rows whose own label lies outside [0, B) are not scored.
+        device per (own bin a, bin b) pair; rows whose own label lies outside [0, B) are not scored.  With `groups`
+        chb_bin_report_grouped: the same tables of chb_audit_rows_grouped's answer.
         Returns (confusion [B, B], unplaced [B], dcnt [B, B], dmin [B, B], dsum [B, B], n_skipped)."""
         labels = self._labels(labels)
+        fn, grouped = self._lib.chb_bin_report, ()
+        if groups is not None:
+            groups = self._groups(groups)
+            fn, grouped = self._lib.chb_bin_report_grouped, (groups.ctypes.data,)
         row_idx, Q, rows = self._row_indices(rows)
         B = int(B)
         nb = max(B, 0) if B <= 8192 else 0   # (beyond the limit the call is refused before it writes anything)
@@ -284,10 +322,13 @@ class Context:
         dmin = np.empty((nb, nb), dtype=np.float64)
         dsum = np.empty((nb, nb), dtype=np.float64)
         skipped = C.c_int64(0)
-        check(self._lib.chb_bin_report(self._h, labels.ctypes.data, B, int(m), row_idx, Q, confusion.ctypes.data,
-                                       unplaced.ctypes.data, dcnt.ctypes.data, dmin.ctypes.data, dsum.ctypes.data,
-                                       C.addressof(skipped)))
+        check(fn(self._h, labels.ctypes.data, *grouped, B, int(m), row_idx, Q, confusion.ctypes.data,
+                 unplaced.ctypes.data, dcnt.ctypes.data, dmin.ctypes.data, dsum.ctypes.data, C.addressof(skipped)))
         return confusion, unplaced, dcnt, dmin, dsum, int(skipped.value)
+
+    def bin_report_grouped(self, labels, groups, B, m, rows=None):
+        """chb_bin_report_grouped: bin_report of the leave-group-out distances (audit_rows_grouped)."""
+        return self.bin_report(labels, B, m, rows, groups=groups)
 
     @staticmethod
     def _pair_lists(rows, bins, rows_name):
@@ -300,15 +341,24 @@ class Context:
             raise ValueError(f"{rows_name} and bins must have one entry per pair: {rows.shape[0]} and {bins.shape[0]}")
         return rows, bins
 
-    def audit_pairs(self, labels, B, m, rows, bins):
+    def audit_pairs(self, labels, B, m, rows, bins, groups=None):
         """chb_audit_pairs: dist [P], entry p bit for bit audit_rows(labels, B, m, rows)[1][p, bins[p]] -- the leave-one-out
-        hull distance of the RESIDENT row rows[p] to bin bins[p] -- at the cost of the listed pairs only."""
+        hull distance of the RESIDENT row rows[p] to bin bins[p] -- at the cost of the listed pairs only.  With `groups`
+        chb_audit_pairs_grouped: the same entries of audit_rows_grouped."""
         rows, bins = self._pair_lists(rows, bins, "rows")
         labels = self._labels(labels)
+        fn, grouped = self._lib.chb_audit_pairs, ()
+        if groups is not None:
+            groups = self._groups(groups)
+            fn, grouped = self._lib.chb_audit_pairs_grouped, (groups.ctypes.data,)
         dist = np.empty(rows.shape[0], dtype=np.float64)
-        check(self._lib.chb_audit_pairs(self._h, labels.ctypes.data, int(B), int(m), rows.ctypes.data, bins.ctypes.data,
-                                        rows.shape[0], dist.ctypes.data))
+        check(fn(self._h, labels.ctypes.data, *grouped, int(B), int(m), rows.ctypes.data, bins.ctypes.data,
+                 rows.shape[0], dist.ctypes.data))
         return dist
+
+    def audit_pairs_grouped(self, labels, groups, B, m, rows, bins):
+        """chb_audit_pairs_grouped: audit_pairs of the leave-group-out distances (audit_rows_grouped)."""
+        return self.audit_pairs(labels, B, m, rows, bins, groups=groups)
 
     def recruit_pairs(self, labels, B, m, Y, row_of, bins):
         """chb_recruit_pairs: dist [P], entry p bit for bit recruit_rows(labels, B, m, Y)[1][row_of[p], bins[p]] -- the hull

@@ -9,6 +9,7 @@ from .algorithm import (  # noqa: F401
     cohesion,
     fit_cluster,
     neighbor_sweep,
+    parent_groups,
     recruit,
     recruit_pairs,
 )

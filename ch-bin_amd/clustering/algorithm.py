@@ -105,12 +105,17 @@ def audit(
     qp_solver: str = "quadprog",
     rows: np.ndarray = None,
     return_distances: bool = False,
+    groups: np.ndarray = None,
 ):
     """How well every contig sits in a finished labelling (no counterpart in the reference, which only logs "Exit due to
     max iteration limit": algorithm.py:74-75): for every sample in `rows` (indices into `samples`; None: all of them) the
     step of algorithm.py:49-58 against the frozen `labels` with that sample taken out of its own bin -- per bin the
     `num_neighbors` nearest other members, the distance to their hull, the strict-'>' argmin over the bins.  Seeds,
     unassigned rows and labellings that did not come from fit_cluster are scored alike.  Nothing changes.
+
+    `groups` (one int64 per sample, negative: no group; `parent_groups` makes them from PARENT_NAME) turns leave-one-out
+    into leave-group-out: every sample that shares the scored row's group id -- the sibling pieces preprocess.py:72-101
+    cut from one parent contig -- is withheld from every bin as well, so a piece is no longer vouched for by its siblings.
 
     Returns (bins, min_dist, margin) -- the bin the row would choose now (-1 where no bin has another member), its hull
     distance, and the gap to the runner-up bin (+inf without one) -- and with return_distances also
@@ -123,9 +128,24 @@ def audit(
     ctx = default_context()
     ctx.set_samples_cached(samples)
     with ctx.using_metric(metric):
-        bins, dist, mind, margin = ctx.audit_rows(labels, int(num_clusters), int(num_neighbors), rows,
-                                                  want_dist=return_distances)
+        if groups is None:
+            bins, dist, mind, margin = ctx.audit_rows(labels, int(num_clusters), int(num_neighbors), rows,
+                                                      want_dist=return_distances)
+        else:
+            bins, dist, mind, margin = ctx.audit_rows_grouped(labels, groups, int(num_clusters), int(num_neighbors), rows,
+                                                              want_dist=return_distances)
     return (bins, mind, margin, dist) if return_distances else (bins, mind, margin)
+
+
+def parent_groups(parent_names) -> np.ndarray:
+    """Group ids for the `groups` argument of the audit calls from one name per sample -- features.csv's PARENT_NAME, under
+    which preprocess.py:72-101 files the pieces `<parent>_S<i>` of a long contig: int64 codes by first occurrence, equal
+    names give equal codes.  Every sample gets a group (a contig that was not cut is a group of one, which withholds
+    nothing but the row itself)."""
+    codes, out = {}, np.empty(len(parent_names), dtype=np.int64)
+    for i, name in enumerate(parent_names):
+        out[i] = codes.setdefault(name, len(codes))
+    return out
 
 
 @dataclasses.dataclass
@@ -168,11 +188,13 @@ def bin_report(
     metric: str = "convex",
     qp_solver: str = "quadprog",
     rows: np.ndarray = None,
+    groups: np.ndarray = None,
 ) -> BinReport:
     """Which bins of a finished labelling bleed into each other (no counterpart in the reference): `audit` for the samples
     in `rows` (None: all of them), reduced on the device by each row's own label -- per bin pair how many rows of bin a
     would choose bin b now, and count / minimum / sum of their hull distances to it.  Only the num_clusters x num_clusters
-    tables come back; rows without a label in [0, num_clusters) are not scored.  Nothing changes."""
+    tables come back; rows without a label in [0, num_clusters) are not scored.  Nothing changes.
+    With `groups` the tables are those of the leave-group-out audit (`audit(..., groups=groups)`)."""
     if metric not in ("convex", "affine", "affine-qp"):
         raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
     check_solver(qp_solver)                                              # solve_qp.py:132
@@ -181,7 +203,9 @@ def bin_report(
     ctx = default_context()
     ctx.set_samples_cached(samples)
     with ctx.using_metric(metric):
-        return BinReport(*ctx.bin_report(labels, int(num_clusters), int(num_neighbors), rows))
+        if groups is None:
+            return BinReport(*ctx.bin_report(labels, int(num_clusters), int(num_neighbors), rows))
+        return BinReport(*ctx.bin_report_grouped(labels, groups, int(num_clusters), int(num_neighbors), rows))
 
 
 @dataclasses.dataclass
@@ -230,12 +254,13 @@ def neighbor_sweep(
     qp_solver: str = "quadprog",
     rows: np.ndarray = None,
     return_distances: bool = False,
+    groups: np.ndarray = None,
 ) -> NeighborSweep:
     """Does a finished labelling hold up at other numbers of neighbours (no counterpart in the reference, whose default
     configuration says 5 and whose function default says 15)?  `audit` of the samples in `rows` (None: all of them) for
     every entry of `neighbors` (distinct values in 1 .. 16) at the cost of little more than the audit at the largest: one
     selection pass on the device serves the whole list, and each entry's result is bit for bit what `audit` returns for it.
-    Nothing changes."""
+    Nothing changes.  With `groups` every entry is `audit(..., groups=groups)`: leave-group-out."""
     if metric not in ("convex", "affine", "affine-qp"):
         raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
     check_solver(qp_solver)                                              # solve_qp.py:132
@@ -246,8 +271,12 @@ def neighbor_sweep(
     ctx = default_context()
     ctx.set_samples_cached(samples)
     with ctx.using_metric(metric):
-        bins, dist, mind, margin = ctx.audit_rows_multi(labels, int(num_clusters), neighbors, rows,
-                                                        want_dist=return_distances)
+        if groups is None:
+            bins, dist, mind, margin = ctx.audit_rows_multi(labels, int(num_clusters), neighbors, rows,
+                                                            want_dist=return_distances)
+        else:
+            bins, dist, mind, margin = ctx.audit_rows_multi_grouped(labels, groups, int(num_clusters), neighbors, rows,
+                                                                    want_dist=return_distances)
     scored = np.arange(samples.shape[0], dtype=np.int64) if rows is None else np.ascontiguousarray(rows, dtype=np.int64)
     return NeighborSweep(neighbors, scored, labels[scored], bins, mind, margin, int(num_clusters), dist)
 
@@ -261,11 +290,12 @@ def audit_pairs(
     num_neighbors: int = 15,
     metric: str = "convex",
     qp_solver: str = "quadprog",
+    groups: np.ndarray = None,
 ) -> np.ndarray:
     """`audit`'s leave-one-out hull distances for a list of (row, bin) pairs instead of every bin of every row (no
     counterpart in the reference): entry p is bit for bit `audit(..., rows=rows, return_distances=True)[3][p, bins[p]]`,
     and only the members of the listed bins are streamed -- 64 pairs of a bin share one pass over it.  Pairs may repeat
-    and come in any order.  Nothing changes.
+    and come in any order.  Nothing changes.  With `groups` the entries are those of `audit(..., groups=groups)`.
 
     Returns distances [len(rows)]."""
     if metric not in ("convex", "affine", "affine-qp"):
@@ -276,7 +306,9 @@ def audit_pairs(
     ctx = default_context()
     ctx.set_samples_cached(samples)
     with ctx.using_metric(metric):
-        return ctx.audit_pairs(labels, int(num_clusters), int(num_neighbors), rows, bins)
+        if groups is None:
+            return ctx.audit_pairs(labels, int(num_clusters), int(num_neighbors), rows, bins)
+        return ctx.audit_pairs_grouped(labels, groups, int(num_clusters), int(num_neighbors), rows, bins)
 
 
 def recruit_pairs(
@@ -315,12 +347,15 @@ def cohesion(
     metric: str = "convex",
     qp_solver: str = "quadprog",
     rows: np.ndarray = None,
+    groups: np.ndarray = None,
 ) -> np.ndarray:
     """How well every contig sits in its OWN bin (no counterpart in the reference): for every sample in `rows` (indices
     into `samples`; None: all of them) the leave-one-out hull distance to the bin its label names -- by definition
     `audit(..., rows=rows, return_distances=True)[3][i, labels[rows[i]]]`, at about 1 / num_clusters of that call's cost,
     since only a row's own bin is streamed for it.  NaN where the row's label lies outside [0, num_clusters): such rows
     are not scored.  +inf where the row is its bin's only member.  Nothing changes.
+    With `groups` (see `audit`) the row's whole group is withheld: how well a contig sits in its bin WITHOUT the other
+    pieces of its own parent -- +inf where the bin holds nothing else.
 
     Returns distances [len(rows)]."""
     if metric not in ("convex", "affine", "affine-qp"):
@@ -336,5 +371,9 @@ def cohesion(
     ctx = default_context()
     ctx.set_samples_cached(samples)
     with ctx.using_metric(metric):
-        out[scored] = ctx.audit_pairs(labels, int(num_clusters), int(num_neighbors), rows[scored], own[scored])
+        if groups is None:
+            out[scored] = ctx.audit_pairs(labels, int(num_clusters), int(num_neighbors), rows[scored], own[scored])
+        else:
+            out[scored] = ctx.audit_pairs_grouped(labels, groups, int(num_clusters), int(num_neighbors), rows[scored],
+                                                  own[scored])
     return out

@@ -278,11 +278,12 @@ struct ChunkHalf {
 // chb_recruit_rows, chb_audit_rows, chb_*_rows_multi, chb_bin_report, chb_*_pairs (ScoreRun): the calls' own buffers, nothing of a fit.
 // While the kernels of chunk k run on the context's stream, copy brings chunk k + 1 up into the other half and chunk
 // k - 1 down.  Not per half: the call's CSR over the labels (ptr, memb) and chb_bin_report's B x B tables rep_* (zeroed at
-// the call's start), which collect what the chunks' rows say.
+// the call's start), which collect what the chunks' rows say.  The chb_*_grouped calls add the dense group ids: grp of
+// every resident sample, mgrp parallel to memb.
 struct RowScoring {
     ChunkHalf half[2];
-    DevBuf<int> ptr, memb;
-    PinBuf<int> hptr, hmemb;
+    DevBuf<int> ptr, memb, mgrp, grp;
+    PinBuf<int> hptr, hmemb, hmgrp, hgrp;
     DevBuf<long long> rep_conf, rep_unplaced, rep_cnt;
     DevBuf<double> rep_min, rep_sum;
     hipStream_t copy = nullptr;
@@ -2543,10 +2544,14 @@ struct ScoreRequest {
     // chb_*_pairs: Q pairs (row, bin) in place of the grid, the rows resident or (Y set) rows of Y; dist_out is [Q], one
     // double per pair in the caller's order, and there is no row reduction
     const PairPlan *pairs = nullptr;
+    // chb_*_grouped: one group id per resident sample, negative = no group; besides the scored row every sample of its
+    // group is withheld (leave-group-out).  grouped marks the call, whose groups must not be null
+    bool grouped = false;
+    const int64_t *groups = nullptr;
 };
 
 // The argument checks of the entry points, for all of them in this order: null context; ranges and a malformed list
-// (CHB_EINVAL); null arguments; outputs; no samples; D; more than 16 neighbours (CHB_EUNSUPPORTED); more than 8192 bins;
+// (CHB_EINVAL); null arguments (a grouped call's groups, whatever Q, among them); outputs; no samples; D; more than 16 neighbours (CHB_EUNSUPPORTED); more than 8192 bins;
 // an open stepwise fit; Q == 0 (CHB_OK: nothing further is read); the row_idx rules.
 // D: the rows' number of columns in the calls that take Y, nullptr in the others.  list: the call takes ms / nm, whose
 // largest entry becomes rq.m.  no_output: the refusal's text when every output that counts for the call is null, else nullptr.
@@ -2570,6 +2575,7 @@ int score_check_args(chb_ctx *h, const char *who, ScoreRequest &rq, const int64_
         return fail(CHB_EINVAL, "Q < 0, B < 1 or m < 1");
     }
     if (rq.Q > 0 && (!rq.labels || (D && !rq.Y))) return fail(CHB_EINVAL, "null argument");
+    if (rq.grouped && !rq.groups) return fail(CHB_EINVAL, std::string(who) + ": groups is null (the call without groups is the one to use)");
     if (no_output) return fail(CHB_EINVAL, no_output);
     if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
     if (D && *D != h->D) return fail(CHB_EINVAL, "the rows must have the resident samples' number of columns");
@@ -2599,7 +2605,7 @@ struct ScoreRun {
     int slot[kMaxM] = {0};                  // list entry j's slice on the device = the number of smaller entries
     size_t n_memb = 0;
     int64_t chunk = 0, n = 0;               // rows per chunk (a plan: its cuts), chunks
-    RecruitPairArgs a{};
+    RecruitGroupArgs a{};
     int64_t start(int64_t k) const { return rq.pairs ? rq.pairs->cut[(size_t)k] : rq.plan ? rq.plan->cut[(size_t)k] : k * chunk; }
     int rows(int64_t k) const { return (int)(std::min<int64_t>(start(k + 1), rq.Q) - start(k)); }
     ChunkHalf &half(int64_t k) { return sc.half[k & 1]; }
@@ -2612,8 +2618,24 @@ struct ScoreRun {
             for (hipEvent_t *ev : {&b.up, &b.done, &b.down}) HIPCHK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
         return CHB_OK;
     }
+    // chb_*_grouped: the caller's group ids (any non-negative int64, not dense) as dense int32 ids in pinned memory, once
+    // per call; every sample without a group gets -1, which the kernel never takes for a group
+    int dense_groups()
+    {
+        if (!rq.groups) return CHB_OK;
+        const int64_t N = h->N, *groups = rq.groups;
+        HIPCHK(sc.hgrp.ensure((size_t)N));
+        std::vector<int64_t> ids;
+        for (int64_t i = 0; i < N; ++i)
+            if (groups[i] >= 0) ids.push_back(groups[i]);
+        std::sort(ids.begin(), ids.end());
+        ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+        for (int64_t i = 0; i < N; ++i)
+            sc.hgrp.p[i] = groups[i] < 0 ? -1 : (int)(std::lower_bound(ids.begin(), ids.end(), groups[i]) - ids.begin());
+        return CHB_OK;
+    }
     // CSR over the labels (host counting sort into pinned memory; members of a bin in index order -- the selection does
-    // not depend on it)
+    // not depend on it); with groups also every member's group id, parallel to the member list
     int label_csr()
     {
         const int64_t N = h->N, B = rq.B, *labels = rq.labels;
@@ -2628,6 +2650,10 @@ struct ScoreRun {
         std::vector<int> cur(ptr, ptr + B);
         for (int64_t i = 0; i < N; ++i)
             if (labels[i] >= 0 && labels[i] < B) sc.hmemb.p[cur[(size_t)labels[i]]++] = (int)i;
+        if (!rq.groups) return CHB_OK;
+        HIPCHK(sc.hmgrp.ensure(n_memb));
+        sc.hmgrp.p[0] = -1;   // (without a member: n_memb is 1 and the entry is never read)
+        for (int e = 0; e < ptr[B]; ++e) sc.hmgrp.p[e] = sc.hgrp.p[sc.hmemb.p[e]];
         return CHB_OK;
     }
     // a list of m: its mask for the kernel, and where the unpack step finds entry j's slice
@@ -2650,6 +2676,10 @@ struct ScoreRun {
         const int halves = rq.Q > chunk ? 2 : 1;   // (a plan's longest chunk is shorter than Q whenever it has a second)
         HIPCHK(sc.ptr.ensure((size_t)B + 1));
         HIPCHK(sc.memb.ensure(n_memb));
+        if (rq.groups) {
+            HIPCHK(sc.mgrp.ensure(n_memb));
+            HIPCHK(sc.grp.ensure((size_t)h->N));
+        }
         for (int i = 0; i < halves; ++i) {
             ChunkHalf &b = sc.half[i];
             HIPCHK(rq.Y ? b.Y.ensure((size_t)chunk * h->Dp) : b.qid.ensure((size_t)chunk));
@@ -2698,6 +2728,10 @@ struct ScoreRun {
         HIPCHK(hipMemcpyAsync(sc.memb.p, sc.hmemb.p, sizeof(int) * n_memb, hipMemcpyHostToDevice, s));
         a.X = h->X.p; a.D = h->D; a.Dp = h->Dp; a.bin_ptr = sc.ptr.p; a.memb_id = sc.memb.p;
         a.B = (int)rq.B; a.m = rq.m; a.metric = h->metric;
+        if (!rq.groups) return CHB_OK;
+        HIPCHK(hipMemcpyAsync(sc.mgrp.p, sc.hmgrp.p, sizeof(int) * n_memb, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(sc.grp.p, sc.hgrp.p, sizeof(int) * (size_t)h->N, hipMemcpyHostToDevice, s));
+        a.memb_grp = sc.mgrp.p; a.grp = sc.grp.p;
         return CHB_OK;
     }
     // The order of a step -- kernels of k, upload of k + 1, download of k, unpack of k - 1 -- keeps the copy stream from
@@ -2718,7 +2752,7 @@ struct ScoreRun {
     {
         HIPCHK(hipSetDevice(h->dev));
         int rc;
-        if ((rc = ensure_copy_stream()) || (rc = label_csr())) return rc;
+        if ((rc = ensure_copy_stream()) || (rc = dense_groups()) || (rc = label_csr())) return rc;
         list_slots();
         if ((rc = size_buffers()) || (rc = reset_report_tables()) || (rc = kernel_args())) return rc;
         const hipError_t e = pipeline();
@@ -2805,14 +2839,17 @@ struct ScoreRun {
         HIPTRY(hipStreamWaitEvent(s, b.up, 0));
         if (any_out) HIPTRY(hipStreamWaitEvent(s, b.down, 0));   // (chunk k - 2 has been copied out of this half's results)
         a.Y = audit ? nullptr : b.Y.p; a.qid = audit ? b.qid.p : nullptr; a.dist = b.dist.p; a.nq = nq;
+        // (with groups: the same launches, the leave-group-out instantiation of the kernel)
         if (rq.pairs) {   // one launch: the tiles' kernel, no row reduction behind it
             a.tile = b.tile.p; a.ntile = b.ntile;
             Timed t(h, audit ? "audit_pairs" : "recruit_pairs", (double)nq);
-            launch_recruit_pairs(a, s);
+            if (a.memb_grp) launch_recruit_grouped(a, s);
+            else launch_recruit_pairs(a, s);
         } else {
             Timed t(h, a.mmask ? (audit ? "audit_multi" : "recruit_multi") : (audit ? "audit" : "recruit"),
                     (double)nq * (double)rq.B * (double)ns);
-            launch_recruit(a, s);
+            if (a.memb_grp) launch_recruit_grouped(a, s);
+            else launch_recruit(a, s);
             launch_recruit_reduce(b.dist.p, nq * ns, (int)rq.B, b.bin.p, b.min.p, b.margin.p, s);
         }
         if (rq.plan) {
@@ -2899,12 +2936,32 @@ int chb_audit_rows_multi(chb_ctx *h, const int64_t *labels, int64_t B, const int
     return score_rows(h, "chb_audit_rows_multi", rq, nullptr, true);
 }
 
-int chb_bin_report(chb_ctx *h, const int64_t *labels, int64_t B, int m, const int64_t *row_idx, int64_t Q,
-                   int64_t *confusion, int64_t *unplaced, int64_t *dcnt, double *dmin, double *dsum, int64_t *n_skipped)
+int chb_audit_rows_grouped(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
+                           int64_t Q, int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
 {
-    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, m, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
+    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, m, nullptr, 0, bin_out, dist_out, min_dist_out, margin_out};
+    rq.grouped = true; rq.groups = groups;
+    return score_rows(h, "chb_audit_rows_grouped", rq, nullptr, false);
+}
+
+int chb_audit_rows_multi_grouped(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, const int *ms, int nm,
+                                 const int64_t *row_idx, int64_t Q, int64_t *bin_out, double *dist_out, double *min_dist_out,
+                                 double *margin_out)
+{
+    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, 0, ms, nm, bin_out, dist_out, min_dist_out, margin_out};
+    rq.grouped = true; rq.groups = groups;
+    return score_rows(h, "chb_audit_rows_multi_grouped", rq, nullptr, true);
+}
+
+namespace {
+
+// chb_bin_report and its grouped form behind the request
+int bin_report(chb_ctx *h, const char *who, ScoreRequest &rq, int64_t *confusion, int64_t *unplaced, int64_t *dcnt,
+               double *dmin, double *dsum, int64_t *n_skipped)
+{
+    const int64_t *labels = rq.labels, *row_idx = rq.row_idx, B = rq.B, Q = rq.Q;
     const bool any = confusion || unplaced || dcnt || dmin || dsum || n_skipped;
-    int rc = score_check_args(h, "chb_bin_report", rq, nullptr, false, any ? nullptr : "every output is null");
+    int rc = score_check_args(h, who, rq, nullptr, false, any ? nullptr : "every output is null");
     if (rc != CHB_OK) return rc;
     const ReportOut out{confusion, unplaced, dcnt, dmin, dsum};
     ReportPlan plan;
@@ -2914,6 +2971,24 @@ int chb_bin_report(chb_ctx *h, const int64_t *labels, int64_t B, int m, const in
     rq.row_idx = nullptr; rq.plan = &plan; rq.Q = Qv;   // the plan's positions, already in label order
     rc = ScoreRun{h, rq}.run();
     return rc != CHB_OK ? rc : plan.copy_tables(h, out);
+}
+
+}  // namespace
+
+int chb_bin_report(chb_ctx *h, const int64_t *labels, int64_t B, int m, const int64_t *row_idx, int64_t Q,
+                   int64_t *confusion, int64_t *unplaced, int64_t *dcnt, double *dmin, double *dsum, int64_t *n_skipped)
+{
+    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, m, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
+    return bin_report(h, "chb_bin_report", rq, confusion, unplaced, dcnt, dmin, dsum, n_skipped);
+}
+
+int chb_bin_report_grouped(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
+                           int64_t Q, int64_t *confusion, int64_t *unplaced, int64_t *dcnt, double *dmin, double *dsum,
+                           int64_t *n_skipped)
+{
+    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, m, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
+    rq.grouped = true; rq.groups = groups;
+    return bin_report(h, "chb_bin_report_grouped", rq, confusion, unplaced, dcnt, dmin, dsum, n_skipped);
 }
 
 namespace {
@@ -2943,6 +3018,16 @@ int chb_audit_pairs(chb_ctx *h, const int64_t *labels, int64_t B, int m, const i
     ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, P, m, nullptr, 0, nullptr, dist_out, nullptr, nullptr};
     // (row_idx is not "all rows" here: its range is checked like chb_audit_rows' list)
     const int rc = score_check_args(h, "chb_audit_pairs", rq, nullptr, false,
+                                    pairs_missing(P, row_idx, bin_idx, dist_out, "row_idx, bin_idx or dist_out is null"));
+    return rc != CHB_OK || P == 0 ? rc : score_pairs(h, rq, row_idx, bin_idx);
+}
+
+int chb_audit_pairs_grouped(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
+                            const int64_t *bin_idx, int64_t P, double *dist_out)
+{
+    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, P, m, nullptr, 0, nullptr, dist_out, nullptr, nullptr};
+    rq.grouped = true; rq.groups = groups;
+    const int rc = score_check_args(h, "chb_audit_pairs_grouped", rq, nullptr, false,
                                     pairs_missing(P, row_idx, bin_idx, dist_out, "row_idx, bin_idx or dist_out is null"));
     return rc != CHB_OK || P == 0 ? rc : score_pairs(h, rq, row_idx, bin_idx);
 }

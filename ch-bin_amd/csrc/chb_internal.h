@@ -391,10 +391,18 @@ struct RecruitPairArgs : RecruitArgs {
     const int4 *tile;      // [ntile]
     int ntile;
 };
+// leave-group-out (chb_*_grouped; resident rows only, qid set): dense int32 group ids, negative = no group; a member is
+// withheld from a row's lists when it is the row or shares the row's non-negative group id.  tile is null for the dense
+// grid.  (Its own struct again: the ungrouped kernels keep the kernel arguments they have.)
+struct RecruitGroupArgs : RecruitPairArgs {
+    const int *memb_grp;   // [n_memb] group id of memb_id's entry at the same place
+    const int *grp;        // [N] group id of every resident sample: the scored rows' own
+};
 constexpr int kRecruitChunk = 16384;   // rows of Y uploaded (recruit) or positions of row_idx (audit) scored per launch
 constexpr int kRecruitMaxBins = 8192;
 void launch_recruit(const RecruitArgs &a, hipStream_t s);   // (a.qid set: the audit instantiation)
 void launch_recruit_pairs(const RecruitPairArgs &a, hipStream_t s);
+void launch_recruit_grouped(const RecruitGroupArgs &a, hipStream_t s);   // (a.tile set: the pairs' instantiation)
 // bin[q] = strict-'>' argmin over dist[q][0 .. B) (-1: all +inf), mind[q] its distance, margin[q] = runner-up minus it (+inf
 // without a finite runner-up)
 void launch_recruit_reduce(const double *dist, int nq, int B, int *bin, double *mind, double *margin, hipStream_t s);

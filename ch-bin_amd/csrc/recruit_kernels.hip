@@ -30,6 +30,9 @@
 // the work items come from a tile table the host cut from the pairs in bin order, and a pair's one distance is stored at
 // its position; there is no reduction kernel behind it.
 //
+// The chb_*_grouped calls run the resident instantiations with one more exclusion (template parameter kGrouped): besides
+// the row itself every sample that shares the row's group id -- the sibling pieces of one parent contig -- is withheld.
+//
 // chb_bin_report runs the audit's two kernels on positions grouped by their own label and a third, bin_report_kernel
 // (below), that folds each chunk's distances and bins into B x B tables keyed (own label, bin).
 #include "chb_internal.h"
@@ -52,6 +55,7 @@ struct RecruitStage {
     double q[2][kKChunk][kLdsStride];
     double p[2][kKChunk][kLdsStride];
     int mid[2][kPTile];
+    int grp[2][kPTile];   // (kGrouped: the members' group ids, next to mid; the union's size is RecruitSolve's)
 };
 struct RecruitSolve {
     double Qt[4][4][16][kQ16Ld];   // [wavefront][16-lane group][row][col], padded
@@ -84,11 +88,24 @@ union RecruitLds {
 // kernel -- the staged rows of a short tile's tail are the next tile's (or the chunk's last), read and never offered --
 // so a pair's distance has the bits of the dense call's entry.  The `false` instantiations are unchanged: the three
 // places sit behind `if constexpr (kPairs)`.  There is no list of m for pairs.
-template <bool kResident, bool kMulti, bool kPairs>
-__global__ __launch_bounds__(256, 2) void recruit_kernel(std::conditional_t<kPairs, RecruitPairArgs, RecruitArgs> a,
-                                                         int nqt, int total)
+//
+// kGrouped (chb_*_grouped, resident rows only): leave-group-out.  Every sample carries a dense int32 group id, negative
+// for a sample without a group; besides the row itself every member of the row's group is withheld, whichever bin is
+// being scored.  A member's group id travels with its sample index -- a.memb_grp is parallel to a.memb_id, loaded by the
+// same thread at the same step and staged next to mid -- and each thread keeps the group ids of its 4 rows (a.grp, read
+// once per work item where own[] is read) next to own[].  One more compare per offer, nothing else: a candidate's
+// distance does not depend on its tile position, the lists are a total order on (distance, index), and the Gram tile and
+// the solve depend on the list alone, so a row's result is what the ungrouped kernel gives on labels from which the
+// row's group has been taken out.  The `false` instantiations are unchanged: every place sits behind
+// `if constexpr (kGrouped)`.
+template <bool kGrouped, bool kPairs>
+using recruit_args_t = std::conditional_t<kGrouped, RecruitGroupArgs, std::conditional_t<kPairs, RecruitPairArgs, RecruitArgs>>;
+
+template <bool kResident, bool kMulti, bool kPairs, bool kGrouped = false>
+__global__ __launch_bounds__(256, 2) void recruit_kernel(recruit_args_t<kGrouped, kPairs> a, int nqt, int total)
 {
     static_assert(!(kMulti && kPairs), "pairs are scored for a single m");
+    static_assert(kResident || !kGrouped, "groups are a property of the resident samples");
     __shared__ __attribute__((aligned(16))) RecruitLds lds;
 
     // XCD-aware order: blocks b and b+8 share an XCD (and its L2), so hand each XCD a contiguous range of work
@@ -131,18 +148,25 @@ __global__ __launch_bounds__(256, 2) void recruit_kernel(std::conditional_t<kPai
 #pragma unroll
         for (int i = 0; i < 4; ++i) own[i] = a.qid[min(pos0 + 4 * ty + i, a.nq - 1)];
     }
+    // ... and their group ids (negative: no group)
+    int owng[4];
+    if constexpr (kGrouped) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) owng[i] = a.grp[own[i]];
+    }
     const double *prow = a.X + 2 * skp;
     const int nch = a.Dp / kKChunk;
     const int ntile = (nmem + kPTile - 1) / kPTile;
     const int nsteps = ntile * nch;
 
     double2 rq, rp;
-    int pmid = -1;
+    int pmid = -1, pgrp = -1;
     int nt = 0, nc = 0;  // (tile, chunk) of the step being prefetched
     auto prefetch = [&]() {
         if (nc == 0) {
             const int e = nt * kPTile + srow;
             pmid = e < nmem ? a.memb_id[mb + e] : -1;
+            if constexpr (kGrouped) pgrp = e < nmem ? a.memb_grp[mb + e] : -1;
             prow = a.X + (size_t)(pmid < 0 ? 0 : pmid) * a.Dp + 2 * skp;
         }
         rq = *reinterpret_cast<const double2 *>(qrow + nc * kKChunk);
@@ -153,7 +177,10 @@ __global__ __launch_bounds__(256, 2) void recruit_kernel(std::conditional_t<kPai
         lds.st.q[buf][2 * skp + 1][srow] = rq.y;
         lds.st.p[buf][2 * skp][srow] = rp.x;
         lds.st.p[buf][2 * skp + 1][srow] = rp.y;
-        if (nc == 0 && skp == 0) lds.st.mid[nt & 1][srow] = pmid;
+        if (nc == 0 && skp == 0) {
+            lds.st.mid[nt & 1][srow] = pmid;
+            if constexpr (kGrouped) lds.st.grp[nt & 1][srow] = pgrp;
+        }
         if (++nc == nch) { nc = 0; ++nt; }
     };
 
@@ -198,6 +225,11 @@ __global__ __launch_bounds__(256, 2) void recruit_kernel(std::conditional_t<kPai
             int mid[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) mid[j] = lds.st.mid[ct & 1][(j < 2) ? 2 * tx + j : 32 + 2 * tx + (j - 2)];
+            int gm[4];
+            if constexpr (kGrouped) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) gm[j] = lds.st.grp[ct & 1][(j < 2) ? 2 * tx + j : 32 + 2 * tx + (j - 2)];
+            }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 bool qvalid;
@@ -208,6 +240,7 @@ __global__ __launch_bounds__(256, 2) void recruit_kernel(std::conditional_t<kPai
                 for (int j = 0; j < 4; ++j) {
                     bool offer = qvalid && mid[j] >= 0;
                     if constexpr (kResident) offer = offer && mid[j] != own[i];   // only the row itself: a twin stays
+                    if constexpr (kGrouped) offer = offer && !(gm[j] >= 0 && gm[j] == owng[i]);   // ... and its group
                     s[j] = offer ? acc[i][j] : kInf;
                     acc[i][j] = 0.0;
                 }
@@ -297,7 +330,7 @@ __global__ __launch_bounds__(256, 2) void recruit_kernel(std::conditional_t<kPai
         nn[0] = nn[1]; nn[1] = nn[2]; nn[2] = nn[3];
         idv[0] = idv[1]; idv[1] = idv[2]; idv[2] = idv[3];
         if constexpr (kResident) { own[0] = own[1]; own[1] = own[2]; own[2] = own[3]; }
-    }
+    }   // (owng[] is dead behind the tile loop: nothing to shift)
 }
 
 // strict-'>' scan over each row of B distances (algorithm.py:57: lowest index among equal minima, -1 when every entry
@@ -450,6 +483,23 @@ void launch_recruit_pairs(const RecruitPairArgs &a, hipStream_t s)
     const int grid = ((a.ntile + 7) / 8) * 8;
     if (a.qid) hipLaunchKernelGGL((recruit_kernel<true, false, true>), dim3(grid), dim3(256), 0, s, a, 0, a.ntile);
     else hipLaunchKernelGGL((recruit_kernel<false, false, true>), dim3(grid), dim3(256), 0, s, a, 0, a.ntile);
+}
+
+// the leave-group-out instantiations: the dense grid (a.tile null; a list of m with a.mmask) or the tile table
+void launch_recruit_grouped(const RecruitGroupArgs &a, hipStream_t s)
+{
+    if (a.tile) {
+        if (a.nq <= 0 || a.ntile <= 0) return;
+        const int grid = ((a.ntile + 7) / 8) * 8;
+        hipLaunchKernelGGL((recruit_kernel<true, false, true, true>), dim3(grid), dim3(256), 0, s, a, 0, a.ntile);
+        return;
+    }
+    if (a.nq <= 0 || a.B <= 0) return;
+    const int nqt = (a.nq + kQTile - 1) / kQTile;
+    const int total = nqt * a.B;
+    const int grid = ((total + 7) / 8) * 8;
+    if (a.mmask) hipLaunchKernelGGL((recruit_kernel<true, true, false, true>), dim3(grid), dim3(256), 0, s, a, nqt, total);
+    else hipLaunchKernelGGL((recruit_kernel<true, false, false, true>), dim3(grid), dim3(256), 0, s, a, nqt, total);
 }
 
 void launch_recruit_reduce(const double *dist, int nq, int B, int *bin, double *mind, double *margin, hipStream_t s)

@@ -240,6 +240,45 @@ int chb_recruit_pairs(chb_ctx *h, const int64_t *labels, int64_t B, int m,
                       const double *Y, int64_t Q, int64_t D,
                       const int64_t *row_of, const int64_t *bin_idx, int64_t P, double *dist_out);
 
+/* Leave-group-out audit: the four audit-side calls with a row's whole GROUP withheld, not only the row.  CH-Bin cuts long
+ * contigs into pieces (preprocess.py:72-101) whose rows are nearly identical; with only the row itself withheld a
+ * piece's nearest members are its own siblings and every margin looks sound.  groups[N] holds one int64 per resident
+ * sample: any non-negative value is a group id (values up to 2^62, not dense), a negative value means no group.  For a
+ * scored sample r the withheld set is
+ *     W(r) = {r} + {p : groups[p] >= 0 and groups[p] == groups[r]},
+ * removed from the candidates of EVERY bin (siblings may carry different labels).  Everything else is the ungrouped
+ * call's definition: the selection arithmetic and the (distance, index) order, a twin with equal coordinates but another
+ * group stays a candidate, +inf for a bin with no member left, the strict-'>' scan and the margins.  A row with
+ * groups[r] < 0 is scored exactly as the ungrouped call scores it.
+ * Each call is defined by its ungrouped form: with labels_g = labels in which every member of group g is set to -1, the
+ * result for a row of g is bit for bit what the ungrouped call returns for that row on labels_g (a candidate's distance
+ * does not depend on where it sits among the members, the lists are a total order on (distance, index), and the Gram
+ * tile and the solve depend on the list alone).  chb_bin_report_grouped keys its tables by the rows' labels in `labels`
+ * and sums dsum in chb_bin_report's order.
+ *   - the argument list is the ungrouped call's with groups after labels.  groups == NULL is CHB_EINVAL (use the
+ *     ungrouped call); every other check is the ungrouped call's, in its order, on the host before anything is enqueued:
+ *     m <= 16 and B <= 8192 (CHB_EUNSUPPORTED beyond), CHB_ESTATE without resident samples or while a stepwise fit is
+ *     open (the fit stays usable), Q = 0 / P = 0 a no-op, row_idx == NULL all rows;
+ *   - one launch per chunk exactly as in the ungrouped call -- the kernel does the withholding with one more compare per
+ *     offered member -- through the same chunks, streams and pinned buffers; the profile names ("audit", "audit_multi",
+ *     "audit_pairs", "bin_report") and the counters "recruit_chunk", "recruit_multi_rows", "pair_tiles" are the ungrouped
+ *     call's.  The group ids are made dense int32 on the host once per call; 4 bytes per resident sample and 4 per
+ *     labelled sample go up next to the member list;
+ *   - there is no context-level group state and no recruit form (new rows have no siblings among the samples); the calls
+ *     use no state of a fit and leave no trace on the context. */
+int chb_audit_rows_grouped(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m,
+                           const int64_t *row_idx, int64_t Q,
+                           int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out);
+int chb_audit_rows_multi_grouped(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B,
+                                 const int *ms, int nm, const int64_t *row_idx, int64_t Q,
+                                 int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out);
+int chb_audit_pairs_grouped(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m,
+                            const int64_t *row_idx, const int64_t *bin_idx, int64_t P, double *dist_out);
+int chb_bin_report_grouped(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m,
+                           const int64_t *row_idx, int64_t Q,
+                           int64_t *confusion, int64_t *unplaced, int64_t *dcnt, double *dmin, double *dsum,
+                           int64_t *n_skipped);
+
 /* distance_matrix.py:47-62 find_nearest_from_cluster with the reference's exact signature: the
  * caller supplies one row of a distance matrix (any provenance) and the current labels; selects
  * among {p : labels[p] == c} the (up to) m smallest by (row[p], p).  out_idx[m] (-1 padded). */
