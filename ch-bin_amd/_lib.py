@@ -63,6 +63,12 @@ SIGNATURES = {
                                           C.c_int64, C.c_void_p]),
     "chb_bin_report_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the pair calls with witnesses: dist_out and the three [P, m] arrays at the end (groups may be NULL)
+    "chb_audit_pairs_witness": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "chb_recruit_pairs_witness": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                            C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
     "chb_find_nearest_from_row": (C.c_int, [C.c_void_p, C.c_int64, _i64p, _f64p, C.c_int64, C.c_int,
                                             _i64p, C.POINTER(C.c_int32)]),
     "chb_hull_distance_batch": (C.c_int, [C.c_void_p, _i64p, C.c_int64, _i64p, C.c_int, _f64p,
@@ -372,6 +378,43 @@ class Context:
         check(self._lib.chb_recruit_pairs(self._h, labels.ctypes.data, int(B), int(m), Y.ctypes.data, *Y.shape,
                                           row_of.ctypes.data, bins.ctypes.data, row_of.shape[0], dist.ctypes.data))
         return dist
+
+    @staticmethod
+    def _witness_arrays(P, m):
+        """dist [P] and the three [P, m] arrays of a witness call (refused calls write nothing: m as given, at least 0)"""
+        m = max(int(m), 0)
+        return (np.empty(P, dtype=np.float64), np.empty((P, m), dtype=np.int64), np.empty((P, m), dtype=np.float64),
+                np.empty((P, m), dtype=np.float64))
+
+    def audit_pairs_witness(self, labels, B, m, rows, bins, groups=None):
+        """chb_audit_pairs_witness: audit_pairs (with `groups` audit_pairs_grouped) together with the hull each distance
+        was measured to.  Returns (dist [P], neighbors [P, m], neighbor_dist [P, m], weights [P, m]): dist bit for bit
+        the plain call's; per pair the selected members' sample indices in the kernel's list order ((distance, index)
+        ascending; -1 padding), their distances to the row (+inf padding) and their weights in the hull's nearest point
+        under the context's metric (0 padding; not unique where vertices are dependent)."""
+        rows, bins = self._pair_lists(rows, bins, "rows")
+        labels = self._labels(labels)
+        if groups is not None:
+            groups = self._groups(groups)
+        dist, idx, nd, alpha = self._witness_arrays(rows.shape[0], m)
+        check(self._lib.chb_audit_pairs_witness(self._h, labels.ctypes.data, None if groups is None else groups.ctypes.data,
+                                                int(B), int(m), rows.ctypes.data, bins.ctypes.data, rows.shape[0],
+                                                dist.ctypes.data, idx.ctypes.data, nd.ctypes.data, alpha.ctypes.data))
+        return dist, idx, nd, alpha
+
+    def recruit_pairs_witness(self, labels, B, m, Y, row_of, bins):
+        """chb_recruit_pairs_witness: recruit_pairs together with the hull each distance was measured to; returns what
+        audit_pairs_witness returns, for the NEW rows Y[row_of[p]] (nothing is withheld)."""
+        row_of, bins = self._pair_lists(row_of, bins, "row_of")
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim != 2:
+            raise ValueError("rows must be a 2-D array")
+        labels = self._labels(labels)
+        dist, idx, nd, alpha = self._witness_arrays(row_of.shape[0], m)
+        check(self._lib.chb_recruit_pairs_witness(self._h, labels.ctypes.data, int(B), int(m), Y.ctypes.data, *Y.shape,
+                                                  row_of.ctypes.data, bins.ctypes.data, row_of.shape[0],
+                                                  dist.ctypes.data, idx.ctypes.data, nd.ctypes.data, alpha.ctypes.data))
+        return dist, idx, nd, alpha
 
     def find_nearest_from_row(self, c, labels, row, m):
         labels = np.ascontiguousarray(labels, dtype=np.int64)

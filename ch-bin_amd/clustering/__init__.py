@@ -3,6 +3,7 @@ argument meaning and error behaviour) on top of libchbin_hip.so."""
 from .algorithm import (  # noqa: F401
     BinReport,
     NeighborSweep,
+    Witness,
     audit,
     audit_pairs,
     bin_report,
@@ -12,6 +13,8 @@ from .algorithm import (  # noqa: F401
     parent_groups,
     recruit,
     recruit_pairs,
+    recruit_witness,
+    witness,
 )
 from .distance_matrix import (  # noqa: F401
     create_distance_matrix,

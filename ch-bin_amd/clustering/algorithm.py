@@ -377,3 +377,109 @@ def cohesion(
             out[scored] = ctx.audit_pairs_grouped(labels, groups, int(num_clusters), int(num_neighbors), rows[scored],
                                                   own[scored])
     return out
+
+
+@dataclasses.dataclass
+class Witness:
+    """What `witness` / `recruit_witness` return: per scored (row, bin) pair the hull its distance was measured to.
+    Plain numpy, nothing here touches the GPU.
+
+    dist [P]: the pair's hull distance, bit for bit `audit_pairs` / `recruit_pairs`' entry (+inf: the bin had no member
+    to offer).  neighbors [P, m]: the sample indices of the hull's vertices -- the bin's members nearest to the row, in
+    (distance, index) order, after the call's withholding -- padded with -1 where the bin had fewer than m.
+    neighbor_dist [P, m]: each vertex's Euclidean distance to the row (+inf padding).  weights [P, m]: each vertex's
+    weight in the nearest point of the hull (0 padding): that point is sum_a weights[p, a] * samples[neighbors[p, a]].
+
+    Under the convex metric the weights are >= 0 and sum to 1, and a zero weight means the vertex does not take part
+    in the nearest point.  Under the affine metrics they sum to 1 and MAY BE NEGATIVE: the nearest point of the affine
+    hull need not lie between the vertices, so a weight is a coordinate, not a share.  Where vertices are dependent --
+    twins with equal coordinates, more vertices than the dimension allows -- the nearest point is unique but the weights
+    are not: any optimal vector is a valid answer, and two pieces of software (or two numbers of neighbours) may spread
+    the same point differently over the twins."""
+    dist: np.ndarray
+    neighbors: np.ndarray
+    neighbor_dist: np.ndarray
+    weights: np.ndarray
+
+    @property
+    def count(self) -> np.ndarray:
+        """[P]: the number of vertices of each pair's hull (0: an empty bin, dist +inf)."""
+        return np.count_nonzero(self.neighbors >= 0, axis=1)
+
+    @property
+    def support(self) -> np.ndarray:
+        """[P, m] bool: the real vertices with a weight other than 0 -- the ones the nearest point is made of."""
+        return (self.neighbors >= 0) & (self.weights != 0)
+
+    def nearest_point(self, samples: np.ndarray) -> np.ndarray:
+        """[P, D]: the nearest point of each pair's hull, sum_a weights * samples[neighbors] with padding skipped
+        (a row of zeros for a pair without vertices)."""
+        samples = np.asarray(samples, dtype=np.float64)
+        real = self.neighbors >= 0
+        rows = np.where(real[:, :, None], samples[np.where(real, self.neighbors, 0)], 0.0)   # [P, m, D], padding zeroed
+        return np.einsum("pa,pad->pd", np.where(real, self.weights, 0.0), rows)
+
+    def residual_by_block(self, samples: np.ndarray, points: np.ndarray, blocks) -> np.ndarray:
+        """[P, len(blocks)]: the squared residual ||points - nearest_point||^2 summed over each column range
+        (begin, end) of `blocks` -- where a pair's distance comes from: composition (the k-mer blocks of features.csv)
+        or abundance (its coverage block).  `points` [P, D] are the scored rows, samples[rows] or new_rows[row_of].
+        Over a partition of the columns the blocks sum to dist**2 up to rounding.  NaN for a pair without vertices."""
+        points = np.asarray(points, dtype=np.float64)
+        r2 = (points - self.nearest_point(samples)) ** 2
+        out = np.stack([r2[:, int(b):int(e)].sum(axis=1) for b, e in blocks], axis=1) if len(blocks) \
+            else np.zeros((r2.shape[0], 0))
+        out[self.count == 0] = np.nan
+        return out
+
+
+def witness(
+    samples: np.ndarray,
+    labels: np.ndarray,
+    rows: np.ndarray,
+    bins: np.ndarray,
+    num_clusters: int,
+    num_neighbors: int = 15,
+    metric: str = "convex",
+    qp_solver: str = "quadprog",
+    groups: np.ndarray = None,
+) -> Witness:
+    """Which contigs vouch for a (row, bin) pair (no counterpart in the reference): `audit_pairs` on the same arguments,
+    returning with every distance the members of the bin that form the hull it was measured to, their distances to the
+    row and their weights in the hull's nearest point -- see `Witness` for what the weights mean under the affine metric
+    and why they are not unique among twins.  With `groups` the hulls are leave-group-out, as in `audit_pairs`.
+    Nothing changes."""
+    if metric not in ("convex", "affine", "affine-qp"):
+        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
+    check_solver(qp_solver)                                              # solve_qp.py:132
+
+    samples = np.ascontiguousarray(samples, dtype=np.float64)
+    ctx = default_context()
+    ctx.set_samples_cached(samples)
+    with ctx.using_metric(metric):
+        return Witness(*ctx.audit_pairs_witness(labels, int(num_clusters), int(num_neighbors), rows, bins, groups=groups))
+
+
+def recruit_witness(
+    samples: np.ndarray,
+    labels: np.ndarray,
+    new_rows: np.ndarray,
+    row_of: np.ndarray,
+    bins: np.ndarray,
+    num_clusters: int,
+    num_neighbors: int = 15,
+    metric: str = "convex",
+    qp_solver: str = "quadprog",
+) -> Witness:
+    """`witness` for rows that are NOT samples: `recruit_pairs` on the same arguments together with the hull each
+    distance was measured to.  Nothing is withheld: a new row equal to a sample has that sample as a vertex at distance
+    0.  The weights' meaning under the affine metric and their non-uniqueness among twins are `Witness`'s."""
+    if metric not in ("convex", "affine", "affine-qp"):
+        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
+    check_solver(qp_solver)                                              # solve_qp.py:132
+
+    samples = np.ascontiguousarray(samples, dtype=np.float64)
+    new_rows = np.ascontiguousarray(new_rows, dtype=np.float64)
+    ctx = default_context()
+    ctx.set_samples_cached(samples)
+    with ctx.using_metric(metric):
+        return Witness(*ctx.recruit_pairs_witness(labels, int(num_clusters), int(num_neighbors), new_rows, row_of, bins))

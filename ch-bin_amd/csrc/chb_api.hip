@@ -270,6 +270,12 @@ struct ChunkHalf {
     PinBuf<int> hbin, hqid;
     PinBuf<int2> hseg;
     PinBuf<int4> htile;
+    // chb_*_pairs_witness only (first allocated by the context's first such call): the chunk's witness records, kWitnessSlots
+    // slots per position (RecruitWitnessArgs)
+    DevBuf<int> wid;
+    DevBuf<double> wd, walpha;
+    PinBuf<int> hwid;
+    PinBuf<double> hwd, hwalpha;
     hipEvent_t up = nullptr, done = nullptr, down = nullptr;
     int nseg = 0, ntile = 0;
     void destroy_events() { for (hipEvent_t ev : {up, done, down}) if (ev) (void)hipEventDestroy(ev); }
@@ -2548,6 +2554,10 @@ struct ScoreRequest {
     // group is withheld (leave-group-out).  grouped marks the call, whose groups must not be null
     bool grouped = false;
     const int64_t *groups = nullptr;
+    // chb_*_pairs_witness: a pair call that also returns, per pair, the hull's members, their selection distances and
+    // their weights ([Q][m] each, in the caller's order; each may be null, not all three); dist_out may then be null
+    bool witness = false;
+    int64_t *w_idx = nullptr; double *w_dist = nullptr, *w_alpha = nullptr;
 };
 
 // The argument checks of the entry points, for all of them in this order: null context; ranges and a malformed list
@@ -2599,13 +2609,13 @@ struct ScoreRun {
     const ScoreRequest rq;
     RowScoring &sc = h->score;
     hipStream_t s = h->stream;
-    const bool audit = !rq.Y /* the rows are resident */, any_out = rq.bin_out || rq.dist_out || rq.min_dist_out || rq.margin_out;
+    const bool audit = !rq.Y /* the rows are resident */, any_out = rq.bin_out || rq.dist_out || rq.min_dist_out || rq.margin_out || rq.witness;
     const int ns = rq.nm > 0 ? rq.nm : 1;   // result slices per chunk
     const size_t width = rq.pairs ? 1 : (size_t)rq.B;   // distances per result row
     int slot[kMaxM] = {0};                  // list entry j's slice on the device = the number of smaller entries
     size_t n_memb = 0;
     int64_t chunk = 0, n = 0;               // rows per chunk (a plan: its cuts), chunks
-    RecruitGroupArgs a{};
+    RecruitWitnessArgs a{};   // (the launchers without witnesses take the part of it that is theirs)
     int64_t start(int64_t k) const { return rq.pairs ? rq.pairs->cut[(size_t)k] : rq.plan ? rq.plan->cut[(size_t)k] : k * chunk; }
     int rows(int64_t k) const { return (int)(std::min<int64_t>(start(k + 1), rq.Q) - start(k)); }
     ChunkHalf &half(int64_t k) { return sc.half[k & 1]; }
@@ -2689,6 +2699,15 @@ struct ScoreRun {
             if (rq.pairs) {   // the tile table, and no row reduction
                 HIPCHK(b.tile.ensure((size_t)rq.pairs->max_tiles));
                 HIPCHK(b.htile.ensure((size_t)rq.pairs->max_tiles));
+                if (rq.witness) {   // the records: the kernel writes all three, what the caller wants comes down
+                    const size_t slots = (size_t)chunk * kWitnessSlots;
+                    HIPCHK(b.wid.ensure(slots));
+                    HIPCHK(b.wd.ensure(slots));
+                    HIPCHK(b.walpha.ensure(slots));
+                    if (rq.w_idx) HIPCHK(b.hwid.ensure(slots));
+                    if (rq.w_dist) HIPCHK(b.hwd.ensure(slots));
+                    if (rq.w_alpha) HIPCHK(b.hwalpha.ensure(slots));
+                }
                 continue;
             }
             HIPCHK(b.bin.ensure(res));
@@ -2843,7 +2862,10 @@ struct ScoreRun {
         if (rq.pairs) {   // one launch: the tiles' kernel, no row reduction behind it
             a.tile = b.tile.p; a.ntile = b.ntile;
             Timed t(h, audit ? "audit_pairs" : "recruit_pairs", (double)nq);
-            if (a.memb_grp) launch_recruit_grouped(a, s);
+            if (rq.witness) {
+                a.w_id = b.wid.p; a.w_d = b.wd.p; a.w_alpha = b.walpha.p;
+                launch_recruit_witness(a, s);
+            } else if (a.memb_grp) launch_recruit_grouped(a, s);
             else launch_recruit_pairs(a, s);
         } else {
             Timed t(h, a.mmask ? (audit ? "audit_multi" : "recruit_multi") : (audit ? "audit" : "recruit"),
@@ -2871,10 +2893,15 @@ struct ScoreRun {
         if (rq.min_dist_out) HIPTRY(hipMemcpyAsync(b.hmin.p, b.min.p, sizeof(double) * nr, hipMemcpyDeviceToHost, c));
         if (rq.margin_out) HIPTRY(hipMemcpyAsync(b.hmargin.p, b.margin.p, sizeof(double) * nr, hipMemcpyDeviceToHost, c));
         if (rq.bin_out) HIPTRY(hipMemcpyAsync(b.hbin.p, b.bin.p, sizeof(int) * nr, hipMemcpyDeviceToHost, c));
+        const size_t slots = nr * kWitnessSlots;   // (pairs: nr positions)
+        if (rq.w_idx) HIPTRY(hipMemcpyAsync(b.hwid.p, b.wid.p, sizeof(int) * slots, hipMemcpyDeviceToHost, c));
+        if (rq.w_dist) HIPTRY(hipMemcpyAsync(b.hwd.p, b.wd.p, sizeof(double) * slots, hipMemcpyDeviceToHost, c));
+        if (rq.w_alpha) HIPTRY(hipMemcpyAsync(b.hwalpha.p, b.walpha.p, sizeof(double) * slots, hipMemcpyDeviceToHost, c));
         return hipEventRecord(b.down, c);
     }
     // (a list of m: ns slices of nq rows each, on the device in ascending order of m; slice slot[j] goes to out + j * Q + t0;
-    // pairs: the position's double goes to the place of its pair in the caller's order)
+    // pairs: the position's double goes to the place of its pair in the caller's order, and so do the first m of the
+    // kWitnessSlots slots of its witness record)
     hipError_t unpack(int64_t k)
     {
         ChunkHalf &b = half(k);
@@ -2883,7 +2910,15 @@ struct ScoreRun {
         HIPTRY(hipEventSynchronize(b.down));
         if (rq.pairs) {
             const int64_t *ord = rq.pairs->ord.data() + t0;
-            for (int i = 0; i < nq; ++i) rq.dist_out[ord[i]] = b.hdist.p[i];
+            if (rq.dist_out)
+                for (int i = 0; i < nq; ++i) rq.dist_out[ord[i]] = b.hdist.p[i];
+            const size_t m = (size_t)rq.m;
+            for (int i = 0; i < nq && rq.witness; ++i) {
+                const size_t from = (size_t)i * kWitnessSlots, to = (size_t)ord[i] * m;
+                for (size_t v = 0; v < m && rq.w_idx; ++v) rq.w_idx[to + v] = b.hwid.p[from + v];
+                if (rq.w_dist) memcpy(rq.w_dist + to, b.hwd.p + from, sizeof(double) * m);
+                if (rq.w_alpha) memcpy(rq.w_alpha + to, b.hwalpha.p + from, sizeof(double) * m);
+            }
             return hipSuccess;
         }
         for (int j = 0; j < ns; ++j) {
@@ -3038,6 +3073,52 @@ int chb_recruit_pairs(chb_ctx *h, const int64_t *labels, int64_t B, int m, const
     ScoreRequest rq{labels, B, Y, nullptr, nullptr, P, m, nullptr, 0, nullptr, dist_out, nullptr, nullptr};
     const int rc = score_check_args(h, "chb_recruit_pairs", rq, &D, false,
                                     pairs_missing(P, row_of, bin_idx, dist_out, "row_of, bin_idx or dist_out is null"));
+    if (rc != CHB_OK) return rc;
+    if (Q < 0) return fail(CHB_EINVAL, "Q < 0");
+    for (int64_t p = 0; p < P; ++p)
+        if (row_of[p] < 0 || row_of[p] >= Q) return fail(CHB_EINVAL, "row_of entry outside [0, Q)");
+    return P == 0 ? CHB_OK : score_pairs(h, rq, row_of, bin_idx);
+}
+
+namespace {
+
+// the refusal of a witness call's null arguments: the lists, then "no witness output at all" (dist_out may be null here)
+const char *witness_missing(int64_t P, const void *row, const void *bin_idx, const void *nbr_idx, const void *nbr_dist,
+                            const void *alpha, const char *lists)
+{
+    if (P <= 0) return nullptr;
+    if (!row || !bin_idx) return lists;
+    return nbr_idx || nbr_dist || alpha ? nullptr
+        : "nbr_idx, nbr_dist and alpha are all null (the call without witnesses is the one to use)";
+}
+
+void witness_outputs(ScoreRequest &rq, int64_t *nbr_idx, double *nbr_dist, double *alpha)
+{
+    rq.witness = true; rq.w_idx = nbr_idx; rq.w_dist = nbr_dist; rq.w_alpha = alpha;
+}
+
+}  // namespace
+
+int chb_audit_pairs_witness(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
+                            const int64_t *bin_idx, int64_t P, double *dist_out, int64_t *nbr_idx, double *nbr_dist,
+                            double *alpha)
+{
+    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, P, m, nullptr, 0, nullptr, dist_out, nullptr, nullptr};
+    rq.groups = groups;   // (null: leave-one-out, the ungrouped kernel)
+    witness_outputs(rq, nbr_idx, nbr_dist, alpha);
+    const int rc = score_check_args(h, "chb_audit_pairs_witness", rq, nullptr, false,
+                                    witness_missing(P, row_idx, bin_idx, nbr_idx, nbr_dist, alpha, "row_idx or bin_idx is null"));
+    return rc != CHB_OK || P == 0 ? rc : score_pairs(h, rq, row_idx, bin_idx);
+}
+
+int chb_recruit_pairs_witness(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
+                              const int64_t *row_of, const int64_t *bin_idx, int64_t P, double *dist_out, int64_t *nbr_idx,
+                              double *nbr_dist, double *alpha)
+{
+    ScoreRequest rq{labels, B, Y, nullptr, nullptr, P, m, nullptr, 0, nullptr, dist_out, nullptr, nullptr};
+    witness_outputs(rq, nbr_idx, nbr_dist, alpha);
+    const int rc = score_check_args(h, "chb_recruit_pairs_witness", rq, &D, false,
+                                    witness_missing(P, row_of, bin_idx, nbr_idx, nbr_dist, alpha, "row_of or bin_idx is null"));
     if (rc != CHB_OK) return rc;
     if (Q < 0) return fail(CHB_EINVAL, "Q < 0");
     for (int64_t p = 0; p < P; ++p)

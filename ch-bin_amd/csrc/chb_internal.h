@@ -398,11 +398,23 @@ struct RecruitGroupArgs : RecruitPairArgs {
     const int *memb_grp;   // [n_memb] group id of memb_id's entry at the same place
     const int *grp;        // [N] group id of every resident sample: the scored rows' own
 };
+// the pair calls with witnesses (chb_*_pairs_witness; a.tile set): besides its distance every position gets a record of
+// kWitnessSlots slots, slot a = vertex a of the hull the distance was measured to -- entry a of the row's selection list,
+// in list order.  Slots [0, m) of a scored position are written, the rest never: w_id = the vertex's sample index (-1:
+// no such vertex), w_d = its selection distance (+inf), w_alpha = its weight as solve16 returned it (0).  memb_grp / grp
+// are null without groups.  (Its own struct once more: the kernels without witnesses keep the arguments they have.)
+constexpr int kWitnessSlots = 16;
+struct RecruitWitnessArgs : RecruitGroupArgs {
+    int *w_id;             // [nq][kWitnessSlots]
+    double *w_d;           // [nq][kWitnessSlots]
+    double *w_alpha;       // [nq][kWitnessSlots]
+};
 constexpr int kRecruitChunk = 16384;   // rows of Y uploaded (recruit) or positions of row_idx (audit) scored per launch
 constexpr int kRecruitMaxBins = 8192;
 void launch_recruit(const RecruitArgs &a, hipStream_t s);   // (a.qid set: the audit instantiation)
 void launch_recruit_pairs(const RecruitPairArgs &a, hipStream_t s);
 void launch_recruit_grouped(const RecruitGroupArgs &a, hipStream_t s);   // (a.tile set: the pairs' instantiation)
+void launch_recruit_witness(const RecruitWitnessArgs &a, hipStream_t s);   // (a.qid / a.memb_grp choose the instantiation)
 // bin[q] = strict-'>' argmin over dist[q][0 .. B) (-1: all +inf), mind[q] its distance, margin[q] = runner-up minus it (+inf
 // without a finite runner-up)
 void launch_recruit_reduce(const double *dist, int nq, int B, int *bin, double *mind, double *margin, hipStream_t s);

@@ -33,6 +33,9 @@
 // The chb_*_grouped calls run the resident instantiations with one more exclusion (template parameter kGrouped): besides
 // the row itself every sample that shares the row's group id -- the sibling pieces of one parent contig -- is withheld.
 //
+// chb_audit_pairs_witness / chb_recruit_pairs_witness run the pairs' kernel body with one more output (template parameter
+// kWitness): per pair the vertices the distance was measured to, their selection distances and their weights.
+//
 // chb_bin_report runs the audit's two kernels on positions grouped by their own label and a third, bin_report_kernel
 // (below), that folds each chunk's distances and bins into B x B tables keyed (own label, bin).
 #include "chb_internal.h"
@@ -98,14 +101,24 @@ union RecruitLds {
 // the solve depend on the list alone, so a row's result is what the ungrouped kernel gives on labels from which the
 // row's group has been taken out.  The `false` instantiations are unchanged: every place sits behind
 // `if constexpr (kGrouped)`.
-template <bool kGrouped, bool kPairs>
-using recruit_args_t = std::conditional_t<kGrouped, RecruitGroupArgs, std::conditional_t<kPairs, RecruitPairArgs, RecruitArgs>>;
+//
+// kWitness (chb_*_pairs_witness, pairs only): what the solve knew and the plain kernels drop.  In phase 2 lane (kq, row)
+// holds vertex `row` of its group's problem: its sample id (idv[0]), its selection distance -- select_into keeps the
+// ROOTED distance in ld[], entry tx of row 4 ty + i, and tx == row, ty == 4 w + kq: the same lane -- and, behind solve16,
+// its weight.  ld[] is kept alive past the tile loop (wdv[], shifted with nn[] / idv[]) and the lanes row < m store the
+// three to slot `row` of the position's record (RecruitWitnessArgs), padding where row >= n: plain vector stores, one
+// record per pair.  Nothing that the distance depends on differs, so a pair's distance has the plain pair kernel's bits.
+// The `false` instantiations are unchanged: every place sits behind `if constexpr (kWitness)`.
+template <bool kGrouped, bool kPairs, bool kWitness>
+using recruit_args_t = std::conditional_t<kWitness, RecruitWitnessArgs,
+    std::conditional_t<kGrouped, RecruitGroupArgs, std::conditional_t<kPairs, RecruitPairArgs, RecruitArgs>>>;
 
-template <bool kResident, bool kMulti, bool kPairs, bool kGrouped = false>
-__global__ __launch_bounds__(256, 2) void recruit_kernel(recruit_args_t<kGrouped, kPairs> a, int nqt, int total)
+template <bool kResident, bool kMulti, bool kPairs, bool kGrouped = false, bool kWitness = false>
+__global__ __launch_bounds__(256, 2) void recruit_kernel(recruit_args_t<kGrouped, kPairs, kWitness> a, int nqt, int total)
 {
     static_assert(!(kMulti && kPairs), "pairs are scored for a single m");
     static_assert(kResident || !kGrouped, "groups are a property of the resident samples");
+    static_assert(kPairs || !kWitness, "witnesses travel with the pair calls: one record per listed pair");
     __shared__ __attribute__((aligned(16))) RecruitLds lds;
 
     // XCD-aware order: blocks b and b+8 share an XCD (and its L2), so hand each XCD a contiguous range of work
@@ -255,6 +268,11 @@ __global__ __launch_bounds__(256, 2) void recruit_kernel(recruit_args_t<kGrouped
     int nn[4], idv[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) { nn[i] = lc[i]; idv[i] = tx < lc[i] ? li[i] : -1; }
+    [[maybe_unused]] double wdv[4];   // (kWitness: the selection distance of my list entry, next to idv)
+    if constexpr (kWitness) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) wdv[i] = tx < lc[i] ? ld[i] : kInf;
+    }
     const int row = lane & 15, kq = lane >> 4;
     const int Dk = (a.D + 7) & ~7;
 #pragma unroll 1
@@ -315,10 +333,22 @@ __global__ __launch_bounds__(256, 2) void recruit_kernel(recruit_args_t<kGrouped
             }
         } else {
         double dist = kInf;
+        [[maybe_unused]] double wal = 0.0;   // (kWitness: my vertex's weight)
         if (n > 0) {
             double alpha = 0.0;
             const double val = solve16(&lds.so.Qt[w][kq][0][0], &lds.so.sv[w][kq][0], n, a.metric, lane, alpha);
             dist = sqrt(fmax(val, 0.0));
+            if constexpr (kWitness) wal = alpha;
+        }
+        if constexpr (kWitness) {
+            // slot `row` of the position's record (qpos < a.nq: a tile's counted rows lie inside its chunk)
+            if (4 * ty + i < nrow && row < m) {
+                const size_t o = (size_t)qpos * kWitnessSlots + row;
+                const bool real = row < n;
+                a.w_id[o] = real ? idm : -1;
+                a.w_d[o] = real ? wdv[0] : kInf;
+                a.w_alpha[o] = real ? wal : 0.0;
+            }
         }
         if constexpr (kPairs) {
             if (tx == 0 && 4 * ty + i < nrow) a.dist[qpos] = dist;
@@ -330,6 +360,7 @@ __global__ __launch_bounds__(256, 2) void recruit_kernel(recruit_args_t<kGrouped
         nn[0] = nn[1]; nn[1] = nn[2]; nn[2] = nn[3];
         idv[0] = idv[1]; idv[1] = idv[2]; idv[2] = idv[3];
         if constexpr (kResident) { own[0] = own[1]; own[1] = own[2]; own[2] = own[3]; }
+        if constexpr (kWitness) { wdv[0] = wdv[1]; wdv[1] = wdv[2]; wdv[2] = wdv[3]; }
     }   // (owng[] is dead behind the tile loop: nothing to shift)
 }
 
@@ -500,6 +531,16 @@ void launch_recruit_grouped(const RecruitGroupArgs &a, hipStream_t s)
     const int grid = ((total + 7) / 8) * 8;
     if (a.mmask) hipLaunchKernelGGL((recruit_kernel<true, true, false, true>), dim3(grid), dim3(256), 0, s, a, nqt, total);
     else hipLaunchKernelGGL((recruit_kernel<true, false, false, true>), dim3(grid), dim3(256), 0, s, a, nqt, total);
+}
+
+// the pair kernels that also store every position's witness record
+void launch_recruit_witness(const RecruitWitnessArgs &a, hipStream_t s)
+{
+    if (a.nq <= 0 || a.ntile <= 0) return;
+    const int grid = ((a.ntile + 7) / 8) * 8;
+    if (!a.qid) hipLaunchKernelGGL((recruit_kernel<false, false, true, false, true>), dim3(grid), dim3(256), 0, s, a, 0, a.ntile);
+    else if (a.memb_grp) hipLaunchKernelGGL((recruit_kernel<true, false, true, true, true>), dim3(grid), dim3(256), 0, s, a, 0, a.ntile);
+    else hipLaunchKernelGGL((recruit_kernel<true, false, true, false, true>), dim3(grid), dim3(256), 0, s, a, 0, a.ntile);
 }
 
 void launch_recruit_reduce(const double *dist, int nq, int B, int *bin, double *mind, double *margin, hipStream_t s)

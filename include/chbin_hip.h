@@ -279,6 +279,51 @@ int chb_bin_report_grouped(chb_ctx *h, const int64_t *labels, const int64_t *gro
                            int64_t *confusion, int64_t *unplaced, int64_t *dcnt, double *dmin, double *dsum,
                            int64_t *n_skipped);
 
+/* Witnesses for pair scoring: the pair calls' distances together with what each was measured against -- which members of
+ * the bin form the hull, how far each is from the row, and with what weights they make the hull's nearest point.  The
+ * plain pair calls compute all of it and return one double; these return it, one record of m slots per pair.
+ *   - dist_out[p] (P doubles; may be NULL here) is bit for bit what the matching plain call returns for pair p, +inf
+ *     included: chb_audit_pairs (groups == NULL), chb_audit_pairs_grouped (groups != NULL: the withheld set W(r) above) or
+ *     chb_recruit_pairs, on the same other arguments and metric;
+ *   - nbr_idx[p*m + a] is the sample index of vertex a of the hull that distance was measured to: the members the kernel
+ *     selected for the pair, in the order of its own list, after the call's withholding (the row itself; with groups also
+ *     its group; nothing for chb_recruit_pairs_witness -- a new row equal to a sample has that sample as a vertex at
+ *     distance 0).  Slots at or past the number of members left are -1 (chb_topm_per_bin's convention): fewer than m real
+ *     slots mean the bin had no more members to offer, and a pair with none has dist_out +inf and every slot padding.
+ *     The list's order is (distance, sample index) ascending, where "distance" is the ROOTED value reported in nbr_dist,
+ *     not the squared sum under it: two members whose squared sums differ but round to the same square root are ordered
+ *     by index.  That is chb_topm_per_bin's order too (both keep their lists with the same code);
+ *   - nbr_dist[p*m + a] is that member's Euclidean distance to the row in the selection arithmetic -- the correctly
+ *     rounded sqrt of the k-sequential unfused sum of squared differences, chb_pairwise_distance's entry bit for bit.
+ *     Padding is +inf;
+ *   - alpha[p*m + a] is the weight of vertex a in the nearest point of the hull under the context's metric
+ *     (chb_set_metric), exactly as the solver that produced dist_out returned it: the nearest point is
+ *     sum_a alpha[p*m + a] X[nbr_idx[p*m + a]] and dist_out[p] its distance from the row, up to the solver's tolerance.
+ *     Padding is 0.  Convex metric: the weights are >= 0 and sum to 1; a weight of exactly 0 means the vertex is not in
+ *     the solver's support.  Affine metric: they sum to 1 and may be negative (the nearest point of the affine hull need
+ *     not lie between the vertices).  Where the vertices are dependent -- twins with equal coordinates, more vertices than
+ *     dimensions allow -- the nearest point is unique but the weights are not: any optimal vector is a valid answer and
+ *     the one returned is whichever the active-set iteration ended on;
+ *   - each of nbr_idx, nbr_dist, alpha may be NULL; with P > 0 all three NULL is CHB_EINVAL (the call without witnesses is
+ *     the one to use).  Outputs are in the caller's pair order; pairs may repeat and get equal records;
+ *   - every other rule is the plain pair call's, in its order, on the host before anything is enqueued: m <= 16 and
+ *     B <= 8192 (CHB_EUNSUPPORTED beyond); CHB_ESTATE without resident samples or while a stepwise fit is open (the fit
+ *     stays usable); bin_idx in [0, B), row_idx in [0, N), row_of in [0, Q), D the resident samples' (CHB_EINVAL); P = 0 a
+ *     no-op; no state of a fit is used and nothing of the context changes but the counter "pair_tiles"; no collective;
+ *   - chunks, tiles and streams are the pair calls' (bin order, tiles of at most 64 pairs, chunks of whole tiles up to 16384
+ *     pairs), one launch per chunk under the plain calls' profile names "audit_pairs" / "recruit_pairs".  On the device a
+ *     pair's record is 16 slots in each of three arrays (int32 index, double distance, double weight: 320 bytes per pair)
+ *     of which the kernel writes the first m; the arrays the caller asked for come down on the copy stream through pinned
+ *     buffers of their own and the host unpack compacts 16 slots to m and int32 to int64.  These buffers are allocated by
+ *     a context's first witness call: a context that never makes one allocates nothing more than before. */
+int chb_audit_pairs_witness(chb_ctx *h, const int64_t *labels, const int64_t *groups /* may be NULL */,
+                            int64_t B, int m, const int64_t *row_idx, const int64_t *bin_idx, int64_t P,
+                            double *dist_out, int64_t *nbr_idx, double *nbr_dist, double *alpha);
+int chb_recruit_pairs_witness(chb_ctx *h, const int64_t *labels, int64_t B, int m,
+                              const double *Y, int64_t Q, int64_t D,
+                              const int64_t *row_of, const int64_t *bin_idx, int64_t P,
+                              double *dist_out, int64_t *nbr_idx, double *nbr_dist, double *alpha);
+
 /* distance_matrix.py:47-62 find_nearest_from_cluster with the reference's exact signature: the
  * caller supplies one row of a distance matrix (any provenance) and the current labels; selects
  * among {p : labels[p] == c} the (up to) m smallest by (row[p], p).  out_idx[m] (-1 padded). */
