@@ -120,32 +120,47 @@ __device__ __forceinline__ double min_norm_point(const double (&Q)[Sym<M>::NP], 
         for (int i = 0; i < M; ++i) alpha[i] = (i == 0) ? 1.0 : 0.0;
         return scale == 0.0 ? 0.0 : scale;
     }
-    unsigned S = 1u << i0, banned = 0u;
+    // Full-set start: the first cycle has no entering vertex (jb = -1) -- it solves on all m vertices from the uniform
+    // weights.  All beta > 0 (a query inside its neighbours' cloud: the rule, see DESIGN.md section 5, "Solver start") ends
+    // the method after this one solve, where growing the support from the nearest vertex takes one solve per vertex of
+    // it; some beta <= 0 runs Wolfe's minor cycles down from the full set; a collapsed pivot (an affinely dependent set:
+    // duplicates, m > D + 1) starts again from the nearest vertex alone, which adds one vertex per major cycle and bans
+    // the dependent ones.
+    unsigned S = (1u << m) - 1u, banned = 0u;
+    const double uni = 1.0 / (double)m;
 #pragma unroll
-    for (int i = 0; i < M; ++i) alpha[i] = (i == i0) ? 1.0 : 0.0;
+    for (int i = 0; i < M; ++i) alpha[i] = i < m ? uni : 0.0;
     const double tol = 1.4210854715202004e-14 * scale;  // 64 eps * scale
 
-    for (int it = 0; it < 3 * M + 8; ++it) {
-        double g[M];
-        double val = 0.0;
-#pragma unroll
-        for (int i = 0; i < M; ++i) {
-            double gi = 0.0;
-#pragma unroll
-            for (int j = 0; j < M; ++j) gi += Q[Sym<M>::at(i, j)] * alpha[j];
-            g[i] = gi;
-            val += alpha[i] * gi;
-        }
+    for (int it = -1; it < 3 * M + 8; ++it) {
         int jb = -1;
-        double gmin = kInf;
+        if (it >= 0) {
+            double g[M];
+            double val = 0.0;
 #pragma unroll
-        for (int i = 0; i < M; ++i)
-            if (i < m && !(((S | banned) >> i) & 1u) && g[i] < gmin) { gmin = g[i]; jb = i; }
-        if (jb < 0 || !(gmin < val - tol)) break;
-        S |= 1u << jb;
+            for (int i = 0; i < M; ++i) {
+                double gi = 0.0;
+#pragma unroll
+                for (int j = 0; j < M; ++j) gi += Q[Sym<M>::at(i, j)] * alpha[j];
+                g[i] = gi;
+                val += alpha[i] * gi;
+            }
+            double gmin = kInf;
+#pragma unroll
+            for (int i = 0; i < M; ++i)
+                if (i < m && !(((S | banned) >> i) & 1u) && g[i] < gmin) { gmin = g[i]; jb = i; }
+            if (jb < 0 || !(gmin < val - tol)) break;
+            S |= 1u << jb;
+        }
         for (int mi = 0; mi <= M; ++mi) {
             double beta[M];
             if (!solve_affine<M>(Q, scale, S, beta)) {
+                if (jb < 0) {   // the full-set start met a dependent set: the nearest vertex alone
+                    S = 1u << i0;
+#pragma unroll
+                    for (int i = 0; i < M; ++i) alpha[i] = (i == i0) ? 1.0 : 0.0;
+                    break;
+                }
                 S &= ~(1u << jb);
                 banned |= 1u << jb;
                 break;
@@ -155,8 +170,10 @@ __device__ __forceinline__ double min_norm_point(const double (&Q)[Sym<M>::NP], 
             for (int i = 0; i < M; ++i)
                 if (((S >> i) & 1u) && !(beta[i] > 0.0)) allpos = false;
             if (allpos) {
+                // (the full-set start cut down to one vertex: its weight is 1, as where the method starts from that vertex)
+                const bool one = jb < 0 && (S & (S - 1u)) == 0u;
 #pragma unroll
-                for (int i = 0; i < M; ++i) alpha[i] = ((S >> i) & 1u) ? beta[i] : 0.0;
+                for (int i = 0; i < M; ++i) alpha[i] = ((S >> i) & 1u) ? (one ? 1.0 : beta[i]) : 0.0;
                 break;
             }
             double theta = 1.0;
@@ -557,11 +574,15 @@ __device__ __forceinline__ double diag_rows8(const double *X, int Dp, int Dk, in
 // arithmetic, ~1e-15 relative, comes out of that slack).  That covers the m nearest, and any (m+1)-th candidate that the
 // kTieRel = 1e-11 test could call a tie of the m-th.  So the selected set, the tie hand-off to the exact path and the hull's
 // vertex set are what they are without the trim; only the slot a Gram entry is summed in can differ (its last bit).
-// A pair keeps its survivors (at most kTrimKeep, in shortlist order) in LDS and is classed by their number; one with more
-// survivors stays as it was.
+// A pair keeps its survivors (at most kTrimKeep, in shortlist order) in the LDS id list and is classed by their number; one
+// with more survivors stays as it was.
+// The LDS id list (sIds) also takes the ids of every untrimmed pair of at most kTrimKeep candidates: at classification the
+// lane that owns the pair loads them (all 64 pairs of the wavefront in one round trip), so that a pass starts on its row
+// sweep without a dependent global load of the ids first.  Only pairs of kTrimKeep < n <= 16 candidates fetch theirs in
+// the pass.
 constexpr int kTrimMax = 32;     // two candidates per lane of a 16-lane group
-constexpr int kTrimKeep = 8;     // ids per pair in LDS
-constexpr int kNbTrimmed = -1;   // base count of a trimmed pair in the passes: its ids come from the LDS list
+constexpr int kTrimKeep = 8;     // ids per pair in the LDS list
+constexpr int kNbInLds = -1;     // base count of a pair in the passes whose ids come from the LDS list
 constexpr double kTrimSlack = 1e-6;
 constexpr double kTrimGamma = 2.5e-5;   // fp32 summation of up to 161 terms (kGamma of prefilter_kernels.hip)
 
@@ -632,6 +653,7 @@ __global__ __launch_bounds__(64 * WAVES, CHB_FUSED_OCC) void hull_select_qp_kern
     constexpr int NR = (NPC + 15) / 16;
     constexpr int NCLS = C - M + 1;            // classes of the one-sweep form: widths M, M + 1, ..., C
     static_assert(C <= 8 && M <= C && C - M <= 3, "candidate Gram in registers");
+    static_assert(C <= kTrimKeep, "the narrow passes take their ids from the LDS list");
     __shared__ double sQ[WAVES][NPM][65];   // (65: the 16 lanes of a group store 16 entries of ONE problem column -- a stride of 64 doubles would put them all on one bank)
     __shared__ double sT[WAVES][4][NR * 16];   // candidate Gram of the group's pair
     __shared__ double sTh[WAVES][4][2];        // squared distances of ranks m-1 and m
@@ -639,7 +661,7 @@ __global__ __launch_bounds__(64 * WAVES, CHB_FUSED_OCC) void hull_select_qp_kern
     __shared__ int sN[WAVES][64];
     __shared__ int sOrd[WAVES][64];            // problem (lane) of each work position, narrow shortlists first
     __shared__ int sSlowN, sSlowBase;
-    __shared__ int sTrim[WAVES][64][kTrimKeep];   // the survivors of a trimmed pair (see "Trim" above)
+    __shared__ int sIds[WAVES][64][kTrimKeep];    // candidate ids of a pair with at most kTrimKeep of them (see "Trim" above)
     __shared__ int sTrimN[WAVES][64];             // ... their number; 0: the pair is not trimmed
     __shared__ int sTrimCtr[3];                   // pairs through the trim, their candidates before and after
 
@@ -781,8 +803,8 @@ __global__ __launch_bounds__(64 * WAVES, CHB_FUSED_OCC) void hull_select_qp_kern
                     const unsigned b0 = (unsigned)(__ballot(k0) >> gbase) & 0xffffu, b1 = (unsigned)(__ballot(k1) >> gbase) & 0xffffu;
                     const int nk = badm != 0u ? n_g : __popc(b0) + __popc(b1);
                     if (has && badm == 0u && nk <= kTrimKeep) {
-                        if (k0) sTrim[w][pl][__popc(b0 & ((1u << l16) - 1u))] = id0;
-                        if (k1) sTrim[w][pl][__popc(b0) + __popc(b1 & ((1u << l16) - 1u))] = id1;
+                        if (k0) sIds[w][pl][__popc(b0 & ((1u << l16) - 1u))] = id0;
+                        if (k1) sIds[w][pl][__popc(b0) + __popc(b1 & ((1u << l16) - 1u))] = id1;
                         if (l16 == 0) sTrimN[w][pl] = nk;
                     }
                     if (has && l16 == 0) { c_pairs += 1; c_in += n_g; c_kept += nk; }
@@ -794,8 +816,16 @@ __global__ __launch_bounds__(64 * WAVES, CHB_FUSED_OCC) void hull_select_qp_kern
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_s_waitcnt(0xC07F);
                 const int nt = sTrimN[w][lane];
-                if (nt > 0) { n = nt; nb = kNbTrimmed; }
+                if (nt > 0) { n = nt; nb = kNbInLds; }
             }
+        }
+        // ---- ids of the untrimmed pairs with at most kTrimKeep candidates: base ids, then the batch-entry ids, loaded by the
+        // pair's own lane into the LDS list (the wild-index check stays where a pass reads them)
+        if (changed && nb != kNbInLds && n > 0 && n <= kTrimKeep) {
+#pragma unroll
+            for (int i = 0; i < kTrimKeep; ++i)
+                if (i < n) sIds[w][lane][i] = i < nb ? a.cand[slot * kCandCap + i] : a.candu[slot * kCandCapU + (i - nb)];
+            nb = kNbInLds;
         }
         // class 0: nothing to compute here.  Classes 1 .. NCLS: ONE sweep over max(n, M) = M + k - 1 candidate
         // rows (full candidate Gram).  Class NCLS + 1 (C < n <= 16): a distance sweep over all candidates,
@@ -827,13 +857,9 @@ __global__ __launch_bounds__(64 * WAVES, CHB_FUSED_OCC) void hull_select_qp_kern
             const int pl = has ? sOrd[w][op] : 0;
             const int n_s = __shfl(n, pl, 64);
             const int n_g = has ? n_s : 0;
-            const int nb_g = __shfl(nb, pl, 64);
             const int qid_g = __shfl(qid, pl, 64);
-            const size_t slot_g = (size_t)__shfl(c, pl, 64) * a.Kcap + (size_t)__shfl(pos, pl, 64);
             int idm = -1;
-            if (l16 < n_g)
-                idm = nb_g == kNbTrimmed ? sTrim[w][pl][l16]
-                      : l16 < nb_g ? a.cand[slot_g * kCandCap + l16] : a.candu[slot_g * kCandCapU + (l16 - nb_g)];
+            if (l16 < n_g) idm = sIds[w][pl][l16];   // (n_g <= C <= kTrimKeep: every narrow pair's ids are in the LDS list)
             if ((unsigned)idm >= (unsigned)a.n_samples && idm != -1) {   // never a row address from a wild index
                 if (a.short_cnt != nullptr) atomicAdd(a.short_cnt, 1);
                 idm = -1;
@@ -915,7 +941,7 @@ __global__ __launch_bounds__(64 * WAVES, CHB_FUSED_OCC) void hull_select_qp_kern
             const size_t slot_g = (size_t)__shfl(c, pl, 64) * a.Kcap + (size_t)__shfl(pos, pl, 64);
             int idm = -1;
             if (l16 < n_g)
-                idm = nb_g == kNbTrimmed ? sTrim[w][pl][l16]
+                idm = nb_g == kNbInLds ? sIds[w][pl][l16]
                       : l16 < nb_g ? a.cand[slot_g * kCandCap + l16] : a.candu[slot_g * kCandCapU + (l16 - nb_g)];
             if ((unsigned)idm >= (unsigned)a.n_samples && idm != -1) {   // never a row address from a wild index
                 if (a.short_cnt != nullptr) atomicAdd(a.short_cnt, 1);
