@@ -69,6 +69,11 @@ SIGNATURES = {
     "chb_recruit_pairs_witness": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
                                             C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]),
+    # the k nearest bins per row: the dense calls' arguments with k after m and the two [Q, k] arrays (groups may be NULL)
+    "chb_audit_rows_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_int64, C.c_void_p, C.c_void_p]),
+    "chb_recruit_rows_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64,
+                                           C.c_int64, C.c_void_p, C.c_void_p]),
     "chb_find_nearest_from_row": (C.c_int, [C.c_void_p, C.c_int64, _i64p, _f64p, C.c_int64, C.c_int,
                                             _i64p, C.POINTER(C.c_int32)]),
     "chb_hull_distance_batch": (C.c_int, [C.c_void_p, _i64p, C.c_int64, _i64p, C.c_int, _f64p,
@@ -415,6 +420,37 @@ class Context:
                                                   row_of.ctypes.data, bins.ctypes.data, row_of.shape[0],
                                                   dist.ctypes.data, idx.ctypes.data, nd.ctypes.data, alpha.ctypes.data))
         return dist, idx, nd, alpha
+
+    @staticmethod
+    def _nearest_arrays(Q, k):
+        """bins [Q, k] and dist [Q, k] of a nearest-bins call (refused calls write nothing: k as given, at least 0)"""
+        k = max(int(k), 0)
+        return np.empty((Q, k), dtype=np.int64), np.empty((Q, k), dtype=np.float64)
+
+    def audit_rows_nearest(self, labels, B, m, k, rows=None, groups=None):
+        """chb_audit_rows_nearest: the k nearest bins of every RESIDENT row in `rows` (None: every row in order), ranked on
+        the device: the finite entries of audit_rows' (with `groups` audit_rows_grouped's) dist row in (distance, bin)
+        order, bit for bit.  Returns (bins [Q, k], dist [Q, k]); slots past the number of finite entries hold -1 / +inf."""
+        labels = self._labels(labels)
+        if groups is not None:
+            groups = self._groups(groups)
+        row_idx, Q, rows = self._row_indices(rows)
+        bins, dist = self._nearest_arrays(Q, k)
+        check(self._lib.chb_audit_rows_nearest(self._h, labels.ctypes.data, None if groups is None else groups.ctypes.data,
+                                               int(B), int(m), int(k), row_idx, Q, bins.ctypes.data, dist.ctypes.data))
+        return bins, dist
+
+    def recruit_rows_nearest(self, labels, B, m, k, Y):
+        """chb_recruit_rows_nearest: audit_rows_nearest for the NEW rows Y (nothing is withheld), ranked from
+        recruit_rows' dist rows.  Returns (bins [Q, k], dist [Q, k])."""
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim != 2:
+            raise ValueError("rows must be a 2-D array")
+        labels = self._labels(labels)
+        bins, dist = self._nearest_arrays(Y.shape[0], k)
+        check(self._lib.chb_recruit_rows_nearest(self._h, labels.ctypes.data, int(B), int(m), int(k), Y.ctypes.data,
+                                                 *Y.shape, bins.ctypes.data, dist.ctypes.data))
+        return bins, dist
 
     def find_nearest_from_row(self, c, labels, row, m):
         labels = np.ascontiguousarray(labels, dtype=np.int64)

@@ -2,6 +2,7 @@
 argument meaning and error behaviour) on top of libchbin_hip.so."""
 from .algorithm import (  # noqa: F401
     BinReport,
+    NearestBins,
     NeighborSweep,
     Witness,
     audit,
@@ -9,9 +10,11 @@ from .algorithm import (  # noqa: F401
     bin_report,
     cohesion,
     fit_cluster,
+    nearest_bins,
     neighbor_sweep,
     parent_groups,
     recruit,
+    recruit_nearest_bins,
     recruit_pairs,
     recruit_witness,
     witness,

@@ -483,3 +483,101 @@ def recruit_witness(
     ctx.set_samples_cached(samples)
     with ctx.using_metric(metric):
         return Witness(*ctx.recruit_pairs_witness(labels, int(num_clusters), int(num_neighbors), new_rows, row_of, bins))
+
+
+@dataclasses.dataclass
+class NearestBins:
+    """What `nearest_bins` / `recruit_nearest_bins` return: per scored row its k nearest bins, nearest first.  Plain numpy,
+    nothing here touches the GPU.
+
+    bins [n, k], dist [n, k]: the finite entries of the row's distances to every bin (`audit` / `recruit` with
+    return_distances, bit for bit) in (distance, bin) order -- exact ties go to the lower bin.  A row with fewer than k
+    bins at a finite distance is padded with bin -1 at distance +inf.  Slot 0 is the bin `audit` / `recruit` choose."""
+    bins: np.ndarray
+    dist: np.ndarray
+
+    @property
+    def count(self) -> np.ndarray:
+        """[n]: the real slots of each row (0: no bin has a member to offer)."""
+        return np.count_nonzero(self.bins >= 0, axis=1)
+
+    @property
+    def margin(self) -> np.ndarray:
+        """[n]: dist[:, 1] - dist[:, 0], `audit`'s margin bit for bit; +inf for a row without a runner-up."""
+        if self.bins.shape[1] < 2:
+            raise ValueError("the margin needs the runner-up: ask for k >= 2")
+        out = np.full(self.bins.shape[0], np.inf)
+        real = self.bins[:, 1] >= 0
+        out[real] = self.dist[real, 1] - self.dist[real, 0]
+        return out
+
+    def ambiguous(self, tol: float, relative: bool = False) -> np.ndarray:
+        """[n] bool: the rows whose runner-up is within `tol` of their nearest bin (relative: within tol times the nearest
+        bin's distance).  A row without a runner-up is never ambiguous."""
+        margin = self.margin
+        real = self.bins[:, 1] >= 0
+        out = np.zeros(self.bins.shape[0], dtype=bool)
+        out[real] = margin[real] <= (tol * self.dist[real, 0] if relative else tol)
+        return out
+
+    def pairs(self, ranks=(0, 1), mask=None):
+        """(positions, bins): the real entries of the slots `ranks` of the rows `mask` selects (bool [n]; None: all), row
+        by row -- the two lists `audit_pairs` / `witness` take once positions are turned into sample indices
+        (rows[positions]; positions themselves for rows=None), and `recruit_pairs` / `recruit_witness` take as they are
+        (row_of = positions)."""
+        ranks = np.asarray(ranks, dtype=np.int64).reshape(-1)
+        take = self.bins[:, ranks] >= 0
+        if mask is not None:
+            take &= np.asarray(mask, dtype=bool)[:, None]
+        pos, slot = np.nonzero(take)
+        return pos.astype(np.int64), self.bins[pos, ranks[slot]].astype(np.int64)
+
+
+def nearest_bins(
+    samples: np.ndarray,
+    labels: np.ndarray,
+    num_clusters: int,
+    k: int = 3,
+    num_neighbors: int = 15,
+    metric: str = "convex",
+    qp_solver: str = "quadprog",
+    rows: np.ndarray = None,
+    groups: np.ndarray = None,
+) -> NearestBins:
+    """Which bins come next (no counterpart in the reference): `audit` on the same arguments, returning per row the k
+    nearest bins with their leave-one-out hull distances instead of the nearest alone -- ranked on the device, so the
+    len(rows) x num_clusters table never crosses to the host.  With `groups` the distances are leave-group-out.
+    Nothing changes."""
+    if metric not in ("convex", "affine", "affine-qp"):
+        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
+    check_solver(qp_solver)                                              # solve_qp.py:132
+
+    samples = np.ascontiguousarray(samples, dtype=np.float64)
+    ctx = default_context()
+    ctx.set_samples_cached(samples)
+    with ctx.using_metric(metric):
+        return NearestBins(*ctx.audit_rows_nearest(labels, int(num_clusters), int(num_neighbors), int(k), rows, groups=groups))
+
+
+def recruit_nearest_bins(
+    samples: np.ndarray,
+    labels: np.ndarray,
+    rows: np.ndarray,
+    num_clusters: int,
+    k: int = 3,
+    num_neighbors: int = 15,
+    metric: str = "convex",
+    qp_solver: str = "quadprog",
+) -> NearestBins:
+    """`nearest_bins` for `rows` that are NOT samples: `recruit` on the same arguments, returning per row the k nearest
+    bins with their hull distances.  Nothing is withheld and nothing changes."""
+    if metric not in ("convex", "affine", "affine-qp"):
+        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
+    check_solver(qp_solver)                                              # solve_qp.py:132
+
+    samples = np.ascontiguousarray(samples, dtype=np.float64)
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    ctx = default_context()
+    ctx.set_samples_cached(samples)
+    with ctx.using_metric(metric):
+        return NearestBins(*ctx.recruit_rows_nearest(labels, int(num_clusters), int(num_neighbors), int(k), rows))

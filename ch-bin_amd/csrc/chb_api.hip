@@ -276,6 +276,12 @@ struct ChunkHalf {
     DevBuf<double> wd, walpha;
     PinBuf<int> hwid;
     PinBuf<double> hwd, hwalpha;
+    // chb_*_rows_nearest only (first allocated by the context's first such call): the chunk's k nearest bins per row and
+    // their distances
+    DevBuf<int> nbin;
+    DevBuf<double> ndist;
+    PinBuf<int> hnbin;
+    PinBuf<double> hndist;
     hipEvent_t up = nullptr, done = nullptr, down = nullptr;
     int nseg = 0, ntile = 0;
     void destroy_events() { for (hipEvent_t ev : {up, done, down}) if (ev) (void)hipEventDestroy(ev); }
@@ -2558,10 +2564,15 @@ struct ScoreRequest {
     // their weights ([Q][m] each, in the caller's order; each may be null, not all three); dist_out may then be null
     bool witness = false;
     int64_t *w_idx = nullptr; double *w_dist = nullptr, *w_alpha = nullptr;
+    // chb_*_rows_nearest: a dense call whose rows are ranked on the device in place of the row reduction; per row the
+    // near_k nearest bins and their distances ([Q][near_k] each, either may be null, not both).  nearest marks the call
+    bool nearest = false;
+    int near_k = 0;
+    int64_t *near_bin = nullptr; double *near_dist = nullptr;
 };
 
 // The argument checks of the entry points, for all of them in this order: null context; ranges and a malformed list
-// (CHB_EINVAL); null arguments (a grouped call's groups, whatever Q, among them); outputs; no samples; D; more than 16 neighbours (CHB_EUNSUPPORTED); more than 8192 bins;
+// (CHB_EINVAL; a nearest-bins call's k < 1 among them); null arguments (a grouped call's groups, whatever Q, among them); outputs; no samples; D; more than 16 neighbours (CHB_EUNSUPPORTED), then a nearest-bins call's k > 16; more than 8192 bins;
 // an open stepwise fit; Q == 0 (CHB_OK: nothing further is read); the row_idx rules.
 // D: the rows' number of columns in the calls that take Y, nullptr in the others.  list: the call takes ms / nm, whose
 // largest entry becomes rq.m.  no_output: the refusal's text when every output that counts for the call is null, else nullptr.
@@ -2584,12 +2595,14 @@ int score_check_args(chb_ctx *h, const char *who, ScoreRequest &rq, const int64_
     } else if (rq.Q < 0 || rq.B < 1 || rq.m < 1) {
         return fail(CHB_EINVAL, "Q < 0, B < 1 or m < 1");
     }
+    if (rq.nearest && rq.near_k < 1) return fail(CHB_EINVAL, "k < 1");
     if (rq.Q > 0 && (!rq.labels || (D && !rq.Y))) return fail(CHB_EINVAL, "null argument");
     if (rq.grouped && !rq.groups) return fail(CHB_EINVAL, std::string(who) + ": groups is null (the call without groups is the one to use)");
     if (no_output) return fail(CHB_EINVAL, no_output);
     if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
     if (D && *D != h->D) return fail(CHB_EINVAL, "the rows must have the resident samples' number of columns");
     if (rq.m > kMaxM) return fail(CHB_EUNSUPPORTED, std::string(who) + " supports at most 16 neighbours");
+    if (rq.nearest && rq.near_k > kMaxNearest) return fail(CHB_EUNSUPPORTED, std::string(who) + " supports at most 16 nearest bins (k)");
     if (rq.B > kRecruitMaxBins) return fail(CHB_EUNSUPPORTED, std::string(who) + " supports at most 8192 bins");
     if (h->batch.open || (h->fit_open && h->stepwise))
         return fail(CHB_ESTATE, "a stepwise fit is open on this context (chb_fit_begin): chb_set_samples ends it");
@@ -2609,7 +2622,7 @@ struct ScoreRun {
     const ScoreRequest rq;
     RowScoring &sc = h->score;
     hipStream_t s = h->stream;
-    const bool audit = !rq.Y /* the rows are resident */, any_out = rq.bin_out || rq.dist_out || rq.min_dist_out || rq.margin_out || rq.witness;
+    const bool audit = !rq.Y /* the rows are resident */, any_out = rq.bin_out || rq.dist_out || rq.min_dist_out || rq.margin_out || rq.witness || rq.nearest;
     const int ns = rq.nm > 0 ? rq.nm : 1;   // result slices per chunk
     const size_t width = rq.pairs ? 1 : (size_t)rq.B;   // distances per result row
     int slot[kMaxM] = {0};                  // list entry j's slice on the device = the number of smaller entries
@@ -2708,6 +2721,14 @@ struct ScoreRun {
                     if (rq.w_dist) HIPCHK(b.hwd.ensure(slots));
                     if (rq.w_alpha) HIPCHK(b.hwalpha.ensure(slots));
                 }
+                continue;
+            }
+            if (rq.nearest) {   // the ranked slots in place of the row reduction's three arrays
+                const size_t slots = (size_t)chunk * (size_t)rq.near_k;
+                HIPCHK(b.nbin.ensure(slots));
+                HIPCHK(b.ndist.ensure(slots));
+                if (rq.near_bin) HIPCHK(b.hnbin.ensure(slots));
+                if (rq.near_dist) HIPCHK(b.hndist.ensure(slots));
                 continue;
             }
             HIPCHK(b.bin.ensure(res));
@@ -2872,7 +2893,11 @@ struct ScoreRun {
                     (double)nq * (double)rq.B * (double)ns);
             if (a.memb_grp) launch_recruit_grouped(a, s);
             else launch_recruit(a, s);
-            launch_recruit_reduce(b.dist.p, nq * ns, (int)rq.B, b.bin.p, b.min.p, b.margin.p, s);
+            if (!rq.nearest) launch_recruit_reduce(b.dist.p, nq * ns, (int)rq.B, b.bin.p, b.min.p, b.margin.p, s);
+        }
+        if (rq.nearest) {   // the same table, ranked in place of the reduction (whose outputs nobody would read)
+            Timed t(h, "nearest_bins", (double)nq * (double)rq.B);
+            launch_nearest_bins(b.dist.p, nq, (int)rq.B, rq.near_k, b.nbin.p, b.ndist.p, s);
         }
         if (rq.plan) {
             const BinReportArgs r{b.dist.p, b.bin.p, b.seg.p, b.nseg, (int)rq.B,
@@ -2897,6 +2922,9 @@ struct ScoreRun {
         if (rq.w_idx) HIPTRY(hipMemcpyAsync(b.hwid.p, b.wid.p, sizeof(int) * slots, hipMemcpyDeviceToHost, c));
         if (rq.w_dist) HIPTRY(hipMemcpyAsync(b.hwd.p, b.wd.p, sizeof(double) * slots, hipMemcpyDeviceToHost, c));
         if (rq.w_alpha) HIPTRY(hipMemcpyAsync(b.hwalpha.p, b.walpha.p, sizeof(double) * slots, hipMemcpyDeviceToHost, c));
+        const size_t near = nr * (size_t)rq.near_k;   // (a nearest-bins call: nr rows)
+        if (rq.near_bin) HIPTRY(hipMemcpyAsync(b.hnbin.p, b.nbin.p, sizeof(int) * near, hipMemcpyDeviceToHost, c));
+        if (rq.near_dist) HIPTRY(hipMemcpyAsync(b.hndist.p, b.ndist.p, sizeof(double) * near, hipMemcpyDeviceToHost, c));
         return hipEventRecord(b.down, c);
     }
     // (a list of m: ns slices of nq rows each, on the device in ascending order of m; slice slot[j] goes to out + j * Q + t0;
@@ -2919,6 +2947,12 @@ struct ScoreRun {
                 if (rq.w_dist) memcpy(rq.w_dist + to, b.hwd.p + from, sizeof(double) * m);
                 if (rq.w_alpha) memcpy(rq.w_alpha + to, b.hwalpha.p + from, sizeof(double) * m);
             }
+            return hipSuccess;
+        }
+        if (rq.nearest) {   // near_k slots per row, in the caller's row order already
+            const size_t near = (size_t)nq * (size_t)rq.near_k, to = (size_t)t0 * (size_t)rq.near_k;
+            for (size_t i = 0; i < near && rq.near_bin; ++i) rq.near_bin[to + i] = b.hnbin.p[i];
+            if (rq.near_dist) memcpy(rq.near_dist + to, b.hndist.p, sizeof(double) * near);
             return hipSuccess;
         }
         for (int j = 0; j < ns; ++j) {
@@ -3124,6 +3158,33 @@ int chb_recruit_pairs_witness(chb_ctx *h, const int64_t *labels, int64_t B, int 
     for (int64_t p = 0; p < P; ++p)
         if (row_of[p] < 0 || row_of[p] >= Q) return fail(CHB_EINVAL, "row_of entry outside [0, Q)");
     return P == 0 ? CHB_OK : score_pairs(h, rq, row_of, bin_idx);
+}
+
+namespace {
+
+// the two nearest-bins calls: the dense call's request with the ranked outputs in place of the reduced ones
+int score_nearest(chb_ctx *h, const char *who, ScoreRequest &rq, const int64_t *D, int k, int64_t *near_bin, double *near_dist)
+{
+    rq.nearest = true; rq.near_k = k; rq.near_bin = near_bin; rq.near_dist = near_dist;
+    const int rc = score_check_args(h, who, rq, D, false, near_bin || near_dist ? nullptr : "near_bin and near_dist are both null");
+    return rc != CHB_OK || rq.Q == 0 ? rc : ScoreRun{h, rq}.run();
+}
+
+}  // namespace
+
+int chb_audit_rows_nearest(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, int k,
+                           const int64_t *row_idx, int64_t Q, int64_t *near_bin, double *near_dist)
+{
+    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, m, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
+    rq.groups = groups;   // (null: leave-one-out, the ungrouped kernel)
+    return score_nearest(h, "chb_audit_rows_nearest", rq, nullptr, k, near_bin, near_dist);
+}
+
+int chb_recruit_rows_nearest(chb_ctx *h, const int64_t *labels, int64_t B, int m, int k, const double *Y, int64_t Q, int64_t D,
+                             int64_t *near_bin, double *near_dist)
+{
+    ScoreRequest rq{labels, B, Y, nullptr, nullptr, Q, m, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
+    return score_nearest(h, "chb_recruit_rows_nearest", rq, &D, k, near_bin, near_dist);
 }
 
 int chb_find_nearest_from_row(chb_ctx *h, int64_t c, const int64_t *labels, const double *row,

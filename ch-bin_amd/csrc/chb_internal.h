@@ -418,6 +418,11 @@ void launch_recruit_witness(const RecruitWitnessArgs &a, hipStream_t s);   // (a
 // bin[q] = strict-'>' argmin over dist[q][0 .. B) (-1: all +inf), mind[q] its distance, margin[q] = runner-up minus it (+inf
 // without a finite runner-up)
 void launch_recruit_reduce(const double *dist, int nq, int B, int *bin, double *mind, double *margin, hipStream_t s);
+// chb_*_rows_nearest: the finite entries of dist[q][0 .. B) ranked by (distance, bin) ascending; nb_dist[q*k + j] is the
+// j-th distance bit for bit, nb_bin[q*k + j] its bin, and slots at or past the number of finite entries hold -1 / +inf.
+// 1 <= k <= kMaxNearest
+constexpr int kMaxNearest = 16;
+void launch_nearest_bins(const double *dist, int nq, int B, int k, int *nb_bin, double *nb_dist, hipStream_t s);
 
 // ---- bin report (recruit_kernels.hip, chb_bin_report): an audit chunk's dist[nq][B] and bin[nq] folded into B x B tables
 // keyed (the row's own label, bin).  The chunk's positions are grouped by label; seg names each label's run.

@@ -38,6 +38,9 @@
 //
 // chb_bin_report runs the audit's two kernels on positions grouped by their own label and a third, bin_report_kernel
 // (below), that folds each chunk's distances and bins into B x B tables keyed (own label, bin).
+//
+// chb_audit_rows_nearest / chb_recruit_rows_nearest run the dense kernel and, in place of the row reduction,
+// nearest_bins_kernel (below): each row's k least finite distances with their bins, in (distance, bin) order.
 #include "chb_internal.h"
 #include "hull_solve16.h"
 
@@ -399,6 +402,103 @@ __global__ __launch_bounds__(256) void recruit_reduce_kernel(const double *dist,
     margin[q] = runner == kInf ? kInf : runner - best;
 }
 
+// chb_*_rows_nearest: the k nearest bins of every row of dist[nrows][B], ranked where the table lies.
+//
+// select_into's insertion scheme on the plain value: the 16 lanes of a group offer up to NC (distance, bin) candidates
+// each to the group's list, lane t of which holds entry t; the list is ordered by lex_less on (distance, bin) -- a total
+// order, the bins of a row being distinct -- and keeps the k <= 16 least.  +inf is "no candidate": it never enters the
+// list.  No sqrt (the table holds distances) and no tau_from slack (what is compared is what is stored).  A sibling of
+// select_into, which is compiled as it was.  Wave-synchronous; all 64 lanes must call it together.
+template <int NC>
+__device__ __forceinline__ void select_near(double (&s)[NC], const int (&cb)[NC], double &ld, int &li, int &lc, double &e,
+                                            int &ei, int k, int tx, int gbase)
+{
+    // (e, ei): the list's k-th entry, kept by the caller from call to call; (+inf, INT_MAX) while the list is short: every
+    // finite candidate is less
+#pragma unroll
+    for (int j = 0; j < NC; ++j)
+        if (!(s[j] < kInf) || !lex_less(s[j], cb[j], e, ei)) s[j] = kInf;
+    for (;;) {
+        double bs = s[0];
+        int bi = cb[0], bj = 0;
+#pragma unroll
+        for (int j = 1; j < NC; ++j)
+            if (lex_less(s[j], cb[j], bs, bi)) { bs = s[j]; bi = cb[j]; bj = j; }
+        if (!__any(bs < kInf)) break;   // (the common round once the lists are full: no lane of the wavefront has a survivor)
+        double gs = bs;
+        int gi = bi;
+#pragma unroll
+        for (int off = 8; off >= 1; off >>= 1) {
+            const double os = __shfl_xor(gs, off, 16);
+            const int oi = __shfl_xor(gi, off, 16);
+            if (lex_less(os, oi, gs, gi)) { gs = os; gi = oi; }
+        }
+        const bool have = gs < kInf;   // (false for the groups without a survivor while another group has one)
+        if (have && bs == gs && bi == gi) {
+#pragma unroll
+            for (int j = 0; j < NC; ++j)
+                if (j == bj) s[j] = kInf;
+        }
+        const bool lt = (tx < lc) && lex_less(ld, li, gs, gi);
+        const unsigned long long bal = __ballot(lt);
+        const int pos = __popcll((bal >> gbase) & 0xffffull);
+        const double ud = __shfl_up(ld, 1, 16);
+        const int ui = __shfl_up(li, 1, 16);
+        const bool ins = have && pos < k;   // (pos < k: a candidate that is not less than a full list's k-th entry was dropped)
+        if (ins) {
+            if (tx == pos) { ld = gs; li = gi; }
+            else if (tx > pos) { ld = ud; li = ui; }
+            lc = lc + 1 < k ? lc + 1 : k;
+        }
+        e = __shfl(ld, k - 1, 16);
+        ei = __shfl(li, k - 1, 16);
+        if (ins && lc >= k) {
+#pragma unroll
+            for (int j = 0; j < NC; ++j)
+                if (!lex_less(s[j], cb[j], e, ei)) s[j] = kInf;
+        }
+    }
+}
+
+// 16 lanes per row, four rows per wavefront, sixteen per workgroup; the list lives in registers, there is no LDS.  A round
+// covers kNearPer * 16 consecutive bins of the row: load j of lane t is bin c0 + 16 j + t, so the 16 lanes of a row read 128
+// consecutive bytes per load, and the next round's loads are issued ahead of this round's insertions.  A bin at or past B
+// is +inf without a load.  Every wavefront runs the same ceil(B / 64) rounds: a row at or past nrows scans the last
+// row (all 64 lanes stay in the cross-lane calls) and stores nothing.  Lanes t < k store slot t: plain vector stores, bin
+// -1 and +inf at or past the number of finite entries.
+constexpr int kNearPer = 4;
+__global__ __launch_bounds__(256) void nearest_bins_kernel(const double *dist, int nrows, int B, int k, int *nb_bin,
+                                                           double *nb_dist)
+{
+    const int tx = threadIdx.x & 15, gbase = threadIdx.x & 48;
+    const int q = (int)blockIdx.x * 16 + (int)(threadIdx.x >> 4);
+    const bool valid = q < nrows;
+    const double *row = dist + (size_t)(valid ? q : nrows - 1) * (size_t)B;
+    double ld = kInf, e = kInf;   // my list entry; the list's k-th entry
+    int li = INT_MAX, lc = 0, ei = INT_MAX;
+    double nx[kNearPer];
+    auto load = [&](int c0) {
+#pragma unroll
+        for (int j = 0; j < kNearPer; ++j) {
+            const int c = c0 + 16 * j + tx;
+            nx[j] = c < B ? row[c] : kInf;
+        }
+    };
+    load(0);
+    for (int c0 = 0; c0 < B; c0 += 16 * kNearPer) {
+        double s[kNearPer];
+        int cb[kNearPer];
+#pragma unroll
+        for (int j = 0; j < kNearPer; ++j) { s[j] = nx[j]; cb[j] = c0 + 16 * j + tx; }
+        if (c0 + 16 * kNearPer < B) load(c0 + 16 * kNearPer);
+        select_near<kNearPer>(s, cb, ld, li, lc, e, ei, k, tx, gbase);
+    }
+    if (!valid || tx >= k) return;
+    const size_t o = (size_t)q * (size_t)k + (size_t)tx;
+    nb_bin[o] = tx < lc ? li : -1;
+    nb_dist[o] = tx < lc ? ld : kInf;
+}
+
 // chb_bin_report: one chunk's dist[nq][B] and bin[nq] folded into the B x B tables keyed (the row's own label, bin).
 //
 // The chunk's positions are grouped by label (the host sorts them), seg names each label's run.  One workgroup owns
@@ -547,6 +647,12 @@ void launch_recruit_reduce(const double *dist, int nq, int B, int *bin, double *
 {
     if (nq <= 0) return;
     hipLaunchKernelGGL(recruit_reduce_kernel, dim3((nq + 31) / 32), dim3(256), 0, s, dist, nq, B, bin, mind, margin);
+}
+
+void launch_nearest_bins(const double *dist, int nq, int B, int k, int *nb_bin, double *nb_dist, hipStream_t s)
+{
+    if (nq <= 0 || B <= 0 || k <= 0) return;
+    hipLaunchKernelGGL(nearest_bins_kernel, dim3((nq + 15) / 16), dim3(256), 0, s, dist, nq, B, k, nb_bin, nb_dist);
 }
 
 }  // namespace chb

@@ -324,6 +324,40 @@ int chb_recruit_pairs_witness(chb_ctx *h, const int64_t *labels, int64_t B, int 
                               const int64_t *row_of, const int64_t *bin_idx, int64_t P,
                               double *dist_out, int64_t *nbr_idx, double *nbr_dist, double *alpha);
 
+/* Nearest bins per row: the k closest bins of every row with their distances, ranked on the device -- "which bin, and
+ * which bins come next" without the Q x B table crossing the host boundary (shortlists of (row, bin) pairs for the pair
+ * and witness calls, soft membership, recruits whose second choice is as close as their first).
+ * Both calls are defined by the dense call on the same arguments and metric: chb_audit_rows (groups == NULL),
+ * chb_audit_rows_grouped (groups != NULL: the withheld set W(r) above) or chb_recruit_rows.  With d[.] that call's dist_out
+ * row for position q:
+ *   - the FINITE entries are ranked by (d[c], c) ascending: a total order, exact ties go to the lower bin;
+ *   - near_dist[q*k + j] is the j-th distance, bit for bit, and near_bin[q*k + j] its bin;
+ *   - slots at or past the number of finite entries hold bin -1 and distance +inf.  k > B is allowed and pads.  There is
+ *     no NaN: every distance is sqrt(fmax(val, 0)).
+ * So slot 0 is the dense call's bin_out / min_dist_out, and near_dist[q*k + 1] - near_dist[q*k] is its margin_out bit for
+ * bit where slot 1 is real (the margin is +inf where it is not).
+ *   - near_bin, near_dist: Q*k each; either may be NULL, both NULL is CHB_EINVAL;
+ *   - k < 1 is CHB_EINVAL (with the range checks of Q, B and m); k > 16 is CHB_EUNSUPPORTED, right behind m > 16;
+ *   - every other rule is the dense call's, in its order, on the host before anything is enqueued: row_idx == NULL means
+ *     all rows and Q must then be N; every row_idx[q] in [0, N); D the resident samples' (CHB_EINVAL); B <= 8192
+ *     (CHB_EUNSUPPORTED beyond); CHB_ESTATE without resident samples or while a stepwise fit is open (the fit stays
+ *     usable); Q = 0 is a no-op; no collective; the call uses no state of a fit and leaves every counter, memo and switch
+ *     of the context as it found it;
+ *   - chunks, streams and events are the dense calls' (16384 rows per chunk).  Per chunk the dense call's kernel runs
+ *     under its profile name "audit" / "recruit" and leaves the chunk's rows x B table on the device; a second kernel,
+ *     profile name "nearest_bins" (work units = (row, bin) pairs), ranks it there in place of the row reduction: 16 lanes
+ *     per row keep the row's sorted list in registers.  k int32 bins and k doubles per row come down through pinned
+ *     buffers of their own -- 12 k bytes per row instead of 8 B -- and the host unpack widens int32 to int64.  The table
+ *     itself is never copied and no pinned memory is held for it.  The buffers are allocated by a context's first such
+ *     call: a context that never makes one allocates nothing more than before.
+ * There is no list-of-m form, no pair form and no bin-report form. */
+int chb_audit_rows_nearest(chb_ctx *h, const int64_t *labels, const int64_t *groups /* may be NULL */,
+                           int64_t B, int m, int k, const int64_t *row_idx, int64_t Q,
+                           int64_t *near_bin, double *near_dist);
+int chb_recruit_rows_nearest(chb_ctx *h, const int64_t *labels, int64_t B, int m, int k,
+                             const double *Y, int64_t Q, int64_t D,
+                             int64_t *near_bin, double *near_dist);
+
 /* distance_matrix.py:47-62 find_nearest_from_cluster with the reference's exact signature: the
  * caller supplies one row of a distance matrix (any provenance) and the current labels; selects
  * among {p : labels[p] == c} the (up to) m smallest by (row[p], p).  out_idx[m] (-1 padded). */
@@ -488,7 +522,9 @@ int chb_profile_reset(chb_ctx *h);
  * (chb_audit_rows_multi / chb_recruit_rows_multi: the same pair of launches for one chunk and a list of m; work units =
  * (row, bin, m) triples) | "audit_pairs" / "recruit_pairs" (chb_audit_pairs / chb_recruit_pairs: the one launch of a chunk;
  * work units = pairs) | "bin_report" (chb_bin_report: the launch
- * that folds one chunk's distances and bins into the B x B tables; work units = (row, bin) pairs).  For m <= 16 "hull_qp" is the fused selection + hull-distance kernel and
+ * that folds one chunk's distances and bins into the B x B tables; work units = (row, bin) pairs) | "nearest_bins"
+ * (chb_audit_rows_nearest / chb_recruit_rows_nearest: the launch that ranks one chunk's rows x B table, behind the dense
+ * kernel booked under "audit" / "recruit"; work units = (row, bin) pairs).  For m <= 16 "hull_qp" is the fused selection + hull-distance kernel and
  * "slow_path" the exact path for what it leaves over; "rescore*" then only appear for m > 16 or CHB_FUSED=0. */
 int chb_profile_get(chb_ctx *h, const char *kernel, double *total_ms, int64_t *launches,
                     double *work_units);
