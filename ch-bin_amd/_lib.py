@@ -74,6 +74,16 @@ SIGNATURES = {
                                          C.c_int64, C.c_void_p, C.c_void_p]),
     "chb_recruit_rows_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64,
                                            C.c_int64, C.c_void_p, C.c_void_p]),
+    # one entry point for every m up to 64: the dense and pair calls' arguments (groups may be NULL), the pair forms with
+    # idx_out [P, m] at the end (may be NULL)
+    "chb_audit_rows_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "chb_recruit_rows_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "chb_audit_pairs_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_int64, C.c_void_p, C.c_void_p]),
+    "chb_recruit_pairs_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                         C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "chb_find_nearest_from_row": (C.c_int, [C.c_void_p, C.c_int64, _i64p, _f64p, C.c_int64, C.c_int,
                                             _i64p, C.POINTER(C.c_int32)]),
     "chb_hull_distance_batch": (C.c_int, [C.c_void_p, _i64p, C.c_int64, _i64p, C.c_int, _f64p,
@@ -451,6 +461,71 @@ class Context:
         check(self._lib.chb_recruit_rows_nearest(self._h, labels.ctypes.data, int(B), int(m), int(k), Y.ctypes.data,
                                                  *Y.shape, bins.ctypes.data, dist.ctypes.data))
         return bins, dist
+
+    def audit_rows_wide(self, labels, B, m, rows=None, want_dist=True, groups=None):
+        """chb_audit_rows_wide: audit_rows (with `groups` audit_rows_grouped) for any m in 1 .. 64 -- m <= 16 forwards to
+        those calls bit for bit, 16 < m <= 64 runs the wide kernels.  Returns what audit_rows returns."""
+        labels = self._labels(labels)
+        if groups is not None:
+            groups = self._groups(groups)
+        row_idx, Q, rows = self._row_indices(rows)
+        bins = np.empty(Q, dtype=np.int64)
+        dist = np.empty((Q, int(B)), dtype=np.float64) if want_dist else None
+        mind = np.empty(Q, dtype=np.float64)
+        margin = np.empty(Q, dtype=np.float64)
+        check(self._lib.chb_audit_rows_wide(self._h, labels.ctypes.data, None if groups is None else groups.ctypes.data,
+                                            int(B), int(m), row_idx, Q, bins.ctypes.data,
+                                            None if dist is None else dist.ctypes.data, mind.ctypes.data, margin.ctypes.data))
+        return bins, dist, mind, margin
+
+    def recruit_rows_wide(self, labels, B, m, Y, want_dist=True):
+        """chb_recruit_rows_wide: recruit_rows for any m in 1 .. 64.  Returns what recruit_rows returns."""
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim != 2:
+            raise ValueError("rows must be a 2-D array")
+        labels = self._labels(labels)
+        Q = Y.shape[0]
+        bins = np.empty(Q, dtype=np.int64)
+        dist = np.empty((Q, int(B)), dtype=np.float64) if want_dist else None
+        mind = np.empty(Q, dtype=np.float64)
+        margin = np.empty(Q, dtype=np.float64)
+        check(self._lib.chb_recruit_rows_wide(self._h, labels.ctypes.data, int(B), int(m), Y.ctypes.data, *Y.shape,
+                                              bins.ctypes.data, None if dist is None else dist.ctypes.data,
+                                              mind.ctypes.data, margin.ctypes.data))
+        return bins, dist, mind, margin
+
+    def audit_pairs_wide(self, labels, B, m, rows, bins, groups=None, want_idx=False):
+        """chb_audit_pairs_wide: audit_pairs (with `groups` audit_pairs_grouped) for any m in 1 .. 64; entry p is bit for
+        bit audit_rows_wide(labels, B, m, rows, groups=groups)[1][p, bins[p]].  Returns dist [P], or with want_idx
+        (dist, idx [P, m]): per pair the selected members' sample indices in (distance, index) order, -1 padded -- what
+        topm_per_bin returns for the row."""
+        rows, bins = self._pair_lists(rows, bins, "rows")
+        labels = self._labels(labels)
+        if groups is not None:
+            groups = self._groups(groups)
+        P = rows.shape[0]
+        dist = np.empty(P, dtype=np.float64)
+        idx = np.empty((P, max(int(m), 0)), dtype=np.int64) if want_idx else None
+        check(self._lib.chb_audit_pairs_wide(self._h, labels.ctypes.data, None if groups is None else groups.ctypes.data,
+                                             int(B), int(m), rows.ctypes.data, bins.ctypes.data, P, dist.ctypes.data,
+                                             None if idx is None else idx.ctypes.data))
+        return (dist, idx) if want_idx else dist
+
+    def recruit_pairs_wide(self, labels, B, m, Y, row_of, bins, want_idx=False):
+        """chb_recruit_pairs_wide: recruit_pairs for any m in 1 .. 64; entry p is bit for bit
+        recruit_rows_wide(labels, B, m, Y)[1][row_of[p], bins[p]].  Returns dist [P] or, with want_idx, (dist, idx [P, m])."""
+        row_of, bins = self._pair_lists(row_of, bins, "row_of")
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim != 2:
+            raise ValueError("rows must be a 2-D array")
+        labels = self._labels(labels)
+        P = row_of.shape[0]
+        dist = np.empty(P, dtype=np.float64)
+        idx = np.empty((P, max(int(m), 0)), dtype=np.int64) if want_idx else None
+        check(self._lib.chb_recruit_pairs_wide(self._h, labels.ctypes.data, int(B), int(m), Y.ctypes.data, *Y.shape,
+                                               row_of.ctypes.data, bins.ctypes.data, P, dist.ctypes.data,
+                                               None if idx is None else idx.ctypes.data))
+        return (dist, idx) if want_idx else dist
 
     def find_nearest_from_row(self, c, labels, row, m):
         labels = np.ascontiguousarray(labels, dtype=np.int64)

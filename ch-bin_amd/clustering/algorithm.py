@@ -66,6 +66,12 @@ def fit_cluster(
     return labels
 
 
+# audit / recruit / audit_pairs / recruit_pairs / cohesion: up to this many neighbours the calls they have always made;
+# beyond it (up to 64; the library refuses more) the chb_*_wide calls.  bin_report, neighbor_sweep, witness and
+# nearest_bins have no wide form and keep refusing more than 16.
+_TILED_MAX_NEIGHBORS = 16
+
+
 def recruit(
     samples: np.ndarray,
     labels: np.ndarray,
@@ -91,8 +97,8 @@ def recruit(
     ctx = default_context()
     ctx.set_samples_cached(samples)
     with ctx.using_metric(metric):
-        bins, dist, _, _ = ctx.recruit_rows(labels, int(num_clusters), int(num_neighbors), rows,
-                                            want_dist=return_distances)
+        score = ctx.recruit_rows_wide if int(num_neighbors) > _TILED_MAX_NEIGHBORS else ctx.recruit_rows
+        bins, dist, _, _ = score(labels, int(num_clusters), int(num_neighbors), rows, want_dist=return_distances)
     return (bins, dist) if return_distances else bins
 
 
@@ -128,7 +134,10 @@ def audit(
     ctx = default_context()
     ctx.set_samples_cached(samples)
     with ctx.using_metric(metric):
-        if groups is None:
+        if int(num_neighbors) > _TILED_MAX_NEIGHBORS:
+            bins, dist, mind, margin = ctx.audit_rows_wide(labels, int(num_clusters), int(num_neighbors), rows,
+                                                           want_dist=return_distances, groups=groups)
+        elif groups is None:
             bins, dist, mind, margin = ctx.audit_rows(labels, int(num_clusters), int(num_neighbors), rows,
                                                       want_dist=return_distances)
         else:
@@ -306,6 +315,8 @@ def audit_pairs(
     ctx = default_context()
     ctx.set_samples_cached(samples)
     with ctx.using_metric(metric):
+        if int(num_neighbors) > _TILED_MAX_NEIGHBORS:
+            return ctx.audit_pairs_wide(labels, int(num_clusters), int(num_neighbors), rows, bins, groups=groups)
         if groups is None:
             return ctx.audit_pairs(labels, int(num_clusters), int(num_neighbors), rows, bins)
         return ctx.audit_pairs_grouped(labels, groups, int(num_clusters), int(num_neighbors), rows, bins)
@@ -336,6 +347,8 @@ def recruit_pairs(
     ctx = default_context()
     ctx.set_samples_cached(samples)
     with ctx.using_metric(metric):
+        if int(num_neighbors) > _TILED_MAX_NEIGHBORS:
+            return ctx.recruit_pairs_wide(labels, int(num_clusters), int(num_neighbors), new_rows, row_of, bins)
         return ctx.recruit_pairs(labels, int(num_clusters), int(num_neighbors), new_rows, row_of, bins)
 
 
@@ -371,7 +384,10 @@ def cohesion(
     ctx = default_context()
     ctx.set_samples_cached(samples)
     with ctx.using_metric(metric):
-        if groups is None:
+        if int(num_neighbors) > _TILED_MAX_NEIGHBORS:
+            out[scored] = ctx.audit_pairs_wide(labels, int(num_clusters), int(num_neighbors), rows[scored], own[scored],
+                                               groups=groups)
+        elif groups is None:
             out[scored] = ctx.audit_pairs(labels, int(num_clusters), int(num_neighbors), rows[scored], own[scored])
         else:
             out[scored] = ctx.audit_pairs_grouped(labels, groups, int(num_clusters), int(num_neighbors), rows[scored],

@@ -282,6 +282,10 @@ struct ChunkHalf {
     DevBuf<double> ndist;
     PinBuf<int> hnbin;
     PinBuf<double> hndist;
+    // chb_*_pairs_wide only (first allocated by the context's first such call): the chunk's selection lists, m + 1 ints
+    // per position (RecruitWideArgs), per half because idx_out copies them down while the next chunk's kernels run
+    DevBuf<int> wlist;
+    PinBuf<int> hwlist;
     hipEvent_t up = nullptr, done = nullptr, down = nullptr;
     int nseg = 0, ntile = 0;
     void destroy_events() { for (hipEvent_t ev : {up, done, down}) if (ev) (void)hipEventDestroy(ev); }
@@ -301,6 +305,11 @@ struct RowScoring {
     hipStream_t copy = nullptr;
     int64_t multi_rows = 0;   // rows per launch of the last chb_audit_rows_multi / chb_recruit_rows_multi
     int64_t pair_tiles = 0;   // tiles (work items) of the last chb_audit_pairs / chb_recruit_pairs
+    // the dense wide calls (16 < m <= 64): the selection lists of one chunk, rows x B x (m + 1) ints within kWideListBytes
+    // (one buffer: a chunk's kernels follow the previous chunk's on the stream and nothing copies it down); first
+    // allocated by the context's first such call
+    DevBuf<int> wlist;
+    int64_t wide_rows = 0;    // rows per launch of the last wide call
 };
 
 // Multi-GPU: one context per process per GPU, RCCL communicator over all ranks
@@ -2569,11 +2578,17 @@ struct ScoreRequest {
     bool nearest = false;
     int near_k = 0;
     int64_t *near_bin = nullptr; double *near_dist = nullptr;
+    // chb_*_wide with 16 < m <= 64: the two wide kernels per chunk in place of recruit_kernel; the pair forms may return
+    // the selection lists ([Q][m], -1 padded, in the caller's order)
+    bool wide = false;
+    int64_t *idx_out = nullptr;
 };
 
 // The argument checks of the entry points, for all of them in this order: null context; ranges and a malformed list
 // (CHB_EINVAL; a nearest-bins call's k < 1 among them); null arguments (a grouped call's groups, whatever Q, among them); outputs; no samples; D; more than 16 neighbours (CHB_EUNSUPPORTED), then a nearest-bins call's k > 16; more than 8192 bins;
 // an open stepwise fit; Q == 0 (CHB_OK: nothing further is read); the row_idx rules.
+// (A wide call, rq.wide: more than 64 neighbours, then more than 32 on a device without the LDS for 64 vertices, in place of
+// "more than 16".)
 // D: the rows' number of columns in the calls that take Y, nullptr in the others.  list: the call takes ms / nm, whose
 // largest entry becomes rq.m.  no_output: the refusal's text when every output that counts for the call is null, else nullptr.
 int score_check_args(chb_ctx *h, const char *who, ScoreRequest &rq, const int64_t *D, bool list, const char *no_output)
@@ -2601,7 +2616,11 @@ int score_check_args(chb_ctx *h, const char *who, ScoreRequest &rq, const int64_
     if (no_output) return fail(CHB_EINVAL, no_output);
     if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
     if (D && *D != h->D) return fail(CHB_EINVAL, "the rows must have the resident samples' number of columns");
-    if (rq.m > kMaxM) return fail(CHB_EUNSUPPORTED, std::string(who) + " supports at most 16 neighbours");
+    if (rq.wide) {   // (the wide calls: the limit lifted to 64, and the LDS the 64-vertex solve kernel needs)
+        if (rq.m > kMaxMGeneric) return fail(CHB_EUNSUPPORTED, std::string(who) + " supports at most 64 neighbours");
+        if (rq.m > 32 && !hull_generic_supported())
+            return fail(CHB_EUNSUPPORTED, std::string(who) + ": more than 32 neighbours need 66 KiB of LDS per workgroup, which this device does not grant");
+    } else if (rq.m > kMaxM) return fail(CHB_EUNSUPPORTED, std::string(who) + " supports at most 16 neighbours");
     if (rq.nearest && rq.near_k > kMaxNearest) return fail(CHB_EUNSUPPORTED, std::string(who) + " supports at most 16 nearest bins (k)");
     if (rq.B > kRecruitMaxBins) return fail(CHB_EUNSUPPORTED, std::string(who) + " supports at most 8192 bins");
     if (h->batch.open || (h->fit_open && h->stepwise))
@@ -2622,7 +2641,7 @@ struct ScoreRun {
     const ScoreRequest rq;
     RowScoring &sc = h->score;
     hipStream_t s = h->stream;
-    const bool audit = !rq.Y /* the rows are resident */, any_out = rq.bin_out || rq.dist_out || rq.min_dist_out || rq.margin_out || rq.witness || rq.nearest;
+    const bool audit = !rq.Y /* the rows are resident */, any_out = rq.bin_out || rq.dist_out || rq.min_dist_out || rq.margin_out || rq.witness || rq.nearest || rq.idx_out;
     const int ns = rq.nm > 0 ? rq.nm : 1;   // result slices per chunk
     const size_t width = rq.pairs ? 1 : (size_t)rq.B;   // distances per result row
     int slot[kMaxM] = {0};                  // list entry j's slice on the device = the number of smaller entries
@@ -2693,7 +2712,11 @@ struct ScoreRun {
     {
         const int64_t B = rq.B;
         if (rq.nm > 0) sc.multi_rows = std::max<int64_t>(kQTile, kRecruitChunk / rq.nm / kQTile * kQTile);
-        chunk = rq.pairs ? rq.pairs->max_rows : std::min<int64_t>(rq.Q, rq.nm > 0 ? sc.multi_rows : kRecruitChunk);
+        if (rq.wide) {   // the largest multiple of 64 rows whose lists fit the buffer, in [64, 16384]
+            const int64_t fit = kWideListBytes / ((int64_t)width * (rq.m + 1) * (int64_t)sizeof(int)) / kQTile * kQTile;
+            sc.wide_rows = std::min<int64_t>(kRecruitChunk, std::max<int64_t>(kQTile, fit));
+        }
+        chunk = rq.pairs ? rq.pairs->max_rows : std::min<int64_t>(rq.Q, rq.nm > 0 ? sc.multi_rows : rq.wide ? sc.wide_rows : kRecruitChunk);
         n = rq.pairs ? (int64_t)rq.pairs->cut.size() - 1 : rq.plan ? (int64_t)rq.plan->cut.size() - 1 : (rq.Q + chunk - 1) / chunk;
         const size_t res = (size_t)chunk * (size_t)ns;   // result rows of a chunk
         const int halves = rq.Q > chunk ? 2 : 1;   // (a plan's longest chunk is shorter than Q whenever it has a second)
@@ -2703,6 +2726,7 @@ struct ScoreRun {
             HIPCHK(sc.mgrp.ensure(n_memb));
             HIPCHK(sc.grp.ensure((size_t)h->N));
         }
+        if (rq.wide && !rq.pairs) HIPCHK(sc.wlist.ensure((size_t)chunk * width * (size_t)(rq.m + 1)));
         for (int i = 0; i < halves; ++i) {
             ChunkHalf &b = sc.half[i];
             HIPCHK(rq.Y ? b.Y.ensure((size_t)chunk * h->Dp) : b.qid.ensure((size_t)chunk));
@@ -2712,6 +2736,10 @@ struct ScoreRun {
             if (rq.pairs) {   // the tile table, and no row reduction
                 HIPCHK(b.tile.ensure((size_t)rq.pairs->max_tiles));
                 HIPCHK(b.htile.ensure((size_t)rq.pairs->max_tiles));
+                if (rq.wide) {
+                    HIPCHK(b.wlist.ensure((size_t)chunk * (size_t)(rq.m + 1)));
+                    if (rq.idx_out) HIPCHK(b.hwlist.ensure((size_t)chunk * (size_t)(rq.m + 1)));
+                }
                 if (rq.witness) {   // the records: the kernel writes all three, what the caller wants comes down
                     const size_t slots = (size_t)chunk * kWitnessSlots;
                     HIPCHK(b.wid.ensure(slots));
@@ -2880,7 +2908,24 @@ struct ScoreRun {
         if (any_out) HIPTRY(hipStreamWaitEvent(s, b.down, 0));   // (chunk k - 2 has been copied out of this half's results)
         a.Y = audit ? nullptr : b.Y.p; a.qid = audit ? b.qid.p : nullptr; a.dist = b.dist.p; a.nq = nq;
         // (with groups: the same launches, the leave-group-out instantiation of the kernel)
-        if (rq.pairs) {   // one launch: the tiles' kernel, no row reduction behind it
+        if (rq.wide) {   // selection, solve and -- dense -- the row reduction; the work of both is the (row, bin) problems
+            RecruitWideArgs wa{};
+            static_cast<RecruitGroupArgs &>(wa) = a;
+            wa.tile = rq.pairs ? b.tile.p : nullptr; wa.ntile = rq.pairs ? b.ntile : 0;
+            wa.list = rq.pairs ? b.wlist.p : sc.wlist.p;
+            const double work = (double)nq * (double)width;
+            {
+                Timed t(h, rq.pairs ? (audit ? "audit_pairs_wide_select" : "recruit_pairs_wide_select")
+                                    : (audit ? "audit_wide_select" : "recruit_wide_select"), work);
+                launch_recruit_select_wide(wa, s);
+            }
+            {
+                Timed t(h, rq.pairs ? (audit ? "audit_pairs_wide_solve" : "recruit_pairs_wide_solve")
+                                    : (audit ? "audit_wide_solve" : "recruit_wide_solve"), work);
+                launch_hull_wide(wa, s);
+            }
+            if (!rq.pairs) launch_recruit_reduce(b.dist.p, nq, (int)rq.B, b.bin.p, b.min.p, b.margin.p, s);
+        } else if (rq.pairs) {   // one launch: the tiles' kernel, no row reduction behind it
             a.tile = b.tile.p; a.ntile = b.ntile;
             Timed t(h, audit ? "audit_pairs" : "recruit_pairs", (double)nq);
             if (rq.witness) {
@@ -2922,6 +2967,7 @@ struct ScoreRun {
         if (rq.w_idx) HIPTRY(hipMemcpyAsync(b.hwid.p, b.wid.p, sizeof(int) * slots, hipMemcpyDeviceToHost, c));
         if (rq.w_dist) HIPTRY(hipMemcpyAsync(b.hwd.p, b.wd.p, sizeof(double) * slots, hipMemcpyDeviceToHost, c));
         if (rq.w_alpha) HIPTRY(hipMemcpyAsync(b.hwalpha.p, b.walpha.p, sizeof(double) * slots, hipMemcpyDeviceToHost, c));
+        if (rq.idx_out) HIPTRY(hipMemcpyAsync(b.hwlist.p, b.wlist.p, sizeof(int) * nr * (size_t)(rq.m + 1), hipMemcpyDeviceToHost, c));
         const size_t near = nr * (size_t)rq.near_k;   // (a nearest-bins call: nr rows)
         if (rq.near_bin) HIPTRY(hipMemcpyAsync(b.hnbin.p, b.nbin.p, sizeof(int) * near, hipMemcpyDeviceToHost, c));
         if (rq.near_dist) HIPTRY(hipMemcpyAsync(b.hndist.p, b.ndist.p, sizeof(double) * near, hipMemcpyDeviceToHost, c));
@@ -2941,6 +2987,8 @@ struct ScoreRun {
             if (rq.dist_out)
                 for (int i = 0; i < nq; ++i) rq.dist_out[ord[i]] = b.hdist.p[i];
             const size_t m = (size_t)rq.m;
+            for (int i = 0; i < nq && rq.idx_out; ++i)   // (the record's first int is the list's length; the ids are padded already)
+                for (size_t v = 0; v < m; ++v) rq.idx_out[(size_t)ord[i] * m + v] = b.hwlist.p[(size_t)i * (m + 1) + 1 + v];
             for (int i = 0; i < nq && rq.witness; ++i) {
                 const size_t from = (size_t)i * kWitnessSlots, to = (size_t)ord[i] * m;
                 for (size_t v = 0; v < m && rq.w_idx; ++v) rq.w_idx[to + v] = b.hwid.p[from + v];
@@ -3153,6 +3201,61 @@ int chb_recruit_pairs_witness(chb_ctx *h, const int64_t *labels, int64_t B, int 
     witness_outputs(rq, nbr_idx, nbr_dist, alpha);
     const int rc = score_check_args(h, "chb_recruit_pairs_witness", rq, &D, false,
                                     witness_missing(P, row_of, bin_idx, nbr_idx, nbr_dist, alpha, "row_of or bin_idx is null"));
+    if (rc != CHB_OK) return rc;
+    if (Q < 0) return fail(CHB_EINVAL, "Q < 0");
+    for (int64_t p = 0; p < P; ++p)
+        if (row_of[p] < 0 || row_of[p] >= Q) return fail(CHB_EINVAL, "row_of entry outside [0, Q)");
+    return P == 0 ? CHB_OK : score_pairs(h, rq, row_of, bin_idx);
+}
+
+// ---- the wide calls: one entry point for every m.  m <= 16 forwards to the existing call (its result, its refusals and their
+// texts); 16 < m <= 64 is the same request in wide mode (ScoreRequest::wide): two kernels per chunk, recruit_wide_kernels.hip
+int chb_audit_rows_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
+                        int64_t Q, int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
+{
+    if (m <= kMaxM)
+        return groups ? chb_audit_rows_grouped(h, labels, groups, B, m, row_idx, Q, bin_out, dist_out, min_dist_out, margin_out)
+                      : chb_audit_rows(h, labels, B, m, row_idx, Q, bin_out, dist_out, min_dist_out, margin_out);
+    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, m, nullptr, 0, bin_out, dist_out, min_dist_out, margin_out};
+    rq.groups = groups; rq.wide = true;   // (null: leave-one-out, the ungrouped kernel)
+    return score_rows(h, "chb_audit_rows_wide", rq, nullptr, false);
+}
+
+int chb_recruit_rows_wide(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
+                          int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
+{
+    if (m <= kMaxM) return chb_recruit_rows(h, labels, B, m, Y, Q, D, bin_out, dist_out, min_dist_out, margin_out);
+    ScoreRequest rq{labels, B, Y, nullptr, nullptr, Q, m, nullptr, 0, bin_out, dist_out, min_dist_out, margin_out};
+    rq.wide = true;
+    return score_rows(h, "chb_recruit_rows_wide", rq, &D, false);
+}
+
+int chb_audit_pairs_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
+                         const int64_t *bin_idx, int64_t P, double *dist_out, int64_t *idx_out)
+{
+    if (m <= kMaxM) {
+        if (idx_out) return chb_audit_pairs_witness(h, labels, groups, B, m, row_idx, bin_idx, P, dist_out, idx_out, nullptr, nullptr);
+        return groups ? chb_audit_pairs_grouped(h, labels, groups, B, m, row_idx, bin_idx, P, dist_out)
+                      : chb_audit_pairs(h, labels, B, m, row_idx, bin_idx, P, dist_out);
+    }
+    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, P, m, nullptr, 0, nullptr, dist_out, nullptr, nullptr};
+    rq.groups = groups; rq.wide = true; rq.idx_out = idx_out;
+    const int rc = score_check_args(h, "chb_audit_pairs_wide", rq, nullptr, false,
+                                    pairs_missing(P, row_idx, bin_idx, dist_out, "row_idx, bin_idx or dist_out is null"));
+    return rc != CHB_OK || P == 0 ? rc : score_pairs(h, rq, row_idx, bin_idx);
+}
+
+int chb_recruit_pairs_wide(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
+                           const int64_t *row_of, const int64_t *bin_idx, int64_t P, double *dist_out, int64_t *idx_out)
+{
+    if (m <= kMaxM) {
+        if (idx_out) return chb_recruit_pairs_witness(h, labels, B, m, Y, Q, D, row_of, bin_idx, P, dist_out, idx_out, nullptr, nullptr);
+        return chb_recruit_pairs(h, labels, B, m, Y, Q, D, row_of, bin_idx, P, dist_out);
+    }
+    ScoreRequest rq{labels, B, Y, nullptr, nullptr, P, m, nullptr, 0, nullptr, dist_out, nullptr, nullptr};
+    rq.wide = true; rq.idx_out = idx_out;
+    const int rc = score_check_args(h, "chb_recruit_pairs_wide", rq, &D, false,
+                                    pairs_missing(P, row_of, bin_idx, dist_out, "row_of, bin_idx or dist_out is null"));
     if (rc != CHB_OK) return rc;
     if (Q < 0) return fail(CHB_EINVAL, "Q < 0");
     for (int64_t p = 0; p < P; ++p)
@@ -3583,6 +3686,7 @@ static const struct { const char *name; int64_t (*get)(const chb_ctx *); } kHost
     CTR("recruit_chunk", kRecruitChunk),   // rows per launch of chb_recruit_rows
     CTR("recruit_multi_rows", h->score.multi_rows),   // ... of the last chb_audit_rows_multi / chb_recruit_rows_multi
     CTR("pair_tiles", h->score.pair_tiles),   // work items of the last chb_audit_pairs / chb_recruit_pairs
+    CTR("recruit_wide_rows", h->score.wide_rows),   // rows per launch of the last chb_*_wide call with more than 16 neighbours
     // chb_kmer_profiles / chb_set_samples_from_sequences: a chunk's limits, the chunks of the last call
     CTR("kmer_chunk_bytes", kKmerChunkBytes), CTR("kmer_chunk_rows", kKmerChunkRows), CTR("kmer_chunks", h->kmer_chunks),
     CTR("prefilter_enabled", (h->sw.use_prefilter && h->shadow_ok) ? 1 : 0),

@@ -409,6 +409,16 @@ struct RecruitWitnessArgs : RecruitGroupArgs {
     double *w_d;           // [nq][kWitnessSlots]
     double *w_alpha;       // [nq][kWitnessSlots]
 };
+// the wide calls (16 < m <= kMaxMGeneric; recruit_wide_kernels.hip): the selection kernel leaves every problem's list in
+// `list` -- its length, then its m sample ids in (distance, index) order, -1 past the length: m + 1 ints per problem --
+// and the solve kernel reads it and stores the problem's distance in dist.  Problem = position of a pair chunk (a.tile
+// set) or pos * B + bin of a dense chunk, the index of its distance in dist.  memb_grp / grp are null without groups.
+struct RecruitWideArgs : RecruitGroupArgs {
+    int *list;             // [problems][m + 1]
+};
+constexpr long long kWideListBytes = 256ll << 20;   // the list buffer of a dense wide chunk stays within this
+void launch_recruit_select_wide(const RecruitWideArgs &a, hipStream_t s);   // (a.qid / a.memb_grp / a.tile choose the instantiation)
+void launch_hull_wide(const RecruitWideArgs &a, hipStream_t s);             // (m <= 32: 17.5 KiB of static LDS; else 66 KiB dynamic)
 constexpr int kRecruitChunk = 16384;   // rows of Y uploaded (recruit) or positions of row_idx (audit) scored per launch
 constexpr int kRecruitMaxBins = 8192;
 void launch_recruit(const RecruitArgs &a, hipStream_t s);   // (a.qid set: the audit instantiation)

@@ -358,6 +358,54 @@ int chb_recruit_rows_nearest(chb_ctx *h, const int64_t *labels, int64_t B, int m
                              const double *Y, int64_t Q, int64_t D,
                              int64_t *near_bin, double *near_dist);
 
+/* Row scoring for any number of neighbours up to CHB_MAX_NEIGHBORS = 64: one entry point per family for every m, so a
+ * labelling fitted with 16 < num_neighbors <= 64 can be audited at its own m and rows can be recruited into it.
+ *   - 1 <= m <= 16 (and every m the existing calls refuse as a bad argument): the call forwards -- chb_audit_rows_wide to
+ *     chb_audit_rows (groups == NULL) or chb_audit_rows_grouped; chb_recruit_rows_wide to chb_recruit_rows;
+ *     chb_audit_pairs_wide to chb_audit_pairs / chb_audit_pairs_grouped, or with idx_out != NULL to chb_audit_pairs_witness
+ *     (nbr_idx = idx_out, no other witness output); chb_recruit_pairs_wide to chb_recruit_pairs or
+ *     chb_recruit_pairs_witness.  Results, return codes and error texts are those calls', bit for bit.
+ *   - 16 < m <= 64: the definition of those calls with the limit lifted.  Per (row, bin) the up to m members nearest by
+ *     (distance, sample index), distances with chb_pairwise_distance's arithmetic; an audit withholds the row itself and,
+ *     with groups, every sample of the row's non-negative group (the withheld set W(r) above); the distance to the
+ *     selected members' hull under the context's metric, +inf for a bin without a candidate; bin_out / min_dist_out /
+ *     margin_out by the dense calls' strict-'>' scan over the row.
+ *     BIT-DEFINED: the selection -- idx_out[p*m + a] is entry a of pair p's list, -1 padded, exactly what chb_topm_per_bin
+ *     returns for a resident row of the same labelling (with the row, and its group, withheld); a pair's dist_out against
+ *     the dense wide call's entry on the same arguments, whatever tile, chunk and list position the pair falls into;
+ *     repeated calls; the row reduction against dist_out.
+ *     NOT bit-defined: a distance against chb_hull_distance_batch on the same list.  The solver is the same, but the Gram
+ *     matrix of the shifted vertices comes from the fp64 matrix core here and from one fused multiply-add per feature
+ *     there: the two agree to rounding (relative 1e-13 on well-conditioned sets).  On affinely dependent sets the affine
+ *     metric has no unique answer and none is promised, as for m <= 16.
+ *   - checks, in the existing calls' order: ranges (Q, B, m: CHB_EINVAL); null arguments; outputs (the dense calls: bin_out
+ *     and dist_out both NULL; the pair calls: row_idx / row_of, bin_idx or dist_out NULL with P > 0 -- idx_out may be NULL);
+ *     no resident samples (CHB_ESTATE); D; m > 64, then m > 32 on a device that does not grant the 66 KiB of LDS per
+ *     workgroup the 64-vertex kernel needs (CHB_EUNSUPPORTED); B > 8192 (CHB_EUNSUPPORTED); an open stepwise fit
+ *     (CHB_ESTATE, the fit stays usable); Q = 0 / P = 0 (CHB_OK, nothing further is read); the ranges of row_idx, then
+ *     bin_idx / row_of.  A refused call writes nothing.
+ *   - the call uses no state of a fit and leaves every counter (but "recruit_wide_rows" and, the pair calls,
+ *     "pair_tiles"), memo and switch of the context as it found it; no collective.
+ *   - two kernels per chunk on the dense calls' pipeline (streams, pinned staging, label CSR, dense group ids, pair plan
+ *     and tile table are theirs): a tiled selection that leaves m + 1 int32 per (row, bin) problem in a device list
+ *     buffer, profile names "audit_wide_select" / "recruit_wide_select" / "audit_pairs_wide_select" /
+ *     "recruit_pairs_wide_select", and one wavefront per problem for the hull, "..._wide_solve" (work units of both =
+ *     (row, bin) problems); the dense calls' row reduction follows.  Rows per chunk: the largest multiple of 64 whose list
+ *     buffer rows * width * (m + 1) * 4 bytes stays within 256 MiB (width = B, or 1 for the pair calls), clamped to
+ *     [64, 16384]: chb_counter "recruit_wide_rows".  The list buffer and the idx_out staging are allocated by a context's
+ *     first wide call with m > 16 and freed with the context. */
+int chb_audit_rows_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups /* may be NULL */, int64_t B, int m,
+                        const int64_t *row_idx, int64_t Q,
+                        int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out);
+int chb_recruit_rows_wide(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
+                          int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out);
+int chb_audit_pairs_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups /* may be NULL */, int64_t B, int m,
+                         const int64_t *row_idx, const int64_t *bin_idx, int64_t P,
+                         double *dist_out, int64_t *idx_out /* may be NULL: [P][m], -1 padded */);
+int chb_recruit_pairs_wide(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
+                           const int64_t *row_of, const int64_t *bin_idx, int64_t P,
+                           double *dist_out, int64_t *idx_out /* may be NULL */);
+
 /* distance_matrix.py:47-62 find_nearest_from_cluster with the reference's exact signature: the
  * caller supplies one row of a distance matrix (any provenance) and the current labels; selects
  * among {p : labels[p] == c} the (up to) m smallest by (row[p], p).  out_idx[m] (-1 padded). */
@@ -524,7 +572,9 @@ int chb_profile_reset(chb_ctx *h);
  * work units = pairs) | "bin_report" (chb_bin_report: the launch
  * that folds one chunk's distances and bins into the B x B tables; work units = (row, bin) pairs) | "nearest_bins"
  * (chb_audit_rows_nearest / chb_recruit_rows_nearest: the launch that ranks one chunk's rows x B table, behind the dense
- * kernel booked under "audit" / "recruit"; work units = (row, bin) pairs).  For m <= 16 "hull_qp" is the fused selection + hull-distance kernel and
+ * kernel booked under "audit" / "recruit"; work units = (row, bin) pairs) | "audit_wide_select" / "audit_wide_solve" and their
+ * "recruit_" / "_pairs_" counterparts (the chb_*_wide calls with m > 16: a chunk's selection and hull launches; work units =
+ * (row, bin) problems).  For m <= 16 "hull_qp" is the fused selection + hull-distance kernel and
  * "slow_path" the exact path for what it leaves over; "rescore*" then only appear for m > 16 or CHB_FUSED=0. */
 int chb_profile_get(chb_ctx *h, const char *kernel, double *total_ms, int64_t *launches,
                     double *work_units);
@@ -558,6 +608,7 @@ int chb_fit_stats(chb_ctx *h, int64_t *out4);
  * "recruit_multi_rows" (rows per launch of the last chb_audit_rows_multi / chb_recruit_rows_multi call: 16384 / nm rounded
  * down to a multiple of 64; 0 before the first), "pair_tiles" (tiles of at most 64 pairs of one bin -- the kernel's work
  * items -- of the last chb_audit_pairs / chb_recruit_pairs call that had pairs; 0 before the first),
+ * "recruit_wide_rows" (rows per launch of the last chb_*_wide call with m > 16: see there; 0 before the first),
  * "kmer_chunk_bytes" / "kmer_chunk_rows" (the most bases / contigs of one sequence chunk of chb_kmer_profiles and
  * chb_set_samples_from_sequences: constants), "kmer_chunks" (chunks of the last such call) */
 int chb_counter(chb_ctx *h, const char *name, int64_t *out);
