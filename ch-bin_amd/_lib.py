@@ -84,6 +84,18 @@ SIGNATURES = {
                                        C.c_int64, C.c_void_p, C.c_void_p]),
     "chb_recruit_pairs_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
                                          C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    # nearest bins, bin report and witnesses for every m up to 64: the m <= 16 calls' arguments (groups may be NULL)
+    "chb_audit_rows_nearest_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
+                                              C.c_int64, C.c_void_p, C.c_void_p]),
+    "chb_recruit_rows_nearest_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64,
+                                                C.c_int64, C.c_void_p, C.c_void_p]),
+    "chb_bin_report_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "chb_audit_pairs_witness_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
+                                               C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "chb_recruit_pairs_witness_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
+                                                 C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]),
     "chb_find_nearest_from_row": (C.c_int, [C.c_void_p, C.c_int64, _i64p, _f64p, C.c_int64, C.c_int,
                                             _i64p, C.POINTER(C.c_int32)]),
     "chb_hull_distance_batch": (C.c_int, [C.c_void_p, _i64p, C.c_int64, _i64p, C.c_int, _f64p,
@@ -526,6 +538,80 @@ class Context:
                                                row_of.ctypes.data, bins.ctypes.data, P, dist.ctypes.data,
                                                None if idx is None else idx.ctypes.data))
         return (dist, idx) if want_idx else dist
+
+    def audit_rows_nearest_wide(self, labels, B, m, k, rows=None, groups=None):
+        """chb_audit_rows_nearest_wide: audit_rows_nearest for any m in 1 .. 64 -- m <= 16 forwards to it bit for bit,
+        16 < m <= 64 ranks audit_rows_wide's dist rows on the device.  Returns what audit_rows_nearest returns."""
+        labels = self._labels(labels)
+        if groups is not None:
+            groups = self._groups(groups)
+        row_idx, Q, rows = self._row_indices(rows)
+        bins, dist = self._nearest_arrays(Q, k)
+        check(self._lib.chb_audit_rows_nearest_wide(self._h, labels.ctypes.data,
+                                                    None if groups is None else groups.ctypes.data, int(B), int(m), int(k),
+                                                    row_idx, Q, bins.ctypes.data, dist.ctypes.data))
+        return bins, dist
+
+    def recruit_rows_nearest_wide(self, labels, B, m, k, Y):
+        """chb_recruit_rows_nearest_wide: recruit_rows_nearest for any m in 1 .. 64 (16 < m <= 64: ranked from
+        recruit_rows_wide's dist rows).  Returns (bins [Q, k], dist [Q, k])."""
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim != 2:
+            raise ValueError("rows must be a 2-D array")
+        labels = self._labels(labels)
+        bins, dist = self._nearest_arrays(Y.shape[0], k)
+        check(self._lib.chb_recruit_rows_nearest_wide(self._h, labels.ctypes.data, int(B), int(m), int(k), Y.ctypes.data,
+                                                      *Y.shape, bins.ctypes.data, dist.ctypes.data))
+        return bins, dist
+
+    def bin_report_wide(self, labels, B, m, rows=None, groups=None):
+        """chb_bin_report_wide: bin_report (with `groups` bin_report_grouped) for any m in 1 .. 64 -- m <= 16 forwards bit
+        for bit, 16 < m <= 64 sums up audit_rows_wide's answer.  Returns what bin_report returns."""
+        labels = self._labels(labels)
+        if groups is not None:
+            groups = self._groups(groups)
+        row_idx, Q, rows = self._row_indices(rows)
+        B = int(B)
+        nb = max(B, 0) if B <= 8192 else 0   # (beyond the limit the call is refused before it writes anything)
+        confusion = np.empty((nb, nb), dtype=np.int64)
+        unplaced = np.empty(nb, dtype=np.int64)
+        dcnt = np.empty((nb, nb), dtype=np.int64)
+        dmin = np.empty((nb, nb), dtype=np.float64)
+        dsum = np.empty((nb, nb), dtype=np.float64)
+        skipped = C.c_int64(0)
+        check(self._lib.chb_bin_report_wide(self._h, labels.ctypes.data, None if groups is None else groups.ctypes.data,
+                                            B, int(m), row_idx, Q, confusion.ctypes.data, unplaced.ctypes.data,
+                                            dcnt.ctypes.data, dmin.ctypes.data, dsum.ctypes.data, C.addressof(skipped)))
+        return confusion, unplaced, dcnt, dmin, dsum, int(skipped.value)
+
+    def audit_pairs_witness_wide(self, labels, B, m, rows, bins, groups=None):
+        """chb_audit_pairs_witness_wide: audit_pairs_witness for any m in 1 .. 64 -- m <= 16 forwards bit for bit; at
+        16 < m <= 64 dist and neighbors are audit_pairs_wide's dist and idx, neighbor_dist the members' selection
+        distances and weights what the wide solve kernel returned.  Returns what audit_pairs_witness returns."""
+        rows, bins = self._pair_lists(rows, bins, "rows")
+        labels = self._labels(labels)
+        if groups is not None:
+            groups = self._groups(groups)
+        dist, idx, nd, alpha = self._witness_arrays(rows.shape[0], m)
+        check(self._lib.chb_audit_pairs_witness_wide(self._h, labels.ctypes.data,
+                                                     None if groups is None else groups.ctypes.data, int(B), int(m),
+                                                     rows.ctypes.data, bins.ctypes.data, rows.shape[0], dist.ctypes.data,
+                                                     idx.ctypes.data, nd.ctypes.data, alpha.ctypes.data))
+        return dist, idx, nd, alpha
+
+    def recruit_pairs_witness_wide(self, labels, B, m, Y, row_of, bins):
+        """chb_recruit_pairs_witness_wide: recruit_pairs_witness for any m in 1 .. 64.  Returns what it returns."""
+        row_of, bins = self._pair_lists(row_of, bins, "row_of")
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim != 2:
+            raise ValueError("rows must be a 2-D array")
+        labels = self._labels(labels)
+        dist, idx, nd, alpha = self._witness_arrays(row_of.shape[0], m)
+        check(self._lib.chb_recruit_pairs_witness_wide(self._h, labels.ctypes.data, int(B), int(m), Y.ctypes.data, *Y.shape,
+                                                       row_of.ctypes.data, bins.ctypes.data, row_of.shape[0],
+                                                       dist.ctypes.data, idx.ctypes.data, nd.ctypes.data,
+                                                       alpha.ctypes.data))
+        return dist, idx, nd, alpha
 
     def find_nearest_from_row(self, c, labels, row, m):
         labels = np.ascontiguousarray(labels, dtype=np.int64)

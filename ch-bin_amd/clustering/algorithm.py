@@ -66,9 +66,9 @@ def fit_cluster(
     return labels
 
 
-# audit / recruit / audit_pairs / recruit_pairs / cohesion: up to this many neighbours the calls they have always made;
-# beyond it (up to 64; the library refuses more) the chb_*_wide calls.  bin_report, neighbor_sweep, witness and
-# nearest_bins have no wide form and keep refusing more than 16.
+# audit / recruit / audit_pairs / recruit_pairs / cohesion / bin_report / witness / recruit_witness / nearest_bins /
+# recruit_nearest_bins: up to this many neighbours the calls they have always made; beyond it (up to 64; the library
+# refuses more) the chb_*_wide calls.  neighbor_sweep has no wide form and keeps refusing entries above 16.
 _TILED_MAX_NEIGHBORS = 16
 
 
@@ -212,6 +212,8 @@ def bin_report(
     ctx = default_context()
     ctx.set_samples_cached(samples)
     with ctx.using_metric(metric):
+        if int(num_neighbors) > _TILED_MAX_NEIGHBORS:
+            return BinReport(*ctx.bin_report_wide(labels, int(num_clusters), int(num_neighbors), rows, groups=groups))
         if groups is None:
             return BinReport(*ctx.bin_report(labels, int(num_clusters), int(num_neighbors), rows))
         return BinReport(*ctx.bin_report_grouped(labels, groups, int(num_clusters), int(num_neighbors), rows))
@@ -472,7 +474,8 @@ def witness(
     ctx = default_context()
     ctx.set_samples_cached(samples)
     with ctx.using_metric(metric):
-        return Witness(*ctx.audit_pairs_witness(labels, int(num_clusters), int(num_neighbors), rows, bins, groups=groups))
+        score = ctx.audit_pairs_witness_wide if int(num_neighbors) > _TILED_MAX_NEIGHBORS else ctx.audit_pairs_witness
+        return Witness(*score(labels, int(num_clusters), int(num_neighbors), rows, bins, groups=groups))
 
 
 def recruit_witness(
@@ -498,7 +501,8 @@ def recruit_witness(
     ctx = default_context()
     ctx.set_samples_cached(samples)
     with ctx.using_metric(metric):
-        return Witness(*ctx.recruit_pairs_witness(labels, int(num_clusters), int(num_neighbors), new_rows, row_of, bins))
+        score = ctx.recruit_pairs_witness_wide if int(num_neighbors) > _TILED_MAX_NEIGHBORS else ctx.recruit_pairs_witness
+        return Witness(*score(labels, int(num_clusters), int(num_neighbors), new_rows, row_of, bins))
 
 
 @dataclasses.dataclass
@@ -572,7 +576,8 @@ def nearest_bins(
     ctx = default_context()
     ctx.set_samples_cached(samples)
     with ctx.using_metric(metric):
-        return NearestBins(*ctx.audit_rows_nearest(labels, int(num_clusters), int(num_neighbors), int(k), rows, groups=groups))
+        score = ctx.audit_rows_nearest_wide if int(num_neighbors) > _TILED_MAX_NEIGHBORS else ctx.audit_rows_nearest
+        return NearestBins(*score(labels, int(num_clusters), int(num_neighbors), int(k), rows, groups=groups))
 
 
 def recruit_nearest_bins(
@@ -596,4 +601,5 @@ def recruit_nearest_bins(
     ctx = default_context()
     ctx.set_samples_cached(samples)
     with ctx.using_metric(metric):
-        return NearestBins(*ctx.recruit_rows_nearest(labels, int(num_clusters), int(num_neighbors), int(k), rows))
+        score = ctx.recruit_rows_nearest_wide if int(num_neighbors) > _TILED_MAX_NEIGHBORS else ctx.recruit_rows_nearest
+        return NearestBins(*score(labels, int(num_clusters), int(num_neighbors), int(k), rows))

@@ -286,6 +286,10 @@ struct ChunkHalf {
     // per position (RecruitWideArgs), per half because idx_out copies them down while the next chunk's kernels run
     DevBuf<int> wlist;
     PinBuf<int> hwlist;
+    // chb_*_pairs_witness_wide only (first allocated by the context's first such call with more than 16 neighbours): the
+    // chunk's witness records, m slots per position (RecruitWideWitnessArgs); the members' ids are wlist's
+    DevBuf<double> wwd, wwalpha;
+    PinBuf<double> hwwd, hwwalpha;
     hipEvent_t up = nullptr, done = nullptr, down = nullptr;
     int nseg = 0, ntile = 0;
     void destroy_events() { for (hipEvent_t ev : {up, done, down}) if (ev) (void)hipEventDestroy(ev); }
@@ -2452,13 +2456,16 @@ struct ReportOut { int64_t *confusion, *unplaced, *dcnt; double *dmin, *dsum; };
 // stable counting sort, so a label's positions keep the order of row_idx -- and the chunks cut from that order: at most
 // kRecruitChunk positions each, cut back to the last kReportBlock-row block boundary of the label a cut would split, so
 // that no summation block of dsum (BinReportArgs) lies in two chunks.
+// (chb_bin_report_wide with more than 16 neighbours: at most `limit` positions each, the rows a dense wide chunk may hold
+// -- a multiple of kReportBlock, so a cut never falls back onto the cut before it.)
 struct ReportPlan {
     int64_t B = 0;
+    int64_t max_rows = 0;            // of any chunk
     std::vector<int> ord;            // [Qv] sample index of every scored position, grouped by label
     std::vector<int64_t> lab_ptr;    // [B + 1] label a's run is ord[lab_ptr[a] .. lab_ptr[a + 1])
     std::vector<int64_t> cut;        // chunk k is ord[cut[k] .. cut[k + 1])
     // the plan of the positions row_idx[0 .. Q) (nullptr: position = sample); returns Qv, the others are only counted
-    int64_t build(const int64_t *labels, int64_t B_, const int64_t *row_idx, int64_t Q)
+    int64_t build(const int64_t *labels, int64_t B_, const int64_t *row_idx, int64_t Q, int64_t limit = kRecruitChunk)
     {
         B = B_;
         lab_ptr.assign((size_t)B + 1, 0);
@@ -2478,11 +2485,12 @@ struct ReportPlan {
         }
         cut.assign(1, 0);
         while (cut.back() < Qv) {
-            int64_t c1 = std::min<int64_t>(Qv, cut.back() + kRecruitChunk);
+            int64_t c1 = std::min<int64_t>(Qv, cut.back() + limit);
             if (c1 < Qv) {   // inside (or at the start of) the label whose run holds position c1
                 const size_t l = (size_t)(std::upper_bound(lab_ptr.begin(), lab_ptr.end(), c1) - lab_ptr.begin()) - 1;
                 c1 -= (c1 - lab_ptr[l]) % kReportBlock;
             }
+            max_rows = std::max(max_rows, c1 - cut.back());
             cut.push_back(c1);
         }
         return Qv;
@@ -2579,7 +2587,8 @@ struct ScoreRequest {
     int near_k = 0;
     int64_t *near_bin = nullptr; double *near_dist = nullptr;
     // chb_*_wide with 16 < m <= 64: the two wide kernels per chunk in place of recruit_kernel; the pair forms may return
-    // the selection lists ([Q][m], -1 padded, in the caller's order)
+    // the selection lists ([Q][m], -1 padded, in the caller's order).  Combines with nearest (the ranking reads the wide
+    // chunk's table), plan (cut at wide_chunk_rows) and witness (m slots per pair: the ids are idx_out, w_idx stays null)
     bool wide = false;
     int64_t *idx_out = nullptr;
 };
@@ -2630,6 +2639,13 @@ int score_check_args(chb_ctx *h, const char *who, ScoreRequest &rq, const int64_
     for (int64_t q = 0; rq.row_idx && q < rq.Q; ++q)
         if (rq.row_idx[q] < 0 || rq.row_idx[q] >= h->N) return fail(CHB_EINVAL, "row_idx entry outside [0, N)");
     return CHB_OK;
+}
+
+// rows of a dense wide chunk: the largest multiple of 64 whose width x (m + 1) int lists fit the list buffer, in [64, 16384]
+int64_t wide_chunk_rows(int64_t width, int m)
+{
+    const int64_t fit = kWideListBytes / (width * (m + 1) * (int64_t)sizeof(int)) / kQTile * kQTile;
+    return std::min<int64_t>(kRecruitChunk, std::max<int64_t>(kQTile, fit));
 }
 
 // One row-scoring call behind its checks: its stages in call order, then the steps of its pipeline.  The chunks go through
@@ -2712,14 +2728,13 @@ struct ScoreRun {
     {
         const int64_t B = rq.B;
         if (rq.nm > 0) sc.multi_rows = std::max<int64_t>(kQTile, kRecruitChunk / rq.nm / kQTile * kQTile);
-        if (rq.wide) {   // the largest multiple of 64 rows whose lists fit the buffer, in [64, 16384]
-            const int64_t fit = kWideListBytes / ((int64_t)width * (rq.m + 1) * (int64_t)sizeof(int)) / kQTile * kQTile;
-            sc.wide_rows = std::min<int64_t>(kRecruitChunk, std::max<int64_t>(kQTile, fit));
-        }
-        chunk = rq.pairs ? rq.pairs->max_rows : std::min<int64_t>(rq.Q, rq.nm > 0 ? sc.multi_rows : rq.wide ? sc.wide_rows : kRecruitChunk);
+        if (rq.wide) sc.wide_rows = wide_chunk_rows((int64_t)width, rq.m);
+        // (a wide plan: cut at wide_rows by its builder, so its longest chunk is what the buffers must hold)
+        chunk = rq.pairs ? rq.pairs->max_rows : rq.plan && rq.wide ? rq.plan->max_rows
+              : std::min<int64_t>(rq.Q, rq.nm > 0 ? sc.multi_rows : rq.wide ? sc.wide_rows : kRecruitChunk);
         n = rq.pairs ? (int64_t)rq.pairs->cut.size() - 1 : rq.plan ? (int64_t)rq.plan->cut.size() - 1 : (rq.Q + chunk - 1) / chunk;
         const size_t res = (size_t)chunk * (size_t)ns;   // result rows of a chunk
-        const int halves = rq.Q > chunk ? 2 : 1;   // (a plan's longest chunk is shorter than Q whenever it has a second)
+        const int halves = rq.Q > chunk ? 2 : 1;   // (a plan's or a pair plan's longest chunk is shorter than Q whenever there is a second)
         HIPCHK(sc.ptr.ensure((size_t)B + 1));
         HIPCHK(sc.memb.ensure(n_memb));
         if (rq.groups) {
@@ -2740,7 +2755,13 @@ struct ScoreRun {
                     HIPCHK(b.wlist.ensure((size_t)chunk * (size_t)(rq.m + 1)));
                     if (rq.idx_out) HIPCHK(b.hwlist.ensure((size_t)chunk * (size_t)(rq.m + 1)));
                 }
-                if (rq.witness) {   // the records: the kernel writes all three, what the caller wants comes down
+                if (rq.witness && rq.wide) {   // m slots per position; the ids are the lists'
+                    const size_t slots = (size_t)chunk * (size_t)rq.m;
+                    HIPCHK(b.wwd.ensure(slots));
+                    HIPCHK(b.wwalpha.ensure(slots));
+                    if (rq.w_dist) HIPCHK(b.hwwd.ensure(slots));
+                    if (rq.w_alpha) HIPCHK(b.hwwalpha.ensure(slots));
+                } else if (rq.witness) {   // the records: the kernel writes all three, what the caller wants comes down
                     const size_t slots = (size_t)chunk * kWitnessSlots;
                     HIPCHK(b.wid.ensure(slots));
                     HIPCHK(b.wd.ensure(slots));
@@ -2909,22 +2930,26 @@ struct ScoreRun {
         a.Y = audit ? nullptr : b.Y.p; a.qid = audit ? b.qid.p : nullptr; a.dist = b.dist.p; a.nq = nq;
         // (with groups: the same launches, the leave-group-out instantiation of the kernel)
         if (rq.wide) {   // selection, solve and -- dense -- the row reduction; the work of both is the (row, bin) problems
-            RecruitWideArgs wa{};
+            RecruitWideWitnessArgs wa{};   // (the launchers without witnesses take the part of it that is theirs)
             static_cast<RecruitGroupArgs &>(wa) = a;
             wa.tile = rq.pairs ? b.tile.p : nullptr; wa.ntile = rq.pairs ? b.ntile : 0;
             wa.list = rq.pairs ? b.wlist.p : sc.wlist.p;
+            if (rq.witness) { wa.w_d = b.wwd.p; wa.w_alpha = b.wwalpha.p; }   // (a pair chunk: the witness forms)
             const double work = (double)nq * (double)width;
             {
                 Timed t(h, rq.pairs ? (audit ? "audit_pairs_wide_select" : "recruit_pairs_wide_select")
                                     : (audit ? "audit_wide_select" : "recruit_wide_select"), work);
-                launch_recruit_select_wide(wa, s);
+                if (rq.witness) launch_recruit_select_wide_witness(wa, s);
+                else launch_recruit_select_wide(wa, s);
             }
             {
                 Timed t(h, rq.pairs ? (audit ? "audit_pairs_wide_solve" : "recruit_pairs_wide_solve")
                                     : (audit ? "audit_wide_solve" : "recruit_wide_solve"), work);
-                launch_hull_wide(wa, s);
+                if (rq.witness) launch_hull_wide_witness(wa, s);
+                else launch_hull_wide(wa, s);
             }
-            if (!rq.pairs) launch_recruit_reduce(b.dist.p, nq, (int)rq.B, b.bin.p, b.min.p, b.margin.p, s);
+            // (a nearest-bins call has no bin / min / margin buffers: the ranking below stands in the reduction's place)
+            if (!rq.pairs && !rq.nearest) launch_recruit_reduce(b.dist.p, nq, (int)rq.B, b.bin.p, b.min.p, b.margin.p, s);
         } else if (rq.pairs) {   // one launch: the tiles' kernel, no row reduction behind it
             a.tile = b.tile.p; a.ntile = b.ntile;
             Timed t(h, audit ? "audit_pairs" : "recruit_pairs", (double)nq);
@@ -2963,10 +2988,16 @@ struct ScoreRun {
         if (rq.min_dist_out) HIPTRY(hipMemcpyAsync(b.hmin.p, b.min.p, sizeof(double) * nr, hipMemcpyDeviceToHost, c));
         if (rq.margin_out) HIPTRY(hipMemcpyAsync(b.hmargin.p, b.margin.p, sizeof(double) * nr, hipMemcpyDeviceToHost, c));
         if (rq.bin_out) HIPTRY(hipMemcpyAsync(b.hbin.p, b.bin.p, sizeof(int) * nr, hipMemcpyDeviceToHost, c));
-        const size_t slots = nr * kWitnessSlots;   // (pairs: nr positions)
-        if (rq.w_idx) HIPTRY(hipMemcpyAsync(b.hwid.p, b.wid.p, sizeof(int) * slots, hipMemcpyDeviceToHost, c));
-        if (rq.w_dist) HIPTRY(hipMemcpyAsync(b.hwd.p, b.wd.p, sizeof(double) * slots, hipMemcpyDeviceToHost, c));
-        if (rq.w_alpha) HIPTRY(hipMemcpyAsync(b.hwalpha.p, b.walpha.p, sizeof(double) * slots, hipMemcpyDeviceToHost, c));
+        if (rq.wide) {   // (a wide witness call: m slots per position, the ids come down as idx_out's lists below)
+            const size_t slots = nr * (size_t)rq.m;
+            if (rq.w_dist) HIPTRY(hipMemcpyAsync(b.hwwd.p, b.wwd.p, sizeof(double) * slots, hipMemcpyDeviceToHost, c));
+            if (rq.w_alpha) HIPTRY(hipMemcpyAsync(b.hwwalpha.p, b.wwalpha.p, sizeof(double) * slots, hipMemcpyDeviceToHost, c));
+        } else {
+            const size_t slots = nr * kWitnessSlots;   // (pairs: nr positions)
+            if (rq.w_idx) HIPTRY(hipMemcpyAsync(b.hwid.p, b.wid.p, sizeof(int) * slots, hipMemcpyDeviceToHost, c));
+            if (rq.w_dist) HIPTRY(hipMemcpyAsync(b.hwd.p, b.wd.p, sizeof(double) * slots, hipMemcpyDeviceToHost, c));
+            if (rq.w_alpha) HIPTRY(hipMemcpyAsync(b.hwalpha.p, b.walpha.p, sizeof(double) * slots, hipMemcpyDeviceToHost, c));
+        }
         if (rq.idx_out) HIPTRY(hipMemcpyAsync(b.hwlist.p, b.wlist.p, sizeof(int) * nr * (size_t)(rq.m + 1), hipMemcpyDeviceToHost, c));
         const size_t near = nr * (size_t)rq.near_k;   // (a nearest-bins call: nr rows)
         if (rq.near_bin) HIPTRY(hipMemcpyAsync(b.hnbin.p, b.nbin.p, sizeof(int) * near, hipMemcpyDeviceToHost, c));
@@ -2989,7 +3020,12 @@ struct ScoreRun {
             const size_t m = (size_t)rq.m;
             for (int i = 0; i < nq && rq.idx_out; ++i)   // (the record's first int is the list's length; the ids are padded already)
                 for (size_t v = 0; v < m; ++v) rq.idx_out[(size_t)ord[i] * m + v] = b.hwlist.p[(size_t)i * (m + 1) + 1 + v];
-            for (int i = 0; i < nq && rq.witness; ++i) {
+            for (int i = 0; i < nq && rq.witness && rq.wide; ++i) {   // (m slots per position)
+                const size_t from = (size_t)i * m, to = (size_t)ord[i] * m;
+                if (rq.w_dist) memcpy(rq.w_dist + to, b.hwwd.p + from, sizeof(double) * m);
+                if (rq.w_alpha) memcpy(rq.w_alpha + to, b.hwwalpha.p + from, sizeof(double) * m);
+            }
+            for (int i = 0; i < nq && rq.witness && !rq.wide; ++i) {
                 const size_t from = (size_t)i * kWitnessSlots, to = (size_t)ord[i] * m;
                 for (size_t v = 0; v < m && rq.w_idx; ++v) rq.w_idx[to + v] = b.hwid.p[from + v];
                 if (rq.w_dist) memcpy(rq.w_dist + to, b.hwd.p + from, sizeof(double) * m);
@@ -3082,7 +3118,7 @@ int bin_report(chb_ctx *h, const char *who, ScoreRequest &rq, int64_t *confusion
     if (rc != CHB_OK) return rc;
     const ReportOut out{confusion, unplaced, dcnt, dmin, dsum};
     ReportPlan plan;
-    const int64_t Qv = plan.build(labels, B, row_idx, Q);
+    const int64_t Qv = plan.build(labels, B, row_idx, Q, rq.wide ? wide_chunk_rows(B, rq.m) : kRecruitChunk);
     if (n_skipped) *n_skipped = Q - Qv;
     if (Qv == 0) { plan.empty_tables(out); return CHB_OK; }
     rq.row_idx = nullptr; rq.plan = &plan; rq.Q = Qv;   // the plan's positions, already in label order
@@ -3263,6 +3299,51 @@ int chb_recruit_pairs_wide(chb_ctx *h, const int64_t *labels, int64_t B, int m, 
     return P == 0 ? CHB_OK : score_pairs(h, rq, row_of, bin_idx);
 }
 
+int chb_audit_pairs_witness_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m,
+                                 const int64_t *row_idx, const int64_t *bin_idx, int64_t P, double *dist_out, int64_t *nbr_idx,
+                                 double *nbr_dist, double *alpha)
+{
+    if (m <= kMaxM) return chb_audit_pairs_witness(h, labels, groups, B, m, row_idx, bin_idx, P, dist_out, nbr_idx, nbr_dist, alpha);
+    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, P, m, nullptr, 0, nullptr, dist_out, nullptr, nullptr};
+    rq.groups = groups; rq.wide = true;
+    witness_outputs(rq, nullptr, nbr_dist, alpha);
+    rq.idx_out = nbr_idx;   // (the members are the selection list: chb_audit_pairs_wide's idx_out)
+    const int rc = score_check_args(h, "chb_audit_pairs_witness_wide", rq, nullptr, false,
+                                    witness_missing(P, row_idx, bin_idx, nbr_idx, nbr_dist, alpha, "row_idx or bin_idx is null"));
+    return rc != CHB_OK || P == 0 ? rc : score_pairs(h, rq, row_idx, bin_idx);
+}
+
+int chb_recruit_pairs_witness_wide(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
+                                   const int64_t *row_of, const int64_t *bin_idx, int64_t P, double *dist_out,
+                                   int64_t *nbr_idx, double *nbr_dist, double *alpha)
+{
+    if (m <= kMaxM)
+        return chb_recruit_pairs_witness(h, labels, B, m, Y, Q, D, row_of, bin_idx, P, dist_out, nbr_idx, nbr_dist, alpha);
+    ScoreRequest rq{labels, B, Y, nullptr, nullptr, P, m, nullptr, 0, nullptr, dist_out, nullptr, nullptr};
+    rq.wide = true;
+    witness_outputs(rq, nullptr, nbr_dist, alpha);
+    rq.idx_out = nbr_idx;
+    const int rc = score_check_args(h, "chb_recruit_pairs_witness_wide", rq, &D, false,
+                                    witness_missing(P, row_of, bin_idx, nbr_idx, nbr_dist, alpha, "row_of or bin_idx is null"));
+    if (rc != CHB_OK) return rc;
+    if (Q < 0) return fail(CHB_EINVAL, "Q < 0");
+    for (int64_t p = 0; p < P; ++p)
+        if (row_of[p] < 0 || row_of[p] >= Q) return fail(CHB_EINVAL, "row_of entry outside [0, Q)");
+    return P == 0 ? CHB_OK : score_pairs(h, rq, row_of, bin_idx);
+}
+
+int chb_bin_report_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
+                        int64_t Q, int64_t *confusion, int64_t *unplaced, int64_t *dcnt, double *dmin, double *dsum,
+                        int64_t *n_skipped)
+{
+    if (m <= kMaxM)
+        return groups ? chb_bin_report_grouped(h, labels, groups, B, m, row_idx, Q, confusion, unplaced, dcnt, dmin, dsum, n_skipped)
+                      : chb_bin_report(h, labels, B, m, row_idx, Q, confusion, unplaced, dcnt, dmin, dsum, n_skipped);
+    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, m, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
+    rq.groups = groups; rq.wide = true;   // (null: leave-one-out, the ungrouped kernel)
+    return bin_report(h, "chb_bin_report_wide", rq, confusion, unplaced, dcnt, dmin, dsum, n_skipped);
+}
+
 namespace {
 
 // the two nearest-bins calls: the dense call's request with the ranked outputs in place of the reduced ones
@@ -3288,6 +3369,24 @@ int chb_recruit_rows_nearest(chb_ctx *h, const int64_t *labels, int64_t B, int m
 {
     ScoreRequest rq{labels, B, Y, nullptr, nullptr, Q, m, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
     return score_nearest(h, "chb_recruit_rows_nearest", rq, &D, k, near_bin, near_dist);
+}
+
+int chb_audit_rows_nearest_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, int k,
+                                const int64_t *row_idx, int64_t Q, int64_t *near_bin, double *near_dist)
+{
+    if (m <= kMaxM) return chb_audit_rows_nearest(h, labels, groups, B, m, k, row_idx, Q, near_bin, near_dist);
+    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, m, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
+    rq.groups = groups; rq.wide = true;
+    return score_nearest(h, "chb_audit_rows_nearest_wide", rq, nullptr, k, near_bin, near_dist);
+}
+
+int chb_recruit_rows_nearest_wide(chb_ctx *h, const int64_t *labels, int64_t B, int m, int k, const double *Y, int64_t Q,
+                                  int64_t D, int64_t *near_bin, double *near_dist)
+{
+    if (m <= kMaxM) return chb_recruit_rows_nearest(h, labels, B, m, k, Y, Q, D, near_bin, near_dist);
+    ScoreRequest rq{labels, B, Y, nullptr, nullptr, Q, m, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
+    rq.wide = true;
+    return score_nearest(h, "chb_recruit_rows_nearest_wide", rq, &D, k, near_bin, near_dist);
 }
 
 int chb_find_nearest_from_row(chb_ctx *h, int64_t c, const int64_t *labels, const double *row,

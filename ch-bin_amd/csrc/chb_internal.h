@@ -416,9 +416,19 @@ struct RecruitWitnessArgs : RecruitGroupArgs {
 struct RecruitWideArgs : RecruitGroupArgs {
     int *list;             // [problems][m + 1]
 };
+// the wide pair calls with witnesses (chb_*_pairs_witness_wide; a.tile set): m slots per position, slot a = entry a of the
+// position's list.  The selection kernel writes w_d (the entry's rooted selection distance, +inf past the list's length),
+// the solve kernel w_alpha (the vertex's weight as active_set_distance2 on the Wave64 backend returned it, 0 past the
+// length); the ids are the list's.  (Its own struct: the kernels without witnesses keep the arguments they have.)
+struct RecruitWideWitnessArgs : RecruitWideArgs {
+    double *w_d;           // [nq][m]
+    double *w_alpha;       // [nq][m]
+};
 constexpr long long kWideListBytes = 256ll << 20;   // the list buffer of a dense wide chunk stays within this
 void launch_recruit_select_wide(const RecruitWideArgs &a, hipStream_t s);   // (a.qid / a.memb_grp / a.tile choose the instantiation)
 void launch_hull_wide(const RecruitWideArgs &a, hipStream_t s);             // (m <= 32: 17.5 KiB of static LDS; else 66 KiB dynamic)
+void launch_recruit_select_wide_witness(const RecruitWideWitnessArgs &a, hipStream_t s);   // (a.qid / a.memb_grp choose the instantiation)
+void launch_hull_wide_witness(const RecruitWideWitnessArgs &a, hipStream_t s);
 constexpr int kRecruitChunk = 16384;   // rows of Y uploaded (recruit) or positions of row_idx (audit) scored per launch
 constexpr int kRecruitMaxBins = 8192;
 void launch_recruit(const RecruitArgs &a, hipStream_t s);   // (a.qid set: the audit instantiation)

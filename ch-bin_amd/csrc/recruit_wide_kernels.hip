@@ -12,6 +12,8 @@
 //     tiles of the (NV / 16)^2 grid are computed and then mirrored into LDS, every vertex row and the query row are read
 //     once in 16-byte loads, a missing vertex reads the query row (y = 0).  Then active_set_distance2 on the Wave64
 //     backend (hull_solve64.h), the driver and backend of hull_generic_kernel.
+// The witness forms of both (chb_*_pairs_witness_wide, pairs only) store m doubles each per pair behind what the plain
+// forms do and nothing before it: (a) every list entry's rooted distance, (b) every lane's weight.
 //
 // Numerics: the selection arithmetic is chb_pairwise_distance's, bit for bit -- sum_k (y_k - p_k)^2 sequentially in k with
 // separate multiply and add (fp contraction is off from the pragma below on), a correctly rounded sqrt, members ordered
@@ -26,16 +28,26 @@
 #include <limits.h>
 #include <math.h>
 
+#include <type_traits>
+
 namespace chb {
 namespace {
 
 // the lower-triangle tile (bi, bj), bj <= bi, of the block grid
 __device__ __forceinline__ constexpr int wide_tile(int bi, int bj) { return bi * (bi + 1) / 2 + bj; }
 
+// the witness forms (chb_*_pairs_witness_wide) take the record buffers behind the plain arguments; the plain forms keep
+// the arguments they have
+template <bool kWitness>
+using wide_args_t = std::conditional_t<kWitness, RecruitWideWitnessArgs, RecruitWideArgs>;
+
 // Problem g of the chunk: its list is a.list[g (m + 1) ..], its distance goes to a.dist[g] -- position g of a pair
 // chunk (a.tile set), entry (g / B, g % B) of a dense chunk's [nq][B] table.
-template <int NV>
-__global__ __launch_bounds__(64) void hull_wide_kernel(RecruitWideArgs a, int nprob)
+// kWitness (pairs only): lane a < m also stores the weight of vertex a as active_set_distance2 returned it, 0 where the
+// list has no such vertex, to a.w_alpha[g m + a]: one plain vector store per lane behind the solve, nothing before it.
+// The `false` instantiations are unchanged: every place sits behind `if constexpr (kWitness)`.
+template <int NV, bool kWitness = false>
+__global__ __launch_bounds__(64) void hull_wide_kernel(wide_args_t<kWitness> a, int nprob)
 {
     constexpr int NB = NV / 16, NT = NB * (NB + 1) / 2;
     using Lds = GenLdsT<NV>;
@@ -56,6 +68,9 @@ __global__ __launch_bounds__(64) void hull_wide_kernel(RecruitWideArgs a, int np
     const int n = min(lst[0], min(m, NV));   // (never more than the capacity, whatever the buffer holds)
     if (n <= 0) {
         if (lane == 0) a.dist[g] = kInf;
+        if constexpr (kWitness) {
+            if (lane < m) a.w_alpha[(size_t)g * (size_t)m + lane] = 0.0;   // (no vertex: the record's padding)
+        }
         return;
     }
     const int pos = a.tile ? g : g / a.B;
@@ -146,6 +161,9 @@ __global__ __launch_bounds__(64) void hull_wide_kernel(RecruitWideArgs a, int np
     double alpha = 0.0;
     const double val = active_set_distance2(w, n, a.metric, scale, alpha);
     if (lane == 0) a.dist[g] = sqrt(fmax(val, 0.0));
+    if constexpr (kWitness) {
+        if (lane < m) a.w_alpha[(size_t)g * (size_t)m + lane] = mine ? alpha : 0.0;
+    }
 }
 
 }  // namespace
@@ -171,10 +189,14 @@ struct WideStage {
 // lists of its 4 rows take 4 x 4 (distance, id) entries next to the 4 x 4 micro-tile: 48 + 32 VGPRs.  With the rows' own ids in
 // LDS and the slabs shifted last-first (no copy of the list is live) every instantiation fits the 256 registers a wavefront
 // has at two workgroups per CU without scratch, so the 64-row tile and the occupancy of recruit_kernel both stay.
-template <bool kResident, bool kPairs, bool kGrouped>
-__global__ __launch_bounds__(256, 2) void recruit_select_wide_kernel(RecruitWideArgs a, int nqt, int total)
+// kWitness (chb_*_pairs_witness_wide, pairs only): behind a problem's ids every entry's rooted selection distance -- the
+// slab value the lane holds -- goes to a.w_d[problem m ..], +inf past the list's length, by the same lane-per-entry
+// vector stores.  The `false` instantiations are unchanged: every place sits behind `if constexpr (kWitness)`.
+template <bool kResident, bool kPairs, bool kGrouped, bool kWitness = false>
+__global__ __launch_bounds__(256, 2) void recruit_select_wide_kernel(wide_args_t<kWitness> a, int nqt, int total)
 {
     static_assert(kResident || !kGrouped, "groups are a property of the resident samples");
+    static_assert(kPairs || !kWitness, "witnesses travel with the pair calls: one record per listed pair");
     __shared__ __attribute__((aligned(16))) WideStage lds;
 
     // XCD-aware order: blocks b and b+8 share an XCD (and its L2), so hand each XCD a contiguous range of work
@@ -237,7 +259,17 @@ __global__ __launch_bounds__(256, 2) void recruit_select_wide_kernel(RecruitWide
             const int e = nt * kPTile + srow;
             pmid = e < nmem ? a.memb_id[mb + e] : -1;
             if constexpr (kGrouped) pgrp = e < nmem ? a.memb_grp[mb + e] : -1;
-            prow = a.X + (size_t)(pmid < 0 ? 0 : pmid) * a.Dp + 2 * skp;
+            if constexpr (kWitness) {
+                // With the record stores behind the loop the grouped form came out three registers short and spilled
+                // its copy of a.X + 2 skp, a 64-bit pair that lives across the whole tile loop.  Here the column
+                // offset stays 32 bits wide and joins the row's offset once per tile; the empty asm statements keep
+                // the compiler from splitting the sum up again.  No scratch, two workgroups per CU as before.
+                int col = 2 * skp;
+                asm volatile("" : "+v"(col));
+                size_t off = (size_t)(pmid < 0 ? 0 : pmid) * a.Dp + (size_t)col;
+                asm volatile("" : "+v"(off));
+                prow = a.X + off;
+            } else prow = a.X + (size_t)(pmid < 0 ? 0 : pmid) * a.Dp + 2 * skp;
         }
         rq = *reinterpret_cast<const double2 *>(qrow + nc * kKChunk);
         rp = *reinterpret_cast<const double2 *>(prow + nc * kKChunk);
@@ -338,7 +370,23 @@ __global__ __launch_bounds__(256, 2) void recruit_select_wide_kernel(RecruitWide
             const int e = 16 * r + tx;
             if (r < ns && e < m) out[1 + e] = e < lc[i] ? li[i][r] : -1;
         }
+        if constexpr (kWitness) {
+            double *wd = a.w_d + prob * (size_t)m;
+#pragma unroll
+            for (int r = 0; r < kWideSlabs; ++r) {
+                const int e = 16 * r + tx;
+                if (r < ns && e < m) wd[e] = e < lc[i] ? ld[i][r] : kInf;
+            }
+        }
     }
+}
+
+template <bool kResident, bool kGrouped>
+void launch_select_witness(const RecruitWideWitnessArgs &a, hipStream_t s)
+{
+    if (a.nq <= 0 || a.ntile <= 0) return;
+    const int grid = ((a.ntile + 7) / 8) * 8;
+    hipLaunchKernelGGL((recruit_select_wide_kernel<kResident, true, kGrouped, true>), dim3(grid), dim3(256), 0, s, a, 0, a.ntile);
 }
 
 template <bool kResident, bool kGrouped>
@@ -367,6 +415,14 @@ void launch_recruit_select_wide(const RecruitWideArgs &a, hipStream_t s)
     else launch_select<true, false>(a, s);
 }
 
+// the witness form: a pair chunk (a.tile set), a.w_d written here
+void launch_recruit_select_wide_witness(const RecruitWideWitnessArgs &a, hipStream_t s)
+{
+    if (!a.qid) launch_select_witness<false, false>(a, s);
+    else if (a.memb_grp) launch_select_witness<true, true>(a, s);
+    else launch_select_witness<true, false>(a, s);
+}
+
 // one wavefront per problem: nq x B of a dense chunk, nq of a pair chunk
 void launch_hull_wide(const RecruitWideArgs &a, hipStream_t s)
 {
@@ -381,6 +437,19 @@ void launch_hull_wide(const RecruitWideArgs &a, hipStream_t s)
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(hull_wide_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)sizeof(GenLdsT<64>));
     hipLaunchKernelGGL((hull_wide_kernel<64>), dim3((unsigned)nprob), dim3(64), sizeof(GenLdsT<64>), s, a, (int)nprob);
+}
+
+// the witness form: one wavefront per position of a pair chunk, a.w_alpha written here
+void launch_hull_wide_witness(const RecruitWideWitnessArgs &a, hipStream_t s)
+{
+    if (a.nq <= 0) return;
+    if (a.m <= 32) {
+        hipLaunchKernelGGL((hull_wide_kernel<32, true>), dim3((unsigned)a.nq), dim3(64), 0, s, a, a.nq);
+        return;
+    }
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(hull_wide_kernel<64, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)sizeof(GenLdsT<64>));
+    hipLaunchKernelGGL((hull_wide_kernel<64, true>), dim3((unsigned)a.nq), dim3(64), sizeof(GenLdsT<64>), s, a, a.nq);
 }
 
 }  // namespace chb

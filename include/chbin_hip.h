@@ -406,6 +406,58 @@ int chb_recruit_pairs_wide(chb_ctx *h, const int64_t *labels, int64_t B, int m, 
                            const int64_t *row_of, const int64_t *bin_idx, int64_t P,
                            double *dist_out, int64_t *idx_out /* may be NULL */);
 
+/* Nearest bins, bin report and pair witnesses for any number of neighbours up to CHB_MAX_NEIGHBORS = 64: what a user turns
+ * to after an audit at 16 < m <= 64 -- which bins come next, which bins bleed into each other, which contigs vouch for a
+ * pair and with what weights.
+ *   - 1 <= m <= 16 (and every m the existing calls refuse as a bad argument): each forwards -- chb_audit_rows_nearest_wide to
+ *     chb_audit_rows_nearest, chb_recruit_rows_nearest_wide to chb_recruit_rows_nearest, chb_bin_report_wide to
+ *     chb_bin_report (groups == NULL) or chb_bin_report_grouped, chb_audit_pairs_witness_wide to chb_audit_pairs_witness,
+ *     chb_recruit_pairs_witness_wide to chb_recruit_pairs_witness.  Results, return codes and error texts are those
+ *     calls', bit for bit.
+ *   - 16 < m <= 64: each is defined by the wide call above on the same arguments and metric.
+ *     NEAREST BINS: the finite entries of the dist_out row of chb_audit_rows_wide / chb_recruit_rows_wide ranked by
+ *     (distance, bin) ascending, bit for bit, exact ties to the lower bin, -1 / +inf padding, k > B pads: slot 0 is that
+ *     call's bin_out / min_dist_out, slot 1 minus slot 0 its margin_out bit for bit.  The chunk's rows x B table is ranked
+ *     on the device in place of the row reduction (profile name "nearest_bins") and never comes down.
+ *     BIN REPORT: the tables of chb_bin_report's definition applied to chb_audit_rows_wide's distances (with groups: the
+ *     leave-group-out ones).  confusion, unplaced, dcnt and dmin are exact; dsum follows the block order documented for
+ *     chb_bin_report (blocks of 64 positions of a label, no chunk boundary inside a block), so it is bit-identical from
+ *     call to call and independent of where chunks fall -- the chunks are cut at "recruit_wide_rows" positions (as few as
+ *     64 with many bins and large m), then back to the label's block boundary.
+ *     WITNESS: dist_out is bit for bit chb_audit_pairs_wide / chb_recruit_pairs_wide; nbr_idx those calls' idx_out (hence
+ *     chb_topm_per_bin's list); nbr_dist[p*m + a] the member's rooted selection distance, chb_pairwise_distance's entry
+ *     bit for bit, +inf padding; alpha[p*m + a] the weight of vertex a exactly as the one-wavefront solver returned it
+ *     for the problem that produced dist_out, 0 padding.  A pair without vertices has +inf, all -1, all +inf, all 0.  The
+ *     meaning under the affine metric and the non-uniqueness among dependent vertices are as documented for m <= 16.
+ *     Each of nbr_idx, nbr_dist, alpha may be NULL; all three NULL with P > 0 is CHB_EINVAL.
+ *   - checks, in the existing calls' order: ranges (Q / P, B, m, and k < 1: CHB_EINVAL); null arguments; outputs; no
+ *     resident samples (CHB_ESTATE); D; m > 64, then m > 32 on a device that does not grant the 66 KiB of LDS per workgroup
+ *     (CHB_EUNSUPPORTED); k > 16 (CHB_EUNSUPPORTED); B > 8192 (CHB_EUNSUPPORTED); an open stepwise fit (CHB_ESTATE, the fit
+ *     stays usable); Q = 0 / P = 0 (CHB_OK, nothing further is read); the ranges of row_idx, then bin_idx / row_of.  A
+ *     refused call writes nothing.
+ *   - the call uses no state of a fit and leaves every counter (but "recruit_wide_rows" and, the pair forms,
+ *     "pair_tiles"), memo and switch of the context as it found it; no collective.
+ *   - the wide calls' pipeline and profile names ("..._wide_select", "..._wide_solve"), then "nearest_bins" /
+ *     "bin_report" as for m <= 16.  The witness forms of the two kernels add, per pair, m doubles each behind the list's
+ *     ids: the selection kernel the entries' distances, the solve kernel the lanes' weights; only what the caller asked
+ *     for comes down, through pinned buffers of their own, and the host unpacks it to the caller's pair order.  These
+ *     buffers are allocated by a context's first such call with m > 16 and freed with the context. */
+int chb_audit_rows_nearest_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups /* may be NULL */, int64_t B, int m,
+                                int k, const int64_t *row_idx, int64_t Q, int64_t *near_bin, double *near_dist);
+int chb_recruit_rows_nearest_wide(chb_ctx *h, const int64_t *labels, int64_t B, int m, int k,
+                                  const double *Y, int64_t Q, int64_t D, int64_t *near_bin, double *near_dist);
+int chb_bin_report_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups /* may be NULL */, int64_t B, int m,
+                        const int64_t *row_idx, int64_t Q,
+                        int64_t *confusion, int64_t *unplaced, int64_t *dcnt, double *dmin, double *dsum,
+                        int64_t *n_skipped);
+int chb_audit_pairs_witness_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups /* may be NULL */, int64_t B, int m,
+                                 const int64_t *row_idx, const int64_t *bin_idx, int64_t P,
+                                 double *dist_out, int64_t *nbr_idx, double *nbr_dist, double *alpha);
+int chb_recruit_pairs_witness_wide(chb_ctx *h, const int64_t *labels, int64_t B, int m,
+                                   const double *Y, int64_t Q, int64_t D,
+                                   const int64_t *row_of, const int64_t *bin_idx, int64_t P,
+                                   double *dist_out, int64_t *nbr_idx, double *nbr_dist, double *alpha);
+
 /* distance_matrix.py:47-62 find_nearest_from_cluster with the reference's exact signature: the
  * caller supplies one row of a distance matrix (any provenance) and the current labels; selects
  * among {p : labels[p] == c} the (up to) m smallest by (row[p], p).  out_idx[m] (-1 padded). */
