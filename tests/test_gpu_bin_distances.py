@@ -15,25 +15,18 @@ replayed by the oracle with all B distances of every visit (oracle.sweep(..., wa
 The cases cover the shortlist builds the product uses (threshold pools, tile skipping, the persistent member pack, several
 bins per workgroup), the hull kernels (fused m <= 5, 16-lane, wide rows, generic m > 16, list-based) and data edges.  A
 counter of each fit shows that the build under test really ran."""
-import json
-import os
-import subprocess
-import sys
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
+import fit_replay as R
+# the replay and the two checks live in fit_replay.py (shared with test_gpu_fit_neighbors.py); other modules of the suite
+# take these names from here
+from fit_replay import CHILD, DEV_LIB, QP_TOL, ROOT, TINY, oracle_replay  # noqa: F401
+from fit_replay import ctx_env as _ctx_env, margin as _margin, min2 as _min2  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-QP_TOL = 1e-9
-# scale of the scaled-data case (its distances are compared relative, to 1e-9).  Not 1e-150: there the Gram entries of the
-# reference's QP form (2 X X^T, ~1e-300) multiply to below the fp64 range and the oracle's distances are off by ~3e-2
-# relative to the enumerator's (from 1e-100 down); at 1e-50 they agree to ~3e-16 of the scale, like unscaled data
-TINY = 1e-50
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV_LIB = os.path.join(ROOT, "ch-bin_amd", "libchbin_hip_dev.so")
 
 # name: N, D, B, m, sweeps, batch (0 = default), generator keywords, product switches, expected counters
 #   (counter, op, value); "bpw": also run with CHB_SL_BPW = 3 / above 64 (pool-forced cases)
@@ -85,57 +78,12 @@ CASES = {
                                bpw=(3, 80)),
 }
 NAMES = list(CASES)
-COUNTERS = ["pool_batches", "pool_state", "tile_skip_state", "tile_skipped", "tile_seen", "tile_unloaded", "pack_builds",
-            "pack_incremental_batches", "fused_enabled", "prefilter_enabled", "shortlist_short", "batch_size"]
+COUNTERS = list(R.COUNTERS)
 
 
 def case_data(name):
     """(X, initial, perms) of a case; deterministic."""
-    from chbin_amd import synth
-    c = CASES[name]
-    N, D, B = c["N"], c["D"], c["B"]
-    gen = dict(c["gen"])
-    X, initial, true = synth.make_synthetic(N, D, B, seed=N + D + B + c["m"], **gen)
-    xf = c.get("xform")
-    if xf == "dups":
-        rng = np.random.default_rng(1)
-        X[rng.choice(N, N // 3, replace=False)] = X[rng.choice(N, N // 3, replace=False)]
-    elif xf == "tiny":
-        X = X * TINY
-    elif xf == "small_bins":
-        # bin B-2: two seeds taken from bin 0's seeds; bin B-1: no seed at all (the contigs the generator put there move)
-        initial[initial == B - 2] = -1
-        initial[initial == B - 1] = -1
-        initial[np.flatnonzero(initial == 0)[:2]] = B - 2
-    perms = synth.draw_permutations(initial, c["its"], seed=0)
-    return np.ascontiguousarray(X), initial, perms
-
-
-def oracle_replay(X, B, initial, perms, m, its, metric="convex"):
-    """The reference loop over perms[:its] (algorithm.py:12-76), with ALL B hull distances of its last sweep's visits.
-    Returns (labels, sweeps run, changes per sweep, N x B distances of the last sweep: NaN rows for the seeds)."""
-    from oracle import oracle as O
-    if its > 1:
-        before, its_b, ch_b = O.fit_cluster(X, B, initial, perms[: its - 1], m, its - 1, metric=metric)
-        if its_b < its - 1:   # (converged early: the reference's last sweep is sweep its_b)
-            return oracle_replay(X, B, initial, perms, m, its_b, metric)
-    else:
-        before, ch_b = initial.copy(), np.zeros(0, dtype=np.int64)
-    after, _, alld = O.sweep(X, B, before, perms[its - 1], m, want_all=True, metric=metric)
-    full = np.full((len(X), B), np.nan)
-    full[perms[its - 1]] = alld
-    return after, its, np.append(ch_b, np.count_nonzero(after != before)), full
-
-
-def _min2(d):
-    """Row minimum and second-smallest entry (the argmin kernel's winner and runner-up), NaN rows kept NaN."""
-    s = np.sort(d, axis=1)
-    return s[:, 0], s[:, 1] if d.shape[1] > 1 else np.full(len(d), np.inf)
-
-
-def _margin(best, second):
-    with np.errstate(invalid="ignore"):
-        return np.where(second == np.inf, np.inf, second - best)
+    return R.case_data(CASES[name])
 
 
 @pytest.fixture(scope="module")
@@ -161,127 +109,18 @@ def _oracle(data, name):
     return data[name]["oracle"].result()
 
 
-def _ctx_env(env):
-    from chbin_amd import _lib
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return _lib.Context(0)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
-
-
-def _check_counters(name, cnt):
-    ops = {">": lambda a, b: a > b, "==": lambda a, b: a == b}
-    for k, op, v in CASES[name]["expect"]:
-        assert ops[op](cnt[k], v), (name, k, cnt[k], op, v)
-
-
 @pytest.mark.parametrize("name", NAMES)
 def test_product_min_dist_and_margin(data, name):
     """(a) product library: labels, sweeps and changes equal the oracle's; min_dist is the row minimum of the oracle's
     distances and margin second-smallest minus smallest (0 on ties, +inf without a runner-up); seeds are NaN."""
-    c, d = CASES[name], data[name]
-    ctx = _ctx_env(c.get("env", {}))
-    try:
-        ctx.set_samples(d["X"])
-        if c.get("metric"):
-            ctx.set_metric(c["metric"])
-        lab, its, ch, mind, margin = ctx.fit_cluster_margins(c["B"], d["initial"], d["perms"], c["m"], c["its"],
-                                                            batch=c["batch"], want_min_dist=True)
-        assert ctx.counter("shortlist_short") == 0
-        cnt = {k: ctx.counter(k) for k in COUNTERS}
-    finally:
-        ctx.close()
-    want, its_o, ch_o, alld = _oracle(data, name)
-    assert its == its_o and np.array_equal(ch, ch_o) and np.array_equal(lab, want), (name, its, its_o, ch, ch_o)
-    mv = d["initial"] < 0
-    assert np.all(np.isnan(mind[~mv])) and np.all(np.isnan(margin[~mv]))
-    best, second = _min2(alld[mv])
-    tol = 1e-9 * np.abs(best) if c.get("xform") == "tiny" else QP_TOL
-    assert np.array_equal(np.isinf(mind[mv]), np.isinf(best))
-    fin = np.isfinite(best)
-    assert np.all(np.abs(mind[mv] - best)[fin] <= (tol[fin] if np.ndim(tol) else tol)), name
-    want_margin = _margin(best, second)
-    assert np.array_equal(np.isinf(margin[mv]), np.isinf(want_margin)) and not np.any(np.isnan(margin[mv]))
-    fin = np.isfinite(want_margin)
-    tol_m = 2e-9 * np.maximum(np.abs(best), np.abs(second)) if c.get("xform") == "tiny" else 2 * QP_TOL
-    assert np.all(np.abs(margin[mv] - want_margin)[fin] <= (tol_m[fin] if np.ndim(tol_m) else tol_m)), name
-    print(f"\n[a] {name}: {its} sweeps, {int(mv.sum())} movable x {c['B']} bins, min margin "
-          f"{np.min(margin[mv]):.3g}; counters {cnt}")
-
-
-CHILD = r"""
-import json, os, sys
-job = json.load(open(sys.argv[1]))
-sys.path.insert(0, job["root"])
-import numpy as np
-import chbin_amd
-from chbin_amd import _lib
-res = {}
-for c in job["cases"]:
-    d = np.load(c["npz"])
-    old = {k: os.environ.get(k) for k in c["env"]}
-    os.environ.update(c["env"])
-    try:
-        ctx = _lib.Context(0)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
-    try:
-        ctx.set_samples(d["X"])
-        if c["metric"]:
-            ctx.set_metric(c["metric"])
-        os.environ["CHB_DEV_ALL_DIST"] = c["dump"]
-        try:
-            lab, its, ch, mind, margin = ctx.fit_cluster_margins(c["B"], d["initial"], d["perms"], c["m"], c["its"],
-                                                                batch=c["batch"], want_min_dist=True)
-        finally:
-            del os.environ["CHB_DEV_ALL_DIST"]
-        cnt = {k: int(ctx.counter(k)) for k in job["counters"]}
-    finally:
-        ctx.close()
-    np.savez(c["out"], labels=lab, changed=ch, mind=mind, margin=margin)
-    res[c["name"]] = {"its": int(its), "counters": cnt}
-    print(c["name"], its, cnt, flush=True)
-json.dump(res, open(job["result"], "w"))
-"""
+    R.check_product(name, CASES[name], data[name], _oracle(data, name), COUNTERS)
 
 
 def _run_child(data, tag, names, env):
     """One developer-library child over `names` (contexts one after another, each with its case's switches); returns
-    {name: (result record, dumped N x B distances, outputs)}."""
-    if not os.path.exists(DEV_LIB):
-        pytest.fail("developer library not built (__graft_entry__.build() makes it)")
-    tmp = data["_tmp"]
-    cases = []
-    for name in names:
-        c = CASES[name]
-        cases.append(dict(name=name, npz=data[name]["npz"], B=c["B"], m=c["m"], its=c["its"], batch=c["batch"],
-                          metric=c.get("metric"), env=dict(c.get("env", {})),
-                          dump=str(tmp / f"{tag}_{name}.f64"), out=str(tmp / f"{tag}_{name}_out.npz")))
-    job = dict(root=ROOT, cases=cases, counters=COUNTERS, result=str(tmp / f"{tag}.json"))
-    (tmp / f"{tag}_job.json").write_text(json.dumps(job))
-    (tmp / "child.py").write_text(CHILD)
-    e = dict(os.environ, CHBIN_LIB=DEV_LIB, CHB_SL_BOUNDS="1", CHB_SL_VALIDATE="1", **env)
-    p = subprocess.run([sys.executable, str(tmp / "child.py"), str(tmp / f"{tag}_job.json")], env=e,
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
-    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
-    res = json.loads((tmp / f"{tag}.json").read_text())
-    out = {}
-    for c in cases:
-        N, B = CASES[c["name"]]["N"], c["B"]
-        alld = np.fromfile(c["dump"], dtype=np.float64)
-        assert alld.size == N * B, (c["name"], alld.size)
-        out[c["name"]] = (res[c["name"]], alld.reshape(N, B), dict(np.load(c["out"])))
-    return out
+    {name: (result record, dumped N x B distances, outputs)}.  Cases and counters are this module's at the time of the
+    call."""
+    return R.run_child(data, tag, names, env, CASES, COUNTERS)
 
 
 @pytest.fixture(scope="module")
@@ -301,26 +140,7 @@ def dev_runs(data):
 
 
 def _check_all_distances(data, name, rec, got, outs, what):
-    c, d = CASES[name], data[name]
-    want, its_o, ch_o, alld = _oracle(data, name)
-    assert rec["its"] == its_o and np.array_equal(outs["changed"], ch_o) and np.array_equal(outs["labels"], want), \
-        (what, name, rec["its"], its_o)
-    assert rec["counters"]["shortlist_short"] == 0, (what, name)
-    _check_counters(name, rec["counters"])
-    mv = d["initial"] < 0
-    assert np.all(np.isnan(got[~mv])) and not np.any(np.isnan(got[mv])), (what, name)
-    g, o = got[mv], alld[mv]
-    assert np.array_equal(np.isinf(g), np.isinf(o)), (what, name, np.argwhere(np.isinf(g) != np.isinf(o))[:8])
-    fin = np.isfinite(o)
-    err = np.abs(g[fin] - o[fin])
-    bound = 1e-9 * np.abs(o[fin]) if c.get("xform") == "tiny" else QP_TOL
-    bad = np.flatnonzero(err > bound)
-    assert bad.size == 0, (what, name, f"{bad.size} of {err.size} distances off, worst {err.max():.3g}")
-    # the winner and runner-up of the dumped rows are what min_dist / margin report (and what (a) saw)
-    best, second = _min2(g)
-    assert np.array_equal(outs["mind"][mv], best), (what, name)
-    assert np.array_equal(outs["margin"][mv], _margin(best, second))
-    return err.max() if err.size else 0.0
+    return R.check_all_distances(name, CASES[name], data[name], _oracle(data, name), rec, got, outs, what)
 
 
 @pytest.mark.parametrize("name", NAMES)
