@@ -269,9 +269,49 @@ class Context:
             raise ValueError("groups must have one entry per resident sample")
         return groups
 
-    def _score_rows(self, name, labels, B, want_dist, m=None, ms=None, rows=None, Y=None, groups=None):
-        """The four row-scoring calls: chb_<name>_rows for one m, of the new rows Y or the resident rows `rows`, or with a
-        list `ms` its _multi form, whose outputs carry a leading axis of len(ms); with `groups` the audit's _grouped form."""
+    # ---- row scoring: one private method per call shape (_score_rows, _bin_report, _score_pairs), parameterised by the C
+    # symbol; the public methods below differ in the symbol they name and in where their arguments go
+    @staticmethod
+    def _ptr(a):
+        return None if a is None else a.ctypes.data
+
+    @staticmethod
+    def _new_rows(Y):
+        """The rows of a recruit call: 2-D float64."""
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim != 2:
+            raise ValueError("rows must be a 2-D array")
+        return Y
+
+    def _frozen(self, symbol, labels, groups, slot):
+        """(C function, [labels] or [labels, groups]) of a call against a frozen labelling, both checked.  groups go to a
+        symbol that has a slot for them (`slot`: the _wide, _witness and _nearest audits, None passing NULL); given to any
+        other symbol they select its _grouped form."""
+        head = [self._labels(labels)]
+        if groups is not None:
+            head.append(self._groups(groups))
+            if not slot:
+                symbol += "_grouped"
+        elif slot:
+            head.append(None)
+        return getattr(self._lib, symbol), head
+
+    @staticmethod
+    def _dense_arrays(lead, Q, B, want_dist):
+        """bins [*lead, Q], dist [*lead, Q, B] or None, min_dist [*lead, Q], margin [*lead, Q] of a dense call"""
+        return (np.empty(lead + (Q,), dtype=np.int64), np.empty(lead + (Q, int(B)), dtype=np.float64) if want_dist else None,
+                np.empty(lead + (Q,), dtype=np.float64), np.empty(lead + (Q,), dtype=np.float64))
+
+    @staticmethod
+    def _nearest_arrays(Q, k):
+        """bins [Q, k] and dist [Q, k] of a nearest-bins call (refused calls write nothing: k as given, at least 0)"""
+        k = max(int(k), 0)
+        return np.empty((Q, k), dtype=np.int64), np.empty((Q, k), dtype=np.float64)
+
+    def _score_rows(self, symbol, labels, B, want_dist, m=None, ms=None, k=None, rows=None, Y=None, groups=None, slot=False):
+        """The dense calls: `symbol` for one m, of the new rows Y or the resident rows `rows`, or with a list `ms` its _multi
+        form, whose outputs carry a leading axis of len(ms); with `groups` the audit's leave-group-out form (_frozen).
+        Returns (bins, dist or None, min_dist, margin), or with `k`, a _nearest symbol, (bins [Q, k], dist [Q, k])."""
         if groups is not None and Y is not None:
             raise ValueError("groups belong to resident samples: rows that are not samples have no siblings to withhold")
         if ms is not None:
@@ -279,85 +319,72 @@ class Context:
             if ms.ndim != 1:
                 raise ValueError("ms must be a 1-D list of neighbour counts")
         if Y is not None:
-            Y = np.ascontiguousarray(Y, dtype=np.float64)
-            if Y.ndim != 2:
-                raise ValueError("rows must be a 2-D array")
-        labels = self._labels(labels)
+            Y = self._new_rows(Y)
+        fn, head = self._frozen(symbol, labels, groups, slot)
         if Y is not None:
             source = (Y.ctypes.data, *Y.shape)
         else:
             *source, rows = self._row_indices(rows)
-        lead, Q = () if ms is None else ms.shape, source[1]
-        bins = np.empty(lead + (Q,), dtype=np.int64)
-        dist = np.empty(lead + (Q, int(B)), dtype=np.float64) if want_dist else None
-        mind = np.empty(lead + (Q,), dtype=np.float64)
-        margin = np.empty(lead + (Q,), dtype=np.float64)
-        fn = f"chb_{name}_rows" if ms is None else f"chb_{name}_rows_multi"
-        grouped = ()
-        if groups is not None:
-            groups = self._groups(groups)
-            fn, grouped = fn + "_grouped", (groups.ctypes.data,)
-        fn = getattr(self._lib, fn)
+        Q = source[1]
         neighbours = (int(m),) if ms is None else (ms.ctypes.data, ms.shape[0])
-        check(fn(self._h, labels.ctypes.data, *grouped, int(B), *neighbours, *source,
-                 bins.ctypes.data, None if dist is None else dist.ctypes.data, mind.ctypes.data, margin.ctypes.data))
-        return bins, dist, mind, margin
+        if k is None:
+            out = self._dense_arrays(() if ms is None else ms.shape, Q, B, want_dist)
+        else:
+            neighbours, out = neighbours + (int(k),), self._nearest_arrays(Q, k)
+        check(fn(self._h, *map(self._ptr, head), int(B), *neighbours, *source, *map(self._ptr, out)))
+        return out
 
     def recruit_rows(self, labels, B, m, Y, want_dist=True):
         """chb_recruit_rows: hull distance of the NEW rows Y (not samples) to every bin of the frozen `labels`.
         Returns (bins [Q], dist [Q, B] or None, min_dist [Q], margin [Q])."""
-        return self._score_rows("recruit", labels, B, want_dist, m=m, Y=Y)
+        return self._score_rows("chb_recruit_rows", labels, B, want_dist, m=m, Y=Y)
 
     def audit_rows(self, labels, B, m, rows=None, want_dist=True):
         """chb_audit_rows: leave-one-out hull distance of the RESIDENT rows `rows` (sample indices, repeats allowed; None:
         every row in order) to every bin of the frozen `labels`; a row is withheld from its own bin's candidates.
         Returns (bins [Q], dist [Q, B] or None, min_dist [Q], margin [Q])."""
-        return self._score_rows("audit", labels, B, want_dist, m=m, rows=rows)
+        return self._score_rows("chb_audit_rows", labels, B, want_dist, m=m, rows=rows)
 
     def audit_rows_multi(self, labels, B, ms, rows=None, want_dist=True):
         """chb_audit_rows_multi: audit_rows for every m of the list `ms` (distinct values in 1 .. 16, at most 16 of them,
         any order) from one selection pass; slice j of every result is bit for bit audit_rows(labels, B, ms[j], rows).
         Returns (bins [nm, Q], dist [nm, Q, B] or None, min_dist [nm, Q], margin [nm, Q])."""
-        return self._score_rows("audit", labels, B, want_dist, ms=ms, rows=rows)
+        return self._score_rows("chb_audit_rows_multi", labels, B, want_dist, ms=ms, rows=rows)
 
     def audit_rows_grouped(self, labels, groups, B, m, rows=None, want_dist=True):
         """chb_audit_rows_grouped: audit_rows with every sample that shares the scored row's group id withheld as well
         (leave-group-out; `groups` int64 per resident sample, negative: no group) -- for a row of group g bit for bit
         audit_rows on `labels` with g's members set to -1.  Returns what audit_rows returns."""
-        return self._score_rows("audit", labels, B, want_dist, m=m, rows=rows, groups=groups)
+        return self._score_rows("chb_audit_rows", labels, B, want_dist, m=m, rows=rows, groups=groups)
 
     def audit_rows_multi_grouped(self, labels, groups, B, ms, rows=None, want_dist=True):
         """chb_audit_rows_multi_grouped: audit_rows_grouped for every m of the list `ms` from one selection pass."""
-        return self._score_rows("audit", labels, B, want_dist, ms=ms, rows=rows, groups=groups)
+        return self._score_rows("chb_audit_rows_multi", labels, B, want_dist, ms=ms, rows=rows, groups=groups)
 
     def recruit_rows_multi(self, labels, B, ms, Y, want_dist=True):
         """chb_recruit_rows_multi: recruit_rows for every m of the list `ms` from one selection pass; slice j of every
         result is bit for bit recruit_rows(labels, B, ms[j], Y).
         Returns (bins [nm, Q], dist [nm, Q, B] or None, min_dist [nm, Q], margin [nm, Q])."""
-        return self._score_rows("recruit", labels, B, want_dist, ms=ms, Y=Y)
+        return self._score_rows("chb_recruit_rows_multi", labels, B, want_dist, ms=ms, Y=Y)
+
+    def _bin_report(self, symbol, labels, B, m, rows, groups, slot):
+        """The report calls: `symbol` (with `groups` its leave-group-out form: _frozen) and its five tables."""
+        fn, head = self._frozen(symbol, labels, groups, slot)
+        row_idx, Q, rows = self._row_indices(rows)
+        B = int(B)
+        nb = max(B, 0) if B <= 8192 else 0   # (beyond the limit the call is refused before it writes anything)
+        tables = (np.empty((nb, nb), dtype=np.int64), np.empty(nb, dtype=np.int64), np.empty((nb, nb), dtype=np.int64),
+                  np.empty((nb, nb), dtype=np.float64), np.empty((nb, nb), dtype=np.float64))
+        skipped = C.c_int64(0)
+        check(fn(self._h, *map(self._ptr, head), B, int(m), row_idx, Q, *map(self._ptr, tables), C.addressof(skipped)))
+        return (*tables, int(skipped.value))
 
     def bin_report(self, labels, B, m, rows=None, groups=None):
         """chb_bin_report: chb_audit_rows' answer for the RESIDENT rows `rows` (None: every row in order) summed up on the
         device per (own bin a, bin b) pair; rows whose own label lies outside [0, B) are not scored.  With `groups`
         chb_bin_report_grouped: the same tables of chb_audit_rows_grouped's answer.
         Returns (confusion [B, B], unplaced [B], dcnt [B, B], dmin [B, B], dsum [B, B], n_skipped)."""
-        labels = self._labels(labels)
-        fn, grouped = self._lib.chb_bin_report, ()
-        if groups is not None:
-            groups = self._groups(groups)
-            fn, grouped = self._lib.chb_bin_report_grouped, (groups.ctypes.data,)
-        row_idx, Q, rows = self._row_indices(rows)
-        B = int(B)
-        nb = max(B, 0) if B <= 8192 else 0   # (beyond the limit the call is refused before it writes anything)
-        confusion = np.empty((nb, nb), dtype=np.int64)
-        unplaced = np.empty(nb, dtype=np.int64)
-        dcnt = np.empty((nb, nb), dtype=np.int64)
-        dmin = np.empty((nb, nb), dtype=np.float64)
-        dsum = np.empty((nb, nb), dtype=np.float64)
-        skipped = C.c_int64(0)
-        check(fn(self._h, labels.ctypes.data, *grouped, B, int(m), row_idx, Q, confusion.ctypes.data,
-                 unplaced.ctypes.data, dcnt.ctypes.data, dmin.ctypes.data, dsum.ctypes.data, C.addressof(skipped)))
-        return confusion, unplaced, dcnt, dmin, dsum, int(skipped.value)
+        return self._bin_report("chb_bin_report", labels, B, m, rows, groups, slot=False)
 
     def bin_report_grouped(self, labels, groups, B, m, rows=None):
         """chb_bin_report_grouped: bin_report of the leave-group-out distances (audit_rows_grouped)."""
@@ -374,20 +401,33 @@ class Context:
             raise ValueError(f"{rows_name} and bins must have one entry per pair: {rows.shape[0]} and {bins.shape[0]}")
         return rows, bins
 
+    def _score_pairs(self, symbol, labels, B, m, rows, bins, Y=None, groups=None, slot=False, idx=None, witness=False):
+        """The pair calls: `symbol` for the pairs (rows[p], bins[p]) of resident rows or, with Y, of rows of Y (`rows` is
+        then row_of); with `groups` the audit's leave-group-out form (_frozen).  Returns dist [P]; for a symbol with an
+        idx_out (`idx` not None: whether it is wanted, else it is passed NULL) dist or (dist, idx [P, m]); for a `witness`
+        symbol (dist, neighbors, neighbor_dist, weights), the last three [P, m].
+        (A refused call writes nothing: the [P, m] arrays take m as given, at least 0.)"""
+        rows, bins = self._pair_lists(rows, bins, "rows" if Y is None else "row_of")
+        if Y is not None:
+            Y = self._new_rows(Y)
+        fn, head = self._frozen(symbol, labels, groups, slot)
+        P, m_out = rows.shape[0], max(int(m), 0)
+        out = [np.empty(P, dtype=np.float64)]
+        if witness:
+            out += [np.empty((P, m_out), dtype=np.int64), np.empty((P, m_out), dtype=np.float64),
+                    np.empty((P, m_out), dtype=np.float64)]
+        elif idx is not None:
+            out.append(np.empty((P, m_out), dtype=np.int64) if idx else None)
+        source = () if Y is None else (Y.ctypes.data, *Y.shape)
+        check(fn(self._h, *map(self._ptr, head), int(B), int(m), *source, rows.ctypes.data, bins.ctypes.data, P,
+                 *map(self._ptr, out)))
+        return tuple(out) if witness or idx else out[0]
+
     def audit_pairs(self, labels, B, m, rows, bins, groups=None):
         """chb_audit_pairs: dist [P], entry p bit for bit audit_rows(labels, B, m, rows)[1][p, bins[p]] -- the leave-one-out
         hull distance of the RESIDENT row rows[p] to bin bins[p] -- at the cost of the listed pairs only.  With `groups`
         chb_audit_pairs_grouped: the same entries of audit_rows_grouped."""
-        rows, bins = self._pair_lists(rows, bins, "rows")
-        labels = self._labels(labels)
-        fn, grouped = self._lib.chb_audit_pairs, ()
-        if groups is not None:
-            groups = self._groups(groups)
-            fn, grouped = self._lib.chb_audit_pairs_grouped, (groups.ctypes.data,)
-        dist = np.empty(rows.shape[0], dtype=np.float64)
-        check(fn(self._h, labels.ctypes.data, *grouped, int(B), int(m), rows.ctypes.data, bins.ctypes.data,
-                 rows.shape[0], dist.ctypes.data))
-        return dist
+        return self._score_pairs("chb_audit_pairs", labels, B, m, rows, bins, groups=groups)
 
     def audit_pairs_grouped(self, labels, groups, B, m, rows, bins):
         """chb_audit_pairs_grouped: audit_pairs of the leave-group-out distances (audit_rows_grouped)."""
@@ -396,22 +436,7 @@ class Context:
     def recruit_pairs(self, labels, B, m, Y, row_of, bins):
         """chb_recruit_pairs: dist [P], entry p bit for bit recruit_rows(labels, B, m, Y)[1][row_of[p], bins[p]] -- the hull
         distance of the NEW row Y[row_of[p]] to bin bins[p]."""
-        row_of, bins = self._pair_lists(row_of, bins, "row_of")
-        Y = np.ascontiguousarray(Y, dtype=np.float64)
-        if Y.ndim != 2:
-            raise ValueError("rows must be a 2-D array")
-        labels = self._labels(labels)
-        dist = np.empty(row_of.shape[0], dtype=np.float64)
-        check(self._lib.chb_recruit_pairs(self._h, labels.ctypes.data, int(B), int(m), Y.ctypes.data, *Y.shape,
-                                          row_of.ctypes.data, bins.ctypes.data, row_of.shape[0], dist.ctypes.data))
-        return dist
-
-    @staticmethod
-    def _witness_arrays(P, m):
-        """dist [P] and the three [P, m] arrays of a witness call (refused calls write nothing: m as given, at least 0)"""
-        m = max(int(m), 0)
-        return (np.empty(P, dtype=np.float64), np.empty((P, m), dtype=np.int64), np.empty((P, m), dtype=np.float64),
-                np.empty((P, m), dtype=np.float64))
+        return self._score_pairs("chb_recruit_pairs", labels, B, m, row_of, bins, Y=Y)
 
     def audit_pairs_witness(self, labels, B, m, rows, bins, groups=None):
         """chb_audit_pairs_witness: audit_pairs (with `groups` audit_pairs_grouped) together with the hull each distance
@@ -419,199 +444,70 @@ class Context:
         the plain call's; per pair the selected members' sample indices in the kernel's list order ((distance, index)
         ascending; -1 padding), their distances to the row (+inf padding) and their weights in the hull's nearest point
         under the context's metric (0 padding; not unique where vertices are dependent)."""
-        rows, bins = self._pair_lists(rows, bins, "rows")
-        labels = self._labels(labels)
-        if groups is not None:
-            groups = self._groups(groups)
-        dist, idx, nd, alpha = self._witness_arrays(rows.shape[0], m)
-        check(self._lib.chb_audit_pairs_witness(self._h, labels.ctypes.data, None if groups is None else groups.ctypes.data,
-                                                int(B), int(m), rows.ctypes.data, bins.ctypes.data, rows.shape[0],
-                                                dist.ctypes.data, idx.ctypes.data, nd.ctypes.data, alpha.ctypes.data))
-        return dist, idx, nd, alpha
+        return self._score_pairs("chb_audit_pairs_witness", labels, B, m, rows, bins, groups=groups, slot=True, witness=True)
 
     def recruit_pairs_witness(self, labels, B, m, Y, row_of, bins):
         """chb_recruit_pairs_witness: recruit_pairs together with the hull each distance was measured to; returns what
         audit_pairs_witness returns, for the NEW rows Y[row_of[p]] (nothing is withheld)."""
-        row_of, bins = self._pair_lists(row_of, bins, "row_of")
-        Y = np.ascontiguousarray(Y, dtype=np.float64)
-        if Y.ndim != 2:
-            raise ValueError("rows must be a 2-D array")
-        labels = self._labels(labels)
-        dist, idx, nd, alpha = self._witness_arrays(row_of.shape[0], m)
-        check(self._lib.chb_recruit_pairs_witness(self._h, labels.ctypes.data, int(B), int(m), Y.ctypes.data, *Y.shape,
-                                                  row_of.ctypes.data, bins.ctypes.data, row_of.shape[0],
-                                                  dist.ctypes.data, idx.ctypes.data, nd.ctypes.data, alpha.ctypes.data))
-        return dist, idx, nd, alpha
-
-    @staticmethod
-    def _nearest_arrays(Q, k):
-        """bins [Q, k] and dist [Q, k] of a nearest-bins call (refused calls write nothing: k as given, at least 0)"""
-        k = max(int(k), 0)
-        return np.empty((Q, k), dtype=np.int64), np.empty((Q, k), dtype=np.float64)
+        return self._score_pairs("chb_recruit_pairs_witness", labels, B, m, row_of, bins, Y=Y, witness=True)
 
     def audit_rows_nearest(self, labels, B, m, k, rows=None, groups=None):
         """chb_audit_rows_nearest: the k nearest bins of every RESIDENT row in `rows` (None: every row in order), ranked on
         the device: the finite entries of audit_rows' (with `groups` audit_rows_grouped's) dist row in (distance, bin)
         order, bit for bit.  Returns (bins [Q, k], dist [Q, k]); slots past the number of finite entries hold -1 / +inf."""
-        labels = self._labels(labels)
-        if groups is not None:
-            groups = self._groups(groups)
-        row_idx, Q, rows = self._row_indices(rows)
-        bins, dist = self._nearest_arrays(Q, k)
-        check(self._lib.chb_audit_rows_nearest(self._h, labels.ctypes.data, None if groups is None else groups.ctypes.data,
-                                               int(B), int(m), int(k), row_idx, Q, bins.ctypes.data, dist.ctypes.data))
-        return bins, dist
+        return self._score_rows("chb_audit_rows_nearest", labels, B, None, m=m, k=k, rows=rows, groups=groups, slot=True)
 
     def recruit_rows_nearest(self, labels, B, m, k, Y):
         """chb_recruit_rows_nearest: audit_rows_nearest for the NEW rows Y (nothing is withheld), ranked from
         recruit_rows' dist rows.  Returns (bins [Q, k], dist [Q, k])."""
-        Y = np.ascontiguousarray(Y, dtype=np.float64)
-        if Y.ndim != 2:
-            raise ValueError("rows must be a 2-D array")
-        labels = self._labels(labels)
-        bins, dist = self._nearest_arrays(Y.shape[0], k)
-        check(self._lib.chb_recruit_rows_nearest(self._h, labels.ctypes.data, int(B), int(m), int(k), Y.ctypes.data,
-                                                 *Y.shape, bins.ctypes.data, dist.ctypes.data))
-        return bins, dist
+        return self._score_rows("chb_recruit_rows_nearest", labels, B, None, m=m, k=k, Y=Y)
 
     def audit_rows_wide(self, labels, B, m, rows=None, want_dist=True, groups=None):
         """chb_audit_rows_wide: audit_rows (with `groups` audit_rows_grouped) for any m in 1 .. 64 -- m <= 16 forwards to
         those calls bit for bit, 16 < m <= 64 runs the wide kernels.  Returns what audit_rows returns."""
-        labels = self._labels(labels)
-        if groups is not None:
-            groups = self._groups(groups)
-        row_idx, Q, rows = self._row_indices(rows)
-        bins = np.empty(Q, dtype=np.int64)
-        dist = np.empty((Q, int(B)), dtype=np.float64) if want_dist else None
-        mind = np.empty(Q, dtype=np.float64)
-        margin = np.empty(Q, dtype=np.float64)
-        check(self._lib.chb_audit_rows_wide(self._h, labels.ctypes.data, None if groups is None else groups.ctypes.data,
-                                            int(B), int(m), row_idx, Q, bins.ctypes.data,
-                                            None if dist is None else dist.ctypes.data, mind.ctypes.data, margin.ctypes.data))
-        return bins, dist, mind, margin
+        return self._score_rows("chb_audit_rows_wide", labels, B, want_dist, m=m, rows=rows, groups=groups, slot=True)
 
     def recruit_rows_wide(self, labels, B, m, Y, want_dist=True):
         """chb_recruit_rows_wide: recruit_rows for any m in 1 .. 64.  Returns what recruit_rows returns."""
-        Y = np.ascontiguousarray(Y, dtype=np.float64)
-        if Y.ndim != 2:
-            raise ValueError("rows must be a 2-D array")
-        labels = self._labels(labels)
-        Q = Y.shape[0]
-        bins = np.empty(Q, dtype=np.int64)
-        dist = np.empty((Q, int(B)), dtype=np.float64) if want_dist else None
-        mind = np.empty(Q, dtype=np.float64)
-        margin = np.empty(Q, dtype=np.float64)
-        check(self._lib.chb_recruit_rows_wide(self._h, labels.ctypes.data, int(B), int(m), Y.ctypes.data, *Y.shape,
-                                              bins.ctypes.data, None if dist is None else dist.ctypes.data,
-                                              mind.ctypes.data, margin.ctypes.data))
-        return bins, dist, mind, margin
+        return self._score_rows("chb_recruit_rows_wide", labels, B, want_dist, m=m, Y=Y)
 
     def audit_pairs_wide(self, labels, B, m, rows, bins, groups=None, want_idx=False):
         """chb_audit_pairs_wide: audit_pairs (with `groups` audit_pairs_grouped) for any m in 1 .. 64; entry p is bit for
         bit audit_rows_wide(labels, B, m, rows, groups=groups)[1][p, bins[p]].  Returns dist [P], or with want_idx
         (dist, idx [P, m]): per pair the selected members' sample indices in (distance, index) order, -1 padded -- what
         topm_per_bin returns for the row."""
-        rows, bins = self._pair_lists(rows, bins, "rows")
-        labels = self._labels(labels)
-        if groups is not None:
-            groups = self._groups(groups)
-        P = rows.shape[0]
-        dist = np.empty(P, dtype=np.float64)
-        idx = np.empty((P, max(int(m), 0)), dtype=np.int64) if want_idx else None
-        check(self._lib.chb_audit_pairs_wide(self._h, labels.ctypes.data, None if groups is None else groups.ctypes.data,
-                                             int(B), int(m), rows.ctypes.data, bins.ctypes.data, P, dist.ctypes.data,
-                                             None if idx is None else idx.ctypes.data))
-        return (dist, idx) if want_idx else dist
+        return self._score_pairs("chb_audit_pairs_wide", labels, B, m, rows, bins, groups=groups, slot=True, idx=bool(want_idx))
 
     def recruit_pairs_wide(self, labels, B, m, Y, row_of, bins, want_idx=False):
         """chb_recruit_pairs_wide: recruit_pairs for any m in 1 .. 64; entry p is bit for bit
         recruit_rows_wide(labels, B, m, Y)[1][row_of[p], bins[p]].  Returns dist [P] or, with want_idx, (dist, idx [P, m])."""
-        row_of, bins = self._pair_lists(row_of, bins, "row_of")
-        Y = np.ascontiguousarray(Y, dtype=np.float64)
-        if Y.ndim != 2:
-            raise ValueError("rows must be a 2-D array")
-        labels = self._labels(labels)
-        P = row_of.shape[0]
-        dist = np.empty(P, dtype=np.float64)
-        idx = np.empty((P, max(int(m), 0)), dtype=np.int64) if want_idx else None
-        check(self._lib.chb_recruit_pairs_wide(self._h, labels.ctypes.data, int(B), int(m), Y.ctypes.data, *Y.shape,
-                                               row_of.ctypes.data, bins.ctypes.data, P, dist.ctypes.data,
-                                               None if idx is None else idx.ctypes.data))
-        return (dist, idx) if want_idx else dist
+        return self._score_pairs("chb_recruit_pairs_wide", labels, B, m, row_of, bins, Y=Y, idx=bool(want_idx))
 
     def audit_rows_nearest_wide(self, labels, B, m, k, rows=None, groups=None):
         """chb_audit_rows_nearest_wide: audit_rows_nearest for any m in 1 .. 64 -- m <= 16 forwards to it bit for bit,
         16 < m <= 64 ranks audit_rows_wide's dist rows on the device.  Returns what audit_rows_nearest returns."""
-        labels = self._labels(labels)
-        if groups is not None:
-            groups = self._groups(groups)
-        row_idx, Q, rows = self._row_indices(rows)
-        bins, dist = self._nearest_arrays(Q, k)
-        check(self._lib.chb_audit_rows_nearest_wide(self._h, labels.ctypes.data,
-                                                    None if groups is None else groups.ctypes.data, int(B), int(m), int(k),
-                                                    row_idx, Q, bins.ctypes.data, dist.ctypes.data))
-        return bins, dist
+        return self._score_rows("chb_audit_rows_nearest_wide", labels, B, None, m=m, k=k, rows=rows, groups=groups, slot=True)
 
     def recruit_rows_nearest_wide(self, labels, B, m, k, Y):
         """chb_recruit_rows_nearest_wide: recruit_rows_nearest for any m in 1 .. 64 (16 < m <= 64: ranked from
         recruit_rows_wide's dist rows).  Returns (bins [Q, k], dist [Q, k])."""
-        Y = np.ascontiguousarray(Y, dtype=np.float64)
-        if Y.ndim != 2:
-            raise ValueError("rows must be a 2-D array")
-        labels = self._labels(labels)
-        bins, dist = self._nearest_arrays(Y.shape[0], k)
-        check(self._lib.chb_recruit_rows_nearest_wide(self._h, labels.ctypes.data, int(B), int(m), int(k), Y.ctypes.data,
-                                                      *Y.shape, bins.ctypes.data, dist.ctypes.data))
-        return bins, dist
+        return self._score_rows("chb_recruit_rows_nearest_wide", labels, B, None, m=m, k=k, Y=Y)
 
     def bin_report_wide(self, labels, B, m, rows=None, groups=None):
         """chb_bin_report_wide: bin_report (with `groups` bin_report_grouped) for any m in 1 .. 64 -- m <= 16 forwards bit
         for bit, 16 < m <= 64 sums up audit_rows_wide's answer.  Returns what bin_report returns."""
-        labels = self._labels(labels)
-        if groups is not None:
-            groups = self._groups(groups)
-        row_idx, Q, rows = self._row_indices(rows)
-        B = int(B)
-        nb = max(B, 0) if B <= 8192 else 0   # (beyond the limit the call is refused before it writes anything)
-        confusion = np.empty((nb, nb), dtype=np.int64)
-        unplaced = np.empty(nb, dtype=np.int64)
-        dcnt = np.empty((nb, nb), dtype=np.int64)
-        dmin = np.empty((nb, nb), dtype=np.float64)
-        dsum = np.empty((nb, nb), dtype=np.float64)
-        skipped = C.c_int64(0)
-        check(self._lib.chb_bin_report_wide(self._h, labels.ctypes.data, None if groups is None else groups.ctypes.data,
-                                            B, int(m), row_idx, Q, confusion.ctypes.data, unplaced.ctypes.data,
-                                            dcnt.ctypes.data, dmin.ctypes.data, dsum.ctypes.data, C.addressof(skipped)))
-        return confusion, unplaced, dcnt, dmin, dsum, int(skipped.value)
+        return self._bin_report("chb_bin_report_wide", labels, B, m, rows, groups, slot=True)
 
     def audit_pairs_witness_wide(self, labels, B, m, rows, bins, groups=None):
         """chb_audit_pairs_witness_wide: audit_pairs_witness for any m in 1 .. 64 -- m <= 16 forwards bit for bit; at
         16 < m <= 64 dist and neighbors are audit_pairs_wide's dist and idx, neighbor_dist the members' selection
         distances and weights what the wide solve kernel returned.  Returns what audit_pairs_witness returns."""
-        rows, bins = self._pair_lists(rows, bins, "rows")
-        labels = self._labels(labels)
-        if groups is not None:
-            groups = self._groups(groups)
-        dist, idx, nd, alpha = self._witness_arrays(rows.shape[0], m)
-        check(self._lib.chb_audit_pairs_witness_wide(self._h, labels.ctypes.data,
-                                                     None if groups is None else groups.ctypes.data, int(B), int(m),
-                                                     rows.ctypes.data, bins.ctypes.data, rows.shape[0], dist.ctypes.data,
-                                                     idx.ctypes.data, nd.ctypes.data, alpha.ctypes.data))
-        return dist, idx, nd, alpha
+        return self._score_pairs("chb_audit_pairs_witness_wide", labels, B, m, rows, bins, groups=groups, slot=True,
+                                 witness=True)
 
     def recruit_pairs_witness_wide(self, labels, B, m, Y, row_of, bins):
         """chb_recruit_pairs_witness_wide: recruit_pairs_witness for any m in 1 .. 64.  Returns what it returns."""
-        row_of, bins = self._pair_lists(row_of, bins, "row_of")
-        Y = np.ascontiguousarray(Y, dtype=np.float64)
-        if Y.ndim != 2:
-            raise ValueError("rows must be a 2-D array")
-        labels = self._labels(labels)
-        dist, idx, nd, alpha = self._witness_arrays(row_of.shape[0], m)
-        check(self._lib.chb_recruit_pairs_witness_wide(self._h, labels.ctypes.data, int(B), int(m), Y.ctypes.data, *Y.shape,
-                                                       row_of.ctypes.data, bins.ctypes.data, row_of.shape[0],
-                                                       dist.ctypes.data, idx.ctypes.data, nd.ctypes.data,
-                                                       alpha.ctypes.data))
-        return dist, idx, nd, alpha
+        return self._score_pairs("chb_recruit_pairs_witness_wide", labels, B, m, row_of, bins, Y=Y, witness=True)
 
     def find_nearest_from_row(self, c, labels, row, m):
         labels = np.ascontiguousarray(labels, dtype=np.int64)

@@ -1,4 +1,5 @@
 """Mirror of ch_bin/core/clustering/algorithm.py."""
+import contextlib
 import dataclasses
 import logging
 
@@ -72,6 +73,19 @@ def fit_cluster(
 _TILED_MAX_NEIGHBORS = 16
 
 
+@contextlib.contextmanager
+def _resident(samples, metric, qp_solver):
+    """How every function below starts: the reference's two refusals, before the context is touched; then the process-wide
+    context with `samples` resident and `metric` selected for the length of the with statement."""
+    if metric not in ("convex", "affine", "affine-qp"):
+        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
+    check_solver(qp_solver)                                              # solve_qp.py:132
+    ctx = default_context()
+    ctx.set_samples_cached(np.ascontiguousarray(samples, dtype=np.float64))
+    with ctx.using_metric(metric):
+        yield ctx
+
+
 def recruit(
     samples: np.ndarray,
     labels: np.ndarray,
@@ -88,15 +102,8 @@ def recruit(
     hull, the strict-'>' argmin over the bins (-1 where no bin has a member).  Neither `samples` nor `labels` change.
 
     Returns `bins` [len(rows)] or, with return_distances, (bins, distances [len(rows), num_clusters])."""
-    if metric not in ("convex", "affine", "affine-qp"):
-        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
-    check_solver(qp_solver)                                              # solve_qp.py:132
-
-    samples = np.ascontiguousarray(samples, dtype=np.float64)
-    rows = np.ascontiguousarray(rows, dtype=np.float64)
-    ctx = default_context()
-    ctx.set_samples_cached(samples)
-    with ctx.using_metric(metric):
+    with _resident(samples, metric, qp_solver) as ctx:
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
         score = ctx.recruit_rows_wide if int(num_neighbors) > _TILED_MAX_NEIGHBORS else ctx.recruit_rows
         bins, dist, _, _ = score(labels, int(num_clusters), int(num_neighbors), rows, want_dist=return_distances)
     return (bins, dist) if return_distances else bins
@@ -126,14 +133,7 @@ def audit(
     Returns (bins, min_dist, margin) -- the bin the row would choose now (-1 where no bin has another member), its hull
     distance, and the gap to the runner-up bin (+inf without one) -- and with return_distances also
     distances [len(rows), num_clusters]."""
-    if metric not in ("convex", "affine", "affine-qp"):
-        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
-    check_solver(qp_solver)                                              # solve_qp.py:132
-
-    samples = np.ascontiguousarray(samples, dtype=np.float64)
-    ctx = default_context()
-    ctx.set_samples_cached(samples)
-    with ctx.using_metric(metric):
+    with _resident(samples, metric, qp_solver) as ctx:
         if int(num_neighbors) > _TILED_MAX_NEIGHBORS:
             bins, dist, mind, margin = ctx.audit_rows_wide(labels, int(num_clusters), int(num_neighbors), rows,
                                                            want_dist=return_distances, groups=groups)
@@ -204,14 +204,7 @@ def bin_report(
     would choose bin b now, and count / minimum / sum of their hull distances to it.  Only the num_clusters x num_clusters
     tables come back; rows without a label in [0, num_clusters) are not scored.  Nothing changes.
     With `groups` the tables are those of the leave-group-out audit (`audit(..., groups=groups)`)."""
-    if metric not in ("convex", "affine", "affine-qp"):
-        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
-    check_solver(qp_solver)                                              # solve_qp.py:132
-
-    samples = np.ascontiguousarray(samples, dtype=np.float64)
-    ctx = default_context()
-    ctx.set_samples_cached(samples)
-    with ctx.using_metric(metric):
+    with _resident(samples, metric, qp_solver) as ctx:
         if int(num_neighbors) > _TILED_MAX_NEIGHBORS:
             return BinReport(*ctx.bin_report_wide(labels, int(num_clusters), int(num_neighbors), rows, groups=groups))
         if groups is None:
@@ -272,23 +265,16 @@ def neighbor_sweep(
     every entry of `neighbors` (distinct values in 1 .. 16) at the cost of little more than the audit at the largest: one
     selection pass on the device serves the whole list, and each entry's result is bit for bit what `audit` returns for it.
     Nothing changes.  With `groups` every entry is `audit(..., groups=groups)`: leave-group-out."""
-    if metric not in ("convex", "affine", "affine-qp"):
-        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
-    check_solver(qp_solver)                                              # solve_qp.py:132
-
-    samples = np.ascontiguousarray(samples, dtype=np.float64)
-    labels = np.ascontiguousarray(labels, dtype=np.int64)
-    neighbors = np.ascontiguousarray(neighbors, dtype=np.int64)
-    ctx = default_context()
-    ctx.set_samples_cached(samples)
-    with ctx.using_metric(metric):
+    with _resident(samples, metric, qp_solver) as ctx:
+        labels = np.ascontiguousarray(labels, dtype=np.int64)
+        neighbors = np.ascontiguousarray(neighbors, dtype=np.int64)
         if groups is None:
             bins, dist, mind, margin = ctx.audit_rows_multi(labels, int(num_clusters), neighbors, rows,
                                                             want_dist=return_distances)
         else:
             bins, dist, mind, margin = ctx.audit_rows_multi_grouped(labels, groups, int(num_clusters), neighbors, rows,
                                                                     want_dist=return_distances)
-    scored = np.arange(samples.shape[0], dtype=np.int64) if rows is None else np.ascontiguousarray(rows, dtype=np.int64)
+    scored = np.arange(np.shape(samples)[0], dtype=np.int64) if rows is None else np.ascontiguousarray(rows, dtype=np.int64)
     return NeighborSweep(neighbors, scored, labels[scored], bins, mind, margin, int(num_clusters), dist)
 
 
@@ -309,14 +295,7 @@ def audit_pairs(
     and come in any order.  Nothing changes.  With `groups` the entries are those of `audit(..., groups=groups)`.
 
     Returns distances [len(rows)]."""
-    if metric not in ("convex", "affine", "affine-qp"):
-        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
-    check_solver(qp_solver)                                              # solve_qp.py:132
-
-    samples = np.ascontiguousarray(samples, dtype=np.float64)
-    ctx = default_context()
-    ctx.set_samples_cached(samples)
-    with ctx.using_metric(metric):
+    with _resident(samples, metric, qp_solver) as ctx:
         if int(num_neighbors) > _TILED_MAX_NEIGHBORS:
             return ctx.audit_pairs_wide(labels, int(num_clusters), int(num_neighbors), rows, bins, groups=groups)
         if groups is None:
@@ -340,15 +319,8 @@ def recruit_pairs(
     bin bins[p].  Nothing changes.
 
     Returns distances [len(row_of)]."""
-    if metric not in ("convex", "affine", "affine-qp"):
-        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
-    check_solver(qp_solver)                                              # solve_qp.py:132
-
-    samples = np.ascontiguousarray(samples, dtype=np.float64)
-    new_rows = np.ascontiguousarray(new_rows, dtype=np.float64)
-    ctx = default_context()
-    ctx.set_samples_cached(samples)
-    with ctx.using_metric(metric):
+    with _resident(samples, metric, qp_solver) as ctx:
+        new_rows = np.ascontiguousarray(new_rows, dtype=np.float64)
         if int(num_neighbors) > _TILED_MAX_NEIGHBORS:
             return ctx.recruit_pairs_wide(labels, int(num_clusters), int(num_neighbors), new_rows, row_of, bins)
         return ctx.recruit_pairs(labels, int(num_clusters), int(num_neighbors), new_rows, row_of, bins)
@@ -373,19 +345,12 @@ def cohesion(
     pieces of its own parent -- +inf where the bin holds nothing else.
 
     Returns distances [len(rows)]."""
-    if metric not in ("convex", "affine", "affine-qp"):
-        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
-    check_solver(qp_solver)                                              # solve_qp.py:132
-
-    samples = np.ascontiguousarray(samples, dtype=np.float64)
-    labels = np.ascontiguousarray(labels, dtype=np.int64)
-    rows = np.arange(samples.shape[0], dtype=np.int64) if rows is None else np.ascontiguousarray(rows, dtype=np.int64)
-    own = labels[rows]
-    scored = (own >= 0) & (own < int(num_clusters))
-    out = np.full(rows.shape[0], np.nan)
-    ctx = default_context()
-    ctx.set_samples_cached(samples)
-    with ctx.using_metric(metric):
+    with _resident(samples, metric, qp_solver) as ctx:
+        labels = np.ascontiguousarray(labels, dtype=np.int64)
+        rows = np.arange(np.shape(samples)[0], dtype=np.int64) if rows is None else np.ascontiguousarray(rows, dtype=np.int64)
+        own = labels[rows]
+        scored = (own >= 0) & (own < int(num_clusters))
+        out = np.full(rows.shape[0], np.nan)
         if int(num_neighbors) > _TILED_MAX_NEIGHBORS:
             out[scored] = ctx.audit_pairs_wide(labels, int(num_clusters), int(num_neighbors), rows[scored], own[scored],
                                                groups=groups)
@@ -466,14 +431,7 @@ def witness(
     row and their weights in the hull's nearest point -- see `Witness` for what the weights mean under the affine metric
     and why they are not unique among twins.  With `groups` the hulls are leave-group-out, as in `audit_pairs`.
     Nothing changes."""
-    if metric not in ("convex", "affine", "affine-qp"):
-        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
-    check_solver(qp_solver)                                              # solve_qp.py:132
-
-    samples = np.ascontiguousarray(samples, dtype=np.float64)
-    ctx = default_context()
-    ctx.set_samples_cached(samples)
-    with ctx.using_metric(metric):
+    with _resident(samples, metric, qp_solver) as ctx:
         score = ctx.audit_pairs_witness_wide if int(num_neighbors) > _TILED_MAX_NEIGHBORS else ctx.audit_pairs_witness
         return Witness(*score(labels, int(num_clusters), int(num_neighbors), rows, bins, groups=groups))
 
@@ -492,15 +450,8 @@ def recruit_witness(
     """`witness` for rows that are NOT samples: `recruit_pairs` on the same arguments together with the hull each
     distance was measured to.  Nothing is withheld: a new row equal to a sample has that sample as a vertex at distance
     0.  The weights' meaning under the affine metric and their non-uniqueness among twins are `Witness`'s."""
-    if metric not in ("convex", "affine", "affine-qp"):
-        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
-    check_solver(qp_solver)                                              # solve_qp.py:132
-
-    samples = np.ascontiguousarray(samples, dtype=np.float64)
-    new_rows = np.ascontiguousarray(new_rows, dtype=np.float64)
-    ctx = default_context()
-    ctx.set_samples_cached(samples)
-    with ctx.using_metric(metric):
+    with _resident(samples, metric, qp_solver) as ctx:
+        new_rows = np.ascontiguousarray(new_rows, dtype=np.float64)
         score = ctx.recruit_pairs_witness_wide if int(num_neighbors) > _TILED_MAX_NEIGHBORS else ctx.recruit_pairs_witness
         return Witness(*score(labels, int(num_clusters), int(num_neighbors), new_rows, row_of, bins))
 
@@ -568,14 +519,7 @@ def nearest_bins(
     nearest bins with their leave-one-out hull distances instead of the nearest alone -- ranked on the device, so the
     len(rows) x num_clusters table never crosses to the host.  With `groups` the distances are leave-group-out.
     Nothing changes."""
-    if metric not in ("convex", "affine", "affine-qp"):
-        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
-    check_solver(qp_solver)                                              # solve_qp.py:132
-
-    samples = np.ascontiguousarray(samples, dtype=np.float64)
-    ctx = default_context()
-    ctx.set_samples_cached(samples)
-    with ctx.using_metric(metric):
+    with _resident(samples, metric, qp_solver) as ctx:
         score = ctx.audit_rows_nearest_wide if int(num_neighbors) > _TILED_MAX_NEIGHBORS else ctx.audit_rows_nearest
         return NearestBins(*score(labels, int(num_clusters), int(num_neighbors), int(k), rows, groups=groups))
 
@@ -592,14 +536,7 @@ def recruit_nearest_bins(
 ) -> NearestBins:
     """`nearest_bins` for `rows` that are NOT samples: `recruit` on the same arguments, returning per row the k nearest
     bins with their hull distances.  Nothing is withheld and nothing changes."""
-    if metric not in ("convex", "affine", "affine-qp"):
-        raise NotImplementedError(f"Metric {metric} not implemented")  # hull_distance.py:108
-    check_solver(qp_solver)                                              # solve_qp.py:132
-
-    samples = np.ascontiguousarray(samples, dtype=np.float64)
-    rows = np.ascontiguousarray(rows, dtype=np.float64)
-    ctx = default_context()
-    ctx.set_samples_cached(samples)
-    with ctx.using_metric(metric):
+    with _resident(samples, metric, qp_solver) as ctx:
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
         score = ctx.recruit_rows_nearest_wide if int(num_neighbors) > _TILED_MAX_NEIGHBORS else ctx.recruit_rows_nearest
         return NearestBins(*score(labels, int(num_clusters), int(num_neighbors), int(k), rows))

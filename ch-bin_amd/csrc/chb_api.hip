@@ -144,6 +144,20 @@ struct Buf {
 template <typename T> using DevBuf = Buf<T, false>;
 template <typename T> using PinBuf = Buf<T, true>;
 
+// A device buffer and its pinned twin on the host (the row-scoring calls' chunks: what goes up, what comes down)
+template <typename T>
+struct Mirror {
+    DevBuf<T> d;
+    PinBuf<T> h;
+    hipError_t ensure(size_t n, bool want_host)   // (the host side only where somebody will read or fill it)
+    {
+        HIPTRY(d.ensure(n));
+        return want_host ? h.ensure(n) : hipSuccess;
+    }
+    hipError_t up(size_t n, hipStream_t s) { return hipMemcpyAsync(d.p, h.p, sizeof(T) * n, hipMemcpyHostToDevice, s); }
+    hipError_t down(size_t n, hipStream_t s) { return hipMemcpyAsync(h.p, d.p, sizeof(T) * n, hipMemcpyDeviceToHost, s); }
+};
+
 }  // namespace
 
 // device storage behind a MemberPack
@@ -258,44 +272,34 @@ struct Segments {
 };
 
 // One half of the row-scoring calls' double buffer: a chunk of the new rows (padded like X) or of sample indices (qid), its
-// distances and row reductions, on the device and pinned on the host (h*); chb_bin_report's chunks also carry seg, each label's
-// run (BinReportArgs), nseg of them; the pair calls' chunks carry tile, the chunk's tile table (RecruitPairArgs), ntile rows.
+// distances and row reductions, each a Mirror: on the device (.d) and pinned on the host (.h); chb_bin_report's chunks also
+// carry seg, each label's run (BinReportArgs), nseg of them; the pair calls' chunks carry tile, the chunk's tile table
+// (RecruitPairArgs), ntile rows.
 // up / done / down: the upload, the kernels, the download of the chunk in this half are through.
 struct ChunkHalf {
-    DevBuf<double> Y, dist, min, margin;
-    DevBuf<int> bin, qid;
-    DevBuf<int2> seg;
-    DevBuf<int4> tile;
-    PinBuf<double> hY, hdist, hmin, hmargin;
-    PinBuf<int> hbin, hqid;
-    PinBuf<int2> hseg;
-    PinBuf<int4> htile;
-    // chb_*_pairs_witness only (first allocated by the context's first such call): the chunk's witness records, kWitnessSlots
-    // slots per position (RecruitWitnessArgs)
-    DevBuf<int> wid;
-    DevBuf<double> wd, walpha;
-    PinBuf<int> hwid;
-    PinBuf<double> hwd, hwalpha;
+    Mirror<double> Y, dist, min, margin;
+    Mirror<int> bin, qid;
+    Mirror<int2> seg;
+    Mirror<int4> tile;
+    // the witness calls only (first allocated by the context's first such call): the chunk's witness records, a call-wide
+    // number of slots per position (ScoreRun::wslots) -- kWitnessSlots up to 16 neighbours (RecruitWitnessArgs), m beyond
+    // (RecruitWideWitnessArgs), where the members' ids are wlist's and wid stays unused
+    Mirror<int> wid;
+    Mirror<double> wd, walpha;
     // chb_*_rows_nearest only (first allocated by the context's first such call): the chunk's k nearest bins per row and
     // their distances
-    DevBuf<int> nbin;
-    DevBuf<double> ndist;
-    PinBuf<int> hnbin;
-    PinBuf<double> hndist;
-    // chb_*_pairs_wide only (first allocated by the context's first such call): the chunk's selection lists, m + 1 ints
-    // per position (RecruitWideArgs), per half because idx_out copies them down while the next chunk's kernels run
-    DevBuf<int> wlist;
-    PinBuf<int> hwlist;
-    // chb_*_pairs_witness_wide only (first allocated by the context's first such call with more than 16 neighbours): the
-    // chunk's witness records, m slots per position (RecruitWideWitnessArgs); the members' ids are wlist's
-    DevBuf<double> wwd, wwalpha;
-    PinBuf<double> hwwd, hwwalpha;
+    Mirror<int> nbin;
+    Mirror<double> ndist;
+    // the pair calls with more than 16 neighbours only (first allocated by the context's first such call): the chunk's
+    // selection lists, m + 1 ints per position (RecruitWideArgs), per half because idx_out copies them down while the next
+    // chunk's kernels run
+    Mirror<int> wlist;
     hipEvent_t up = nullptr, done = nullptr, down = nullptr;
     int nseg = 0, ntile = 0;
     void destroy_events() { for (hipEvent_t ev : {up, done, down}) if (ev) (void)hipEventDestroy(ev); }
 };
 
-// chb_recruit_rows, chb_audit_rows, chb_*_rows_multi, chb_bin_report, chb_*_pairs (ScoreRun): the calls' own buffers, nothing of a fit.
+// Every row-scoring call (ScoreRun): the calls' own buffers, nothing of a fit.
 // While the kernels of chunk k run on the context's stream, copy brings chunk k + 1 up into the other half and chunk
 // k - 1 down.  Not per half: the call's CSR over the labels (ptr, memb) and chb_bin_report's B x B tables rep_* (zeroed at
 // the call's start), which collect what the chunks' rows say.  The chb_*_grouped calls add the dense group ids: grp of
@@ -2443,8 +2447,9 @@ int chb_hull_distance_points(chb_ctx *h, const double *x, const double *pts, int
     return hull_indexed(h, h->xpts.p, (int)D, Dp, m + 1, &q, 1, idx.data(), m, dist, alpha);
 }
 
-// ======== row scoring (chb_recruit_rows, chb_audit_rows, chb_*_rows_multi, chb_bin_report, chb_*_pairs): the entry point checks its
-// arguments (score_check_args) and fills a ScoreRequest, a ScoreRun carries it through its stages
+// ======== row scoring (chb_recruit_rows, chb_audit_rows, chb_*_rows_multi, chb_bin_report, chb_*_pairs, and their _grouped,
+// _witness, _nearest and _wide forms): the entry point fills a ScoreRequest by name, the body of its call shape (score_rows,
+// bin_report, score_pairs, score_nearest) checks the arguments (score_check_args), a ScoreRun carries it through its stages
 namespace {
 
 constexpr int kRecruitPiece = 2048;   // rows per host-to-device copy of a chunk
@@ -2561,15 +2566,17 @@ struct PairPlan {
     }
 };
 
-// What a row-scoring call asks for, filled by its entry point
+// What a row-scoring call asks for: made by audit() / recruit() below, the rest set by name by its entry point and
+// the call body behind it
 struct ScoreRequest {
-    const int64_t *labels; int64_t B;
+    const int64_t *labels = nullptr; int64_t B = 0;
     // the source, one of four: the new rows Y (recruit); the resident rows row_idx, nullptr meaning all rows (audit);
     // a plan's positions (chb_bin_report: an audit whose chunks are the plan's cuts); a pair plan's positions (below)
-    const double *Y; const int64_t *row_idx; const ReportPlan *plan;
-    int64_t Q;
-    int m; const int *ms; int nm;   // neighbours; nm > 0: the list of a chb_*_rows_multi call, m its largest entry
-    int64_t *bin_out; double *dist_out, *min_dist_out, *margin_out;   // (without a destination: neither downloaded nor unpacked)
+    const double *Y = nullptr; const int64_t *row_idx = nullptr; const ReportPlan *plan = nullptr;
+    int64_t Q = 0;
+    int m = 0; const int *ms = nullptr; int nm = 0;   // neighbours; nm > 0: the list of a chb_*_rows_multi call, m its largest entry
+    // (without a destination: neither downloaded nor unpacked)
+    int64_t *bin_out = nullptr; double *dist_out = nullptr, *min_dist_out = nullptr, *margin_out = nullptr;
     // chb_*_pairs: Q pairs (row, bin) in place of the grid, the rows resident or (Y set) rows of Y; dist_out is [Q], one
     // double per pair in the caller's order, and there is no row reduction
     const PairPlan *pairs = nullptr;
@@ -2591,13 +2598,28 @@ struct ScoreRequest {
     // chunk's table), plan (cut at wide_chunk_rows) and witness (m slots per pair: the ids are idx_out, w_idx stays null)
     bool wide = false;
     int64_t *idx_out = nullptr;
+    // the two makers: Q resident rows row_idx (or pairs of them), Q new rows Y (or pairs of rows of Y)
+    static ScoreRequest audit(const int64_t *labels, int64_t B, int m, const int64_t *row_idx, int64_t Q)
+    {
+        ScoreRequest rq;
+        rq.labels = labels; rq.B = B; rq.m = m; rq.row_idx = row_idx; rq.Q = Q;
+        return rq;
+    }
+    static ScoreRequest recruit(const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q)
+    {
+        ScoreRequest rq;
+        rq.labels = labels; rq.B = B; rq.m = m; rq.Y = Y; rq.Q = Q;
+        return rq;
+    }
 };
 
 // The argument checks of the entry points, for all of them in this order: null context; ranges and a malformed list
-// (CHB_EINVAL; a nearest-bins call's k < 1 among them); null arguments (a grouped call's groups, whatever Q, among them); outputs; no samples; D; more than 16 neighbours (CHB_EUNSUPPORTED), then a nearest-bins call's k > 16; more than 8192 bins;
-// an open stepwise fit; Q == 0 (CHB_OK: nothing further is read); the row_idx rules.
+// (CHB_EINVAL; a nearest-bins call's k < 1 among them); null arguments (a grouped call's groups, whatever Q, among them);
+// outputs; no samples; D; more than 16 neighbours (CHB_EUNSUPPORTED), then a nearest-bins call's k > 16; more than 8192
+// bins; an open stepwise fit; Q == 0 (CHB_OK: nothing further is read); the row_idx rules.
 // (A wide call, rq.wide: more than 64 neighbours, then more than 32 on a device without the LDS for 64 vertices, in place of
-// "more than 16".)
+// "more than 16".  wide_rule sets rq.wide only above 16 neighbours, so a _wide symbol never reaches "more than 16".)
+// who: the name the call goes by in the texts (wide_rule: a _wide symbol's narrow twin up to 16 neighbours).
 // D: the rows' number of columns in the calls that take Y, nullptr in the others.  list: the call takes ms / nm, whose
 // largest entry becomes rq.m.  no_output: the refusal's text when every output that counts for the call is null, else nullptr.
 int score_check_args(chb_ctx *h, const char *who, ScoreRequest &rq, const int64_t *D, bool list, const char *no_output)
@@ -2660,6 +2682,7 @@ struct ScoreRun {
     const bool audit = !rq.Y /* the rows are resident */, any_out = rq.bin_out || rq.dist_out || rq.min_dist_out || rq.margin_out || rq.witness || rq.nearest || rq.idx_out;
     const int ns = rq.nm > 0 ? rq.nm : 1;   // result slices per chunk
     const size_t width = rq.pairs ? 1 : (size_t)rq.B;   // distances per result row
+    const size_t wslots = rq.wide ? (size_t)rq.m : (size_t)kWitnessSlots;   // slots of a position's witness record
     int slot[kMaxM] = {0};                  // list entry j's slice on the device = the number of smaller entries
     size_t n_memb = 0;
     int64_t chunk = 0, n = 0;               // rows per chunk (a plan: its cuts), chunks
@@ -2744,52 +2767,30 @@ struct ScoreRun {
         if (rq.wide && !rq.pairs) HIPCHK(sc.wlist.ensure((size_t)chunk * width * (size_t)(rq.m + 1)));
         for (int i = 0; i < halves; ++i) {
             ChunkHalf &b = sc.half[i];
-            HIPCHK(rq.Y ? b.Y.ensure((size_t)chunk * h->Dp) : b.qid.ensure((size_t)chunk));
-            HIPCHK(rq.Y ? b.hY.ensure((size_t)chunk * h->Dp) : b.hqid.ensure((size_t)chunk));
-            HIPCHK(b.dist.ensure(res * width));
-            if (rq.dist_out) HIPCHK(b.hdist.ensure(res * width));
+            HIPCHK(rq.Y ? b.Y.ensure((size_t)chunk * h->Dp, true) : b.qid.ensure((size_t)chunk, true));
+            HIPCHK(b.dist.ensure(res * width, rq.dist_out));
             if (rq.pairs) {   // the tile table, and no row reduction
-                HIPCHK(b.tile.ensure((size_t)rq.pairs->max_tiles));
-                HIPCHK(b.htile.ensure((size_t)rq.pairs->max_tiles));
-                if (rq.wide) {
-                    HIPCHK(b.wlist.ensure((size_t)chunk * (size_t)(rq.m + 1)));
-                    if (rq.idx_out) HIPCHK(b.hwlist.ensure((size_t)chunk * (size_t)(rq.m + 1)));
-                }
-                if (rq.witness && rq.wide) {   // m slots per position; the ids are the lists'
-                    const size_t slots = (size_t)chunk * (size_t)rq.m;
-                    HIPCHK(b.wwd.ensure(slots));
-                    HIPCHK(b.wwalpha.ensure(slots));
-                    if (rq.w_dist) HIPCHK(b.hwwd.ensure(slots));
-                    if (rq.w_alpha) HIPCHK(b.hwwalpha.ensure(slots));
-                } else if (rq.witness) {   // the records: the kernel writes all three, what the caller wants comes down
-                    const size_t slots = (size_t)chunk * kWitnessSlots;
-                    HIPCHK(b.wid.ensure(slots));
-                    HIPCHK(b.wd.ensure(slots));
-                    HIPCHK(b.walpha.ensure(slots));
-                    if (rq.w_idx) HIPCHK(b.hwid.ensure(slots));
-                    if (rq.w_dist) HIPCHK(b.hwd.ensure(slots));
-                    if (rq.w_alpha) HIPCHK(b.hwalpha.ensure(slots));
+                HIPCHK(b.tile.ensure((size_t)rq.pairs->max_tiles, true));
+                if (rq.wide) HIPCHK(b.wlist.ensure((size_t)chunk * (size_t)(rq.m + 1), rq.idx_out));
+                if (rq.witness) {   // the records: the kernel writes them all, what the caller wants comes down
+                    const size_t slots = (size_t)chunk * wslots;
+                    if (!rq.wide) HIPCHK(b.wid.ensure(slots, rq.w_idx));   // (wide: the ids are the lists')
+                    HIPCHK(b.wd.ensure(slots, rq.w_dist));
+                    HIPCHK(b.walpha.ensure(slots, rq.w_alpha));
                 }
                 continue;
             }
             if (rq.nearest) {   // the ranked slots in place of the row reduction's three arrays
                 const size_t slots = (size_t)chunk * (size_t)rq.near_k;
-                HIPCHK(b.nbin.ensure(slots));
-                HIPCHK(b.ndist.ensure(slots));
-                if (rq.near_bin) HIPCHK(b.hnbin.ensure(slots));
-                if (rq.near_dist) HIPCHK(b.hndist.ensure(slots));
+                HIPCHK(b.nbin.ensure(slots, rq.near_bin));
+                HIPCHK(b.ndist.ensure(slots, rq.near_dist));
                 continue;
             }
-            HIPCHK(b.bin.ensure(res));
-            HIPCHK(b.hbin.ensure(res));
-            HIPCHK(b.min.ensure(res));
-            HIPCHK(b.hmin.ensure(res));
-            HIPCHK(b.margin.ensure(res));
-            HIPCHK(b.hmargin.ensure(res));
-            if (rq.plan) {   // a chunk holds at most one run per label
-                HIPCHK(b.seg.ensure((size_t)std::min<int64_t>(B, chunk) + 1));
-                HIPCHK(b.hseg.ensure((size_t)std::min<int64_t>(B, chunk) + 1));
-            }
+            HIPCHK(b.bin.ensure(res, true));
+            HIPCHK(b.min.ensure(res, true));
+            HIPCHK(b.margin.ensure(res, true));
+            // a chunk holds at most one run per label
+            if (rq.plan) HIPCHK(b.seg.ensure((size_t)std::min<int64_t>(B, chunk) + 1, true));
         }
         return CHB_OK;
     }
@@ -2868,12 +2869,12 @@ struct ScoreRun {
         const int64_t D = h->D, Dp = h->Dp;
         for (int r0 = 0; r0 < nq; r0 += kRecruitPiece) {
             const int nr = std::min(kRecruitPiece, nq - r0);
-            double *dst = b.hY.p + (size_t)r0 * Dp;
+            double *dst = b.Y.h.p + (size_t)r0 * Dp;
             for (int r = 0; r < nr; ++r, dst += Dp) {
                 memcpy(dst, rq.Y + y_of(r0 + r) * D, sizeof(double) * D);
                 for (int64_t j = D; j < Dp; ++j) dst[j] = 0.0;
             }
-            HIPTRY(hipMemcpyAsync(b.Y.p + (size_t)r0 * Dp, b.hY.p + (size_t)r0 * Dp, sizeof(double) * (size_t)nr * Dp,
+            HIPTRY(hipMemcpyAsync(b.Y.d.p + (size_t)r0 * Dp, b.Y.h.p + (size_t)r0 * Dp, sizeof(double) * (size_t)nr * Dp,
                                   hipMemcpyHostToDevice, sc.copy));
         }
         return hipSuccess;
@@ -2891,19 +2892,19 @@ struct ScoreRun {
         const int nq = rows(k);
         const int64_t *ord = pl.ord.data() + start(k), t0 = pl.tcut[(size_t)k];
         b.ntile = (int)(pl.tcut[(size_t)k + 1] - t0);
-        memcpy(b.htile.p, pl.tile.data() + t0, sizeof(int4) * (size_t)b.ntile);
-        HIPTRY(hipMemcpyAsync(b.tile.p, b.htile.p, sizeof(int4) * (size_t)b.ntile, hipMemcpyHostToDevice, sc.copy));
+        memcpy(b.tile.h.p, pl.tile.data() + t0, sizeof(int4) * (size_t)b.ntile);
+        HIPTRY(b.tile.up((size_t)b.ntile, sc.copy));
         if (!audit) return upload_packed(b, nq, [&pl, ord](int r) { return pl.row[ord[r]]; });
-        for (int i = 0; i < nq; ++i) b.hqid.p[i] = (int)pl.row[ord[i]];
-        return hipMemcpyAsync(b.qid.p, b.hqid.p, sizeof(int) * nq, hipMemcpyHostToDevice, sc.copy);
+        for (int i = 0; i < nq; ++i) b.qid.h.p[i] = (int)pl.row[ord[i]];
+        return b.qid.up((size_t)nq, sc.copy);
     }
     // the chunk's sample indices and nothing else: the kernel reads the rows from the resident matrix
     hipError_t upload_indices(ChunkHalf &b, int64_t k)
     {
         const int nq = rows(k);
         const int64_t t0 = start(k);
-        for (int i = 0; i < nq; ++i) b.hqid.p[i] = (int)(rq.row_idx ? rq.row_idx[t0 + i] : t0 + i);
-        return hipMemcpyAsync(b.qid.p, b.hqid.p, sizeof(int) * nq, hipMemcpyHostToDevice, sc.copy);
+        for (int i = 0; i < nq; ++i) b.qid.h.p[i] = (int)(rq.row_idx ? rq.row_idx[t0 + i] : t0 + i);
+        return b.qid.up((size_t)nq, sc.copy);
     }
     // a plan's indices and the chunk's label runs, for bin_report_kernel behind the two audit kernels
     hipError_t upload_plan(ChunkHalf &b, int64_t k)
@@ -2911,15 +2912,15 @@ struct ScoreRun {
         const std::vector<int64_t> &lab_ptr = rq.plan->lab_ptr;
         const int nq = rows(k);
         const int64_t t0 = start(k);
-        memcpy(b.hqid.p, rq.plan->ord.data() + t0, sizeof(int) * nq);
-        int2 *sg = b.hseg.p;   // {label, first position in the chunk} per run, closed by {-1, nq}
+        memcpy(b.qid.h.p, rq.plan->ord.data() + t0, sizeof(int) * nq);
+        int2 *sg = b.seg.h.p;   // {label, first position in the chunk} per run, closed by {-1, nq}
         b.nseg = 0;
         size_t l = (size_t)(std::upper_bound(lab_ptr.begin(), lab_ptr.end(), t0) - lab_ptr.begin()) - 1;
         for (; l < (size_t)rq.B && lab_ptr[l] < t0 + nq; ++l)
             if (lab_ptr[l + 1] > lab_ptr[l]) sg[b.nseg++] = make_int2((int)l, (int)(std::max(lab_ptr[l], t0) - t0));
         sg[b.nseg] = make_int2(-1, nq);
-        HIPTRY(hipMemcpyAsync(b.seg.p, b.hseg.p, sizeof(int2) * ((size_t)b.nseg + 1), hipMemcpyHostToDevice, sc.copy));
-        return hipMemcpyAsync(b.qid.p, b.hqid.p, sizeof(int) * nq, hipMemcpyHostToDevice, sc.copy);
+        HIPTRY(b.seg.up((size_t)b.nseg + 1, sc.copy));
+        return b.qid.up((size_t)nq, sc.copy);
     }
     hipError_t launch(int64_t k)
     {
@@ -2927,14 +2928,14 @@ struct ScoreRun {
         const int nq = rows(k);
         HIPTRY(hipStreamWaitEvent(s, b.up, 0));
         if (any_out) HIPTRY(hipStreamWaitEvent(s, b.down, 0));   // (chunk k - 2 has been copied out of this half's results)
-        a.Y = audit ? nullptr : b.Y.p; a.qid = audit ? b.qid.p : nullptr; a.dist = b.dist.p; a.nq = nq;
+        a.Y = audit ? nullptr : b.Y.d.p; a.qid = audit ? b.qid.d.p : nullptr; a.dist = b.dist.d.p; a.nq = nq;
         // (with groups: the same launches, the leave-group-out instantiation of the kernel)
         if (rq.wide) {   // selection, solve and -- dense -- the row reduction; the work of both is the (row, bin) problems
             RecruitWideWitnessArgs wa{};   // (the launchers without witnesses take the part of it that is theirs)
             static_cast<RecruitGroupArgs &>(wa) = a;
-            wa.tile = rq.pairs ? b.tile.p : nullptr; wa.ntile = rq.pairs ? b.ntile : 0;
-            wa.list = rq.pairs ? b.wlist.p : sc.wlist.p;
-            if (rq.witness) { wa.w_d = b.wwd.p; wa.w_alpha = b.wwalpha.p; }   // (a pair chunk: the witness forms)
+            wa.tile = rq.pairs ? b.tile.d.p : nullptr; wa.ntile = rq.pairs ? b.ntile : 0;
+            wa.list = rq.pairs ? b.wlist.d.p : sc.wlist.p;
+            if (rq.witness) { wa.w_d = b.wd.d.p; wa.w_alpha = b.walpha.d.p; }   // (a pair chunk: the witness forms)
             const double work = (double)nq * (double)width;
             {
                 Timed t(h, rq.pairs ? (audit ? "audit_pairs_wide_select" : "recruit_pairs_wide_select")
@@ -2949,12 +2950,12 @@ struct ScoreRun {
                 else launch_hull_wide(wa, s);
             }
             // (a nearest-bins call has no bin / min / margin buffers: the ranking below stands in the reduction's place)
-            if (!rq.pairs && !rq.nearest) launch_recruit_reduce(b.dist.p, nq, (int)rq.B, b.bin.p, b.min.p, b.margin.p, s);
+            if (!rq.pairs && !rq.nearest) launch_recruit_reduce(b.dist.d.p, nq, (int)rq.B, b.bin.d.p, b.min.d.p, b.margin.d.p, s);
         } else if (rq.pairs) {   // one launch: the tiles' kernel, no row reduction behind it
-            a.tile = b.tile.p; a.ntile = b.ntile;
+            a.tile = b.tile.d.p; a.ntile = b.ntile;
             Timed t(h, audit ? "audit_pairs" : "recruit_pairs", (double)nq);
             if (rq.witness) {
-                a.w_id = b.wid.p; a.w_d = b.wd.p; a.w_alpha = b.walpha.p;
+                a.w_id = b.wid.d.p; a.w_d = b.wd.d.p; a.w_alpha = b.walpha.d.p;
                 launch_recruit_witness(a, s);
             } else if (a.memb_grp) launch_recruit_grouped(a, s);
             else launch_recruit_pairs(a, s);
@@ -2963,14 +2964,14 @@ struct ScoreRun {
                     (double)nq * (double)rq.B * (double)ns);
             if (a.memb_grp) launch_recruit_grouped(a, s);
             else launch_recruit(a, s);
-            if (!rq.nearest) launch_recruit_reduce(b.dist.p, nq * ns, (int)rq.B, b.bin.p, b.min.p, b.margin.p, s);
+            if (!rq.nearest) launch_recruit_reduce(b.dist.d.p, nq * ns, (int)rq.B, b.bin.d.p, b.min.d.p, b.margin.d.p, s);
         }
         if (rq.nearest) {   // the same table, ranked in place of the reduction (whose outputs nobody would read)
             Timed t(h, "nearest_bins", (double)nq * (double)rq.B);
-            launch_nearest_bins(b.dist.p, nq, (int)rq.B, rq.near_k, b.nbin.p, b.ndist.p, s);
+            launch_nearest_bins(b.dist.d.p, nq, (int)rq.B, rq.near_k, b.nbin.d.p, b.ndist.d.p, s);
         }
         if (rq.plan) {
-            const BinReportArgs r{b.dist.p, b.bin.p, b.seg.p, b.nseg, (int)rq.B,
+            const BinReportArgs r{b.dist.d.p, b.bin.d.p, b.seg.d.p, b.nseg, (int)rq.B,
                                   sc.rep_conf.p, sc.rep_unplaced.p, sc.rep_cnt.p, sc.rep_min.p, sc.rep_sum.p};
             Timed t(h, "bin_report", (double)nq * (double)rq.B);
             launch_bin_report(r, s);
@@ -2984,29 +2985,23 @@ struct ScoreRun {
         hipStream_t c = sc.copy;
         const size_t nr = (size_t)rows(k) * (size_t)ns;
         HIPTRY(hipStreamWaitEvent(c, b.done, 0));
-        if (rq.dist_out) HIPTRY(hipMemcpyAsync(b.hdist.p, b.dist.p, sizeof(double) * nr * width, hipMemcpyDeviceToHost, c));
-        if (rq.min_dist_out) HIPTRY(hipMemcpyAsync(b.hmin.p, b.min.p, sizeof(double) * nr, hipMemcpyDeviceToHost, c));
-        if (rq.margin_out) HIPTRY(hipMemcpyAsync(b.hmargin.p, b.margin.p, sizeof(double) * nr, hipMemcpyDeviceToHost, c));
-        if (rq.bin_out) HIPTRY(hipMemcpyAsync(b.hbin.p, b.bin.p, sizeof(int) * nr, hipMemcpyDeviceToHost, c));
-        if (rq.wide) {   // (a wide witness call: m slots per position, the ids come down as idx_out's lists below)
-            const size_t slots = nr * (size_t)rq.m;
-            if (rq.w_dist) HIPTRY(hipMemcpyAsync(b.hwwd.p, b.wwd.p, sizeof(double) * slots, hipMemcpyDeviceToHost, c));
-            if (rq.w_alpha) HIPTRY(hipMemcpyAsync(b.hwwalpha.p, b.wwalpha.p, sizeof(double) * slots, hipMemcpyDeviceToHost, c));
-        } else {
-            const size_t slots = nr * kWitnessSlots;   // (pairs: nr positions)
-            if (rq.w_idx) HIPTRY(hipMemcpyAsync(b.hwid.p, b.wid.p, sizeof(int) * slots, hipMemcpyDeviceToHost, c));
-            if (rq.w_dist) HIPTRY(hipMemcpyAsync(b.hwd.p, b.wd.p, sizeof(double) * slots, hipMemcpyDeviceToHost, c));
-            if (rq.w_alpha) HIPTRY(hipMemcpyAsync(b.hwalpha.p, b.walpha.p, sizeof(double) * slots, hipMemcpyDeviceToHost, c));
-        }
-        if (rq.idx_out) HIPTRY(hipMemcpyAsync(b.hwlist.p, b.wlist.p, sizeof(int) * nr * (size_t)(rq.m + 1), hipMemcpyDeviceToHost, c));
+        if (rq.dist_out) HIPTRY(b.dist.down(nr * width, c));
+        if (rq.min_dist_out) HIPTRY(b.min.down(nr, c));
+        if (rq.margin_out) HIPTRY(b.margin.down(nr, c));
+        if (rq.bin_out) HIPTRY(b.bin.down(nr, c));
+        // (pairs: nr positions; a wide witness call has no w_idx, its ids come down as idx_out's lists)
+        if (rq.w_idx) HIPTRY(b.wid.down(nr * wslots, c));
+        if (rq.w_dist) HIPTRY(b.wd.down(nr * wslots, c));
+        if (rq.w_alpha) HIPTRY(b.walpha.down(nr * wslots, c));
+        if (rq.idx_out) HIPTRY(b.wlist.down(nr * (size_t)(rq.m + 1), c));
         const size_t near = nr * (size_t)rq.near_k;   // (a nearest-bins call: nr rows)
-        if (rq.near_bin) HIPTRY(hipMemcpyAsync(b.hnbin.p, b.nbin.p, sizeof(int) * near, hipMemcpyDeviceToHost, c));
-        if (rq.near_dist) HIPTRY(hipMemcpyAsync(b.hndist.p, b.ndist.p, sizeof(double) * near, hipMemcpyDeviceToHost, c));
+        if (rq.near_bin) HIPTRY(b.nbin.down(near, c));
+        if (rq.near_dist) HIPTRY(b.ndist.down(near, c));
         return hipEventRecord(b.down, c);
     }
     // (a list of m: ns slices of nq rows each, on the device in ascending order of m; slice slot[j] goes to out + j * Q + t0;
     // pairs: the position's double goes to the place of its pair in the caller's order, and so do the first m of the
-    // kWitnessSlots slots of its witness record)
+    // wslots slots of its witness record)
     hipError_t unpack(int64_t k)
     {
         ChunkHalf &b = half(k);
@@ -3016,99 +3011,59 @@ struct ScoreRun {
         if (rq.pairs) {
             const int64_t *ord = rq.pairs->ord.data() + t0;
             if (rq.dist_out)
-                for (int i = 0; i < nq; ++i) rq.dist_out[ord[i]] = b.hdist.p[i];
+                for (int i = 0; i < nq; ++i) rq.dist_out[ord[i]] = b.dist.h.p[i];
             const size_t m = (size_t)rq.m;
             for (int i = 0; i < nq && rq.idx_out; ++i)   // (the record's first int is the list's length; the ids are padded already)
-                for (size_t v = 0; v < m; ++v) rq.idx_out[(size_t)ord[i] * m + v] = b.hwlist.p[(size_t)i * (m + 1) + 1 + v];
-            for (int i = 0; i < nq && rq.witness && rq.wide; ++i) {   // (m slots per position)
-                const size_t from = (size_t)i * m, to = (size_t)ord[i] * m;
-                if (rq.w_dist) memcpy(rq.w_dist + to, b.hwwd.p + from, sizeof(double) * m);
-                if (rq.w_alpha) memcpy(rq.w_alpha + to, b.hwwalpha.p + from, sizeof(double) * m);
-            }
-            for (int i = 0; i < nq && rq.witness && !rq.wide; ++i) {
-                const size_t from = (size_t)i * kWitnessSlots, to = (size_t)ord[i] * m;
-                for (size_t v = 0; v < m && rq.w_idx; ++v) rq.w_idx[to + v] = b.hwid.p[from + v];
-                if (rq.w_dist) memcpy(rq.w_dist + to, b.hwd.p + from, sizeof(double) * m);
-                if (rq.w_alpha) memcpy(rq.w_alpha + to, b.hwalpha.p + from, sizeof(double) * m);
+                for (size_t v = 0; v < m; ++v) rq.idx_out[(size_t)ord[i] * m + v] = b.wlist.h.p[(size_t)i * (m + 1) + 1 + v];
+            for (int i = 0; i < nq && rq.witness; ++i) {
+                const size_t from = (size_t)i * wslots, to = (size_t)ord[i] * m;
+                for (size_t v = 0; v < m && rq.w_idx; ++v) rq.w_idx[to + v] = b.wid.h.p[from + v];
+                if (rq.w_dist) memcpy(rq.w_dist + to, b.wd.h.p + from, sizeof(double) * m);
+                if (rq.w_alpha) memcpy(rq.w_alpha + to, b.walpha.h.p + from, sizeof(double) * m);
             }
             return hipSuccess;
         }
         if (rq.nearest) {   // near_k slots per row, in the caller's row order already
             const size_t near = (size_t)nq * (size_t)rq.near_k, to = (size_t)t0 * (size_t)rq.near_k;
-            for (size_t i = 0; i < near && rq.near_bin; ++i) rq.near_bin[to + i] = b.hnbin.p[i];
-            if (rq.near_dist) memcpy(rq.near_dist + to, b.hndist.p, sizeof(double) * near);
+            for (size_t i = 0; i < near && rq.near_bin; ++i) rq.near_bin[to + i] = b.nbin.h.p[i];
+            if (rq.near_dist) memcpy(rq.near_dist + to, b.ndist.h.p, sizeof(double) * near);
             return hipSuccess;
         }
         for (int j = 0; j < ns; ++j) {
             const size_t from = (size_t)slot[j] * (size_t)nq;
             const int64_t to = (int64_t)j * rq.Q + t0;
-            if (rq.dist_out) memcpy(rq.dist_out + to * B, b.hdist.p + from * (size_t)B, sizeof(double) * (size_t)nq * (size_t)B);
-            if (rq.min_dist_out) memcpy(rq.min_dist_out + to, b.hmin.p + from, sizeof(double) * nq);
-            if (rq.margin_out) memcpy(rq.margin_out + to, b.hmargin.p + from, sizeof(double) * nq);
+            if (rq.dist_out) memcpy(rq.dist_out + to * B, b.dist.h.p + from * (size_t)B, sizeof(double) * (size_t)nq * (size_t)B);
+            if (rq.min_dist_out) memcpy(rq.min_dist_out + to, b.min.h.p + from, sizeof(double) * nq);
+            if (rq.margin_out) memcpy(rq.margin_out + to, b.margin.h.p + from, sizeof(double) * nq);
             if (rq.bin_out)
-                for (int i = 0; i < nq; ++i) rq.bin_out[to + i] = b.hbin.p[from + i];
+                for (int i = 0; i < nq; ++i) rq.bin_out[to + i] = b.bin.h.p[from + i];
         }
         return hipSuccess;
     }
 };
 
-// the four calls that return rows: the request goes through the checks and, unless Q == 0, through a ScoreRun
-int score_rows(chb_ctx *h, const char *who, ScoreRequest &rq, const int64_t *D, bool list)
+// ---- the entry points: each makes its request (ScoreRequest::audit / ::recruit), sets what is its own by name and hands it
+// to the body of its call shape -- score_rows, bin_report, score_pairs or score_nearest
+
+// The wide calls: one entry point for every m.  A _wide symbol is its narrow twin's request with wide = m > kMaxM: two
+// kernels per chunk (recruit_wide_kernels.hip) for 16 < m <= 64, and up to 16 neighbours the twin's call in everything --
+// its result, its refusals and its name in their texts.  Returns the name the call goes by.
+const char *wide_rule(ScoreRequest &rq, const char *wide_name, const char *narrow_name)
 {
-    const int rc = score_check_args(h, who, rq, D, list, rq.bin_out || rq.dist_out ? nullptr : "bin_out and dist_out are both null");
+    rq.wide = rq.m > kMaxM;
+    return rq.wide ? wide_name : narrow_name;
+}
+
+// the calls that return rows: the request goes through the checks and, unless Q == 0, through a ScoreRun
+int score_rows(chb_ctx *h, const char *who, ScoreRequest &rq, const int64_t *D, bool list, int64_t *bin_out, double *dist_out,
+               double *min_dist_out, double *margin_out)
+{
+    rq.bin_out = bin_out; rq.dist_out = dist_out; rq.min_dist_out = min_dist_out; rq.margin_out = margin_out;
+    const int rc = score_check_args(h, who, rq, D, list, bin_out || dist_out ? nullptr : "bin_out and dist_out are both null");
     return rc != CHB_OK || rq.Q == 0 ? rc : ScoreRun{h, rq}.run();
 }
 
-}  // namespace
-
-int chb_recruit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
-                     int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
-{
-    ScoreRequest rq{labels, B, Y, nullptr, nullptr, Q, m, nullptr, 0, bin_out, dist_out, min_dist_out, margin_out};
-    return score_rows(h, "chb_recruit_rows", rq, &D, false);
-}
-
-int chb_audit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const int64_t *row_idx, int64_t Q,
-                   int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
-{
-    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, m, nullptr, 0, bin_out, dist_out, min_dist_out, margin_out};
-    return score_rows(h, "chb_audit_rows", rq, nullptr, false);
-}
-
-int chb_recruit_rows_multi(chb_ctx *h, const int64_t *labels, int64_t B, const int *ms, int nm, const double *Y, int64_t Q,
-                           int64_t D, int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
-{
-    ScoreRequest rq{labels, B, Y, nullptr, nullptr, Q, 0, ms, nm, bin_out, dist_out, min_dist_out, margin_out};
-    return score_rows(h, "chb_recruit_rows_multi", rq, &D, true);
-}
-
-int chb_audit_rows_multi(chb_ctx *h, const int64_t *labels, int64_t B, const int *ms, int nm, const int64_t *row_idx,
-                         int64_t Q, int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
-{
-    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, 0, ms, nm, bin_out, dist_out, min_dist_out, margin_out};
-    return score_rows(h, "chb_audit_rows_multi", rq, nullptr, true);
-}
-
-int chb_audit_rows_grouped(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
-                           int64_t Q, int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
-{
-    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, m, nullptr, 0, bin_out, dist_out, min_dist_out, margin_out};
-    rq.grouped = true; rq.groups = groups;
-    return score_rows(h, "chb_audit_rows_grouped", rq, nullptr, false);
-}
-
-int chb_audit_rows_multi_grouped(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, const int *ms, int nm,
-                                 const int64_t *row_idx, int64_t Q, int64_t *bin_out, double *dist_out, double *min_dist_out,
-                                 double *margin_out)
-{
-    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, 0, ms, nm, bin_out, dist_out, min_dist_out, margin_out};
-    rq.grouped = true; rq.groups = groups;
-    return score_rows(h, "chb_audit_rows_multi_grouped", rq, nullptr, true);
-}
-
-namespace {
-
-// chb_bin_report and its grouped form behind the request
+// chb_bin_report and its grouped and wide forms behind the request
 int bin_report(chb_ctx *h, const char *who, ScoreRequest &rq, int64_t *confusion, int64_t *unplaced, int64_t *dcnt,
                double *dmin, double *dsum, int64_t *n_skipped)
 {
@@ -3126,227 +3081,59 @@ int bin_report(chb_ctx *h, const char *who, ScoreRequest &rq, int64_t *confusion
     return rc != CHB_OK ? rc : plan.copy_tables(h, out);
 }
 
-}  // namespace
-
-int chb_bin_report(chb_ctx *h, const int64_t *labels, int64_t B, int m, const int64_t *row_idx, int64_t Q,
-                   int64_t *confusion, int64_t *unplaced, int64_t *dcnt, double *dmin, double *dsum, int64_t *n_skipped)
+// a witness call's outputs: per pair the hull's members, their selection distances and their weights.  (Wide: the members
+// are the selection list, so their ids come down as idx_out and w_idx stays null.)
+void witness_outputs(ScoreRequest &rq, int64_t *nbr_idx, double *nbr_dist, double *alpha)
 {
-    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, m, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
-    return bin_report(h, "chb_bin_report", rq, confusion, unplaced, dcnt, dmin, dsum, n_skipped);
+    rq.witness = true; rq.w_dist = nbr_dist; rq.w_alpha = alpha;
+    if (rq.wide) rq.idx_out = nbr_idx;
+    else rq.w_idx = nbr_idx;
 }
 
-int chb_bin_report_grouped(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
-                           int64_t Q, int64_t *confusion, int64_t *unplaced, int64_t *dcnt, double *dmin, double *dsum,
-                           int64_t *n_skipped)
+// The pair calls, whole: rq.Q pairs (row, bin_idx), the rows resident (rq.row_idx, which is not "all rows" here: its range
+// is checked like chb_audit_rows' list) or, in the recruit forms, rows row_of of the Y_rows rows of Y, D columns each.
+// Behind score_check_args the recruit forms' own checks, then the bins' range, the plan and the run.
+int score_pairs(chb_ctx *h, const char *who, ScoreRequest &rq, const int64_t *bin_idx, const int64_t *D = nullptr,
+                int64_t Y_rows = 0, const int64_t *row_of = nullptr)
 {
-    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, m, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
-    rq.grouped = true; rq.groups = groups;
-    return bin_report(h, "chb_bin_report_grouped", rq, confusion, unplaced, dcnt, dmin, dsum, n_skipped);
-}
-
-namespace {
-
-// the two pair calls behind score_check_args and their own checks of the rows: the bins' range, the plan, the run
-int score_pairs(chb_ctx *h, ScoreRequest &rq, const int64_t *row, const int64_t *bin_idx)
-{
-    for (int64_t p = 0; p < rq.Q; ++p)
+    const int64_t P = rq.Q, *row = D ? row_of : rq.row_idx;
+    // null arguments: the lists, then dist_out -- which a witness call may leave out, but not with every witness output
+    const char *missing = nullptr;
+    if (P > 0 && rq.witness) {
+        if (!row || !bin_idx) missing = D ? "row_of or bin_idx is null" : "row_idx or bin_idx is null";
+        else if (!rq.w_idx && !rq.idx_out && !rq.w_dist && !rq.w_alpha)
+            missing = "nbr_idx, nbr_dist and alpha are all null (the call without witnesses is the one to use)";
+    } else if (P > 0 && (!row || !bin_idx || !rq.dist_out)) {
+        missing = D ? "row_of, bin_idx or dist_out is null" : "row_idx, bin_idx or dist_out is null";
+    }
+    const int rc = score_check_args(h, who, rq, D, false, missing);
+    if (rc != CHB_OK) return rc;
+    if (D) {
+        if (Y_rows < 0) return fail(CHB_EINVAL, "Q < 0");
+        for (int64_t p = 0; p < P; ++p)
+            if (row_of[p] < 0 || row_of[p] >= Y_rows) return fail(CHB_EINVAL, "row_of entry outside [0, Q)");
+    }
+    if (P == 0) return CHB_OK;
+    for (int64_t p = 0; p < P; ++p)
         if (bin_idx[p] < 0 || bin_idx[p] >= rq.B) return fail(CHB_EINVAL, "bin_idx entry outside [0, B)");
     PairPlan plan;
-    plan.build(row, bin_idx, rq.Q, rq.B);
+    plan.build(row, bin_idx, P, rq.B);
     h->score.pair_tiles = (int64_t)plan.tile.size();
     rq.row_idx = nullptr; rq.pairs = &plan;
     return ScoreRun{h, rq}.run();
 }
 
-const char *pairs_missing(int64_t P, const void *row, const void *bin_idx, const void *dist_out, const char *text)
+// The wide pair calls' idx_out: the selection lists with more than 16 neighbours; up to 16 the narrow witness call's
+// nbr_idx -- and with it that call's rule for what may be null -- or, without idx_out, the plain pair call `plain`
+const char *wide_pairs_rule(ScoreRequest &rq, int64_t *idx_out, const char *wide_name, const char *witness_name, const char *plain)
 {
-    return P > 0 && (!row || !bin_idx || !dist_out) ? text : nullptr;
+    const char *who = wide_rule(rq, wide_name, idx_out ? witness_name : plain);
+    if (rq.wide) rq.idx_out = idx_out;
+    else if (idx_out) witness_outputs(rq, idx_out, nullptr, nullptr);
+    return who;
 }
 
-}  // namespace
-
-int chb_audit_pairs(chb_ctx *h, const int64_t *labels, int64_t B, int m, const int64_t *row_idx, const int64_t *bin_idx,
-                    int64_t P, double *dist_out)
-{
-    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, P, m, nullptr, 0, nullptr, dist_out, nullptr, nullptr};
-    // (row_idx is not "all rows" here: its range is checked like chb_audit_rows' list)
-    const int rc = score_check_args(h, "chb_audit_pairs", rq, nullptr, false,
-                                    pairs_missing(P, row_idx, bin_idx, dist_out, "row_idx, bin_idx or dist_out is null"));
-    return rc != CHB_OK || P == 0 ? rc : score_pairs(h, rq, row_idx, bin_idx);
-}
-
-int chb_audit_pairs_grouped(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
-                            const int64_t *bin_idx, int64_t P, double *dist_out)
-{
-    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, P, m, nullptr, 0, nullptr, dist_out, nullptr, nullptr};
-    rq.grouped = true; rq.groups = groups;
-    const int rc = score_check_args(h, "chb_audit_pairs_grouped", rq, nullptr, false,
-                                    pairs_missing(P, row_idx, bin_idx, dist_out, "row_idx, bin_idx or dist_out is null"));
-    return rc != CHB_OK || P == 0 ? rc : score_pairs(h, rq, row_idx, bin_idx);
-}
-
-int chb_recruit_pairs(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
-                      const int64_t *row_of, const int64_t *bin_idx, int64_t P, double *dist_out)
-{
-    ScoreRequest rq{labels, B, Y, nullptr, nullptr, P, m, nullptr, 0, nullptr, dist_out, nullptr, nullptr};
-    const int rc = score_check_args(h, "chb_recruit_pairs", rq, &D, false,
-                                    pairs_missing(P, row_of, bin_idx, dist_out, "row_of, bin_idx or dist_out is null"));
-    if (rc != CHB_OK) return rc;
-    if (Q < 0) return fail(CHB_EINVAL, "Q < 0");
-    for (int64_t p = 0; p < P; ++p)
-        if (row_of[p] < 0 || row_of[p] >= Q) return fail(CHB_EINVAL, "row_of entry outside [0, Q)");
-    return P == 0 ? CHB_OK : score_pairs(h, rq, row_of, bin_idx);
-}
-
-namespace {
-
-// the refusal of a witness call's null arguments: the lists, then "no witness output at all" (dist_out may be null here)
-const char *witness_missing(int64_t P, const void *row, const void *bin_idx, const void *nbr_idx, const void *nbr_dist,
-                            const void *alpha, const char *lists)
-{
-    if (P <= 0) return nullptr;
-    if (!row || !bin_idx) return lists;
-    return nbr_idx || nbr_dist || alpha ? nullptr
-        : "nbr_idx, nbr_dist and alpha are all null (the call without witnesses is the one to use)";
-}
-
-void witness_outputs(ScoreRequest &rq, int64_t *nbr_idx, double *nbr_dist, double *alpha)
-{
-    rq.witness = true; rq.w_idx = nbr_idx; rq.w_dist = nbr_dist; rq.w_alpha = alpha;
-}
-
-}  // namespace
-
-int chb_audit_pairs_witness(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
-                            const int64_t *bin_idx, int64_t P, double *dist_out, int64_t *nbr_idx, double *nbr_dist,
-                            double *alpha)
-{
-    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, P, m, nullptr, 0, nullptr, dist_out, nullptr, nullptr};
-    rq.groups = groups;   // (null: leave-one-out, the ungrouped kernel)
-    witness_outputs(rq, nbr_idx, nbr_dist, alpha);
-    const int rc = score_check_args(h, "chb_audit_pairs_witness", rq, nullptr, false,
-                                    witness_missing(P, row_idx, bin_idx, nbr_idx, nbr_dist, alpha, "row_idx or bin_idx is null"));
-    return rc != CHB_OK || P == 0 ? rc : score_pairs(h, rq, row_idx, bin_idx);
-}
-
-int chb_recruit_pairs_witness(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
-                              const int64_t *row_of, const int64_t *bin_idx, int64_t P, double *dist_out, int64_t *nbr_idx,
-                              double *nbr_dist, double *alpha)
-{
-    ScoreRequest rq{labels, B, Y, nullptr, nullptr, P, m, nullptr, 0, nullptr, dist_out, nullptr, nullptr};
-    witness_outputs(rq, nbr_idx, nbr_dist, alpha);
-    const int rc = score_check_args(h, "chb_recruit_pairs_witness", rq, &D, false,
-                                    witness_missing(P, row_of, bin_idx, nbr_idx, nbr_dist, alpha, "row_of or bin_idx is null"));
-    if (rc != CHB_OK) return rc;
-    if (Q < 0) return fail(CHB_EINVAL, "Q < 0");
-    for (int64_t p = 0; p < P; ++p)
-        if (row_of[p] < 0 || row_of[p] >= Q) return fail(CHB_EINVAL, "row_of entry outside [0, Q)");
-    return P == 0 ? CHB_OK : score_pairs(h, rq, row_of, bin_idx);
-}
-
-// ---- the wide calls: one entry point for every m.  m <= 16 forwards to the existing call (its result, its refusals and their
-// texts); 16 < m <= 64 is the same request in wide mode (ScoreRequest::wide): two kernels per chunk, recruit_wide_kernels.hip
-int chb_audit_rows_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
-                        int64_t Q, int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
-{
-    if (m <= kMaxM)
-        return groups ? chb_audit_rows_grouped(h, labels, groups, B, m, row_idx, Q, bin_out, dist_out, min_dist_out, margin_out)
-                      : chb_audit_rows(h, labels, B, m, row_idx, Q, bin_out, dist_out, min_dist_out, margin_out);
-    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, m, nullptr, 0, bin_out, dist_out, min_dist_out, margin_out};
-    rq.groups = groups; rq.wide = true;   // (null: leave-one-out, the ungrouped kernel)
-    return score_rows(h, "chb_audit_rows_wide", rq, nullptr, false);
-}
-
-int chb_recruit_rows_wide(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
-                          int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
-{
-    if (m <= kMaxM) return chb_recruit_rows(h, labels, B, m, Y, Q, D, bin_out, dist_out, min_dist_out, margin_out);
-    ScoreRequest rq{labels, B, Y, nullptr, nullptr, Q, m, nullptr, 0, bin_out, dist_out, min_dist_out, margin_out};
-    rq.wide = true;
-    return score_rows(h, "chb_recruit_rows_wide", rq, &D, false);
-}
-
-int chb_audit_pairs_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
-                         const int64_t *bin_idx, int64_t P, double *dist_out, int64_t *idx_out)
-{
-    if (m <= kMaxM) {
-        if (idx_out) return chb_audit_pairs_witness(h, labels, groups, B, m, row_idx, bin_idx, P, dist_out, idx_out, nullptr, nullptr);
-        return groups ? chb_audit_pairs_grouped(h, labels, groups, B, m, row_idx, bin_idx, P, dist_out)
-                      : chb_audit_pairs(h, labels, B, m, row_idx, bin_idx, P, dist_out);
-    }
-    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, P, m, nullptr, 0, nullptr, dist_out, nullptr, nullptr};
-    rq.groups = groups; rq.wide = true; rq.idx_out = idx_out;
-    const int rc = score_check_args(h, "chb_audit_pairs_wide", rq, nullptr, false,
-                                    pairs_missing(P, row_idx, bin_idx, dist_out, "row_idx, bin_idx or dist_out is null"));
-    return rc != CHB_OK || P == 0 ? rc : score_pairs(h, rq, row_idx, bin_idx);
-}
-
-int chb_recruit_pairs_wide(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
-                           const int64_t *row_of, const int64_t *bin_idx, int64_t P, double *dist_out, int64_t *idx_out)
-{
-    if (m <= kMaxM) {
-        if (idx_out) return chb_recruit_pairs_witness(h, labels, B, m, Y, Q, D, row_of, bin_idx, P, dist_out, idx_out, nullptr, nullptr);
-        return chb_recruit_pairs(h, labels, B, m, Y, Q, D, row_of, bin_idx, P, dist_out);
-    }
-    ScoreRequest rq{labels, B, Y, nullptr, nullptr, P, m, nullptr, 0, nullptr, dist_out, nullptr, nullptr};
-    rq.wide = true; rq.idx_out = idx_out;
-    const int rc = score_check_args(h, "chb_recruit_pairs_wide", rq, &D, false,
-                                    pairs_missing(P, row_of, bin_idx, dist_out, "row_of, bin_idx or dist_out is null"));
-    if (rc != CHB_OK) return rc;
-    if (Q < 0) return fail(CHB_EINVAL, "Q < 0");
-    for (int64_t p = 0; p < P; ++p)
-        if (row_of[p] < 0 || row_of[p] >= Q) return fail(CHB_EINVAL, "row_of entry outside [0, Q)");
-    return P == 0 ? CHB_OK : score_pairs(h, rq, row_of, bin_idx);
-}
-
-int chb_audit_pairs_witness_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m,
-                                 const int64_t *row_idx, const int64_t *bin_idx, int64_t P, double *dist_out, int64_t *nbr_idx,
-                                 double *nbr_dist, double *alpha)
-{
-    if (m <= kMaxM) return chb_audit_pairs_witness(h, labels, groups, B, m, row_idx, bin_idx, P, dist_out, nbr_idx, nbr_dist, alpha);
-    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, P, m, nullptr, 0, nullptr, dist_out, nullptr, nullptr};
-    rq.groups = groups; rq.wide = true;
-    witness_outputs(rq, nullptr, nbr_dist, alpha);
-    rq.idx_out = nbr_idx;   // (the members are the selection list: chb_audit_pairs_wide's idx_out)
-    const int rc = score_check_args(h, "chb_audit_pairs_witness_wide", rq, nullptr, false,
-                                    witness_missing(P, row_idx, bin_idx, nbr_idx, nbr_dist, alpha, "row_idx or bin_idx is null"));
-    return rc != CHB_OK || P == 0 ? rc : score_pairs(h, rq, row_idx, bin_idx);
-}
-
-int chb_recruit_pairs_witness_wide(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
-                                   const int64_t *row_of, const int64_t *bin_idx, int64_t P, double *dist_out,
-                                   int64_t *nbr_idx, double *nbr_dist, double *alpha)
-{
-    if (m <= kMaxM)
-        return chb_recruit_pairs_witness(h, labels, B, m, Y, Q, D, row_of, bin_idx, P, dist_out, nbr_idx, nbr_dist, alpha);
-    ScoreRequest rq{labels, B, Y, nullptr, nullptr, P, m, nullptr, 0, nullptr, dist_out, nullptr, nullptr};
-    rq.wide = true;
-    witness_outputs(rq, nullptr, nbr_dist, alpha);
-    rq.idx_out = nbr_idx;
-    const int rc = score_check_args(h, "chb_recruit_pairs_witness_wide", rq, &D, false,
-                                    witness_missing(P, row_of, bin_idx, nbr_idx, nbr_dist, alpha, "row_of or bin_idx is null"));
-    if (rc != CHB_OK) return rc;
-    if (Q < 0) return fail(CHB_EINVAL, "Q < 0");
-    for (int64_t p = 0; p < P; ++p)
-        if (row_of[p] < 0 || row_of[p] >= Q) return fail(CHB_EINVAL, "row_of entry outside [0, Q)");
-    return P == 0 ? CHB_OK : score_pairs(h, rq, row_of, bin_idx);
-}
-
-int chb_bin_report_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
-                        int64_t Q, int64_t *confusion, int64_t *unplaced, int64_t *dcnt, double *dmin, double *dsum,
-                        int64_t *n_skipped)
-{
-    if (m <= kMaxM)
-        return groups ? chb_bin_report_grouped(h, labels, groups, B, m, row_idx, Q, confusion, unplaced, dcnt, dmin, dsum, n_skipped)
-                      : chb_bin_report(h, labels, B, m, row_idx, Q, confusion, unplaced, dcnt, dmin, dsum, n_skipped);
-    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, m, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
-    rq.groups = groups; rq.wide = true;   // (null: leave-one-out, the ungrouped kernel)
-    return bin_report(h, "chb_bin_report_wide", rq, confusion, unplaced, dcnt, dmin, dsum, n_skipped);
-}
-
-namespace {
-
-// the two nearest-bins calls: the dense call's request with the ranked outputs in place of the reduced ones
+// the nearest-bins calls: the dense call's request with the ranked outputs in place of the reduced ones
 int score_nearest(chb_ctx *h, const char *who, ScoreRequest &rq, const int64_t *D, int k, int64_t *near_bin, double *near_dist)
 {
     rq.nearest = true; rq.near_k = k; rq.near_bin = near_bin; rq.near_dist = near_dist;
@@ -3356,10 +3143,185 @@ int score_nearest(chb_ctx *h, const char *who, ScoreRequest &rq, const int64_t *
 
 }  // namespace
 
+int chb_recruit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
+                     int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
+{
+    ScoreRequest rq = ScoreRequest::recruit(labels, B, m, Y, Q);
+    return score_rows(h, "chb_recruit_rows", rq, &D, false, bin_out, dist_out, min_dist_out, margin_out);
+}
+
+int chb_audit_rows(chb_ctx *h, const int64_t *labels, int64_t B, int m, const int64_t *row_idx, int64_t Q,
+                   int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
+{
+    ScoreRequest rq = ScoreRequest::audit(labels, B, m, row_idx, Q);
+    return score_rows(h, "chb_audit_rows", rq, nullptr, false, bin_out, dist_out, min_dist_out, margin_out);
+}
+
+int chb_recruit_rows_multi(chb_ctx *h, const int64_t *labels, int64_t B, const int *ms, int nm, const double *Y, int64_t Q,
+                           int64_t D, int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
+{
+    ScoreRequest rq = ScoreRequest::recruit(labels, B, 0, Y, Q);
+    rq.ms = ms; rq.nm = nm;
+    return score_rows(h, "chb_recruit_rows_multi", rq, &D, true, bin_out, dist_out, min_dist_out, margin_out);
+}
+
+int chb_audit_rows_multi(chb_ctx *h, const int64_t *labels, int64_t B, const int *ms, int nm, const int64_t *row_idx,
+                         int64_t Q, int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
+{
+    ScoreRequest rq = ScoreRequest::audit(labels, B, 0, row_idx, Q);
+    rq.ms = ms; rq.nm = nm;
+    return score_rows(h, "chb_audit_rows_multi", rq, nullptr, true, bin_out, dist_out, min_dist_out, margin_out);
+}
+
+int chb_audit_rows_grouped(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
+                           int64_t Q, int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
+{
+    ScoreRequest rq = ScoreRequest::audit(labels, B, m, row_idx, Q);
+    rq.grouped = true; rq.groups = groups;
+    return score_rows(h, "chb_audit_rows_grouped", rq, nullptr, false, bin_out, dist_out, min_dist_out, margin_out);
+}
+
+int chb_audit_rows_multi_grouped(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, const int *ms, int nm,
+                                 const int64_t *row_idx, int64_t Q, int64_t *bin_out, double *dist_out, double *min_dist_out,
+                                 double *margin_out)
+{
+    ScoreRequest rq = ScoreRequest::audit(labels, B, 0, row_idx, Q);
+    rq.ms = ms; rq.nm = nm; rq.grouped = true; rq.groups = groups;
+    return score_rows(h, "chb_audit_rows_multi_grouped", rq, nullptr, true, bin_out, dist_out, min_dist_out, margin_out);
+}
+
+int chb_bin_report(chb_ctx *h, const int64_t *labels, int64_t B, int m, const int64_t *row_idx, int64_t Q,
+                   int64_t *confusion, int64_t *unplaced, int64_t *dcnt, double *dmin, double *dsum, int64_t *n_skipped)
+{
+    ScoreRequest rq = ScoreRequest::audit(labels, B, m, row_idx, Q);
+    return bin_report(h, "chb_bin_report", rq, confusion, unplaced, dcnt, dmin, dsum, n_skipped);
+}
+
+int chb_bin_report_grouped(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
+                           int64_t Q, int64_t *confusion, int64_t *unplaced, int64_t *dcnt, double *dmin, double *dsum,
+                           int64_t *n_skipped)
+{
+    ScoreRequest rq = ScoreRequest::audit(labels, B, m, row_idx, Q);
+    rq.grouped = true; rq.groups = groups;
+    return bin_report(h, "chb_bin_report_grouped", rq, confusion, unplaced, dcnt, dmin, dsum, n_skipped);
+}
+
+int chb_audit_pairs(chb_ctx *h, const int64_t *labels, int64_t B, int m, const int64_t *row_idx, const int64_t *bin_idx,
+                    int64_t P, double *dist_out)
+{
+    ScoreRequest rq = ScoreRequest::audit(labels, B, m, row_idx, P);
+    rq.dist_out = dist_out;
+    return score_pairs(h, "chb_audit_pairs", rq, bin_idx);
+}
+
+int chb_audit_pairs_grouped(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
+                            const int64_t *bin_idx, int64_t P, double *dist_out)
+{
+    ScoreRequest rq = ScoreRequest::audit(labels, B, m, row_idx, P);
+    rq.dist_out = dist_out; rq.grouped = true; rq.groups = groups;
+    return score_pairs(h, "chb_audit_pairs_grouped", rq, bin_idx);
+}
+
+int chb_recruit_pairs(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
+                      const int64_t *row_of, const int64_t *bin_idx, int64_t P, double *dist_out)
+{
+    ScoreRequest rq = ScoreRequest::recruit(labels, B, m, Y, P);
+    rq.dist_out = dist_out;
+    return score_pairs(h, "chb_recruit_pairs", rq, bin_idx, &D, Q, row_of);
+}
+
+int chb_audit_pairs_witness(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
+                            const int64_t *bin_idx, int64_t P, double *dist_out, int64_t *nbr_idx, double *nbr_dist,
+                            double *alpha)
+{
+    ScoreRequest rq = ScoreRequest::audit(labels, B, m, row_idx, P);
+    rq.dist_out = dist_out; rq.groups = groups;   // (null: leave-one-out, the ungrouped kernel)
+    witness_outputs(rq, nbr_idx, nbr_dist, alpha);
+    return score_pairs(h, "chb_audit_pairs_witness", rq, bin_idx);
+}
+
+int chb_recruit_pairs_witness(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
+                              const int64_t *row_of, const int64_t *bin_idx, int64_t P, double *dist_out, int64_t *nbr_idx,
+                              double *nbr_dist, double *alpha)
+{
+    ScoreRequest rq = ScoreRequest::recruit(labels, B, m, Y, P);
+    rq.dist_out = dist_out;
+    witness_outputs(rq, nbr_idx, nbr_dist, alpha);
+    return score_pairs(h, "chb_recruit_pairs_witness", rq, bin_idx, &D, Q, row_of);
+}
+
+int chb_audit_rows_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
+                        int64_t Q, int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
+{
+    ScoreRequest rq = ScoreRequest::audit(labels, B, m, row_idx, Q);
+    rq.groups = groups;   // (null: leave-one-out, the ungrouped kernel)
+    const char *who = wide_rule(rq, "chb_audit_rows_wide", groups ? "chb_audit_rows_grouped" : "chb_audit_rows");
+    return score_rows(h, who, rq, nullptr, false, bin_out, dist_out, min_dist_out, margin_out);
+}
+
+int chb_recruit_rows_wide(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
+                          int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
+{
+    ScoreRequest rq = ScoreRequest::recruit(labels, B, m, Y, Q);
+    const char *who = wide_rule(rq, "chb_recruit_rows_wide", "chb_recruit_rows");
+    return score_rows(h, who, rq, &D, false, bin_out, dist_out, min_dist_out, margin_out);
+}
+
+int chb_audit_pairs_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
+                         const int64_t *bin_idx, int64_t P, double *dist_out, int64_t *idx_out)
+{
+    ScoreRequest rq = ScoreRequest::audit(labels, B, m, row_idx, P);
+    rq.dist_out = dist_out; rq.groups = groups;
+    const char *who = wide_pairs_rule(rq, idx_out, "chb_audit_pairs_wide", "chb_audit_pairs_witness",
+                                      groups ? "chb_audit_pairs_grouped" : "chb_audit_pairs");
+    return score_pairs(h, who, rq, bin_idx);
+}
+
+int chb_recruit_pairs_wide(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
+                           const int64_t *row_of, const int64_t *bin_idx, int64_t P, double *dist_out, int64_t *idx_out)
+{
+    ScoreRequest rq = ScoreRequest::recruit(labels, B, m, Y, P);
+    rq.dist_out = dist_out;
+    const char *who = wide_pairs_rule(rq, idx_out, "chb_recruit_pairs_wide", "chb_recruit_pairs_witness", "chb_recruit_pairs");
+    return score_pairs(h, who, rq, bin_idx, &D, Q, row_of);
+}
+
+int chb_audit_pairs_witness_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m,
+                                 const int64_t *row_idx, const int64_t *bin_idx, int64_t P, double *dist_out, int64_t *nbr_idx,
+                                 double *nbr_dist, double *alpha)
+{
+    ScoreRequest rq = ScoreRequest::audit(labels, B, m, row_idx, P);
+    rq.dist_out = dist_out; rq.groups = groups;
+    const char *who = wide_rule(rq, "chb_audit_pairs_witness_wide", "chb_audit_pairs_witness");
+    witness_outputs(rq, nbr_idx, nbr_dist, alpha);
+    return score_pairs(h, who, rq, bin_idx);
+}
+
+int chb_recruit_pairs_witness_wide(chb_ctx *h, const int64_t *labels, int64_t B, int m, const double *Y, int64_t Q, int64_t D,
+                                   const int64_t *row_of, const int64_t *bin_idx, int64_t P, double *dist_out,
+                                   int64_t *nbr_idx, double *nbr_dist, double *alpha)
+{
+    ScoreRequest rq = ScoreRequest::recruit(labels, B, m, Y, P);
+    rq.dist_out = dist_out;
+    const char *who = wide_rule(rq, "chb_recruit_pairs_witness_wide", "chb_recruit_pairs_witness");
+    witness_outputs(rq, nbr_idx, nbr_dist, alpha);
+    return score_pairs(h, who, rq, bin_idx, &D, Q, row_of);
+}
+
+int chb_bin_report_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
+                        int64_t Q, int64_t *confusion, int64_t *unplaced, int64_t *dcnt, double *dmin, double *dsum,
+                        int64_t *n_skipped)
+{
+    ScoreRequest rq = ScoreRequest::audit(labels, B, m, row_idx, Q);
+    rq.groups = groups;   // (null: leave-one-out, the ungrouped kernel)
+    const char *who = wide_rule(rq, "chb_bin_report_wide", groups ? "chb_bin_report_grouped" : "chb_bin_report");
+    return bin_report(h, who, rq, confusion, unplaced, dcnt, dmin, dsum, n_skipped);
+}
+
 int chb_audit_rows_nearest(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, int k,
                            const int64_t *row_idx, int64_t Q, int64_t *near_bin, double *near_dist)
 {
-    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, m, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
+    ScoreRequest rq = ScoreRequest::audit(labels, B, m, row_idx, Q);
     rq.groups = groups;   // (null: leave-one-out, the ungrouped kernel)
     return score_nearest(h, "chb_audit_rows_nearest", rq, nullptr, k, near_bin, near_dist);
 }
@@ -3367,26 +3329,25 @@ int chb_audit_rows_nearest(chb_ctx *h, const int64_t *labels, const int64_t *gro
 int chb_recruit_rows_nearest(chb_ctx *h, const int64_t *labels, int64_t B, int m, int k, const double *Y, int64_t Q, int64_t D,
                              int64_t *near_bin, double *near_dist)
 {
-    ScoreRequest rq{labels, B, Y, nullptr, nullptr, Q, m, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
+    ScoreRequest rq = ScoreRequest::recruit(labels, B, m, Y, Q);
     return score_nearest(h, "chb_recruit_rows_nearest", rq, &D, k, near_bin, near_dist);
 }
 
 int chb_audit_rows_nearest_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, int k,
                                 const int64_t *row_idx, int64_t Q, int64_t *near_bin, double *near_dist)
 {
-    if (m <= kMaxM) return chb_audit_rows_nearest(h, labels, groups, B, m, k, row_idx, Q, near_bin, near_dist);
-    ScoreRequest rq{labels, B, nullptr, row_idx, nullptr, Q, m, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
-    rq.groups = groups; rq.wide = true;
-    return score_nearest(h, "chb_audit_rows_nearest_wide", rq, nullptr, k, near_bin, near_dist);
+    ScoreRequest rq = ScoreRequest::audit(labels, B, m, row_idx, Q);
+    rq.groups = groups;
+    const char *who = wide_rule(rq, "chb_audit_rows_nearest_wide", "chb_audit_rows_nearest");
+    return score_nearest(h, who, rq, nullptr, k, near_bin, near_dist);
 }
 
 int chb_recruit_rows_nearest_wide(chb_ctx *h, const int64_t *labels, int64_t B, int m, int k, const double *Y, int64_t Q,
                                   int64_t D, int64_t *near_bin, double *near_dist)
 {
-    if (m <= kMaxM) return chb_recruit_rows_nearest(h, labels, B, m, k, Y, Q, D, near_bin, near_dist);
-    ScoreRequest rq{labels, B, Y, nullptr, nullptr, Q, m, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
-    rq.wide = true;
-    return score_nearest(h, "chb_recruit_rows_nearest_wide", rq, &D, k, near_bin, near_dist);
+    ScoreRequest rq = ScoreRequest::recruit(labels, B, m, Y, Q);
+    const char *who = wide_rule(rq, "chb_recruit_rows_nearest_wide", "chb_recruit_rows_nearest");
+    return score_nearest(h, who, rq, &D, k, near_bin, near_dist);
 }
 
 int chb_find_nearest_from_row(chb_ctx *h, int64_t c, const int64_t *labels, const double *row,
