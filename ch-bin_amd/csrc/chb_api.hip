@@ -3732,6 +3732,19 @@ static int pool_bad_slots(chb_ctx *h, int64_t *out)
     return read_device_int(h, h->pool.bad.p, out);
 }
 
+// the hull kernels' 16-lane exchanges against the shuffles they replace (launch_lane_exchange_check): values that differ
+static int lane_exchange_mismatches(chb_ctx *h, int64_t *out)
+{
+    *out = 0;
+    HIPCHK(hipSetDevice(h->dev));
+    DevBuf<int> bad;
+    HIPCHK(bad.ensure(1));
+    HIPCHK(hipMemsetAsync(bad.p, 0, sizeof(int), h->stream));
+    launch_lane_exchange_check(bad.p, h->stream);
+    HIPCHK(hipGetLastError());
+    return read_device_int(h, bad.p, out);   // (synchronises the stream before the buffer goes)
+}
+
 // the counters the host keeps
 #define CTR(name, expr) {name, [](const chb_ctx *h) -> int64_t { return expr; }}
 static const struct { const char *name; int64_t (*get)(const chb_ctx *); } kHostCounters[] = {
@@ -3761,6 +3774,7 @@ int chb_counter(chb_ctx *h, const char *name, int64_t *out)
     // pairs of the last fit that broke the shortlist stage's contract (0, or the fit failed)
     if (!strcmp(name, "shortlist_short")) return read_device_int(h, h->short_cnt.p, out);
     if (!strcmp(name, "pool_bad_slots")) return pool_bad_slots(h, out);
+    if (!strcmp(name, "lane_exchange_mismatches")) return lane_exchange_mismatches(h, out);
     // regions of the persistent pack that ran full and moved in the last fit (pack_state_fix_kernel)
     if (!strcmp(name, "pack_region_moves")) return read_device_int(h, h->pp.ctl.p ? h->pp.ctl.p + 3 : nullptr, out);
     // pairs the fused kernel left to the exact path

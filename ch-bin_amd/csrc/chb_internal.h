@@ -352,6 +352,9 @@ bool fused_supported(int m, int Dp);
 // stripe: the work striped over the XCDs by bin (from 16 bins on; CHB_FUSED_STRIPE=0: position-major); ptr64: the m <= 5
 // kernel's 64-bit-pointer instantiation whatever the size of X (CHB_FUSED_PTR64=1)
 void launch_hull_select_qp(const FusedArgs &a, bool stripe, bool ptr64, hipStream_t s);
+// self-check of the 16-lane exchanges the hull kernels run on (hull_solve16.h): one workgroup adds to *bad every value that
+// differs from the shuffle form's
+void launch_lane_exchange_check(int *bad, hipStream_t s);
 
 // explicit problems: query sample q[p], hull_idx[p][m_max] compacted, hull_cnt[p] vertices
 // 16 < m <= kMaxMGeneric: one wavefront per problem, Gram and the solver's inverse in LDS (slow, see

@@ -7,6 +7,7 @@
 #include "chb_internal.h"
 
 #include <math.h>
+#include <utility>
 
 namespace chb {
 namespace {
@@ -28,6 +29,57 @@ __device__ __forceinline__ double row_ror_f64(double v)
     const int lo = row_ror_i32<N>(__double2loint(v)), hi = row_ror_i32<N>(__double2hiint(v));
     return __hiloint2double(hi, lo);
 }
+// Exchanges with a fixed pattern inside a 16-lane group, as DPP moves as well (a double is two of them; the bits travel
+// unchanged, NaN payloads included).  row_xor<K>(v): the value of lane l16 ^ K, K = 8 (a rotation by half a row), 2 and 1
+// (quad permutations), 4 (lanes 0-3 and 8-11 take theirs from four lanes up, the others from four lanes down: two moves
+// into one register, each writing its own banks).  row_bcast<V>(v): the value of lane V of the row.  Like a shuffle they
+// stand outside any condition that splits a row: a disabled lane delivers nothing, and here its reader keeps stale bits.
+template <int K>
+__device__ __forceinline__ int row_xor_i32(int v)
+{
+    static_assert(K == 1 || K == 2 || K == 4 || K == 8, "one bit of the lane number inside a row");
+    if constexpr (K == 8) return __builtin_amdgcn_mov_dpp(v, 0x128, 0xF, 0xF, false);       // row_ror:8
+    else if constexpr (K == 2) return __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, false);   // quad_perm:[2,3,0,1]
+    else if constexpr (K == 1) return __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, false);   // quad_perm:[1,0,3,2]
+    else {
+        const int up = __builtin_amdgcn_mov_dpp(v, 0x104, 0xF, 0x5, false);                 // row_shl:4 bank_mask:0x5
+        return __builtin_amdgcn_update_dpp(up, v, 0x114, 0xF, 0xA, false);                  // row_shr:4 bank_mask:0xa
+    }
+}
+template <int V>
+__device__ __forceinline__ int row_bcast_i32(int v)
+{
+    static_assert(V >= 0 && V < 16, "a lane of the row");
+    return __builtin_amdgcn_mov_dpp(v, 0x150 + V, 0xF, 0xF, false);                         // row_newbcast:V
+}
+template <int K>
+__device__ __forceinline__ double row_xor_f64(double v)
+{
+    const int lo = row_xor_i32<K>(__double2loint(v)), hi = row_xor_i32<K>(__double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+template <int V>
+__device__ __forceinline__ double row_bcast_f64(double v)
+{
+    const int lo = row_bcast_i32<V>(__double2loint(v)), hi = row_bcast_i32<V>(__double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+// f(integral constant 0), ..., f(integral constant N - 1): a loop whose counter can be a DPP control
+template <int V>
+struct RowLane {
+    static constexpr int value = V;
+};
+template <class F, int... Vs>
+__device__ __forceinline__ void for_row_lanes_impl(F &&f, std::integer_sequence<int, Vs...>)
+{
+    (f(RowLane<Vs>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void for_row_lanes(F &&f)
+{
+    for_row_lanes_impl(f, std::make_integer_sequence<int, N>{});
+}
+
 __device__ __forceinline__ double group_sum16(double v)
 {
     v += row_ror_f64<8>(v);

@@ -257,8 +257,22 @@ __device__ __forceinline__ double affine_min_norm(const double (&Q)[Sym<M>::NP],
 
 
 // Sum v[e] over the 16 lanes of a group and leave entry e = l16 on lane l16: a reduce-scatter in
-// four halving steps (15 exchanges instead of the 64 of sixteen butterfly reductions).
+// four halving steps (15 exchanges instead of the 64 of sixteen butterfly reductions).  The exchanges are DPP moves
+// (row_xor_f64 of hull_solve16.h): a step waits for no LDS round trip.  Every sum is the pair, in the order, of the
+// shuffle form this replaces (reduce_scatter16_shfl below, kept for the self-check), so the result has the same bits.
 __device__ __forceinline__ double reduce_scatter16(const double (&v)[16], int l16)
+{
+    double t8[8], t4[4], t2[2];
+    const bool b8 = l16 & 8, b4 = l16 & 4, b2 = l16 & 2, b1 = l16 & 1;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) t8[e] = (b8 ? v[e + 8] : v[e]) + row_xor_f64<8>(b8 ? v[e] : v[e + 8]);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) t4[e] = (b4 ? t8[e + 4] : t8[e]) + row_xor_f64<4>(b4 ? t8[e] : t8[e + 4]);
+#pragma unroll
+    for (int e = 0; e < 2; ++e) t2[e] = (b2 ? t4[e + 2] : t4[e]) + row_xor_f64<2>(b2 ? t4[e] : t4[e + 2]);
+    return (b1 ? t2[1] : t2[0]) + row_xor_f64<1>(b1 ? t2[0] : t2[1]);
+}
+__device__ __forceinline__ double reduce_scatter16_shfl(const double (&v)[16], int l16)
 {
     double t8[8], t4[4], t2[2];
     const bool b8 = l16 & 8, b4 = l16 & 4, b2 = l16 & 2, b1 = l16 & 1;
@@ -438,8 +452,7 @@ constexpr double kTieRel = 1e-11;
 // 64-bit row pointers, which is what keeps the kernel free of spills at 3 wavefronts per SIMD (the launcher picks
 // it when the sample matrix is smaller than 4 GiB).
 template <int CC, int NR, bool OFF32>
-__device__ __forceinline__ void gram_rows(const double *X, int Dp, int Dk, int qid, int idm, int gbase, int l16,
-                                          double (&r)[NR])
+__device__ __forceinline__ void gram_rows(const double *X, int Dp, int Dk, int qid, int idm, int l16, double (&r)[NR])
 {   // (Dp: row stride -- whole 128-byte lines; Dk: the columns swept, D rounded up to 8: the padding beyond is never read)
     constexpr int NP = CC * (CC + 1) / 2;
     static_assert(NP <= 16 * NR, "result registers");
@@ -448,13 +461,13 @@ __device__ __forceinline__ void gram_rows(const double *X, int Dp, int Dk, int q
     const unsigned xoff = (unsigned)qid * (unsigned)Dp * 8u;
     const double *vrow[OFF32 ? 1 : CC];
     unsigned voff[OFF32 ? CC : 1];
-#pragma unroll
-    for (int v = 0; v < CC; ++v) {
-        const int idv = __shfl(idm, gbase + v, 64);
+    for_row_lanes<CC>([&](auto lv) {
+        constexpr int v = decltype(lv)::value;
+        const int idv = row_bcast_i32<v>(idm);
         // a missing candidate reads the query row: y = 0, its Gram row / column stays 0 (never used)
-        if (OFF32) voff[v] = (unsigned)(idv >= 0 ? idv : qid) * (unsigned)Dp * 8u;
-        else vrow[v] = X + (size_t)(idv >= 0 ? idv : qid) * Dp;
-    }
+        if (OFF32) voff[OFF32 ? v : 0] = (unsigned)(idv >= 0 ? idv : qid) * (unsigned)Dp * 8u;
+        else vrow[OFF32 ? 0 : v] = X + (size_t)(idv >= 0 ? idv : qid) * Dp;
+    });
     auto xat = [&](int k) { return OFF32 ? reinterpret_cast<const double *>(Xb + (size_t)(xoff + 8u * (unsigned)k)) : xrow + k; };
     auto vat = [&](int v, int k) {
         return OFF32 ? reinterpret_cast<const double *>(Xb + (size_t)(voff[OFF32 ? v : 0] + 8u * (unsigned)k)) : vrow[OFF32 ? 0 : v] + k;
@@ -511,22 +524,22 @@ __device__ __forceinline__ void gram_rows(const double *X, int Dp, int Dk, int q
 #endif
 constexpr int kFusedWide = CHB_FUSED_WIDE;   // widest shortlist the fused kernel takes (one candidate per lane of a group)
 
-// squared distances only: candidate v (v < 8) of every 16-lane group is the one held by lane gbase + v0 + v;
-// on return lane l16 < 8 holds the squared distance of candidate v0 + l16
-template <bool OFF32>
-__device__ __forceinline__ double diag_rows8(const double *X, int Dp, int Dk, int qid, int idm, int gbase, int l16, int v0)
+// squared distances only: candidate v (v < 8) of every 16-lane group is the one held by lane V0 + v of the group;
+// on return lane l16 < 8 holds the squared distance of candidate V0 + l16
+template <bool OFF32, int V0>
+__device__ __forceinline__ double diag_rows8(const double *X, int Dp, int Dk, int qid, int idm, int l16)
 {
     const char *Xb = reinterpret_cast<const char *>(X);
     const double *xrow = X + (size_t)qid * Dp;
     const unsigned xoff = (unsigned)qid * (unsigned)Dp * 8u;
     const double *vrow[OFF32 ? 1 : 8];
     unsigned voff[OFF32 ? 8 : 1];
-#pragma unroll
-    for (int v = 0; v < 8; ++v) {
-        const int idv = __shfl(idm, gbase + v0 + v, 64);
-        if (OFF32) voff[v] = (unsigned)(idv >= 0 ? idv : qid) * (unsigned)Dp * 8u;
-        else vrow[v] = X + (size_t)(idv >= 0 ? idv : qid) * Dp;
-    }
+    for_row_lanes<8>([&](auto lv) {
+        constexpr int v = decltype(lv)::value;
+        const int idv = row_bcast_i32<V0 + v>(idm);
+        if (OFF32) voff[OFF32 ? v : 0] = (unsigned)(idv >= 0 ? idv : qid) * (unsigned)Dp * 8u;
+        else vrow[OFF32 ? 0 : v] = X + (size_t)(idv >= 0 ? idv : qid) * Dp;
+    });
     auto xat = [&](int k) { return OFF32 ? reinterpret_cast<const double *>(Xb + (size_t)(xoff + 8u * (unsigned)k)) : xrow + k; };
     auto vat = [&](int v, int k) {
         return OFF32 ? reinterpret_cast<const double *>(Xb + (size_t)(voff[OFF32 ? v : 0] + 8u * (unsigned)k)) : vrow[OFF32 ? 0 : v] + k;
@@ -591,11 +604,11 @@ constexpr double kTrimGamma = 2.5e-5;   // fp32 summation of up to 161 terms (kG
 // from 128 + 2 * l16 on (one 4-byte load; clamped to the row's last pair, which the mask then clears).
 __device__ __forceinline__ int trim_tail_col(int l16) { return 128 + 2 * l16; }
 
-// <Gs[j], Gs[p]> of the first nmax (uniform) of 16 candidates: candidate v of every 16-lane group is the one lane gbase + v
+// <Gs[j], Gs[p]> of the first nmax (uniform) of 16 candidates: candidate v of every 16-lane group is the one its lane v
 // holds in `ids` (none: the query's own row is read, the value is not used); qm / qt = the lane's 10 columns of the query's
 // row, the halves from column D on cleared (there the rows carry the shortlist kernels' bias constants).  On return lane l16
 // holds the product of candidate l16.
-__device__ __forceinline__ double shadow_dot16(const unsigned short *Gs, int Dz, int qid, int ids, int nmax, int gbase, int l16,
+__device__ __forceinline__ double shadow_dot16(const unsigned short *Gs, int Dz, int qid, int ids, int nmax, int l16,
                                                const uint4 &qm, unsigned qt)
 {
     using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
@@ -606,19 +619,19 @@ __device__ __forceinline__ double shadow_dot16(const unsigned short *Gs, int Dz,
     double acc[16];
 #pragma unroll
     for (int v = 0; v < 16; ++v) acc[v] = 0.0;
-#pragma unroll
-    for (int v0 = 0; v0 < 16; v0 += 4) {
+    for_row_lanes<4>([&](auto lq) {
+        constexpr int v0 = 4 * decltype(lq)::value;
         if (v0 < nmax) {
-#pragma unroll
-            for (int v = v0; v < v0 + 4; ++v) {
-                const int idv = __shfl(ids, gbase + v, 64);
+            for_row_lanes<4>([&](auto lv) {
+                constexpr int v = v0 + decltype(lv)::value;
+                const int idv = row_bcast_i32<v>(ids);
                 const unsigned short *row = Gs + (size_t)(idv >= 0 ? idv : qid) * Dz;
                 const uint4 u = *reinterpret_cast<const uint4 *>(row + 8 * l16);   // (8 * l16 + 8 <= 128 < Dz)
                 const unsigned ut = *reinterpret_cast<const unsigned *>(row + tcol);
                 acc[v] = (double)dot2(ut, qt, dot2(u.w, qm.w, dot2(u.z, qm.z, dot2(u.y, qm.y, dot2(u.x, qm.x, 0.f)))));
-            }
+            });
         }
-    }
+    });
     return reduce_scatter16(acc, l16);
 }
 
@@ -761,9 +774,9 @@ __global__ __launch_bounds__(64 * WAVES, CHB_FUSED_OCC) void hull_select_qp_kern
                     const float2 gj = ta.gq[qid_g];
                     const bool in0 = id0 >= 0, in1 = id1 >= 0;
                     const float2 g0 = ta.gq[in0 ? id0 : qid_g], g1 = ta.gq[in1 ? id1 : qid_g];
-                    const double dot0 = shadow_dot16(ta.Gs, ta.Dz, qid_g, id0, nmax, gbase, l16, qm, qt);
+                    const double dot0 = shadow_dot16(ta.Gs, ta.Dz, qid_g, id0, nmax, l16, qm, qt);
                     double dot1 = 0.0;
-                    if (nmax > 16) dot1 = shadow_dot16(ta.Gs, ta.Dz, qid_g, id1, nmax - 16, gbase, l16, qm, qt);
+                    if (nmax > 16) dot1 = shadow_dot16(ta.Gs, ta.Dz, qid_g, id1, nmax - 16, l16, qm, qt);
                     // the bounds (see "Trim")
                     const double Nj = (double)gj.x, sNj = sqrt(Nj), flush = 0x1p-13 * sqrt((double)a.D);
                     auto bounds = [&](double dot, float2 gp, double &lo, double &hi) {
@@ -781,23 +794,25 @@ __global__ __launch_bounds__(64 * WAVES, CHB_FUSED_OCC) void hull_select_qp_kern
                     bad = bad || (in0 && !(hi0 < kInf)) || (in1 && !(hi1 < kInf));   // NaN or infinite: no bound, keep everything
                     // tau_u: the upper bound of rank m - 1 by (bound, slot)
                     int rank0 = 0, rank1 = 0;
-#pragma unroll
-                    for (int u = 0; u < 16; ++u) {
-                        const double hu = __shfl(hi0, gbase + u, 64);
+                    for_row_lanes<16>([&](auto lu) {
+                        constexpr int u = decltype(lu)::value;
+                        const double hu = row_bcast_f64<u>(hi0);
                         rank0 += (hu < hi0 || (hu == hi0 && u < l16)) ? 1 : 0;
                         rank1 += hu <= hi1 ? 1 : 0;
-                    }
+                    });
                     if (nmax > 16) {
-#pragma unroll
-                        for (int u = 0; u < 16; ++u) {
-                            const double hu = __shfl(hi1, gbase + u, 64);
+                        for_row_lanes<16>([&](auto lu) {
+                            constexpr int u = decltype(lu)::value;
+                            const double hu = row_bcast_f64<u>(hi1);
                             rank0 += hu < hi0 ? 1 : 0;
                             rank1 += (hu < hi1 || (hu == hi1 && u < l16)) ? 1 : 0;
-                        }
+                        });
                     }
                     double tau = (in0 && rank0 == m - 1) ? hi0 : (in1 && rank1 == m - 1) ? hi1 : kInf;
-#pragma unroll
-                    for (int off = 1; off < 16; off <<= 1) tau = fmin(tau, __shfl_xor(tau, off, 64));
+                    tau = fmin(tau, row_xor_f64<1>(tau));
+                    tau = fmin(tau, row_xor_f64<2>(tau));
+                    tau = fmin(tau, row_xor_f64<4>(tau));
+                    tau = fmin(tau, row_xor_f64<8>(tau));
                     const double lim = tau * (1.0 + kTrimSlack);
                     const bool k0 = in0 && !(lo0 > lim), k1 = in1 && !(lo1 > lim);   // (a NaN keeps the candidate)
                     const unsigned badm = (unsigned)(__ballot(bad) >> gbase) & 0xffffu;
@@ -868,10 +883,10 @@ __global__ __launch_bounds__(64 * WAVES, CHB_FUSED_OCC) void hull_select_qp_kern
             // the widest shortlist of the pass (the last problem: they are sorted)
             const int cw = __builtin_amdgcn_readfirstlane(__shfl(n, sOrd[w][min(p0 + 3, nnarrow - 1)], 64));
             double r[NR];
-            if (cw <= M) gram_rows<M, NR, OFF32>(a.X, a.Dp, Dk, qid_g, idm, gbase, l16, r);
-            else if (C >= M + 1 && cw == M + 1) gram_rows<(C >= M + 1 ? M + 1 : M), NR, OFF32>(a.X, a.Dp, Dk, qid_g, idm, gbase, l16, r);
-            else if (C >= M + 2 && cw == M + 2) gram_rows<(C >= M + 2 ? M + 2 : M), NR, OFF32>(a.X, a.Dp, Dk, qid_g, idm, gbase, l16, r);
-            else gram_rows<C, NR, OFF32>(a.X, a.Dp, Dk, qid_g, idm, gbase, l16, r);
+            if (cw <= M) gram_rows<M, NR, OFF32>(a.X, a.Dp, Dk, qid_g, idm, l16, r);
+            else if (C >= M + 1 && cw == M + 1) gram_rows<(C >= M + 1 ? M + 1 : M), NR, OFF32>(a.X, a.Dp, Dk, qid_g, idm, l16, r);
+            else if (C >= M + 2 && cw == M + 2) gram_rows<(C >= M + 2 ? M + 2 : M), NR, OFF32>(a.X, a.Dp, Dk, qid_g, idm, l16, r);
+            else gram_rows<C, NR, OFF32>(a.X, a.Dp, Dk, qid_g, idm, l16, r);
             bool tie = false;
             if (has && n_g <= m) {
                 // every candidate is a hull vertex: the candidate Gram is the hull's (any vertex order)
@@ -952,21 +967,21 @@ __global__ __launch_bounds__(64 * WAVES, CHB_FUSED_OCC) void hull_select_qp_kern
             nmax = max(nmax, __shfl_xor(nmax, 16, 64));
             nmax = max(nmax, __shfl_xor(nmax, 32, 64));
             nmax = __builtin_amdgcn_readfirstlane(nmax);
-            double sv = diag_rows8<OFF32>(a.X, a.Dp, Dk, qid_g, idm, gbase, l16, 0);
+            double sv = diag_rows8<OFF32, 0>(a.X, a.Dp, Dk, qid_g, idm, l16);
             if (nmax > 8) {
-                const double s_hi = diag_rows8<OFF32>(a.X, a.Dp, Dk, qid_g, idm, gbase, l16, 8);
-                const double moved = __shfl(s_hi, gbase + (l16 & 7), 64);
+                const double s_hi = diag_rows8<OFF32, 8>(a.X, a.Dp, Dk, qid_g, idm, l16);
+                const double moved = row_xor_f64<8>(s_hi);   // (lanes 8 .. 15 take candidates 8 .. 15 from lanes 0 .. 7)
                 sv = l16 < 8 ? sv : moved;
             }
             if (l16 >= n_g) sv = kInf;
             // rank by (squared distance, index) among the group's n_g candidates
             int rank = 0;
-#pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                const double su = __shfl(sv, gbase + u, 64);
-                const int iu = __shfl(idm, gbase + u, 64);
+            for_row_lanes<16>([&](auto lu) {
+                constexpr int u = decltype(lu)::value;
+                const double su = row_bcast_f64<u>(sv);
+                const int iu = row_bcast_i32<u>(idm);
                 rank += (u < n_g && u != l16 && (su < sv || (su == sv && iu < idm))) ? 1 : 0;
-            }
+            });
             if (has && l16 < n_g) {
                 if (rank < m) sSel[w][grp][rank] = idm;
                 if (rank == m - 1) sTh[w][grp][0] = sv;
@@ -982,7 +997,7 @@ __global__ __launch_bounds__(64 * WAVES, CHB_FUSED_OCC) void hull_select_qp_kern
                 if (l16 < m) idm2 = sSel[w][grp][l16];
             }
             double r[NR];
-            gram_rows<M, NR, OFF32>(a.X, a.Dp, Dk, qid_g, idm2, gbase, l16, r);
+            gram_rows<M, NR, OFF32>(a.X, a.Dp, Dk, qid_g, idm2, l16, r);
             if (has && !tie) {
 #pragma unroll
                 for (int t = 0; t < NR; ++t)
@@ -1673,7 +1688,71 @@ void dispatch(const QpArgs &a, int nprob, int m, const int *xq, const int *xhull
     }
 }
 
+// Self-check of the 16-lane exchanges of hull_solve16.h (the counter "lane_exchange_mismatches"): one workgroup of 256
+// threads compares every helper, on ints and on doubles, bit for bit with the shuffle it stands for, and the DPP
+// reduce_scatter16 with the shuffle form, and adds the mismatches it sees to *bad.  The values differ from lane to lane
+// and from round to round; the doubles run through NaNs with payloads (quiet and signalling), -0.0, denormals of both
+// signs, infinities and ordinary numbers from 2^-40 to 2^40.  Every exchange stands outside any condition.
+__device__ __forceinline__ unsigned lane_check_hash(unsigned x)
+{
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+__device__ __forceinline__ double lane_check_double(unsigned tid, unsigned round)
+{
+    const unsigned h = lane_check_hash(tid * 977u + round * 131071u + 12345u);
+    const unsigned long long payload = ((unsigned long long)lane_check_hash(h) << 20) ^ h;   // < 2^52
+    const double mixed = ldexp((double)((int)(h % 2001u) - 1000), (int)((h >> 11) % 81u) - 40);
+    switch ((tid * 7u + round * 3u) & 7u) {
+    case 0: return __longlong_as_double((long long)(0x7FF8000000000000ull | (payload & 0x0007FFFFFFFFFFFFull)));   // quiet NaN
+    case 1: return __longlong_as_double((long long)(0xFFF0000000000000ull | (payload & 0x0007FFFFFFFFFFFFull) | 1ull));   // signalling NaN, sign set
+    case 2: return -0.0;
+    case 3: return __longlong_as_double((long long)((payload & 0x000FFFFFFFFFFFFFull) | 1ull));   // denormal
+    case 4: return __longlong_as_double((long long)(0x8000000000000000ull | (payload >> 30) | 1ull));   // tiny negative denormal
+    case 5: return (h & 1u) ? kInf : -kInf;
+    default: return mixed;
+    }
+}
+__global__ __launch_bounds__(256) void lane_exchange_check_kernel(int *bad)
+{
+    const unsigned tid = threadIdx.x;
+    const int lane = (int)(tid & 63u), l16 = lane & 15, gbase = lane & 48;
+    int miss = 0;
+    auto differ = [](double x, double y) { return __double_as_longlong(x) != __double_as_longlong(y) ? 1 : 0; };
+    for (unsigned round = 0; round < 8u; ++round) {
+        const int xi = (int)lane_check_hash(tid * 2654435761u + round);
+        const double xd = lane_check_double(tid, round);
+        miss += row_xor_i32<1>(xi) != __shfl_xor(xi, 1, 64) ? 1 : 0;
+        miss += row_xor_i32<2>(xi) != __shfl_xor(xi, 2, 64) ? 1 : 0;
+        miss += row_xor_i32<4>(xi) != __shfl_xor(xi, 4, 64) ? 1 : 0;
+        miss += row_xor_i32<8>(xi) != __shfl_xor(xi, 8, 64) ? 1 : 0;
+        miss += differ(row_xor_f64<1>(xd), __shfl_xor(xd, 1, 64));
+        miss += differ(row_xor_f64<2>(xd), __shfl_xor(xd, 2, 64));
+        miss += differ(row_xor_f64<4>(xd), __shfl_xor(xd, 4, 64));
+        miss += differ(row_xor_f64<8>(xd), __shfl_xor(xd, 8, 64));
+        for_row_lanes<16>([&](auto lv) {
+            constexpr int v = decltype(lv)::value;
+            miss += row_bcast_i32<v>(xi) != __shfl(xi, gbase + v, 64) ? 1 : 0;
+            miss += differ(row_bcast_f64<v>(xd), __shfl(xd, gbase + v, 64));
+        });
+        // sixteen sums of mixed magnitude per lane: both forms add the same pairs in the same order
+        double v16[16];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const unsigned h = lane_check_hash((tid * 16u + (unsigned)e) * 2246822519u + round * 40503u);
+            v16[e] = ldexp((double)((int)(h % 2001u) - 1000), (int)((h >> 11) % 81u) - 40);
+        }
+        miss += differ(reduce_scatter16(v16, l16), reduce_scatter16_shfl(v16, l16));
+    }
+    if (miss != 0) atomicAdd(bad, miss);
+}
+
 }  // namespace
+
+void launch_lane_exchange_check(int *bad, hipStream_t s)
+{
+    hipLaunchKernelGGL(lane_exchange_check_kernel, dim3(1), dim3(256), 0, s, bad);
+}
 
 void launch_hull_qp(const QpArgs &a, hipStream_t s)
 {

@@ -662,7 +662,9 @@ int chb_fit_stats(chb_ctx *h, int64_t *out4);
  * items -- of the last chb_audit_pairs / chb_recruit_pairs call that had pairs; 0 before the first),
  * "recruit_wide_rows" (rows per launch of the last chb_*_wide call with m > 16: see there; 0 before the first),
  * "kmer_chunk_bytes" / "kmer_chunk_rows" (the most bases / contigs of one sequence chunk of chb_kmer_profiles and
- * chb_set_samples_from_sequences: constants), "kmer_chunks" (chunks of the last such call) */
+ * chb_set_samples_from_sequences: constants), "kmer_chunks" (chunks of the last such call), "lane_exchange_mismatches" (for
+ * tests: one small launch compares the hull kernels' in-register exchanges of a 16-lane group, and the Gram reduction
+ * built on them, bit for bit with the shuffles they replace; the number of differences, always 0) */
 int chb_counter(chb_ctx *h, const char *name, int64_t *out);
 
 #ifdef __cplusplus
