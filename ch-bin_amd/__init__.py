@@ -7,7 +7,8 @@ HIP library or a GPU is missing.
 """
 from . import synth  # noqa: F401
 
-__all__ = ["synth", "recruit", "audit", "bin_report", "neighbor_sweep", "audit_pairs", "recruit_pairs", "cohesion"]
+__all__ = ["synth", "recruit", "audit", "bin_report", "neighbor_sweep", "neighbor_sweep_wide", "audit_pairs", "recruit_pairs",
+           "cohesion"]
 
 
 def __getattr__(name):
@@ -26,7 +27,7 @@ def __getattr__(name):
     if name == "neighbor_sweep":
         from .clustering import neighbor_sweep
         return neighbor_sweep
-    if name in ("audit_pairs", "recruit_pairs", "cohesion"):
+    if name in ("audit_pairs", "recruit_pairs", "cohesion", "neighbor_sweep_wide"):
         from . import clustering
         return getattr(clustering, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -96,6 +96,11 @@ SIGNATURES = {
     "chb_recruit_pairs_witness_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
                                                  C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p]),
+    # the list calls for entries up to 64: the _multi calls' arguments (the audit with groups, which may be NULL)
+    "chb_audit_rows_multi_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
+                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "chb_recruit_rows_multi_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                              C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "chb_find_nearest_from_row": (C.c_int, [C.c_void_p, C.c_int64, _i64p, _f64p, C.c_int64, C.c_int,
                                             _i64p, C.POINTER(C.c_int32)]),
     "chb_hull_distance_batch": (C.c_int, [C.c_void_p, _i64p, C.c_int64, _i64p, C.c_int, _f64p,
@@ -470,6 +475,18 @@ class Context:
     def recruit_rows_wide(self, labels, B, m, Y, want_dist=True):
         """chb_recruit_rows_wide: recruit_rows for any m in 1 .. 64.  Returns what recruit_rows returns."""
         return self._score_rows("chb_recruit_rows_wide", labels, B, want_dist, m=m, Y=Y)
+
+    def audit_rows_multi_wide(self, labels, B, ms, rows=None, want_dist=True, groups=None):
+        """chb_audit_rows_multi_wide: audit_rows_wide for every m of the list `ms` (distinct values in 1 .. 64, at most 16
+        of them, any order) from one wide selection pass for all entries above 16; slice j of every result is bit for bit
+        audit_rows_wide(labels, B, ms[j], rows, groups=groups).  A list without an entry above 16 forwards to
+        audit_rows_multi / audit_rows_multi_grouped.  Returns what audit_rows_multi returns."""
+        return self._score_rows("chb_audit_rows_multi_wide", labels, B, want_dist, ms=ms, rows=rows, groups=groups, slot=True)
+
+    def recruit_rows_multi_wide(self, labels, B, ms, Y, want_dist=True):
+        """chb_recruit_rows_multi_wide: recruit_rows_wide for every m of the list `ms` (entries up to 64); slice j of every
+        result is bit for bit recruit_rows_wide(labels, B, ms[j], Y).  Returns what recruit_rows_multi returns."""
+        return self._score_rows("chb_recruit_rows_multi_wide", labels, B, want_dist, ms=ms, Y=Y)
 
     def audit_pairs_wide(self, labels, B, m, rows, bins, groups=None, want_idx=False):
         """chb_audit_pairs_wide: audit_pairs (with `groups` audit_pairs_grouped) for any m in 1 .. 64; entry p is bit for

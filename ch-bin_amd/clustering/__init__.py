@@ -12,6 +12,7 @@ from .algorithm import (  # noqa: F401
     fit_cluster,
     nearest_bins,
     neighbor_sweep,
+    neighbor_sweep_wide,
     parent_groups,
     recruit,
     recruit_nearest_bins,

@@ -69,7 +69,7 @@ def fit_cluster(
 
 # audit / recruit / audit_pairs / recruit_pairs / cohesion / bin_report / witness / recruit_witness / nearest_bins /
 # recruit_nearest_bins: up to this many neighbours the calls they have always made; beyond it (up to 64; the library
-# refuses more) the chb_*_wide calls.  neighbor_sweep has no wide form and keeps refusing entries above 16.
+# refuses more) the chb_*_wide calls.  neighbor_sweep keeps refusing entries above 16: those go to neighbor_sweep_wide.
 _TILED_MAX_NEIGHBORS = 16
 
 
@@ -264,7 +264,8 @@ def neighbor_sweep(
     configuration says 5 and whose function default says 15)?  `audit` of the samples in `rows` (None: all of them) for
     every entry of `neighbors` (distinct values in 1 .. 16) at the cost of little more than the audit at the largest: one
     selection pass on the device serves the whole list, and each entry's result is bit for bit what `audit` returns for it.
-    Nothing changes.  With `groups` every entry is `audit(..., groups=groups)`: leave-group-out."""
+    Nothing changes.  With `groups` every entry is `audit(..., groups=groups)`: leave-group-out.
+    A list with entries above 16 (up to 64) goes to `neighbor_sweep_wide`."""
     with _resident(samples, metric, qp_solver) as ctx:
         labels = np.ascontiguousarray(labels, dtype=np.int64)
         neighbors = np.ascontiguousarray(neighbors, dtype=np.int64)
@@ -274,6 +275,30 @@ def neighbor_sweep(
         else:
             bins, dist, mind, margin = ctx.audit_rows_multi_grouped(labels, groups, int(num_clusters), neighbors, rows,
                                                                     want_dist=return_distances)
+    scored = np.arange(np.shape(samples)[0], dtype=np.int64) if rows is None else np.ascontiguousarray(rows, dtype=np.int64)
+    return NeighborSweep(neighbors, scored, labels[scored], bins, mind, margin, int(num_clusters), dist)
+
+
+def neighbor_sweep_wide(
+    samples: np.ndarray,
+    labels: np.ndarray,
+    num_clusters: int,
+    neighbors=(5, 15, 24, 32, 64),
+    metric: str = "convex",
+    qp_solver: str = "quadprog",
+    rows: np.ndarray = None,
+    return_distances: bool = False,
+    groups: np.ndarray = None,
+) -> NeighborSweep:
+    """`neighbor_sweep` for a list whose entries go up to 64 (distinct values, at most 16 of them, any order, entries up to
+    16 and above mixed), for a labelling fitted with more than 16 neighbours: one wide selection pass serves every entry
+    above 16 and only the active-set solves repeat; each entry's result is bit for bit what `audit` returns for it.  A list
+    without an entry above 16 is `neighbor_sweep`'s call.  Nothing changes.  With `groups` every entry is `audit(..., groups=groups)`."""
+    with _resident(samples, metric, qp_solver) as ctx:
+        labels = np.ascontiguousarray(labels, dtype=np.int64)
+        neighbors = np.ascontiguousarray(neighbors, dtype=np.int64)
+        bins, dist, mind, margin = ctx.audit_rows_multi_wide(labels, int(num_clusters), neighbors, rows,
+                                                             want_dist=return_distances, groups=groups)
     scored = np.arange(np.shape(samples)[0], dtype=np.int64) if rows is None else np.ascontiguousarray(rows, dtype=np.int64)
     return NeighborSweep(neighbors, scored, labels[scored], bins, mind, margin, int(num_clusters), dist)
 

@@ -2595,7 +2595,9 @@ struct ScoreRequest {
     int64_t *near_bin = nullptr; double *near_dist = nullptr;
     // chb_*_wide with 16 < m <= 64: the two wide kernels per chunk in place of recruit_kernel; the pair forms may return
     // the selection lists ([Q][m], -1 padded, in the caller's order).  Combines with nearest (the ranking reads the wide
-    // chunk's table), plan (cut at wide_chunk_rows) and witness (m slots per pair: the ids are idx_out, w_idx stays null)
+    // chunk's table), plan (cut at wide_chunk_rows) and witness (m slots per pair: the ids are idx_out, w_idx stays null).
+    // With a list (nm > 0: chb_*_rows_multi_wide, a dense call with an entry above 16): one selection at the largest entry,
+    // the entries up to 16 by recruit_kernel's list launch, those above by the solve kernel's list form
     bool wide = false;
     int64_t *idx_out = nullptr;
     // the two makers: Q resident rows row_idx (or pairs of them), Q new rows Y (or pairs of rows of Y)
@@ -2618,7 +2620,8 @@ struct ScoreRequest {
 // outputs; no samples; D; more than 16 neighbours (CHB_EUNSUPPORTED), then a nearest-bins call's k > 16; more than 8192
 // bins; an open stepwise fit; Q == 0 (CHB_OK: nothing further is read); the row_idx rules.
 // (A wide call, rq.wide: more than 64 neighbours, then more than 32 on a device without the LDS for 64 vertices, in place of
-// "more than 16".  wide_rule sets rq.wide only above 16 neighbours, so a _wide symbol never reaches "more than 16".)
+// "more than 16".  wide_rule sets rq.wide only above 16 neighbours, so a _wide symbol never reaches "more than 16".
+// A wide list, chb_*_rows_multi_wide with an entry above 16: the same, and its entries are told apart up to 64.)
 // who: the name the call goes by in the texts (wide_rule: a _wide symbol's narrow twin up to 16 neighbours).
 // D: the rows' number of columns in the calls that take Y, nullptr in the others.  list: the call takes ms / nm, whose
 // largest entry becomes rq.m.  no_output: the refusal's text when every output that counts for the call is null, else nullptr.
@@ -2629,11 +2632,14 @@ int score_check_args(chb_ctx *h, const char *who, ScoreRequest &rq, const int64_
         if (rq.Q < 0 || rq.B < 1) return fail(CHB_EINVAL, "Q < 0 or B < 1");
         if (!rq.ms) return fail(CHB_EINVAL, "ms is null");
         if (rq.nm < 1 || rq.nm > kMaxM) return fail(CHB_EINVAL, "nm must be 1 .. 16");
-        unsigned seen = 0;   // 1 .. 16 distinct entries in 1 .. 16 (an entry above 16 is refused below and sets no bit here)
+        // 1 .. 16 distinct entries in 1 .. 16, a wide list's (chb_*_rows_multi_wide) in 1 .. 64 (an entry above that is
+        // refused below and sets no bit here)
+        const int top = rq.wide ? kMaxMGeneric : kMaxM;
+        unsigned long long seen = 0;
         rq.m = 0;
         for (int j = 0; j < rq.nm; ++j) {
             if (rq.ms[j] < 1) return fail(CHB_EINVAL, "an entry of ms is < 1");
-            const unsigned bit = rq.ms[j] <= kMaxM ? 1u << (rq.ms[j] - 1) : 0;
+            const unsigned long long bit = rq.ms[j] <= top ? 1ull << (rq.ms[j] - 1) : 0;
             if (seen & bit) return fail(CHB_EINVAL, "ms holds a value twice");
             seen |= bit;
             rq.m = std::max(rq.m, rq.ms[j]);
@@ -2684,6 +2690,10 @@ struct ScoreRun {
     const size_t width = rq.pairs ? 1 : (size_t)rq.B;   // distances per result row
     const size_t wslots = rq.wide ? (size_t)rq.m : (size_t)kWitnessSlots;   // slots of a position's witness record
     int slot[kMaxM] = {0};                  // list entry j's slice on the device = the number of smaller entries
+    // a wide list (chb_*_rows_multi_wide): its entries up to 16 -- their number and the largest, for recruit_kernel's list
+    // launch -- and those above, ascending, for the solve kernel's list form; the slices of the first stand before the others'
+    int n_narrow = 0, m_narrow = 0, n_wide = 0;
+    unsigned char m_wide[kMaxM] = {0};
     size_t n_memb = 0;
     int64_t chunk = 0, n = 0;               // rows per chunk (a plan: its cuts), chunks
     RecruitWitnessArgs a{};   // (the launchers without witnesses take the part of it that is theirs)
@@ -2741,20 +2751,27 @@ struct ScoreRun {
     void list_slots()
     {
         for (int j = 0; j < rq.nm; ++j) {
-            a.mmask |= 1u << (rq.ms[j] - 1);
             for (int k = 0; k < rq.nm; ++k) slot[j] += rq.ms[k] < rq.ms[j];
+            if (rq.ms[j] <= kMaxM) {
+                a.mmask |= 1u << (rq.ms[j] - 1);
+                ++n_narrow; m_narrow = std::max(m_narrow, rq.ms[j]);
+            } else m_wide[n_wide++] = (unsigned char)rq.ms[j];   // (only a wide list has such entries: at most 64)
         }
+        std::sort(m_wide, m_wide + n_wide);
     }
     // chunk length and buffers.  A list's chunks are kRecruitChunk / nm rows, rounded down to whole 64-row tiles, so the
     // nm result slices of a chunk fill no more than a single-m chunk's buffers.
     int size_buffers()
     {
         const int64_t B = rq.B;
-        if (rq.nm > 0) sc.multi_rows = std::max<int64_t>(kQTile, kRecruitChunk / rq.nm / kQTile * kQTile);
+        const int64_t list_rows = rq.nm > 0 ? std::max<int64_t>(kQTile, kRecruitChunk / rq.nm / kQTile * kQTile) : 0;
+        if (rq.nm > 0 && !rq.wide) sc.multi_rows = list_rows;
         if (rq.wide) sc.wide_rows = wide_chunk_rows((int64_t)width, rq.m);
+        // (a wide list: both bounds -- the lists of its largest entry within the list buffer, its nm slices within a chunk's)
+        if (rq.wide && rq.nm > 0) sc.wide_rows = std::min(sc.wide_rows, list_rows);
         // (a wide plan: cut at wide_rows by its builder, so its longest chunk is what the buffers must hold)
         chunk = rq.pairs ? rq.pairs->max_rows : rq.plan && rq.wide ? rq.plan->max_rows
-              : std::min<int64_t>(rq.Q, rq.nm > 0 ? sc.multi_rows : rq.wide ? sc.wide_rows : kRecruitChunk);
+              : std::min<int64_t>(rq.Q, rq.wide ? sc.wide_rows : rq.nm > 0 ? sc.multi_rows : kRecruitChunk);
         n = rq.pairs ? (int64_t)rq.pairs->cut.size() - 1 : rq.plan ? (int64_t)rq.plan->cut.size() - 1 : (rq.Q + chunk - 1) / chunk;
         const size_t res = (size_t)chunk * (size_t)ns;   // result rows of a chunk
         const int halves = rq.Q > chunk ? 2 : 1;   // (a plan's or a pair plan's longest chunk is shorter than Q whenever there is a second)
@@ -2937,20 +2954,48 @@ struct ScoreRun {
             wa.list = rq.pairs ? b.wlist.d.p : sc.wlist.p;
             if (rq.witness) { wa.w_d = b.wd.d.p; wa.w_alpha = b.walpha.d.p; }   // (a pair chunk: the witness forms)
             const double work = (double)nq * (double)width;
+            const bool wlist = rq.nm > 0;   // a wide list: (row, bin, entry) work behind one selection at its largest entry
+            if (wlist && n_narrow > 0) {   // the entries up to 16: recruit_kernel's list launch, their slices in front
+                RecruitGroupArgs na = a;
+                na.m = m_narrow;
+                Timed t(h, audit ? "audit_multi" : "recruit_multi", work * (double)n_narrow);
+                if (na.memb_grp) launch_recruit_grouped(na, s);
+                else launch_recruit(na, s);
+            }
             {
-                Timed t(h, rq.pairs ? (audit ? "audit_pairs_wide_select" : "recruit_pairs_wide_select")
-                                    : (audit ? "audit_wide_select" : "recruit_wide_select"), work);
+                Timed t(h, wlist ? (audit ? "audit_multi_wide_select" : "recruit_multi_wide_select")
+                        : rq.pairs ? (audit ? "audit_pairs_wide_select" : "recruit_pairs_wide_select")
+                                   : (audit ? "audit_wide_select" : "recruit_wide_select"), work);
                 if (rq.witness) launch_recruit_select_wide_witness(wa, s);
                 else launch_recruit_select_wide(wa, s);
             }
-            {
+            if (wlist) {
+                // The entries above 16, their slices behind the narrow ones: one wavefront per (problem, entry), those up
+                // to 32 by the 32-vertex kernel and those above by the 64-vertex one.  (One launch for both would solve an
+                // entry of 24 in 66 KiB of LDS, two wavefronts per CU where the 32-vertex kernel's 17.5 KiB allow nine:
+                // measured, it took longer than the single calls together.)
+                RecruitWideListArgs la{};
+                static_cast<RecruitWideArgs &>(la) = wa;
+                la.lstride = rq.m + 1;
+                const int n32 = (int)(std::upper_bound(m_wide, m_wide + n_wide, (unsigned char)32) - m_wide);
+                Timed t(h, audit ? "audit_multi_wide_solve" : "recruit_multi_wide_solve", work * (double)n_wide);
+                for (int g0 = 0, g1 = n32; g0 < n_wide; g0 = g1, g1 = n_wide) {   // [0, n32), [n32, n_wide)
+                    if (g1 == g0) continue;
+                    la.m = m_wide[g1 - 1];
+                    la.nw = g1 - g0;
+                    memset(la.mw, 0, sizeof(la.mw));
+                    memcpy(la.mw, m_wide + g0, (size_t)la.nw);
+                    la.dist = b.dist.d.p + (size_t)(n_narrow + g0) * (size_t)nq * width;
+                    launch_hull_wide_list(la, s);
+                }
+            } else {
                 Timed t(h, rq.pairs ? (audit ? "audit_pairs_wide_solve" : "recruit_pairs_wide_solve")
                                     : (audit ? "audit_wide_solve" : "recruit_wide_solve"), work);
                 if (rq.witness) launch_hull_wide_witness(wa, s);
                 else launch_hull_wide(wa, s);
             }
             // (a nearest-bins call has no bin / min / margin buffers: the ranking below stands in the reduction's place)
-            if (!rq.pairs && !rq.nearest) launch_recruit_reduce(b.dist.d.p, nq, (int)rq.B, b.bin.d.p, b.min.d.p, b.margin.d.p, s);
+            if (!rq.pairs && !rq.nearest) launch_recruit_reduce(b.dist.d.p, nq * ns, (int)rq.B, b.bin.d.p, b.min.d.p, b.margin.d.p, s);
         } else if (rq.pairs) {   // one launch: the tiles' kernel, no row reduction behind it
             a.tile = b.tile.d.p; a.ntile = b.ntile;
             Timed t(h, audit ? "audit_pairs" : "recruit_pairs", (double)nq);
@@ -3265,6 +3310,37 @@ int chb_recruit_rows_wide(chb_ctx *h, const int64_t *labels, int64_t B, int m, c
     ScoreRequest rq = ScoreRequest::recruit(labels, B, m, Y, Q);
     const char *who = wide_rule(rq, "chb_recruit_rows_wide", "chb_recruit_rows");
     return score_rows(h, who, rq, &D, false, bin_out, dist_out, min_dist_out, margin_out);
+}
+
+namespace {
+// wide_rule for a list: wide only with an entry above 16 in a list the narrow list calls would read that far -- every
+// other list, those they refuse as a bad argument before that (ms null, nm outside 1 .. 16) among them, is the narrow
+// twin's request in everything.  Returns the name the call goes by.
+const char *wide_list_rule(ScoreRequest &rq, const char *wide_name, const char *narrow_name)
+{
+    rq.wide = rq.ms && rq.nm >= 1 && rq.nm <= kMaxM && *std::max_element(rq.ms, rq.ms + rq.nm) > kMaxM;
+    return rq.wide ? wide_name : narrow_name;
+}
+}  // namespace
+
+int chb_audit_rows_multi_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, const int *ms, int nm,
+                              const int64_t *row_idx, int64_t Q, int64_t *bin_out, double *dist_out, double *min_dist_out,
+                              double *margin_out)
+{
+    ScoreRequest rq = ScoreRequest::audit(labels, B, 0, row_idx, Q);
+    rq.ms = ms; rq.nm = nm;
+    rq.groups = groups;   // (null: leave-one-out, the ungrouped kernels)
+    const char *who = wide_list_rule(rq, "chb_audit_rows_multi_wide", groups ? "chb_audit_rows_multi_grouped" : "chb_audit_rows_multi");
+    return score_rows(h, who, rq, nullptr, true, bin_out, dist_out, min_dist_out, margin_out);
+}
+
+int chb_recruit_rows_multi_wide(chb_ctx *h, const int64_t *labels, int64_t B, const int *ms, int nm, const double *Y, int64_t Q,
+                                int64_t D, int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out)
+{
+    ScoreRequest rq = ScoreRequest::recruit(labels, B, 0, Y, Q);
+    rq.ms = ms; rq.nm = nm;
+    const char *who = wide_list_rule(rq, "chb_recruit_rows_multi_wide", "chb_recruit_rows_multi");
+    return score_rows(h, who, rq, &D, true, bin_out, dist_out, min_dist_out, margin_out);
 }
 
 int chb_audit_pairs_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,
@@ -3759,7 +3835,7 @@ static const struct { const char *name; int64_t (*get)(const chb_ctx *); } kHost
     CTR("recruit_chunk", kRecruitChunk),   // rows per launch of chb_recruit_rows
     CTR("recruit_multi_rows", h->score.multi_rows),   // ... of the last chb_audit_rows_multi / chb_recruit_rows_multi
     CTR("pair_tiles", h->score.pair_tiles),   // work items of the last chb_audit_pairs / chb_recruit_pairs
-    CTR("recruit_wide_rows", h->score.wide_rows),   // rows per launch of the last chb_*_wide call with more than 16 neighbours
+    CTR("recruit_wide_rows", h->score.wide_rows),   // rows per launch of the last chb_*_wide call with more than 16 neighbours (a list's: its largest entry)
     // chb_kmer_profiles / chb_set_samples_from_sequences: a chunk's limits, the chunks of the last call
     CTR("kmer_chunk_bytes", kKmerChunkBytes), CTR("kmer_chunk_rows", kKmerChunkRows), CTR("kmer_chunks", h->kmer_chunks),
     CTR("prefilter_enabled", (h->sw.use_prefilter && h->shadow_ok) ? 1 : 0),

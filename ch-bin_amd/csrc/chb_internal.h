@@ -427,9 +427,21 @@ struct RecruitWideWitnessArgs : RecruitWideArgs {
     double *w_d;           // [nq][m]
     double *w_alpha;       // [nq][m]
 };
+// a list of m with entries above 16 (chb_*_rows_multi_wide; dense, a.tile null), one launch of the solve kernel's list
+// form: the selection kernel ran at the list's largest entry and left records of lstride = that entry + 1 ints; mw names
+// the nw entries this launch solves in ascending order -- all of them in 17 .. 32 or all in 33 .. 64, the two solve
+// kernels' ranges --, m is the largest of them, and dist holds one [nq][B] slice per such entry in that order; the grid
+// is (problems, nw), a wavefront per problem and entry.  (The
+// entries travel here: mmask has no bits for them.  Its own struct: the other kernels keep the arguments they have.)
+struct RecruitWideListArgs : RecruitWideArgs {
+    int lstride;
+    int nw;
+    unsigned char mw[kMaxM];
+};
 constexpr long long kWideListBytes = 256ll << 20;   // the list buffer of a dense wide chunk stays within this
 void launch_recruit_select_wide(const RecruitWideArgs &a, hipStream_t s);   // (a.qid / a.memb_grp / a.tile choose the instantiation)
 void launch_hull_wide(const RecruitWideArgs &a, hipStream_t s);             // (m <= 32: 17.5 KiB of static LDS; else 66 KiB dynamic)
+void launch_hull_wide_list(const RecruitWideListArgs &a, hipStream_t s);    // (the same split at a.m, the launch's largest entry)
 void launch_recruit_select_wide_witness(const RecruitWideWitnessArgs &a, hipStream_t s);   // (a.qid / a.memb_grp choose the instantiation)
 void launch_hull_wide_witness(const RecruitWideWitnessArgs &a, hipStream_t s);
 constexpr int kRecruitChunk = 16384;   // rows of Y uploaded (recruit) or positions of row_idx (audit) scored per launch

@@ -12,6 +12,9 @@
 //     tiles of the (NV / 16)^2 grid are computed and then mirrored into LDS, every vertex row and the query row are read
 //     once in 16-byte loads, a missing vertex reads the query row (y = 0).  Then active_set_distance2 on the Wave64
 //     backend (hull_solve64.h), the driver and backend of hull_generic_kernel.
+// The list form of (b) (chb_*_rows_multi_wide, dense only) reads the lists (a) left for the list's largest entry: one
+// wavefront per (problem, entry of the launch) -- the entries in 17 .. 32 with NV = 32, those in 33 .. 64 with NV = 64 --
+// on the first m' ids of the problem's record, one slice of distances per entry.
 // The witness forms of both (chb_*_pairs_witness_wide, pairs only) store m doubles each per pair behind what the plain
 // forms do and nothing before it: (a) every list entry's rooted distance, (b) every lane's weight.
 //
@@ -38,17 +41,26 @@ __device__ __forceinline__ constexpr int wide_tile(int bi, int bj) { return bi *
 
 // the witness forms (chb_*_pairs_witness_wide) take the record buffers behind the plain arguments; the plain forms keep
 // the arguments they have
-template <bool kWitness>
-using wide_args_t = std::conditional_t<kWitness, RecruitWideWitnessArgs, RecruitWideArgs>;
+template <bool kWitness, bool kList = false>
+using wide_args_t = std::conditional_t<kList, RecruitWideListArgs, std::conditional_t<kWitness, RecruitWideWitnessArgs, RecruitWideArgs>>;
 
 // Problem g of the chunk: its list is a.list[g (m + 1) ..], its distance goes to a.dist[g] -- position g of a pair
 // chunk (a.tile set), entry (g / B, g % B) of a dense chunk's [nq][B] table.
 // kWitness (pairs only): lane a < m also stores the weight of vertex a as active_set_distance2 returned it, 0 where the
 // list has no such vertex, to a.w_alpha[g m + a]: one plain vector store per lane behind the solve, nothing before it.
 // The `false` instantiations are unchanged: every place sits behind `if constexpr (kWitness)`.
-template <int NV, bool kWitness = false>
-__global__ __launch_bounds__(64) void hull_wide_kernel(wide_args_t<kWitness> a, int nprob)
+// kList (chb_*_rows_multi_wide, dense only): block (g, i) is problem g at the launch's entry i, m' = a.mw[i].  The list
+// buffer holds records of a.lstride ints, written by the selection at the list's largest entry; the m' nearest are the
+// record's first m' ids, so the block does what the single call's does at m = m' -- the same Gram of min(length, m')
+// vertices, the same solve -- and stores its distance in slice i: a.dist[i nq B + g].  A launch holds entries of one
+// kernel only (NV = 32: 17 .. 32, NV = 64: 33 .. 64; the host launches each group it has), so the bits are
+// hull_wide_kernel<NV>'s at m = m'.  (Forming a problem's Gram once and solving its entries in a loop was measured and
+// lost: with the solver one loop deeper the compiler no longer unrolls its loops over the LDS rows, and the solve
+// alone took 1.4 x the single call's.)
+template <int NV, bool kWitness = false, bool kList = false>
+__global__ __launch_bounds__(64) void hull_wide_kernel(wide_args_t<kWitness, kList> a, int nprob)
 {
+    static_assert(!(kWitness && kList), "witnesses travel with the pair calls, lists with the dense ones");
     constexpr int NB = NV / 16, NT = NB * (NB + 1) / 2;
     using Lds = GenLdsT<NV>;
     Lds *Lp;
@@ -63,11 +75,17 @@ __global__ __launch_bounds__(64) void hull_wide_kernel(wide_args_t<kWitness> a, 
     const int lane = threadIdx.x;
     const int g = blockIdx.x;
     if (g >= nprob) return;
-    const int m = a.m;
-    const int *lst = a.list + (size_t)g * (size_t)(m + 1);
+    int m = a.m;
+    const int *lst;
+    double *dst = a.dist;
+    if constexpr (kList) {
+        m = a.mw[blockIdx.y];
+        lst = a.list + (size_t)g * (size_t)a.lstride;
+        dst += (size_t)blockIdx.y * ((size_t)a.nq * (size_t)a.B);
+    } else lst = a.list + (size_t)g * (size_t)(m + 1);
     const int n = min(lst[0], min(m, NV));   // (never more than the capacity, whatever the buffer holds)
     if (n <= 0) {
-        if (lane == 0) a.dist[g] = kInf;
+        if (lane == 0) dst[g] = kInf;
         if constexpr (kWitness) {
             if (lane < m) a.w_alpha[(size_t)g * (size_t)m + lane] = 0.0;   // (no vertex: the record's padding)
         }
@@ -160,7 +178,7 @@ __global__ __launch_bounds__(64) void hull_wide_kernel(wide_args_t<kWitness> a, 
     w.scale = scale; w.diag = diag;
     double alpha = 0.0;
     const double val = active_set_distance2(w, n, a.metric, scale, alpha);
-    if (lane == 0) a.dist[g] = sqrt(fmax(val, 0.0));
+    if (lane == 0) dst[g] = sqrt(fmax(val, 0.0));
     if constexpr (kWitness) {
         if (lane < m) a.w_alpha[(size_t)g * (size_t)m + lane] = mine ? alpha : 0.0;
     }
@@ -437,6 +455,20 @@ void launch_hull_wide(const RecruitWideArgs &a, hipStream_t s)
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(hull_wide_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)sizeof(GenLdsT<64>));
     hipLaunchKernelGGL((hull_wide_kernel<64>), dim3((unsigned)nprob), dim3(64), sizeof(GenLdsT<64>), s, a, (int)nprob);
+}
+
+// the list form: one wavefront per (problem of a dense chunk, entry of the launch), a.nw slices of a.dist written here
+void launch_hull_wide_list(const RecruitWideListArgs &a, hipStream_t s)
+{
+    const long long nprob = (long long)a.nq * (long long)a.B;
+    if (nprob <= 0 || a.nw <= 0) return;
+    if (a.m <= 32) {
+        hipLaunchKernelGGL((hull_wide_kernel<32, false, true>), dim3((unsigned)nprob, (unsigned)a.nw), dim3(64), 0, s, a, (int)nprob);
+        return;
+    }
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(hull_wide_kernel<64, false, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(GenLdsT<64>));
+    hipLaunchKernelGGL((hull_wide_kernel<64, false, true>), dim3((unsigned)nprob, (unsigned)a.nw), dim3(64), sizeof(GenLdsT<64>), s, a, (int)nprob);
 }
 
 // the witness form: one wavefront per position of a pair chunk, a.w_alpha written here

@@ -458,6 +458,40 @@ int chb_recruit_pairs_witness_wide(chb_ctx *h, const int64_t *labels, int64_t B,
                                    const int64_t *row_of, const int64_t *bin_idx, int64_t P,
                                    double *dist_out, int64_t *nbr_idx, double *nbr_dist, double *alpha);
 
+/* The neighbour sweep for lists with entries up to CHB_MAX_NEIGHBORS = 64: chb_audit_rows_multi / chb_recruit_rows_multi
+ * for a list whose entries need not stop at 16, e.g. (5, 15, 24, 32, 64) around a labelling fitted at m = 24 -- one
+ * wide selection pass serves every entry above 16 (and the list calls' one pass those up to 16); only the hull solves
+ * repeat.
+ *   - outputs: m-major and in the order of ms[], as chb_audit_rows_multi's.  Slice j of each is BIT FOR BIT what
+ *     chb_audit_rows_wide(..., groups, ..., ms[j], ...) / chb_recruit_rows_wide(..., ms[j], ...) returns on the same
+ *     other arguments and metric, +inf included (and so, for ms[j] <= 16, chb_audit_rows / _grouped / chb_recruit_rows).
+ *   - max(ms) <= 16, and every list the existing list calls refuse as a bad argument: the call forwards to
+ *     chb_audit_rows_multi (groups == NULL), chb_audit_rows_multi_grouped or chb_recruit_rows_multi.  Result, return
+ *     code, error text and counters ("recruit_multi_rows") are those calls'.
+ *   - max(ms) > 16: entries up to 16 and above may be mixed, in any order.
+ *   - checks, in the list calls' order, all before anything is enqueued: Q < 0 or B < 1; ms NULL; nm outside 1 .. 16; an
+ *     entry < 1; a repeated entry (among 1 .. 64) (all CHB_EINVAL); null arguments; outputs (bin_out and dist_out both
+ *     NULL); no resident samples (CHB_ESTATE); D; max(ms) > 64, then max(ms) > 32 on a device that does not grant the
+ *     66 KiB of LDS per workgroup (CHB_EUNSUPPORTED); B > 8192 (CHB_EUNSUPPORTED); an open stepwise fit (CHB_ESTATE,
+ *     the fit stays usable); Q = 0 (CHB_OK); the row_idx rules.  A refused call writes nothing.
+ *   - per chunk: the entries up to 16, if any, by the list calls' kernel ("audit_multi" / "recruit_multi", work units =
+ *     (row, bin, m) triples over those entries); the wide selection once at max(ms) ("audit_multi_wide_select" /
+ *     "recruit_multi_wide_select", work units = (row, bin) problems, max(ms) + 1 int32 per problem in the list buffer);
+ *     one wavefront per (row, bin, entry above 16) that reads the first m' ids of the problem's list and does what the
+ *     single call's wavefront does at m = m' ("..._multi_wide_solve", work units = those triples; the entries 17 .. 32 on
+ *     the 32-vertex kernel and the entries 33 .. 64 on the 64-vertex kernel, one launch for each group the list has, both
+ *     booked as one); the row reduction over all nm slices.  (A problem's Gram matrix is formed per entry, not once: the
+ *     in-kernel loop over the entries that sharing it needs was measured and cost more than it saved, see DESIGN.md.)
+ *   - rows per chunk: min(the wide calls' figure for max(ms), max(64, 16384 / nm rounded down to a multiple of 64)):
+ *     chb_counter "recruit_wide_rows".  Otherwise the call uses no state of a fit and leaves every counter, memo and
+ *     switch of the context as it found it; no collective. */
+int chb_audit_rows_multi_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups /* may be NULL */, int64_t B,
+                              const int *ms, int nm, const int64_t *row_idx, int64_t Q,
+                              int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out);
+int chb_recruit_rows_multi_wide(chb_ctx *h, const int64_t *labels, int64_t B, const int *ms, int nm,
+                                const double *Y, int64_t Q, int64_t D,
+                                int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out);
+
 /* distance_matrix.py:47-62 find_nearest_from_cluster with the reference's exact signature: the
  * caller supplies one row of a distance matrix (any provenance) and the current labels; selects
  * among {p : labels[p] == c} the (up to) m smallest by (row[p], p).  out_idx[m] (-1 padded). */
@@ -626,7 +660,10 @@ int chb_profile_reset(chb_ctx *h);
  * (chb_audit_rows_nearest / chb_recruit_rows_nearest: the launch that ranks one chunk's rows x B table, behind the dense
  * kernel booked under "audit" / "recruit"; work units = (row, bin) pairs) | "audit_wide_select" / "audit_wide_solve" and their
  * "recruit_" / "_pairs_" counterparts (the chb_*_wide calls with m > 16: a chunk's selection and hull launches; work units =
- * (row, bin) problems).  For m <= 16 "hull_qp" is the fused selection + hull-distance kernel and
+ * (row, bin) problems) | "audit_multi_wide_select" / "audit_multi_wide_solve" and their "recruit_" counterparts
+ * (chb_audit_rows_multi_wide / chb_recruit_rows_multi_wide with an entry above 16: a chunk's one selection launch, work
+ * units = (row, bin) problems, and its list solve launch, work units = (row, bin, entry above 16) triples; the entries up
+ * to 16 are booked under "audit_multi" / "recruit_multi").  For m <= 16 "hull_qp" is the fused selection + hull-distance kernel and
  * "slow_path" the exact path for what it leaves over; "rescore*" then only appear for m > 16 or CHB_FUSED=0. */
 int chb_profile_get(chb_ctx *h, const char *kernel, double *total_ms, int64_t *launches,
                     double *work_units);
@@ -660,7 +697,8 @@ int chb_fit_stats(chb_ctx *h, int64_t *out4);
  * "recruit_multi_rows" (rows per launch of the last chb_audit_rows_multi / chb_recruit_rows_multi call: 16384 / nm rounded
  * down to a multiple of 64; 0 before the first), "pair_tiles" (tiles of at most 64 pairs of one bin -- the kernel's work
  * items -- of the last chb_audit_pairs / chb_recruit_pairs call that had pairs; 0 before the first),
- * "recruit_wide_rows" (rows per launch of the last chb_*_wide call with m > 16: see there; 0 before the first),
+ * "recruit_wide_rows" (rows per launch of the last chb_*_wide call with m > 16, a chb_*_rows_multi_wide call with an
+ * entry above 16 among them: see there; 0 before the first),
  * "kmer_chunk_bytes" / "kmer_chunk_rows" (the most bases / contigs of one sequence chunk of chb_kmer_profiles and
  * chb_set_samples_from_sequences: constants), "kmer_chunks" (chunks of the last such call), "lane_exchange_mismatches" (for
  * tests: one small launch compares the hull kernels' in-register exchanges of a 16-lane group, and the Gram reduction
