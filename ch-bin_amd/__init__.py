@@ -8,13 +8,13 @@ HIP library or a GPU is missing.
 from . import synth  # noqa: F401
 
 __all__ = ["synth", "recruit", "audit", "bin_report", "neighbor_sweep", "neighbor_sweep_wide", "audit_pairs", "recruit_pairs",
-           "cohesion"]
+           "cohesion", "audit_pairs_sweep", "recruit_pairs_sweep", "cohesion_sweep"]
 
 
 def __getattr__(name):
     # chbin_amd.recruit = clustering.recruit, chbin_amd.audit = clustering.audit, chbin_amd.bin_report =
     # clustering.bin_report, chbin_amd.neighbor_sweep = clustering.neighbor_sweep, and audit_pairs / recruit_pairs /
-    # cohesion likewise, resolved on first use (importing the package stays free of ctypes work)
+    # cohesion and their _sweep forms likewise, resolved on first use (importing the package stays free of ctypes work)
     if name == "recruit":
         from .clustering import recruit
         return recruit
@@ -27,7 +27,8 @@ def __getattr__(name):
     if name == "neighbor_sweep":
         from .clustering import neighbor_sweep
         return neighbor_sweep
-    if name in ("audit_pairs", "recruit_pairs", "cohesion", "neighbor_sweep_wide"):
+    if name in ("audit_pairs", "recruit_pairs", "cohesion", "neighbor_sweep_wide", "audit_pairs_sweep", "recruit_pairs_sweep",
+                "cohesion_sweep"):
         from . import clustering
         return getattr(clustering, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -101,6 +101,11 @@ SIGNATURES = {
                                             C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "chb_recruit_rows_multi_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
                                               C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the pair calls for a list with entries up to 64: ms / nm in m's place, dist_out [nm, P] (groups may be NULL)
+    "chb_audit_pairs_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_int64, C.c_void_p]),
+    "chb_recruit_pairs_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "chb_find_nearest_from_row": (C.c_int, [C.c_void_p, C.c_int64, _i64p, _f64p, C.c_int64, C.c_int,
                                             _i64p, C.POINTER(C.c_int32)]),
     "chb_hull_distance_batch": (C.c_int, [C.c_void_p, _i64p, C.c_int64, _i64p, C.c_int, _f64p,
@@ -406,24 +411,36 @@ class Context:
             raise ValueError(f"{rows_name} and bins must have one entry per pair: {rows.shape[0]} and {bins.shape[0]}")
         return rows, bins
 
-    def _score_pairs(self, symbol, labels, B, m, rows, bins, Y=None, groups=None, slot=False, idx=None, witness=False):
+    def _score_pairs(self, symbol, labels, B, m, rows, bins, Y=None, groups=None, slot=False, idx=None, witness=False,
+                     ms=None):
         """The pair calls: `symbol` for the pairs (rows[p], bins[p]) of resident rows or, with Y, of rows of Y (`rows` is
         then row_of); with `groups` the audit's leave-group-out form (_frozen).  Returns dist [P]; for a symbol with an
         idx_out (`idx` not None: whether it is wanted, else it is passed NULL) dist or (dist, idx [P, m]); for a `witness`
-        symbol (dist, neighbors, neighbor_dist, weights), the last three [P, m].
+        symbol (dist, neighbors, neighbor_dist, weights), the last three [P, m]; with a list `ms` in m's place, a _multi
+        symbol, dist [len(ms), P].
         (A refused call writes nothing: the [P, m] arrays take m as given, at least 0.)"""
         rows, bins = self._pair_lists(rows, bins, "rows" if Y is None else "row_of")
+        if ms is not None:
+            ms = np.ascontiguousarray(ms, dtype=np.intc)
+            if ms.ndim != 1:
+                raise ValueError("ms must be a 1-D list of neighbour counts")
         if Y is not None:
             Y = self._new_rows(Y)
         fn, head = self._frozen(symbol, labels, groups, slot)
-        P, m_out = rows.shape[0], max(int(m), 0)
+        P = rows.shape[0]
+        source = () if Y is None else (Y.ctypes.data, *Y.shape)
+        if ms is not None:
+            out = np.empty(ms.shape + (P,), dtype=np.float64)
+            check(fn(self._h, *map(self._ptr, head), int(B), ms.ctypes.data, ms.shape[0], *source, rows.ctypes.data,
+                     bins.ctypes.data, P, out.ctypes.data))
+            return out
+        m_out = max(int(m), 0)
         out = [np.empty(P, dtype=np.float64)]
         if witness:
             out += [np.empty((P, m_out), dtype=np.int64), np.empty((P, m_out), dtype=np.float64),
                     np.empty((P, m_out), dtype=np.float64)]
         elif idx is not None:
             out.append(np.empty((P, m_out), dtype=np.int64) if idx else None)
-        source = () if Y is None else (Y.ctypes.data, *Y.shape)
         check(fn(self._h, *map(self._ptr, head), int(B), int(m), *source, rows.ctypes.data, bins.ctypes.data, P,
                  *map(self._ptr, out)))
         return tuple(out) if witness or idx else out[0]
@@ -499,6 +516,17 @@ class Context:
         """chb_recruit_pairs_wide: recruit_pairs for any m in 1 .. 64; entry p is bit for bit
         recruit_rows_wide(labels, B, m, Y)[1][row_of[p], bins[p]].  Returns dist [P] or, with want_idx, (dist, idx [P, m])."""
         return self._score_pairs("chb_recruit_pairs_wide", labels, B, m, row_of, bins, Y=Y, idx=bool(want_idx))
+
+    def audit_pairs_multi(self, labels, B, ms, rows, bins, groups=None):
+        """chb_audit_pairs_multi: audit_pairs_wide for every m of the list `ms` (distinct values in 1 .. 64, at most 16 of
+        them, any order, entries up to 16 and above mixed) from one selection pass per kernel; row j of the result is bit
+        for bit audit_pairs_wide(labels, B, ms[j], rows, bins, groups=groups).  Returns dist [nm, P]."""
+        return self._score_pairs("chb_audit_pairs_multi", labels, B, None, rows, bins, groups=groups, slot=True, ms=ms)
+
+    def recruit_pairs_multi(self, labels, B, ms, Y, row_of, bins):
+        """chb_recruit_pairs_multi: recruit_pairs_wide for every m of the list `ms` (entries up to 64); row j of the result
+        is bit for bit recruit_pairs_wide(labels, B, ms[j], Y, row_of, bins).  Returns dist [nm, P]."""
+        return self._score_pairs("chb_recruit_pairs_multi", labels, B, None, row_of, bins, Y=Y, ms=ms)
 
     def audit_rows_nearest_wide(self, labels, B, m, k, rows=None, groups=None):
         """chb_audit_rows_nearest_wide: audit_rows_nearest for any m in 1 .. 64 -- m <= 16 forwards to it bit for bit,

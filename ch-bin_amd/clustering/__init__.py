@@ -7,8 +7,10 @@ from .algorithm import (  # noqa: F401
     Witness,
     audit,
     audit_pairs,
+    audit_pairs_sweep,
     bin_report,
     cohesion,
+    cohesion_sweep,
     fit_cluster,
     nearest_bins,
     neighbor_sweep,
@@ -17,6 +19,7 @@ from .algorithm import (  # noqa: F401
     recruit,
     recruit_nearest_bins,
     recruit_pairs,
+    recruit_pairs_sweep,
     recruit_witness,
     witness,
 )

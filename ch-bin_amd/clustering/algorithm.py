@@ -387,6 +387,78 @@ def cohesion(
     return out
 
 
+def audit_pairs_sweep(
+    samples: np.ndarray,
+    labels: np.ndarray,
+    rows: np.ndarray,
+    bins: np.ndarray,
+    num_clusters: int,
+    neighbors=(1, 3, 5, 10, 15),
+    metric: str = "convex",
+    qp_solver: str = "quadprog",
+    groups: np.ndarray = None,
+) -> np.ndarray:
+    """`audit_pairs` for every entry of `neighbors` (distinct values in 1 .. 64, at most 16 of them, any order, entries up
+    to 16 and above mixed) at the cost of little more than the call at the largest: the listed bins' members are streamed
+    once for the whole list, and row j is bit for bit `audit_pairs(..., num_neighbors=neighbors[j])`.  The sweep over each
+    row's nearest bins only (`NearestBins.pairs`), where `neighbor_sweep`'s dense table is num_clusters times the work.
+    Nothing changes.  With `groups` every entry is `audit_pairs(..., groups=groups)`.
+
+    Returns distances [len(neighbors), len(rows)]."""
+    with _resident(samples, metric, qp_solver) as ctx:
+        neighbors = np.ascontiguousarray(neighbors, dtype=np.int64)
+        return ctx.audit_pairs_multi(labels, int(num_clusters), neighbors, rows, bins, groups=groups)
+
+
+def recruit_pairs_sweep(
+    samples: np.ndarray,
+    labels: np.ndarray,
+    new_rows: np.ndarray,
+    row_of: np.ndarray,
+    bins: np.ndarray,
+    num_clusters: int,
+    neighbors=(1, 3, 5, 10, 15),
+    metric: str = "convex",
+    qp_solver: str = "quadprog",
+) -> np.ndarray:
+    """`audit_pairs_sweep` for rows that are NOT samples: row j is bit for bit
+    `recruit_pairs(..., num_neighbors=neighbors[j])`.  Nothing is withheld and nothing changes.
+
+    Returns distances [len(neighbors), len(row_of)]."""
+    with _resident(samples, metric, qp_solver) as ctx:
+        new_rows = np.ascontiguousarray(new_rows, dtype=np.float64)
+        neighbors = np.ascontiguousarray(neighbors, dtype=np.int64)
+        return ctx.recruit_pairs_multi(labels, int(num_clusters), neighbors, new_rows, row_of, bins)
+
+
+def cohesion_sweep(
+    samples: np.ndarray,
+    labels: np.ndarray,
+    num_clusters: int,
+    neighbors=(1, 3, 5, 10, 15),
+    metric: str = "convex",
+    qp_solver: str = "quadprog",
+    rows: np.ndarray = None,
+    groups: np.ndarray = None,
+) -> np.ndarray:
+    """`cohesion` for every entry of `neighbors` (distinct values in 1 .. 64, at most 16 of them, any order): how well every
+    contig sits in its own bin at each number of neighbours, the cheap instrument for choosing one (the reference's
+    configuration says 5, its function default 15) -- one call that streams every bin's members once instead of one
+    `cohesion` per entry.  Row j is bit for bit `cohesion(..., num_neighbors=neighbors[j])`; the columns of rows without a
+    label in [0, num_clusters) are NaN.  Nothing changes.  With `groups` every entry is leave-group-out.
+
+    Returns distances [len(neighbors), len(rows)]."""
+    with _resident(samples, metric, qp_solver) as ctx:
+        labels = np.ascontiguousarray(labels, dtype=np.int64)
+        neighbors = np.ascontiguousarray(neighbors, dtype=np.int64)
+        rows = np.arange(np.shape(samples)[0], dtype=np.int64) if rows is None else np.ascontiguousarray(rows, dtype=np.int64)
+        own = labels[rows]
+        scored = (own >= 0) & (own < int(num_clusters))
+        out = np.full((neighbors.shape[0], rows.shape[0]), np.nan)
+        out[:, scored] = ctx.audit_pairs_multi(labels, int(num_clusters), neighbors, rows[scored], own[scored], groups=groups)
+    return out
+
+
 @dataclasses.dataclass
 class Witness:
     """What `witness` / `recruit_witness` return: per scored (row, bin) pair the hull its distance was measured to.
@@ -520,7 +592,8 @@ class NearestBins:
         """(positions, bins): the real entries of the slots `ranks` of the rows `mask` selects (bool [n]; None: all), row
         by row -- the two lists `audit_pairs` / `witness` take once positions are turned into sample indices
         (rows[positions]; positions themselves for rows=None), and `recruit_pairs` / `recruit_witness` take as they are
-        (row_of = positions)."""
+        (row_of = positions).  `audit_pairs_sweep` / `recruit_pairs_sweep` take the same two lists with a list of
+        num_neighbors: the way to sweep only a row's nearest bins instead of `neighbor_sweep`'s every bin."""
         ranks = np.asarray(ranks, dtype=np.int64).reshape(-1)
         take = self.bins[:, ranks] >= 0
         if mask is not None:

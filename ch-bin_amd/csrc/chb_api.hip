@@ -2578,7 +2578,8 @@ struct ScoreRequest {
     // (without a destination: neither downloaded nor unpacked)
     int64_t *bin_out = nullptr; double *dist_out = nullptr, *min_dist_out = nullptr, *margin_out = nullptr;
     // chb_*_pairs: Q pairs (row, bin) in place of the grid, the rows resident or (Y set) rows of Y; dist_out is [Q], one
-    // double per pair in the caller's order, and there is no row reduction
+    // double per pair in the caller's order, and there is no row reduction.  With a list (nm > 0: chb_*_pairs_multi)
+    // dist_out is [nm][Q], slice j the pair call's answer at ms[j]; the plan and its chunks are the single call's
     const PairPlan *pairs = nullptr;
     // chb_*_grouped: one group id per resident sample, negative = no group; besides the scored row every sample of its
     // group is withheld (leave-group-out).  grouped marks the call, whose groups must not be null
@@ -2765,10 +2766,12 @@ struct ScoreRun {
     {
         const int64_t B = rq.B;
         const int64_t list_rows = rq.nm > 0 ? std::max<int64_t>(kQTile, kRecruitChunk / rq.nm / kQTile * kQTile) : 0;
-        if (rq.nm > 0 && !rq.wide) sc.multi_rows = list_rows;
+        // (a list of pairs, chb_*_pairs_multi: the pair plan's chunks as they are -- nm doubles per pair are at most 2 MiB --
+        // and of the counters only what the single pair call at its largest entry sets)
+        if (rq.nm > 0 && !rq.wide && !rq.pairs) sc.multi_rows = list_rows;
         if (rq.wide) sc.wide_rows = wide_chunk_rows((int64_t)width, rq.m);
         // (a wide list: both bounds -- the lists of its largest entry within the list buffer, its nm slices within a chunk's)
-        if (rq.wide && rq.nm > 0) sc.wide_rows = std::min(sc.wide_rows, list_rows);
+        if (rq.wide && rq.nm > 0 && !rq.pairs) sc.wide_rows = std::min(sc.wide_rows, list_rows);
         // (a wide plan: cut at wide_rows by its builder, so its longest chunk is what the buffers must hold)
         chunk = rq.pairs ? rq.pairs->max_rows : rq.plan && rq.wide ? rq.plan->max_rows
               : std::min<int64_t>(rq.Q, rq.wide ? sc.wide_rows : rq.nm > 0 ? sc.multi_rows : kRecruitChunk);
@@ -2958,12 +2961,16 @@ struct ScoreRun {
             if (wlist && n_narrow > 0) {   // the entries up to 16: recruit_kernel's list launch, their slices in front
                 RecruitGroupArgs na = a;
                 na.m = m_narrow;
-                Timed t(h, audit ? "audit_multi" : "recruit_multi", work * (double)n_narrow);
+                na.tile = wa.tile; na.ntile = wa.ntile;   // (a pair chunk: the tile table's work items)
+                Timed t(h, rq.pairs ? (audit ? "audit_pairs_multi" : "recruit_pairs_multi") : (audit ? "audit_multi" : "recruit_multi"),
+                        work * (double)n_narrow);
                 if (na.memb_grp) launch_recruit_grouped(na, s);
+                else if (rq.pairs) launch_recruit_pairs(na, s);
                 else launch_recruit(na, s);
             }
             {
-                Timed t(h, wlist ? (audit ? "audit_multi_wide_select" : "recruit_multi_wide_select")
+                Timed t(h, wlist ? (rq.pairs ? (audit ? "audit_pairs_multi_wide_select" : "recruit_pairs_multi_wide_select")
+                                             : (audit ? "audit_multi_wide_select" : "recruit_multi_wide_select"))
                         : rq.pairs ? (audit ? "audit_pairs_wide_select" : "recruit_pairs_wide_select")
                                    : (audit ? "audit_wide_select" : "recruit_wide_select"), work);
                 if (rq.witness) launch_recruit_select_wide_witness(wa, s);
@@ -2977,8 +2984,10 @@ struct ScoreRun {
                 RecruitWideListArgs la{};
                 static_cast<RecruitWideArgs &>(la) = wa;
                 la.lstride = rq.m + 1;
+                if (rq.pairs) la.B = 1;   // (a pair chunk: nq problems, and a slice is the chunk's pairs)
                 const int n32 = (int)(std::upper_bound(m_wide, m_wide + n_wide, (unsigned char)32) - m_wide);
-                Timed t(h, audit ? "audit_multi_wide_solve" : "recruit_multi_wide_solve", work * (double)n_wide);
+                Timed t(h, rq.pairs ? (audit ? "audit_pairs_multi_wide_solve" : "recruit_pairs_multi_wide_solve")
+                                    : (audit ? "audit_multi_wide_solve" : "recruit_multi_wide_solve"), work * (double)n_wide);
                 for (int g0 = 0, g1 = n32; g0 < n_wide; g0 = g1, g1 = n_wide) {   // [0, n32), [n32, n_wide)
                     if (g1 == g0) continue;
                     la.m = m_wide[g1 - 1];
@@ -2998,7 +3007,9 @@ struct ScoreRun {
             if (!rq.pairs && !rq.nearest) launch_recruit_reduce(b.dist.d.p, nq * ns, (int)rq.B, b.bin.d.p, b.min.d.p, b.margin.d.p, s);
         } else if (rq.pairs) {   // one launch: the tiles' kernel, no row reduction behind it
             a.tile = b.tile.d.p; a.ntile = b.ntile;
-            Timed t(h, audit ? "audit_pairs" : "recruit_pairs", (double)nq);
+            // (a list, chb_*_pairs_multi without an entry above 16: a.mmask selects the kernel's list form)
+            Timed t(h, a.mmask ? (audit ? "audit_pairs_multi" : "recruit_pairs_multi") : (audit ? "audit_pairs" : "recruit_pairs"),
+                    (double)nq * (double)ns);
             if (rq.witness) {
                 a.w_id = b.wid.d.p; a.w_d = b.wd.d.p; a.w_alpha = b.walpha.d.p;
                 launch_recruit_witness(a, s);
@@ -3055,8 +3066,12 @@ struct ScoreRun {
         HIPTRY(hipEventSynchronize(b.down));
         if (rq.pairs) {
             const int64_t *ord = rq.pairs->ord.data() + t0;
-            if (rq.dist_out)
-                for (int i = 0; i < nq; ++i) rq.dist_out[ord[i]] = b.dist.h.p[i];
+            // (a list: slice slot[j] of the chunk's nq positions goes to the caller's slice j of Q pairs)
+            for (int j = 0; j < ns && rq.dist_out; ++j) {
+                const double *from = b.dist.h.p + (size_t)slot[j] * (size_t)nq;
+                double *to = rq.dist_out + (size_t)j * (size_t)rq.Q;
+                for (int i = 0; i < nq; ++i) to[ord[i]] = from[i];
+            }
             const size_t m = (size_t)rq.m;
             for (int i = 0; i < nq && rq.idx_out; ++i)   // (the record's first int is the list's length; the ids are padded already)
                 for (size_t v = 0; v < m; ++v) rq.idx_out[(size_t)ord[i] * m + v] = b.wlist.h.p[(size_t)i * (m + 1) + 1 + v];
@@ -3138,10 +3153,13 @@ void witness_outputs(ScoreRequest &rq, int64_t *nbr_idx, double *nbr_dist, doubl
 // The pair calls, whole: rq.Q pairs (row, bin_idx), the rows resident (rq.row_idx, which is not "all rows" here: its range
 // is checked like chb_audit_rows' list) or, in the recruit forms, rows row_of of the Y_rows rows of Y, D columns each.
 // Behind score_check_args the recruit forms' own checks, then the bins' range, the plan and the run.
+// list (chb_*_pairs_multi): the call takes ms / nm -- the list calls' checks in score_check_args, the number of rows of Y
+// among its ranges -- and dist_out is [nm][P].
 int score_pairs(chb_ctx *h, const char *who, ScoreRequest &rq, const int64_t *bin_idx, const int64_t *D = nullptr,
-                int64_t Y_rows = 0, const int64_t *row_of = nullptr)
+                int64_t Y_rows = 0, const int64_t *row_of = nullptr, bool list = false)
 {
     const int64_t P = rq.Q, *row = D ? row_of : rq.row_idx;
+    if (h && list && D && Y_rows < 0) return fail(CHB_EINVAL, "Q < 0");
     // null arguments: the lists, then dist_out -- which a witness call may leave out, but not with every witness output
     const char *missing = nullptr;
     if (P > 0 && rq.witness) {
@@ -3151,7 +3169,7 @@ int score_pairs(chb_ctx *h, const char *who, ScoreRequest &rq, const int64_t *bi
     } else if (P > 0 && (!row || !bin_idx || !rq.dist_out)) {
         missing = D ? "row_of, bin_idx or dist_out is null" : "row_idx, bin_idx or dist_out is null";
     }
-    const int rc = score_check_args(h, who, rq, D, false, missing);
+    const int rc = score_check_args(h, who, rq, D, list, missing);
     if (rc != CHB_OK) return rc;
     if (D) {
         if (Y_rows < 0) return fail(CHB_EINVAL, "Q < 0");
@@ -3341,6 +3359,28 @@ int chb_recruit_rows_multi_wide(chb_ctx *h, const int64_t *labels, int64_t B, co
     rq.ms = ms; rq.nm = nm;
     const char *who = wide_list_rule(rq, "chb_recruit_rows_multi_wide", "chb_recruit_rows_multi");
     return score_rows(h, who, rq, &D, true, bin_out, dist_out, min_dist_out, margin_out);
+}
+
+// The pair calls for a list: one symbol for every entry up to 64 and one name in the texts -- there is no narrow twin to
+// forward to.  wide_list_rule only says whether an entry above 16 brings the wide kernels in.
+int chb_audit_pairs_multi(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, const int *ms, int nm,
+                          const int64_t *row_idx, const int64_t *bin_idx, int64_t P, double *dist_out)
+{
+    ScoreRequest rq = ScoreRequest::audit(labels, B, 0, row_idx, P);
+    rq.ms = ms; rq.nm = nm;
+    rq.dist_out = dist_out; rq.groups = groups;   // (null: leave-one-out, the ungrouped kernels)
+    const char *who = wide_list_rule(rq, "chb_audit_pairs_multi", "chb_audit_pairs_multi");
+    return score_pairs(h, who, rq, bin_idx, nullptr, 0, nullptr, true);
+}
+
+int chb_recruit_pairs_multi(chb_ctx *h, const int64_t *labels, int64_t B, const int *ms, int nm, const double *Y, int64_t Q,
+                            int64_t D, const int64_t *row_of, const int64_t *bin_idx, int64_t P, double *dist_out)
+{
+    ScoreRequest rq = ScoreRequest::recruit(labels, B, 0, Y, P);
+    rq.ms = ms; rq.nm = nm;
+    rq.dist_out = dist_out;
+    const char *who = wide_list_rule(rq, "chb_recruit_pairs_multi", "chb_recruit_pairs_multi");
+    return score_pairs(h, who, rq, bin_idx, &D, Q, row_of, true);
 }
 
 int chb_audit_pairs_wide(chb_ctx *h, const int64_t *labels, const int64_t *groups, int64_t B, int m, const int64_t *row_idx,

@@ -389,6 +389,8 @@ struct RecruitArgs {
 // a list of (row, bin) pairs in place of the dense grid (chb_audit_pairs / chb_recruit_pairs): the chunk's nq positions are
 // grouped by bin and every bin's run is cut into tiles of at most kQTile positions; tile[t] = {bin, first position in the
 // chunk, positions, 0}.  Y / qid name the pairs' rows in position order, dist holds one double per position, mmask is 0.
+// With a list of m (chb_*_pairs_multi: mmask set, m its largest entry up to 16) dist holds one slice of nq doubles per
+// entry, [popcount(mmask)][nq] in ascending order of m'.
 // (Its own struct: the dense kernels keep the kernel arguments they have.)
 struct RecruitPairArgs : RecruitArgs {
     const int4 *tile;      // [ntile]
@@ -433,6 +435,8 @@ struct RecruitWideWitnessArgs : RecruitWideArgs {
 // kernels' ranges --, m is the largest of them, and dist holds one [nq][B] slice per such entry in that order; the grid
 // is (problems, nw), a wavefront per problem and entry.  (The
 // entries travel here: mmask has no bits for them.  Its own struct: the other kernels keep the arguments they have.)
+// A pair chunk (chb_*_pairs_multi; a.tile set) is the same launch with B = 1: nq problems, problem g is position g, and
+// the slice stride nq x B is the chunk's pairs -- the kernel's `a.tile ? g : g / a.B` and its stride need nothing else.
 struct RecruitWideListArgs : RecruitWideArgs {
     int lstride;
     int nw;

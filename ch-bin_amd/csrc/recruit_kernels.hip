@@ -28,7 +28,8 @@
 //
 // chb_audit_pairs / chb_recruit_pairs run the same kernel body on a LIST of (row, bin) pairs (template parameter kPairs):
 // the work items come from a tile table the host cut from the pairs in bin order, and a pair's one distance is stored at
-// its position; there is no reduction kernel behind it.
+// its position; there is no reduction kernel behind it.  chb_audit_pairs_multi / chb_recruit_pairs_multi serve a list of m
+// up to 16 from the same work items (kMulti and kPairs together): one slice of the chunk's positions per entry.
 //
 // The chb_*_grouped calls run the resident instantiations with one more exclusion (template parameter kGrouped): besides
 // the row itself every sample that shares the row's group id -- the sibling pieces of one parent contig -- is withheld.
@@ -92,8 +93,14 @@ union RecruitLds {
 // chunk's tile table a.tile = {bin, first position in the chunk, positions}, rows of the tile at or past `positions`
 // score nothing, and the one double of a position goes to a.dist[position].  Nothing else differs from the single-m
 // kernel -- the staged rows of a short tile's tail are the next tile's (or the chunk's last), read and never offered --
-// so a pair's distance has the bits of the dense call's entry.  The `false` instantiations are unchanged: the three
-// places sit behind `if constexpr (kPairs)`.  There is no list of m for pairs.
+// so a pair's distance has the bits of the dense call's entry.  The `false` instantiations are unchanged: the
+// places sit behind `if constexpr (kPairs)`.
+//
+// kMulti && kPairs (chb_audit_pairs_multi / chb_recruit_pairs_multi, the entries up to 16): the work items of the tile
+// table, the list's phase 2 as it is, and one double per (entry, position) -- slice j of a.dist is the chunk's a.nq
+// positions, a.dist[j * a.nq + position], stored for the tile's counted rows as in the pair form.  A position's list is
+// the single pair launch's at a.m, its first m' entries that launch's at m', so slice j has the bits of the pair kernel at
+// the list's j-th smallest entry.
 //
 // kGrouped (chb_*_grouped, resident rows only): leave-group-out.  Every sample carries a dense int32 group id, negative
 // for a sample without a group; besides the row itself every member of the row's group is withheld, whichever bin is
@@ -119,7 +126,6 @@ using recruit_args_t = std::conditional_t<kWitness, RecruitWitnessArgs,
 template <bool kResident, bool kMulti, bool kPairs, bool kGrouped = false, bool kWitness = false>
 __global__ __launch_bounds__(256, 2) void recruit_kernel(recruit_args_t<kGrouped, kPairs, kWitness> a, int nqt, int total)
 {
-    static_assert(!(kMulti && kPairs), "pairs are scored for a single m");
     static_assert(kResident || !kGrouped, "groups are a property of the resident samples");
     static_assert(kPairs || !kWitness, "witnesses travel with the pair calls: one record per listed pair");
     __shared__ __attribute__((aligned(16))) RecruitLds lds;
@@ -332,7 +338,11 @@ __global__ __launch_bounds__(256, 2) void recruit_kernel(recruit_args_t<kGrouped
                     nlast = nj;
                     __builtin_amdgcn_wave_barrier();   // the tile is rewritten for the next list entry
                 }
+                if constexpr (kPairs) {
+                    if (tx == 0 && 4 * ty + i < nrow) a.dist[(size_t)j * a.nq + qpos] = dist;
+                } else {
                 if (tx == 0 && qpos < a.nq) a.dist[((size_t)j * a.nq + qpos) * a.B + c] = dist;
+                }
             }
         } else {
         double dist = kInf;
@@ -607,22 +617,28 @@ void launch_recruit(const RecruitArgs &a, hipStream_t s)
     else hipLaunchKernelGGL((recruit_kernel<false, false, false>), dim3(grid), dim3(256), 0, s, a, nqt, total);
 }
 
-// one work item per row of the tile table
+// one work item per row of the tile table (a list of m with a.mmask)
 void launch_recruit_pairs(const RecruitPairArgs &a, hipStream_t s)
 {
     if (a.nq <= 0 || a.ntile <= 0) return;
     const int grid = ((a.ntile + 7) / 8) * 8;
+    if (a.mmask) {   // a list of m: one slice of a.nq doubles per entry
+        if (a.qid) hipLaunchKernelGGL((recruit_kernel<true, true, true>), dim3(grid), dim3(256), 0, s, a, 0, a.ntile);
+        else hipLaunchKernelGGL((recruit_kernel<false, true, true>), dim3(grid), dim3(256), 0, s, a, 0, a.ntile);
+        return;
+    }
     if (a.qid) hipLaunchKernelGGL((recruit_kernel<true, false, true>), dim3(grid), dim3(256), 0, s, a, 0, a.ntile);
     else hipLaunchKernelGGL((recruit_kernel<false, false, true>), dim3(grid), dim3(256), 0, s, a, 0, a.ntile);
 }
 
-// the leave-group-out instantiations: the dense grid (a.tile null; a list of m with a.mmask) or the tile table
+// the leave-group-out instantiations: the dense grid (a.tile null) or the tile table, either with a list of m (a.mmask)
 void launch_recruit_grouped(const RecruitGroupArgs &a, hipStream_t s)
 {
     if (a.tile) {
         if (a.nq <= 0 || a.ntile <= 0) return;
         const int grid = ((a.ntile + 7) / 8) * 8;
-        hipLaunchKernelGGL((recruit_kernel<true, false, true, true>), dim3(grid), dim3(256), 0, s, a, 0, a.ntile);
+        if (a.mmask) hipLaunchKernelGGL((recruit_kernel<true, true, true, true>), dim3(grid), dim3(256), 0, s, a, 0, a.ntile);
+        else hipLaunchKernelGGL((recruit_kernel<true, false, true, true>), dim3(grid), dim3(256), 0, s, a, 0, a.ntile);
         return;
     }
     if (a.nq <= 0 || a.B <= 0) return;

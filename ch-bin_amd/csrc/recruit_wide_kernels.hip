@@ -14,7 +14,9 @@
 //     backend (hull_solve64.h), the driver and backend of hull_generic_kernel.
 // The list form of (b) (chb_*_rows_multi_wide, dense only) reads the lists (a) left for the list's largest entry: one
 // wavefront per (problem, entry of the launch) -- the entries in 17 .. 32 with NV = 32, those in 33 .. 64 with NV = 64 --
-// on the first m' ids of the problem's record, one slice of distances per entry.
+// on the first m' ids of the problem's record, one slice of distances per entry.  chb_*_pairs_multi run the same list
+// form over a pair chunk behind (a)'s pair form: the arguments say B = 1, so problem g is position g and a slice is the
+// chunk's pairs.
 // The witness forms of both (chb_*_pairs_witness_wide, pairs only) store m doubles each per pair behind what the plain
 // forms do and nothing before it: (a) every list entry's rooted distance, (b) every lane's weight.
 //
@@ -60,7 +62,7 @@ using wide_args_t = std::conditional_t<kList, RecruitWideListArgs, std::conditio
 template <int NV, bool kWitness = false, bool kList = false>
 __global__ __launch_bounds__(64) void hull_wide_kernel(wide_args_t<kWitness, kList> a, int nprob)
 {
-    static_assert(!(kWitness && kList), "witnesses travel with the pair calls, lists with the dense ones");
+    static_assert(!(kWitness && kList), "witnesses travel with the single pair calls: a list has no witness form");
     constexpr int NB = NV / 16, NT = NB * (NB + 1) / 2;
     using Lds = GenLdsT<NV>;
     Lds *Lp;
@@ -458,6 +460,7 @@ void launch_hull_wide(const RecruitWideArgs &a, hipStream_t s)
 }
 
 // the list form: one wavefront per (problem of a dense chunk, entry of the launch), a.nw slices of a.dist written here
+// (a pair chunk: a.tile set and a.B = 1, its nq positions are the problems)
 void launch_hull_wide_list(const RecruitWideListArgs &a, hipStream_t s)
 {
     const long long nprob = (long long)a.nq * (long long)a.B;

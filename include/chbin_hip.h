@@ -492,6 +492,49 @@ int chb_recruit_rows_multi_wide(chb_ctx *h, const int64_t *labels, int64_t B, co
                                 const double *Y, int64_t Q, int64_t D,
                                 int64_t *bin_out, double *dist_out, double *min_dist_out, double *margin_out);
 
+/* The pair calls for a LIST of neighbour counts: chb_audit_pairs_wide / chb_recruit_pairs_wide for every entry of ms[]
+ * from one selection pass per kernel -- the profile of `cohesion` over (1, 3, 5, 10, 15) in one call instead of five that
+ * each stream the same members, or the sweep over each row's two or three nearest bins where the dense sweep's table
+ * (chb_audit_rows_multi_wide) is B times the work.
+ *   - ms holds nm distinct values, 1 <= nm <= 16, each in 1 .. CHB_MAX_NEIGHBORS = 64; entries up to 16 and above may be
+ *     mixed, in any order.  One symbol per family for the whole range: these calls have no narrow twin.
+ *   - dist_out [nm][P], m-major and in the order of ms[], pairs in the caller's order (they may repeat): dist_out + j * P
+ *     is BIT FOR BIT what chb_audit_pairs_wide(h, labels, groups, B, ms[j], row_idx, bin_idx, P, dist, NULL) /
+ *     chb_recruit_pairs_wide(h, labels, B, ms[j], Y, Q, D, row_of, bin_idx, P, dist, NULL) returns on the same arguments
+ *     and metric, +inf included -- for ms[j] <= 16 that is chb_audit_pairs / _grouped / chb_recruit_pairs, and so the
+ *     dense calls' entries.
+ *   - why the bits hold: the m' nearest members are a prefix of the max(ms)-nearest list under the total order
+ *     (distance, index), so one selection serves every entry.  Up to 16 the m' x m' problem is the leading block of the
+ *     one Gram tile, exactly as in chb_audit_rows_multi; above 16 the solve wavefront reads nothing but the list, whose
+ *     first m' ids are what the single call's selection leaves at m = m'.
+ *   - checks, in the list calls' and pair calls' order, all on the host before anything is enqueued: null context; P < 0,
+ *     Q < 0 or B < 1; ms NULL; nm outside 1 .. 16; an entry < 1; a repeated entry among 1 .. 64 (all CHB_EINVAL); with
+ *     P > 0 a null labels / row_idx / row_of / bin_idx / Y / dist_out (CHB_EINVAL); no resident samples (CHB_ESTATE); D
+ *     other than the resident samples' (CHB_EINVAL); max(ms) > 64, then max(ms) > 32 on a device that does not grant the
+ *     66 KiB of LDS per workgroup (CHB_EUNSUPPORTED); B > 8192 (CHB_EUNSUPPORTED); an open stepwise fit (CHB_ESTATE, the
+ *     fit stays usable); P = 0 (CHB_OK, nothing further is read); the ranges of row_idx / row_of, then of bin_idx
+ *     (CHB_EINVAL).  A refused call writes nothing.
+ *   - the plan is the single pair call's, unchanged: stable counting sort by bin, tiles of at most 64 pairs, chunks of whole
+ *     tiles up to 16384 pairs -- chb_counter "pair_tiles" is the single call's.  A chunk's nm result slices are nm doubles
+ *     per pair (at most 2 MiB: the chunks are not shortened for the list), its list buffer max(ms) + 1 int32 per pair.
+ *   - per chunk: the entries up to 16, if any, in one launch of the pair kernel's list form ("audit_pairs_multi" /
+ *     "recruit_pairs_multi", work units = (pair, entry up to 16)); with an entry above 16 the wide selection's pair form
+ *     once at max(ms) ("audit_pairs_multi_wide_select" / "recruit_...", work units = pairs) and one wavefront per (pair,
+ *     entry above 16) on the first m' ids of the pair's list ("..._pairs_multi_wide_solve", work units = those; the
+ *     entries 17 .. 32 on the 32-vertex kernel and 33 .. 64 on the 64-vertex kernel, one launch for each group the list
+ *     has, both booked as one).  A list with entries on both sides of 16 runs both selections, as the dense wide list
+ *     does.
+ *   - not offered: an idx_out or a witness form for a list -- the prefix of chb_audit_pairs_wide(..., idx_out) at max(ms)
+ *     is every entry's list -- and a recruit form with groups (rows that are not samples have no siblings).
+ *   - the call uses no state of a fit and leaves every counter, memo and switch of the context as it found it, except
+ *     "pair_tiles" and, with an entry above 16, "recruit_wide_rows" (the single wide pair call's figure); no collective. */
+int chb_audit_pairs_multi(chb_ctx *h, const int64_t *labels, const int64_t *groups /* may be NULL */, int64_t B,
+                          const int *ms, int nm, const int64_t *row_idx, const int64_t *bin_idx, int64_t P,
+                          double *dist_out /* [nm][P] */);
+int chb_recruit_pairs_multi(chb_ctx *h, const int64_t *labels, int64_t B, const int *ms, int nm,
+                            const double *Y, int64_t Q, int64_t D,
+                            const int64_t *row_of, const int64_t *bin_idx, int64_t P, double *dist_out /* [nm][P] */);
+
 /* distance_matrix.py:47-62 find_nearest_from_cluster with the reference's exact signature: the
  * caller supplies one row of a distance matrix (any provenance) and the current labels; selects
  * among {p : labels[p] == c} the (up to) m smallest by (row[p], p).  out_idx[m] (-1 padded). */
@@ -663,7 +706,11 @@ int chb_profile_reset(chb_ctx *h);
  * (row, bin) problems) | "audit_multi_wide_select" / "audit_multi_wide_solve" and their "recruit_" counterparts
  * (chb_audit_rows_multi_wide / chb_recruit_rows_multi_wide with an entry above 16: a chunk's one selection launch, work
  * units = (row, bin) problems, and its list solve launch, work units = (row, bin, entry above 16) triples; the entries up
- * to 16 are booked under "audit_multi" / "recruit_multi").  For m <= 16 "hull_qp" is the fused selection + hull-distance kernel and
+ * to 16 are booked under "audit_multi" / "recruit_multi") | "audit_pairs_multi" / "recruit_pairs_multi"
+ * (chb_audit_pairs_multi / chb_recruit_pairs_multi: a chunk's one launch for the entries up to 16; work units = (pair, entry
+ * up to 16)) | "audit_pairs_multi_wide_select" / "audit_pairs_multi_wide_solve" and their "recruit_" counterparts (the same
+ * calls with an entry above 16: a chunk's one selection launch, work units = pairs, and its list solve launches, work units
+ * = (pair, entry above 16)).  For m <= 16 "hull_qp" is the fused selection + hull-distance kernel and
  * "slow_path" the exact path for what it leaves over; "rescore*" then only appear for m > 16 or CHB_FUSED=0. */
 int chb_profile_get(chb_ctx *h, const char *kernel, double *total_ms, int64_t *launches,
                     double *work_units);
@@ -696,7 +743,8 @@ int chb_fit_stats(chb_ctx *h, int64_t *out4);
  * label guess, one per round), "recruit_chunk" (rows per launch of chb_recruit_rows, chb_audit_rows and -- at most -- chb_bin_report: a constant),
  * "recruit_multi_rows" (rows per launch of the last chb_audit_rows_multi / chb_recruit_rows_multi call: 16384 / nm rounded
  * down to a multiple of 64; 0 before the first), "pair_tiles" (tiles of at most 64 pairs of one bin -- the kernel's work
- * items -- of the last chb_audit_pairs / chb_recruit_pairs call that had pairs; 0 before the first),
+ * items -- of the last chb_audit_pairs / chb_recruit_pairs call that had pairs, their _wide, _witness and _multi forms among
+ * them; 0 before the first),
  * "recruit_wide_rows" (rows per launch of the last chb_*_wide call with m > 16, a chb_*_rows_multi_wide call with an
  * entry above 16 among them: see there; 0 before the first),
  * "kmer_chunk_bytes" / "kmer_chunk_rows" (the most bases / contigs of one sequence chunk of chb_kmer_profiles and
