@@ -15,49 +15,21 @@
 //   No change (f = K) means label_r is the unique fixed point = the sequential result.
 // In sweep 1 the pre-batch labels of the batch are all -1; in later sweeps they are last sweep's
 // labels and a batch typically converges in one round.
-#include "chb_internal.h"
-#include "../../include/chbin_hip.h"
-
-#include <dlfcn.h>
-#include <rccl/rccl.h>
-
-#include <algorithm>
-#include <array>
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <functional>
-#include <limits>
-#include <map>
-#include <string>
-#include <unordered_set>
-#include <vector>
-
-using namespace chb;
+#include "chb_host.h"
 
 namespace {
 
 thread_local std::string g_err;
+
+}  // namespace
+
+namespace chb {
 
 int fail(int code, const std::string &msg)
 {
     g_err = msg;
     return code;
 }
-
-// RCCL is resolved at run time (dlopen) so that the library neither forces a second copy of RCCL
-// into a process that already has one (PyTorch bundles its own) nor needs it for single-GPU use.
-struct RcclApi {
-    void *lib = nullptr;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId *) = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t *, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*AllGather)(const void *, void *, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*Broadcast)(const void *, void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*CommCount)(const ncclComm_t, int *) = nullptr;
-    const char *(*GetErrorString)(ncclResult_t) = nullptr;
-    bool ok = false;
-};
 
 RcclApi *rccl()
 {
@@ -88,412 +60,9 @@ RcclApi *rccl()
     return api.ok ? &api : nullptr;
 }
 
-#define NCCLCHK(expr)                                                                      \
-    do {                                                                                   \
-        ncclResult_t r_ = (expr);                                                          \
-        if (r_ != ncclSuccess)                                                             \
-            return fail(CHB_EHIP, std::string(#expr) + ": " + rccl()->GetErrorString(r_)); \
-    } while (0)
-
-#define HIPCHK(expr)                                                                       \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return fail(CHB_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));      \
-    } while (0)
-
-// (in a function that returns the hipError_t itself)
-#define HIPTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
-
-struct ProfEntry {
-    double ms = 0.0;
-    int64_t launches = 0;
-    double work = 0.0;
-};
-
-struct Pending {
-    hipEvent_t a, b;
-    std::string name;
-    double work;
-};
-
-// A buffer that frees itself: device memory (DevBuf), or pinned host staging (PinBuf; labels, permutations: asynchronous
-// copies at DMA speed instead of the driver's bounce-buffer path for pageable memory)
-template <typename T, bool kPinned>
-struct Buf {
-    T *p = nullptr; size_t cap = 0;
-    hipError_t ensure(size_t n)
-    {
-        if (n <= cap) return hipSuccess;
-        release();
-        const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-        hipError_t e = kPinned ? hipHostMalloc((void **)&p, bytes, hipHostMallocDefault) : hipMalloc((void **)&p, bytes);
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-    hipError_t ensure_zeroed(size_t n, hipStream_t s)   // (all of it zeroed on s whenever this allocated or grew it)
-    {
-        const size_t had = cap;
-        const hipError_t e = ensure(n);
-        return (e != hipSuccess || cap == had) ? e : hipMemsetAsync(p, 0, sizeof(T) * cap, s);
-    }
-    void release() { if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p)); p = nullptr; cap = 0; }
-    Buf() = default; Buf(const Buf &) = delete; Buf &operator=(const Buf &) = delete;
-    ~Buf() { release(); }
-};
-template <typename T> using DevBuf = Buf<T, false>;
-template <typename T> using PinBuf = Buf<T, true>;
-
-// A device buffer and its pinned twin on the host (the row-scoring calls' chunks: what goes up, what comes down)
-template <typename T>
-struct Mirror {
-    DevBuf<T> d;
-    PinBuf<T> h;
-    hipError_t ensure(size_t n, bool want_host)   // (the host side only where somebody will read or fill it)
-    {
-        HIPTRY(d.ensure(n));
-        return want_host ? h.ensure(n) : hipSuccess;
-    }
-    hipError_t up(size_t n, hipStream_t s) { return hipMemcpyAsync(d.p, h.p, sizeof(T) * n, hipMemcpyHostToDevice, s); }
-    hipError_t down(size_t n, hipStream_t s) { return hipMemcpyAsync(h.p, d.p, sizeof(T) * n, hipMemcpyDeviceToHost, s); }
-};
-
-}  // namespace
-
-// device storage behind a MemberPack
-struct PackBufs {
-    DevBuf<unsigned short> Z;
-    DevBuf<float> bias, sn, cs, cb, bb, tsn;   // (bias / sn / cs / cb: the batch-entry pack's per-row columns)
-    DevBuf<int> pad_ptr;
-    hipError_t ensure(size_t rows, size_t B, size_t Dz)
-    {
-        hipError_t e;
-        if ((e = Z.ensure((rows + 64) * Dz)) != hipSuccess) return e;   // + slack: whole 32-row tiles are read
-        DevBuf<float> *f[] = {&bias, &sn, &cs, &cb};
-        for (auto *b : f) if ((e = b->ensure(rows + 64)) != hipSuccess) return e;
-        if ((e = bb.ensure(4 * B)) != hipSuccess) return e;
-        if ((e = tsn.ensure(rows / 32 + B + 68)) != hipSuccess) return e;   // (+ 64: the tile-skipping kernel reads 64 at a time)
-        return pad_ptr.ensure(B + 1);
-    }
-    chb::MemberPack view()
-    {
-        return chb::MemberPack{Z.p, bias.p, sn.p, cs.p, cb.p, tsn.p, pad_ptr.p, reinterpret_cast<float4 *>(bb.p)};
-    }
-};
-
-// The product's switches (include/chbin_hip.h; read_switches): each selects a slower, independent formulation of the same
-// result for the tests' A/B checks.  (A multi-rank fit may turn speculate, allow_skip, pp_allowed off for itself.)
-struct Switches {
-    bool use_prefilter = true;    // CHB_PREFILTER=0: brute-force fp64 selection instead of the fp16 shortlist stage
-    bool allow_fused = true;      // CHB_FUSED=0: m <= 16 also takes the list-based path (exact rescoring, then the hull kernel)
-    bool fused_ptr64 = false;     // CHB_FUSED_PTR64=1: 64-bit row pointers in the m <= 5 fused kernel whatever the size of X
-    bool speculate = true;        // CHB_SPECULATE=0: never enqueue the next batch ahead of the convergence test
-    bool force_gather = false;    // CHB_FORCE_GATHER=1: run the exchange path even with one rank (tests)
-    bool allow_segments = true;   // CHB_SEGMENTS=0: never (A/B tests)
-    bool fused_stripe = true;     // CHB_FUSED_STRIPE=0: position-major work order in the fused kernels
-    bool fused_trim = true;       // CHB_FUSED_TRIM=0: the m <= 5 fused kernel gathers every candidate of a wide shortlist
-    bool pp_allowed = true;       // CHB_PACK_INCR=0: every batch start rebuilds CSR and pack (the form up to round 3; A/B tests)
-    bool pool_allowed = true, pool_force = false;   // CHB_POOL_TAU=0: a bin always streamed twice; =2: pools whatever the size
-    bool allow_skip = true;       // CHB_TILE_SKIP=0: never (A/B tests)
-};
-
-// ---- the context's parts: each feature owns its buffers, host flags, verdict on the running fit, statistics and view for
-// the kernels.  fit_reset: what a fit's start resets; fit_scope: what holds inside a chb_fit_cluster_ex call only (FitScope).
-
-// The persistent base pack (prefilter_kernels.hip): the member pack kept across the batches of a fit
-struct PersistentPack {
-    DevBuf<int> start, cap, fill, live, nt, fill0, start0, memb, row, ctl, ovf, dest;
-    int arena_rows = 0;
-    int64_t mark = 0;       // rows handed out from which on the host asks for a rebuild (pack_state_build)
-    bool fit = false;       // inside chb_fit_cluster (the stepwise entry points and chb_topm_per_bin always rebuild)
-    bool valid = false;     // the pack on the device matches the labels
-    bool batch = false;     // the open batch was started on it
-    bool rebuild = false;   // much of the arena is used up: the next batch start outside a look-ahead window rebuilds
-    int64_t stat_batches = 0, stat_builds = 0;
-    chb::PackState view() { return chb::PackState{start.p, cap.p, fill.p, live.p, nt.p, fill0.p, start0.p, memb.p, row.p, ctl.p, ovf.p, dest.p, arena_rows}; }
-    void fit_reset() { valid = false; batch = false; rebuild = false; }
-    void fit_scope(bool in) { fit = in; if (in) { stat_batches = 0; stat_builds = 0; } else valid = false; }
-};
-
-// Threshold pools of the shortlist stage (prefilter_kernels.hip, "threshold pools"): for every (bin, home bin) the 32
-// base members of the bin nearest to the home bin's centre; built at a fit's start, maintained by every commit
-struct ThresholdPools {
-    DevBuf<unsigned short> Z;
-    DevBuf<int> id, hole, ok, bad;
-    DevBuf<float> key, sn, tsn;
-    bool fit = false;      // inside chb_fit_cluster (the stepwise entry points and chb_topm_per_bin never use pools)
-    bool valid = false;    // the pools on the device match the labels
-    bool kept = false;     // ... and did when the last fit ended (what the counter pool_bad_slots looks at)
-    bool batch_labelled = true;   // the batch about to be opened may hold labelled samples (the fit loop knows; else: true)
-    bool holes = true;     // the open batch may hold labelled samples (their pool slots are holes until the commit)
-    int state = 0;         // this fit: 0 undecided = on, 1 kept on, -1 off (its shortlists came out long: overlapping bins;
-                           // or tile skipping never loads more than 30 % of the tiles: FitRun::note_verdict has both rules)
-    int batches = 0;
-    long long cand = 0, pairs = 0;
-    long long off_key = -1;   // (bins, neighbours, metric) of the fit that turned them off on these samples
-    int64_t stat_batches = 0;
-    chb::PoolState view() { return chb::PoolState{Z.p, id.p, key.p, sn.p, hole.p, tsn.p, ok.p}; }
-    void release() { Z.release(); id.release(); hole.release(); key.release(); sn.release(); tsn.release(); ok.release(); }
-    void fit_reset(bool off) { stat_batches = 0; state = off ? -1 : 0; batches = 0; cand = 0; pairs = 0; }
-    void fit_scope(bool in) { fit = in; kept = !in && valid; batch_labelled = true; if (!in) valid = false; }
-};
-
-// Tile skipping in the base shortlist launch, and the queries' seats it and the pools need
-struct Seating {
-    // shells: the CSR of the base members is keyed (bin, shell of the member's distance from the bin's centre), outermost
-    // shell first, so that the rows of a 32-row tile have similar norms (tile skipping in the shortlist kernel)
-    DevBuf<float> shell_inv;
-    int nsh = 1;
-    // tile skipping (needs the shells above and queries seated by nearest bin centre): nearest-centre keys, the seating
-    // order, and the fit's verdict on whether it pays (0 undecided = on, 1 on, -1 off)
-    DevBuf<unsigned long long> ckey;
-    DevBuf<int> qord, home;
-    // (the fit loop orders the positions of ALL batches of a sweep in one launch; the open batch's part: qord_cur / home_cur)
-    DevBuf<int> qord_all, home_all;
-    DevBuf<int4> geo_all;
-    PinBuf<int4> pin_geo;
-    int *qord_cur = nullptr, *home_cur = nullptr;
-    int state = 0, batches = 0;
-    long long off_key = -1;   // (bins, neighbours, metric) of the fit that found nothing to skip on these samples
-    long long skipped = 0, seen = 0, unloaded = 0;
-    void fit_reset(bool off) { state = off ? -1 : 0; batches = 0; skipped = 0; seen = 0; unloaded = 0; }
-    void unseat() { qord_cur = nullptr; home_cur = nullptr; }   // (no sweep-wide seating: a sweep's start, a fit's end)
-};
-
-// Bins far larger than the rest are cut into segments for the shortlist stage (SegPlan, prefilter_kernels.hip): plan
-// buffers, and the bin sizes last seen by the host (they come home with the rounds' verdicts)
-struct Segments {
-    DevBuf<int> nseg, gflag;
-    DevBuf<int4> items;
-    DevBuf<float> lists;
-    int gcap = 0;
-    int hint_max_tiles = 0, hint_total_tiles = 0;
-    int64_t stat_batches = 0;   // batches of the last fit that ran the segment launches
-};
-
-// One half of the row-scoring calls' double buffer: a chunk of the new rows (padded like X) or of sample indices (qid), its
-// distances and row reductions, each a Mirror: on the device (.d) and pinned on the host (.h); chb_bin_report's chunks also
-// carry seg, each label's run (BinReportArgs), nseg of them; the pair calls' chunks carry tile, the chunk's tile table
-// (RecruitPairArgs), ntile rows.
-// up / done / down: the upload, the kernels, the download of the chunk in this half are through.
-struct ChunkHalf {
-    Mirror<double> Y, dist, min, margin;
-    Mirror<int> bin, qid;
-    Mirror<int2> seg;
-    Mirror<int4> tile;
-    // the witness calls only (first allocated by the context's first such call): the chunk's witness records, a call-wide
-    // number of slots per position (ScoreRun::wslots) -- kWitnessSlots up to 16 neighbours (RecruitWitnessArgs), m beyond
-    // (RecruitWideWitnessArgs), where the members' ids are wlist's and wid stays unused
-    Mirror<int> wid;
-    Mirror<double> wd, walpha;
-    // chb_*_rows_nearest only (first allocated by the context's first such call): the chunk's k nearest bins per row and
-    // their distances
-    Mirror<int> nbin;
-    Mirror<double> ndist;
-    // the pair calls with more than 16 neighbours only (first allocated by the context's first such call): the chunk's
-    // selection lists, m + 1 ints per position (RecruitWideArgs), per half because idx_out copies them down while the next
-    // chunk's kernels run
-    Mirror<int> wlist;
-    hipEvent_t up = nullptr, done = nullptr, down = nullptr;
-    int nseg = 0, ntile = 0;
-    void destroy_events() { for (hipEvent_t ev : {up, done, down}) if (ev) (void)hipEventDestroy(ev); }
-};
-
-// Every row-scoring call (ScoreRun): the calls' own buffers, nothing of a fit.
-// While the kernels of chunk k run on the context's stream, copy brings chunk k + 1 up into the other half and chunk
-// k - 1 down.  Not per half: the call's CSR over the labels (ptr, memb) and chb_bin_report's B x B tables rep_* (zeroed at
-// the call's start), which collect what the chunks' rows say.  The chb_*_grouped calls add the dense group ids: grp of
-// every resident sample, mgrp parallel to memb.
-struct RowScoring {
-    ChunkHalf half[2];
-    DevBuf<int> ptr, memb, mgrp, grp;
-    PinBuf<int> hptr, hmemb, hmgrp, hgrp;
-    DevBuf<long long> rep_conf, rep_unplaced, rep_cnt;
-    DevBuf<double> rep_min, rep_sum;
-    hipStream_t copy = nullptr;
-    int64_t multi_rows = 0;   // rows per launch of the last chb_audit_rows_multi / chb_recruit_rows_multi
-    int64_t pair_tiles = 0;   // tiles (work items) of the last chb_audit_pairs / chb_recruit_pairs
-    // the dense wide calls (16 < m <= 64): the selection lists of one chunk, rows x B x (m + 1) ints within kWideListBytes
-    // (one buffer: a chunk's kernels follow the previous chunk's on the stream and nothing copies it down); first
-    // allocated by the context's first such call
-    DevBuf<int> wlist;
-    int64_t wide_rows = 0;    // rows per launch of the last wide call
-};
-
-// Multi-GPU: one context per process per GPU, RCCL communicator over all ranks
-struct Exchange {
-    ncclComm_t comm = nullptr;
-    // host-staged exchange (chb_comm_init_hook): the same sharded loop with the all-gathers done by a
-    // caller-supplied function on host buffers -- MPI, gloo, pipes; also how two ranks can share one GPU
-    chb_allgather_fn hook = nullptr;
-    void *hook_user = nullptr;
-    std::vector<char> send, recv;
-    DevBuf<int> agree;   // chb_bcast_samples: {status, N, D, root} of every rank; chb_fit_cluster: the fit's agreement table
-    // framed exchange of the sharded loop (aux_kernels.hip: xchg_pack / xchg_unpack): every rank's {header, label slice},
-    // the number of the fit's next exchange (part of the tag every frame carries), and the device's "a rank was out of
-    // step" record {flag, my tag, its tag, rank}
-    DevBuf<int> xg, xerr;
-    int seq = 0;
-};
-
-struct Profile {
-    int level = 0;   // 0 off, 1 every kernel, 2 only the two dominant ones (cheap enough for a timed region)
-    std::map<std::string, ProfEntry> acc;
-    std::vector<Pending> pending;
-};
-
-// What describes the open batch on the host.  LookaheadSnap saves and restores it by copy: anything added here is put
-// back as it was after a failed look-ahead.
-struct BatchState {
-    int K = 0, q_lo = 0, q_hi = 0;
-    int round_in_batch = 0;     // rounds alternate between the list sets 1 and 2 (the other = previous)
-    bool lists_valid = false;   // the open batch was started with need_lists (chb_topm_per_bin)
-    bool open = false;
-    int *bq_cur = nullptr;      // the open batch's sample indices: bq.p, or a window of perm (no copy)
-    int *fc_cur = nullptr;      // slot of the open batch (first_change.p + 0 / kSlotInts), words as SlotWord names them: bin sizes, skip /
-                                // pool statistics and the pack's fill mark ride home with the verdict in one copy of kSlotHome ints
-    double hint_base_members = 0.0, hint_batch_entries = 0.0;   // work-unit hints for the profile (pairs = queries x members streamed)
-};
-
-struct chb_ctx {
-    int dev = 0;
-    Switches sw;
-    hipStream_t stream = nullptr;
-    int rank = 0, world = 1;
-    PersistentPack pp;
-    ThresholdPools pool;
-    Seating seat;
-    Segments seg;
-    RowScoring score;
-    Exchange xchg;
-    Profile prof;
-    BatchState batch;
-    // samples
-    DevBuf<double> X;
-    int64_t N = 0;
-    int D = 0, Dp = 0;
-    // fit state
-    int B = 0, m = 0;
-    int metric = 0;   // CHB_METRIC_CONVEX / CHB_METRIC_AFFINE
-    bool fit_open = false;
-    bool stepwise = false;   // the open fit was begun by chb_fit_begin (the caller drives its batches): chb_recruit_rows / chb_audit_rows refuse
-    DevBuf<int> labels, inb;
-    // batch buffers (the open batch itself: `batch`)
-    int Kcap = 0;
-    DevBuf<int> bq, lab_old, lab_prev, lab_new, first_change;
-    int *fc_host = nullptr;     // pinned landing places of the two verdict slots (kSlotInts ints each, as on the device)
-    hipEvent_t fc_event[2] = {nullptr, nullptr};
-    bool argmin_in_place = false;   // chb_fit_cluster without exchange: argmin also stores the label to lab_prev
-    DevBuf<double> mind, mind2, dist;   // winning hull distance, runner-up (margin report), all distances
-    bool want_margin = false;
-    DevBuf<double> l0d, l1d, l2d;
-    DevBuf<int> l0i, l1i, l0c, l1c, l2i, l2c;
-    int64_t round_active = 0; // `active` of the open batch's last chb_batch_round: may not decrease (include/chbin_hip.h)
-    DevBuf<int> cnt, bin_ptr, cursor, memb_id;
-    DevBuf<int> cnt2, bin_ptr2, cursor2, memb2_id, memb2_code;
-    DevBuf<int> perm;
-    PinBuf<int> pin_a, pin_b, pin_c;   // host staging: labels in, labels out, permutation
-    // two-stage selection: fp16 shadow copies + shortlists (prefilter_kernels.hip)
-    DevBuf<unsigned short> Gs, Zs;     // per sample: query-side row (global centre), member-side row (own bin)
-    DevBuf<float> gq, ms;              // per sample: float2 {||qh||^2, rho}, float4 {bias, rho, ||zh||^2, amax}
-    DevBuf<double> mu_g, colsum_part;  // global mean, scratch of its two-pass sum
-    DevBuf<unsigned int> rmax;
-    double shadow_scale = 1.0;         // S
-    PackBufs pk, pk2;                  // padded member packs: base members, the batch's own entries
-    DevBuf<float> qn;                  // [N][B] float2 exact sample-to-centre norms (per fit)
-    DevBuf<double> centers;
-    int Dz = 0;
-    bool shadow_ok = false, overflow_total_valid = false;
-    DevBuf<int> cand, cand_cnt, flags64, flaglist, nflag, overflow;
-    DevBuf<int> flaglist2, nflag2;   // what the second-chance launch of a pool batch leaves for the brute-force kernel
-    DevBuf<int> active, n_active, act_blk;
-    // fused selection + hull distance (m <= 16): batch-entry candidates of this / the previous round,
-    // the base stage's tau (bound of the m-th nearest distance), the exact path's work list
-    bool fused = false;
-    bool pf_fit = false;        // this fit uses the shortlist stage (use_prefilter, D <= 160, m <= 16)
-    DevBuf<int> candu[2], candu_cnt[2], slow, n_slow;
-    DevBuf<float> tau;
-    // the shortlist stage's contract as checked by the fused kernels (FusedArgs::short_cnt): pairs of this fit whose base
-    // shortlist held fewer than min(m, bin size) candidates or a wild index -- any is an internal error of the fit
-    DevBuf<int> short_cnt;
-    // the m <= 5 fused kernel's trim (FusedArgs::trim_ctr): pairs trimmed in this fit, their candidates before and after
-    DevBuf<unsigned long long> trim_ctr;
-    DevBuf<TrimArgs> trim_args;   // (written with the global shadows: samples_finish)
-    // scratch for the indexed / explicit-point entry points
-    DevBuf<int> xq, xhull, xcnt;
-    DevBuf<double> xdist, xalpha, xpts;
-    // the last fit: chb_fit_stats, its speculative batch size, batches whose successor was enqueued ahead of their verdict
-    // and kept, ... and discarded (the batch needed further rounds)
-    std::array<int64_t, 4> stats{};
-    long long last_batch = 0;
-    int64_t stats_lookahead = 0, stats_lookahead_failed = 0;
-    int64_t kmer_chunks = 0;   // sequence chunks of the last chb_kmer_profiles / chb_set_samples_from_sequences call
-#ifdef CHB_DEV_KNOBS
-    // developer builds: the switches of the tests and tools/ (read_switches; the Makefile says what each does), their state
-    struct DevKnobs {
-        bool sl_bounds = false, sl_validate = false;                            // CHB_SL_BOUNDS, CHB_SL_VALIDATE
-        int inject_short = 0, sl_bpw = 0, skip_never = 0;                       // CHB_SL_INJECT_SHORT, CHB_SL_BPW, CHB_SKIP_NEVER
-        std::string sl_dbg;                                                     // CHB_SL_DBG
-        int64_t pack_rebuild_at = -1;                                           // CHB_PACK_REBUILD_AT (-1: unset)
-        bool hook_spec = false, local_verdict = false, skip_stats_on = false;   // CHB_DEV_HOOK_SPEC, CHB_DEV_LOCAL_VERDICT,
-        int skip_stats[3] = {0, 0, 0};                                          // CHB_DEV_SKIP_STATS
-        int batches = 0, launches = 0;   // batch starts (CHB_SL_INJECT_SHORT), base shortlist launches (CHB_SL_DBG) so far
-        DevBuf<int> viol, verr;          // first out-of-range access; validation error + per-position counters
-        DevBuf<unsigned long long> dbg;  // the timeline
-    } dk;
-#endif
-
-    Lists L0() { return Lists{l0d.p, l0i.p, l0c.p}; }
-    Lists L1() { return Lists{l1d.p, l1i.p, l1c.p}; }
-    Lists L2() { return Lists{l2d.p, l2i.p, l2c.p}; }
-    Lists Lcur() { return (batch.round_in_batch & 1) ? L2() : L1(); }
-    Lists Lprev() { return (batch.round_in_batch & 1) ? L1() : L2(); }
-
-    // The kernels' argument blocks for the positions [lo, hi) of the open batch, with the fields that every launch of a
-    // kind shares; a call site adds only what makes it different, and what nobody sets stays zero.
-    TopmArgs topm_args(int lo, int hi)
-    {
-        TopmArgs a{};
-        a.X = X.p; a.Dp = Dp; a.bq = batch.bq_cur; a.pos_begin = lo; a.pos_end = hi; a.B = B; a.m = m; a.Kcap = Kcap;
-        return a;
-    }
-    // (query side, geometry, scale, overflow counter, the brute-force kernel's work list -- its counter reset by the CSR kernels)
-    ShortlistArgs shortlist_args(int lo, int hi)
-    {
-        ShortlistArgs a{};
-        a.Gs = Gs.p; a.gq = reinterpret_cast<const float2 *>(gq.p); a.qn = reinterpret_cast<const float2 *>(qn.p);
-        a.Dz = Dz; a.S = shadow_scale; a.bq = batch.bq_cur; a.pos_begin = lo; a.pos_end = hi; a.B = B; a.m = m; a.Kcap = Kcap;
-        a.overflow = overflow.p; a.flaglist = flaglist.p; a.nflag = nflag.p;
-        return a;
-    }
-    RescoreArgs rescore_args(int lo, int hi)   // (candidates: the base shortlists)
-    {
-        RescoreArgs a{};
-        a.X = X.p; a.Dp = Dp; a.bq = batch.bq_cur; a.pos_begin = lo; a.pos_end = hi; a.B = B; a.m = m; a.Kcap = Kcap;
-        a.cand = cand.p; a.cand_cnt = cand_cnt.p; a.cand_cap = kCandCap;
-        return a;
-    }
-    QpArgs qp_args(int lo, int hi)
-    {
-        QpArgs a{};
-        a.X = X.p; a.D = D; a.Dp = Dp; a.bq = batch.bq_cur; a.pos_begin = lo; a.pos_end = hi; a.B = B; a.m = m; a.Kcap = Kcap;
-        a.dist = dist.p; a.metric = metric;
-        return a;
-    }
-    FusedArgs fused_args(int lo, int hi)
-    {
-        FusedArgs a{};
-        a.X = X.p; a.n_samples = N; a.D = D; a.Dp = Dp; a.bq = batch.bq_cur; a.pos_begin = lo; a.pos_end = hi;
-        a.B = B; a.m = m; a.Kcap = Kcap; a.dist = dist.p; a.metric = metric;
-        // (the trim sweeps one 160-column slice of the global shadows at the most)
-        if (sw.fused_trim && shadow_ok && Dz <= 160 && D + 3 <= 160) a.trim = trim_args.p;
-        return a;
-    }
-};
-
 // In-place all-gather of `count` elements per rank inside the device buffer `buf` (rank r's slice sits at
 // buf + r * count): RCCL on the context's stream, or the host-staged hook.
-static int exchange_all_gather(chb_ctx *h, void *buf, size_t count, size_t elem, ncclDataType_t dt)
+int exchange_all_gather(chb_ctx *h, void *buf, size_t count, size_t elem, ncclDataType_t dt)
 {
     char *b = static_cast<char *>(buf);
     if (h->xchg.hook != nullptr) {
@@ -511,29 +80,6 @@ static int exchange_all_gather(chb_ctx *h, void *buf, size_t count, size_t elem,
     NCCLCHK(rccl()->AllGather(b + (size_t)h->rank * count * elem, b, count, dt, h->xchg.comm, h->stream));
     return CHB_OK;
 }
-
-namespace {
-
-struct Timed {
-    chb_ctx *h;
-    Pending p;
-    bool on;
-    Timed(chb_ctx *h_, const char *name, double work)
-        : h(h_), on(h_->prof.level == 1 || (h_->prof.level == 2 && (!strcmp(name, "prefilter") || !strcmp(name, "hull_qp"))))
-    {
-        if (!on) return;
-        p.name = name; p.work = work;
-        (void)hipEventCreate(&p.a);
-        (void)hipEventCreate(&p.b);
-        (void)hipEventRecord(p.a, h->stream);
-    }
-    ~Timed()
-    {
-        if (!on) return;
-        (void)hipEventRecord(p.b, h->stream);
-        h->prof.pending.push_back(p);
-    }
-};
 
 void drain_profile(chb_ctx *h)
 {
@@ -625,7 +171,7 @@ int ensure_batch_buffers(chb_ctx *h, int Kcap)
 
 // sync = false (chb_fit_cluster): the uploads and kernels of the fit's start are only enqueued -- the caller goes on with
 // its own host work (permutation check / conversion) while they run, and the stream orders everything behind them
-int fit_begin_impl(chb_ctx *h, int64_t B, const int64_t *initial, int m, bool sync = true)
+int fit_begin_impl(chb_ctx *h, int64_t B, const int64_t *initial, int m, bool sync)
 {
     if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
     if (B <= 0) return fail(CHB_EINVAL, "num_clusters must be positive");
@@ -713,6 +259,10 @@ int fit_begin_impl(chb_ctx *h, int64_t B, const int64_t *initial, int m, bool sy
     return CHB_OK;
 }
 
+}  // namespace chb
+
+namespace {
+
 // The persistent base pack from the labels as they stand (no batch open): compact CSR of all labelled samples, then
 // regions with room to grow.  Allocates on first use (12 N + 1024 B rows: the layout takes at most 3.5 N + 128 B, a commit's
 // moves at most 3 (N + K) + 96 B, the host rebuilds from 5 N + 512 B on) -- hence only ever called outside a look-ahead window.
@@ -762,6 +312,10 @@ int pack_state_build(chb_ctx *h)
     h->pp.stat_builds += 1;
     return CHB_OK;
 }
+
+}  // namespace
+
+namespace chb {
 
 // The threshold pools from the labels as they stand at a fit's start (the CSR fit_begin_impl has just made): allocated on
 // first use, B x B tiles of 32 shadow rows -- 38 MB at 100k x 136 x 64, 410 MB at 1M x 146 x 200; a fit whose pools would
@@ -828,6 +382,10 @@ void read_switches(chb_ctx *h)
         d.skip_stats_on = sscanf(e, "%d,%d,%d", &d.skip_stats[0], &d.skip_stats[1], &d.skip_stats[2]) == 3;
 #endif
 }
+
+}  // namespace chb
+
+namespace {
 
 // ---- batch_begin_dev's hooks for the developer builds' checks and records of the shortlist stage (product build: none)
 #ifdef CHB_DEV_KNOBS
@@ -1081,6 +639,10 @@ void base_topm_plain(chb_ctx *h, const TopmArgs &a)
     if (h->m > kMaxM) launch_topm_generic(a, h->stream); else launch_topm(a, h->stream);
 }
 
+}  // namespace
+
+namespace chb {
+
 // bq already holds the K sample indices (device).  need_lists: the caller wants the exact base lists
 // L0 (chb_topm_per_bin); the fit loop of the fused path (m <= 16) works on the shortlists directly.
 int batch_begin_dev(chb_ctx *h, int K, int q_lo, int q_hi, bool need_lists)
@@ -1105,6 +667,10 @@ int batch_begin_dev(chb_ctx *h, int K, int q_lo, int q_hi, bool need_lists)
     h->batch.open = true;
     return CHB_OK;
 }
+
+}  // namespace chb
+
+namespace {
 
 // ---- a round's three formulations (batch_round_dev picks one; a = its exact selection over the batch's own entries)
 // the batch's own entries as a padded pack, and the update-mode shortlist launch over it, less its thresholds and candidates
@@ -1199,6 +765,10 @@ void round_lists_plain(chb_ctx *h, int lo, int hi, const TopmArgs &a)
     if (h->m > kMaxM) launch_topm_generic(a, h->stream); else launch_topm(a, h->stream);
 }
 
+}  // namespace
+
+namespace chb {
+
 // lab_prev (device) holds the labels of the previous round.  Evaluates [max(active,q_lo), q_hi).
 int batch_round_dev(chb_ctx *h, int active)
 {
@@ -1268,6 +838,10 @@ int batch_commit_dev(chb_ctx *h, const int *final_dev)
     h->pp.batch = false;
     return CHB_OK;
 }
+
+}  // namespace chb
+
+namespace {
 
 // Under an exchange the ranks run ONE fit together: the order of its collectives is a function of the arguments, of the
 // context's switches and of the tile-skipping memo -- so before the first batch every rank all-gathers what it was given
@@ -1893,55 +1467,6 @@ struct FitRun {
 
 }  // namespace
 
-extern "C" {
-
-const char *chb_last_error(void) { return g_err.c_str(); }
-int chb_version(void) { return 1; }
-
-int chb_device_count(void)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-int chb_create(int device_id, chb_ctx **out)
-{
-    if (!out) return fail(CHB_EINVAL, "out is null");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return fail(CHB_ENODEVICE, "no HIP device visible (this library has no CPU fallback)");
-    if (device_id < 0 || device_id >= n) return fail(CHB_EINVAL, "device_id out of range");
-    HIPCHK(hipSetDevice(device_id));
-    chb_ctx *h = new chb_ctx();
-    h->dev = device_id;
-    read_switches(h);
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&h->fc_host, 128, hipHostMallocDefault);
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&h->fc_event[i], hipEventDisableTiming);
-    if (e != hipSuccess) { delete h; return fail(CHB_EHIP, hipGetErrorString(e)); }
-    *out = h;
-    return CHB_OK;
-}
-
-int chb_destroy(chb_ctx *h)
-{
-    if (!h) return CHB_OK;
-    (void)hipSetDevice(h->dev);
-    (void)hipStreamSynchronize(h->stream);
-    if (h->score.copy) (void)hipStreamSynchronize(h->score.copy);
-    drain_profile(h);
-    if (h->xchg.comm && rccl()) { (void)rccl()->CommDestroy(h->xchg.comm); h->xchg.comm = nullptr; }
-    // the handles without an owner; the buffers (DevBuf / PinBuf, PackBufs) free themselves when `delete h` destroys them
-    for (ChunkHalf &half : h->score.half) half.destroy_events();
-    for (hipEvent_t e : h->fc_event) if (e) (void)hipEventDestroy(e);
-    if (h->score.copy) (void)hipStreamDestroy(h->score.copy);
-    if (h->fc_host) (void)hipHostFree(h->fc_host);
-    (void)hipStreamDestroy(h->stream);
-    delete h;
-    return CHB_OK;
-}
-
 // the resident copy X[N][Dp] (rows zero-padded to Dp): filled from `X` (host or device), or -- X == nullptr -- left to
 // be filled by the caller (chb_bcast_samples on a receiving rank)
 static int samples_upload(chb_ctx *h, const double *X, int64_t N, int64_t D, bool from_device)
@@ -2020,12 +1545,65 @@ static int samples_finish(chb_ctx *h)
     return CHB_OK;
 }
 
-static int set_samples_common(chb_ctx *h, const double *X, int64_t N, int64_t D, bool from_device)
+namespace chb {
+
+int set_samples_common(chb_ctx *h, const double *X, int64_t N, int64_t D, bool from_device)
 {
     if (!h) return fail(CHB_EINVAL, "null context");
     if (!X) return fail(CHB_EINVAL, "samples must be a non-empty N x D matrix");
     const int rc = samples_upload(h, X, N, D, from_device);
     return rc ? rc : samples_finish(h);
+}
+
+}  // namespace chb
+
+extern "C" {
+
+const char *chb_last_error(void) { return g_err.c_str(); }
+int chb_version(void) { return 1; }
+
+int chb_device_count(void)
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
+}
+
+int chb_create(int device_id, chb_ctx **out)
+{
+    if (!out) return fail(CHB_EINVAL, "out is null");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
+        return fail(CHB_ENODEVICE, "no HIP device visible (this library has no CPU fallback)");
+    if (device_id < 0 || device_id >= n) return fail(CHB_EINVAL, "device_id out of range");
+    HIPCHK(hipSetDevice(device_id));
+    chb_ctx *h = new chb_ctx();
+    h->dev = device_id;
+    read_switches(h);
+    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&h->fc_host, 128, hipHostMallocDefault);
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&h->fc_event[i], hipEventDisableTiming);
+    if (e != hipSuccess) { delete h; return fail(CHB_EHIP, hipGetErrorString(e)); }
+    *out = h;
+    return CHB_OK;
+}
+
+int chb_destroy(chb_ctx *h)
+{
+    if (!h) return CHB_OK;
+    (void)hipSetDevice(h->dev);
+    (void)hipStreamSynchronize(h->stream);
+    if (h->score.copy) (void)hipStreamSynchronize(h->score.copy);
+    drain_profile(h);
+    if (h->xchg.comm && rccl()) { (void)rccl()->CommDestroy(h->xchg.comm); h->xchg.comm = nullptr; }
+    // the handles without an owner; the buffers (DevBuf / PinBuf, PackBufs) free themselves when `delete h` destroys them
+    for (ChunkHalf &half : h->score.half) half.destroy_events();
+    for (hipEvent_t e : h->fc_event) if (e) (void)hipEventDestroy(e);
+    if (h->score.copy) (void)hipStreamDestroy(h->score.copy);
+    if (h->fc_host) (void)hipHostFree(h->fc_host);
+    (void)hipStreamDestroy(h->stream);
+    delete h;
+    return CHB_OK;
 }
 
 int chb_set_samples(chb_ctx *h, const double *X, int64_t N, int64_t D)
@@ -2083,31 +1661,6 @@ int chb_comm_info(chb_ctx *h, int *rank, int *world, int *comm_ranks, int *trans
     if (h->xchg.comm && rccl()) NCCLCHK(rccl()->CommCount(h->xchg.comm, &cnt));
     if (comm_ranks) *comm_ranks = cnt;
     if (transport) *transport = h->xchg.comm ? 1 : (h->xchg.hook ? 2 : 0);
-    return CHB_OK;
-}
-
-int chb_pairwise_distance(chb_ctx *h, int64_t r0, int64_t r1, double *out)
-{
-    if (!h || !out) return fail(CHB_EINVAL, "null argument");
-    if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
-    if (r0 < 0 || r1 > h->N || r0 > r1) return fail(CHB_EINVAL, "row range out of bounds");
-    HIPCHK(hipSetDevice(h->dev));
-    const int64_t chunk = std::max<int64_t>(64, (int64_t)(1LL << 28) / std::max<int64_t>(h->N, 1));
-    DevBuf<double> buf;
-    HIPCHK(buf.ensure((size_t)std::min(chunk, r1 - r0) * h->N));
-    for (int64_t a = r0; a < r1; a += chunk) {
-        const int64_t b = std::min(r1, a + chunk);
-        {
-            Timed t(h, "pairwise", (double)(b - a) * h->N);
-            launch_pairwise(h->X.p, (int)h->N, h->Dp, (int)a, (int)b, buf.p, h->stream);
-        }
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(out + (a - r0) * h->N, buf.p, sizeof(double) * (b - a) * h->N,
-                               hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) return fail(CHB_EHIP, hipGetErrorString(e));
-    }
     return CHB_OK;
 }
 
@@ -2355,96 +1908,6 @@ int chb_topm_per_bin(chb_ctx *h, const int64_t *labels, int64_t B, int m, const 
     }
     h->fit_open = false;
     return CHB_OK;
-}
-
-static int hull_indexed(chb_ctx *h, const double *Xdev, int D, int Dp, int64_t nrows,
-                        const int64_t *query_idx, int64_t P, const int64_t *hull_idx, int m_max,
-                        double *dist, double *alpha)
-{
-    if (m_max < 1 || m_max > CHB_MAX_NEIGHBORS) return fail(CHB_EUNSUPPORTED, "m_max must be in [1, 64]");
-    if (P <= 0) return CHB_OK;
-    if (m_max > kMaxM && !hull_generic_supported())
-        return fail(CHB_EUNSUPPORTED, "more than 16 hull vertices need 68 KB of LDS per workgroup, which this device does not grant");
-    hipStream_t s = h->stream;
-    // compact each vertex list (padding may sit anywhere at the ABI) and remember the slots
-    std::vector<int> q((size_t)P), hx((size_t)P * m_max, -1), slot((size_t)P * m_max, -1), hn((size_t)P, 0);
-    for (int64_t p = 0; p < P; ++p) {
-        if (query_idx[p] < 0 || query_idx[p] >= nrows) return fail(CHB_EINVAL, "query index out of range");
-        q[(size_t)p] = (int)query_idx[p];
-        int n = 0;
-        for (int a = 0; a < m_max; ++a) {
-            const int64_t id = hull_idx[p * m_max + a];
-            if (id < 0) continue;
-            if (id >= nrows) return fail(CHB_EINVAL, "hull index out of range");
-            hx[(size_t)p * m_max + n] = (int)id;
-            slot[(size_t)p * m_max + n] = a;
-            ++n;
-        }
-        hn[(size_t)p] = n;
-    }
-    HIPCHK(h->xq.ensure((size_t)P));
-    HIPCHK(h->xhull.ensure((size_t)P * m_max));
-    HIPCHK(h->xcnt.ensure((size_t)P));
-    HIPCHK(hipMemcpyAsync(h->xcnt.p, hn.data(), sizeof(int) * P, hipMemcpyHostToDevice, s));
-    HIPCHK(h->xdist.ensure((size_t)P));
-    HIPCHK(h->xalpha.ensure((size_t)P * m_max));
-    HIPCHK(hipMemcpyAsync(h->xq.p, q.data(), sizeof(int) * P, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->xhull.p, hx.data(), sizeof(int) * P * m_max, hipMemcpyHostToDevice, s));
-    {
-        Timed t(h, "hull_qp", (double)P);
-        if (m_max > kMaxM)
-            launch_hull_generic_indexed(Xdev, D, Dp, h->xq.p, h->xhull.p, h->xcnt.p, (int)P, m_max, h->metric,
-                                        h->xdist.p, h->xalpha.p, s);
-        else
-            launch_hull_qp_indexed(Xdev, D, Dp, h->xq.p, h->xhull.p, h->xcnt.p, (int)P, m_max, h->metric, h->xdist.p,
-                                   h->xalpha.p, s);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(dist, h->xdist.p, sizeof(double) * P, hipMemcpyDeviceToHost, s));
-    std::vector<double> al;
-    if (alpha) {
-        al.resize((size_t)P * m_max);
-        HIPCHK(hipMemcpyAsync(al.data(), h->xalpha.p, sizeof(double) * P * m_max, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    if (alpha) {
-        for (size_t i = 0; i < (size_t)P * m_max; ++i) alpha[i] = 0.0;
-        for (int64_t p = 0; p < P; ++p)
-            for (int a = 0; a < m_max; ++a) {
-                const int sl = slot[(size_t)p * m_max + a];
-                if (sl >= 0) alpha[p * m_max + sl] = al[(size_t)p * m_max + a];
-            }
-    }
-    return CHB_OK;
-}
-
-int chb_hull_distance_batch(chb_ctx *h, const int64_t *query_idx, int64_t P, const int64_t *hull_idx,
-                            int m_max, double *dist, double *alpha)
-{
-    if (!h || !query_idx || !hull_idx || !dist) return fail(CHB_EINVAL, "null argument");
-    if (!h->X.p) return fail(CHB_ESTATE, "chb_set_samples has not been called");
-    HIPCHK(hipSetDevice(h->dev));
-    return hull_indexed(h, h->X.p, h->D, h->Dp, h->N, query_idx, P, hull_idx, m_max, dist, alpha);
-}
-
-int chb_hull_distance_points(chb_ctx *h, const double *x, const double *pts, int m, int64_t D,
-                             double *dist, double *alpha)
-{
-    if (!h || !x || !dist || (m > 0 && !pts)) return fail(CHB_EINVAL, "null argument");
-    if (m < 0 || D <= 0) return fail(CHB_EINVAL, "bad m or D");
-    if (m == 0) { *dist = INFINITY; return CHB_OK; }
-    if (m > CHB_MAX_NEIGHBORS) return fail(CHB_EUNSUPPORTED, "more than 64 hull vertices");
-    HIPCHK(hipSetDevice(h->dev));
-    const int Dp = (int)((D + kKChunk - 1) / kKChunk) * kKChunk;
-    std::vector<double> rows((size_t)(m + 1) * Dp, 0.0);
-    memcpy(rows.data(), x, sizeof(double) * D);
-    for (int a = 0; a < m; ++a) memcpy(rows.data() + (size_t)(a + 1) * Dp, pts + (size_t)a * D, sizeof(double) * D);
-    HIPCHK(h->xpts.ensure(rows.size()));
-    HIPCHK(hipMemcpyAsync(h->xpts.p, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice, h->stream));
-    int64_t q = 0;
-    std::vector<int64_t> idx((size_t)m);
-    for (int a = 0; a < m; ++a) idx[(size_t)a] = a + 1;
-    return hull_indexed(h, h->xpts.p, (int)D, Dp, m + 1, &q, 1, idx.data(), m, dist, alpha);
 }
 
 // ======== row scoring (chb_recruit_rows, chb_audit_rows, chb_*_rows_multi, chb_bin_report, chb_*_pairs, and their _grouped,
@@ -3466,37 +2929,6 @@ int chb_recruit_rows_nearest_wide(chb_ctx *h, const int64_t *labels, int64_t B, 
     return score_nearest(h, who, rq, &D, k, near_bin, near_dist);
 }
 
-int chb_find_nearest_from_row(chb_ctx *h, int64_t c, const int64_t *labels, const double *row,
-                              int64_t N, int m, int64_t *out_idx, int32_t *out_cnt)
-{
-    if (!h || !labels || !row || !out_idx || !out_cnt) return fail(CHB_EINVAL, "null argument");
-    if (N <= 0 || N >= (1LL << 31)) return fail(CHB_EINVAL, "bad N");
-    if (m < 1) return fail(CHB_EINVAL, "m must be >= 1");
-    HIPCHK(hipSetDevice(h->dev));
-    hipStream_t s = h->stream;
-    std::vector<int> lab((size_t)N);
-    for (int64_t i = 0; i < N; ++i) lab[(size_t)i] = (labels[i] < -1 || labels[i] > 0x7ffffff0) ? -2 : (int)labels[i];
-    if (c < 0 || c > 0x7ffffff0) { *out_cnt = 0; for (int i = 0; i < m; ++i) out_idx[i] = -1; return CHB_OK; }
-    DevBuf<int> dl, di;
-    DevBuf<double> dr;
-    hipError_t e = dl.ensure((size_t)N);
-    if (e == hipSuccess) e = dr.ensure((size_t)N);
-    if (e == hipSuccess) e = di.ensure((size_t)m + 1);
-    if (e == hipSuccess) e = hipMemcpyAsync(dl.p, lab.data(), sizeof(int) * N, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dr.p, row, sizeof(double) * N, hipMemcpyHostToDevice, s);
-    std::vector<int> out((size_t)m + 1);
-    if (e == hipSuccess) {
-        launch_select_row(dl.p, dr.p, (int)N, (int)c, m, di.p, di.p + m, s);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out.data(), di.p, sizeof(int) * (m + 1), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail(CHB_EHIP, hipGetErrorString(e));
-    for (int i = 0; i < m; ++i) out_idx[i] = out[(size_t)i];
-    *out_cnt = out[(size_t)m];
-    return CHB_OK;
-}
-
 int chb_set_metric(chb_ctx *h, int metric)
 {
     if (!h) return fail(CHB_EINVAL, "null context");
@@ -3553,232 +2985,6 @@ int chb_comm_destroy(chb_ctx *h)
     }
     h->xchg.comm = nullptr; h->rank = 0; h->world = 1;
     return CHB_OK;
-}
-
-int chb_kmer_dim(int k)
-{
-    const int n = kmer_canonical_table(k, nullptr);
-    return n > 0 ? n : fail(CHB_EUNSUPPORTED, "k must be in [1, 7]");
-}
-
-int chb_kmer_frequencies(chb_ctx *h, const unsigned char *seq, const int64_t *offsets, int64_t n, int k,
-                         double *freq_out, uint32_t *counts_out)
-{
-    if (!h || !offsets || !freq_out) return fail(CHB_EINVAL, "null argument");
-    if (n < 0 || n >= (1LL << 31)) return fail(CHB_EINVAL, "bad contig count");
-    std::vector<unsigned short> table;
-    const int dim = kmer_canonical_table(k, &table);
-    if (dim <= 0) return fail(CHB_EUNSUPPORTED, "k must be in [1, 7]");
-    if (n == 0) return CHB_OK;
-    if (offsets[0] != 0) return fail(CHB_EINVAL, "offsets[0] must be 0");
-    const int64_t total = offsets[n];
-    if (total > 0 && !seq) return fail(CHB_EINVAL, "seq is null");
-    HIPCHK(hipSetDevice(h->dev));
-    // one work item per kmer_chunk_windows() windows of a contig
-    const int cw = kmer_chunk_windows();
-    std::vector<int> chunk_ptr((size_t)n + 1);
-    std::vector<long long> off64((size_t)n + 1);
-    int64_t items = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        if (offsets[i + 1] < offsets[i]) return fail(CHB_EINVAL, "offsets must be non-decreasing");
-        chunk_ptr[(size_t)i] = (int)items;
-        const int64_t nwin = offsets[i + 1] - offsets[i] - k + 1;
-        if (nwin > 0) items += (nwin + cw - 1) / cw;
-        if (items >= (1LL << 31) - 1) return fail(CHB_EUNSUPPORTED, "too many bases for one call");
-        off64[(size_t)i] = offsets[i];
-    }
-    chunk_ptr[(size_t)n] = (int)items;
-    off64[(size_t)n] = total;
-    DevBuf<unsigned char> dseq;
-    DevBuf<long long> doff;
-    DevBuf<int> dptr;
-    DevBuf<unsigned short> dtab;
-    DevBuf<unsigned int> dcnt;
-    DevBuf<double> dfreq;
-    hipStream_t s = h->stream;
-    HIPCHK(dseq.ensure((size_t)std::max<int64_t>(total, 1) + 16));
-    HIPCHK(doff.ensure((size_t)n + 1));
-    HIPCHK(dptr.ensure((size_t)n + 1));
-    HIPCHK(dtab.ensure(table.size()));
-    HIPCHK(dcnt.ensure((size_t)n * dim));
-    HIPCHK(dfreq.ensure((size_t)n * dim));
-    if (total > 0) HIPCHK(hipMemcpyAsync(dseq.p, seq, (size_t)total, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(doff.p, off64.data(), sizeof(long long) * (n + 1), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dptr.p, chunk_ptr.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dtab.p, table.data(), sizeof(unsigned short) * table.size(), hipMemcpyHostToDevice, s));
-    {
-        Timed t(h, "kmer_count", (double)total);
-        launch_kmer_count(dseq.p, doff.p, dptr.p, (int)n, (int)items, k, dim, dtab.p, dcnt.p, dfreq.p, s);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(freq_out, dfreq.p, sizeof(double) * (size_t)n * dim, hipMemcpyDeviceToHost, s));
-    if (counts_out)
-        HIPCHK(hipMemcpyAsync(counts_out, dcnt.p, sizeof(uint32_t) * (size_t)n * dim, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return CHB_OK;
-}
-
-// ---- k-mer profiles of a list of k values (kmer_multi_kernels.hip)
-
-static int kmer_list_plan(const int *ks, int nk, KmerMultiPlan *plan, std::vector<unsigned short> *table)
-{
-    if (!ks) return fail(CHB_EINVAL, "null argument");
-    const int dim = kmer_multi_plan(ks, nk, plan, table);
-    if (dim == -2) return fail(CHB_EUNSUPPORTED, "k must be in [1, 7]");
-    if (dim <= 0) return fail(CHB_EINVAL, "ks must hold 1 to 7 distinct values");
-    return dim;
-}
-
-int chb_kmer_profile_dim(const int *ks, int nk)
-{
-    KmerMultiPlan plan;
-    return kmer_list_plan(ks, nk, &plan, nullptr);
-}
-
-// the checks chb_kmer_frequencies makes of its sequence arguments (n > 0)
-static int kmer_check_sequences(const unsigned char *seq, const int64_t *offsets, int64_t n)
-{
-    if (offsets[0] != 0) return fail(CHB_EINVAL, "offsets[0] must be 0");
-    for (int64_t i = 0; i < n; ++i)
-        if (offsets[i + 1] < offsets[i]) return fail(CHB_EINVAL, "offsets must be non-decreasing");
-    if (offsets[n] > 0 && !seq) return fail(CHB_EINVAL, "seq is null");
-    return CHB_OK;
-}
-
-// Rows [0, n) of the device matrix out[n][ld]: the k-mer blocks of the plan and, with dextra, S more columns behind them.
-// The sequence goes up in chunks of whole contigs -- at most kKmerChunkBytes of bases and kKmerChunkRows contigs, a larger
-// contig alone -- one after the other on the context's stream, so that sequence, offsets, work-item table, row map and
-// counts take the room of one chunk whatever n is.  counts_out (optional, host): the raw counts, [n][total_dim].
-// Arguments are checked by the callers; nothing here refuses a call for its values.
-static int kmer_profiles_device(chb_ctx *h, const unsigned char *seq, const int64_t *offsets, int64_t n,
-                                const KmerMultiPlan &plan, const std::vector<unsigned short> &table, double *out, int64_t ld,
-                                const double *dextra, const int64_t *extra_row, int S, uint32_t *counts_out)
-{
-    const int dim = plan.total_dim;
-    const int cw = kmer_multi_chunk_positions();
-    // the chunks: [first contig, one past the last)
-    std::vector<std::pair<int64_t, int64_t>> chunks;
-    int64_t max_bases = 0, max_rows = 0;
-    for (int64_t a = 0; a < n;) {
-        int64_t b = a + 1;
-        while (b < n && b - a < kKmerChunkRows && offsets[b + 1] - offsets[a] <= kKmerChunkBytes) ++b;
-        chunks.emplace_back(a, b);
-        max_bases = std::max(max_bases, offsets[b] - offsets[a]);
-        max_rows = std::max(max_rows, b - a);
-        a = b;
-    }
-    DevBuf<unsigned char> dseq;
-    DevBuf<long long> doff, dxrow;
-    DevBuf<int> dptr;
-    DevBuf<unsigned short> dtab;
-    DevBuf<unsigned int> dcnt;
-    hipStream_t s = h->stream;
-    HIPCHK(dseq.ensure((size_t)std::max<int64_t>(max_bases, 1)));
-    HIPCHK(doff.ensure((size_t)max_rows + 1));
-    HIPCHK(dptr.ensure((size_t)max_rows + 1));
-    if (dextra && extra_row) HIPCHK(dxrow.ensure((size_t)max_rows));
-    HIPCHK(dtab.ensure(table.size()));
-    HIPCHK(dcnt.ensure((size_t)max_rows * dim));
-    HIPCHK(hipMemcpyAsync(dtab.p, table.data(), sizeof(unsigned short) * table.size(), hipMemcpyHostToDevice, s));
-    std::vector<int> item_ptr;
-    std::vector<long long> off64, xrow;
-    h->kmer_chunks = 0;
-    for (const auto &c : chunks) {
-        const int64_t a = c.first, rows = c.second - c.first, base0 = offsets[a], bases = offsets[c.second] - base0;
-        // one work item per cw start positions of a contig, of the L - kmin + 1 that begin a k-mer of the list
-        item_ptr.assign((size_t)rows + 1, 0);
-        off64.assign((size_t)rows + 1, 0);
-        int64_t items = 0;
-        for (int64_t i = 0; i < rows; ++i) {
-            item_ptr[(size_t)i] = (int)items;
-            off64[(size_t)i] = offsets[a + i] - base0;
-            const int64_t nstart = offsets[a + i + 1] - offsets[a + i] - plan.kmin + 1;
-            if (nstart > 0) items += (nstart + cw - 1) / cw;
-            if (items >= (1LL << 31) - 1) return fail(CHB_EUNSUPPORTED, "a contig is too long for one call");
-        }
-        item_ptr[(size_t)rows] = (int)items;
-        off64[(size_t)rows] = bases;
-        if (bases > 0) HIPCHK(hipMemcpyAsync(dseq.p, seq + base0, (size_t)bases, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(doff.p, off64.data(), sizeof(long long) * (rows + 1), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(dptr.p, item_ptr.data(), sizeof(int) * (rows + 1), hipMemcpyHostToDevice, s));
-        if (dextra && extra_row) {
-            xrow.assign(extra_row + a, extra_row + a + rows);
-            HIPCHK(hipMemcpyAsync(dxrow.p, xrow.data(), sizeof(long long) * rows, hipMemcpyHostToDevice, s));
-        }
-        {
-            Timed t(h, "kmer_multi", (double)bases);
-            launch_kmer_multi(dseq.p, doff.p, dptr.p, (int)rows, (int)items, plan, dtab.p, dcnt.p, out + (size_t)a * ld, ld,
-                              dextra, dextra && extra_row ? dxrow.p : nullptr, a, S, s);
-        }
-        HIPCHK(hipGetLastError());
-        if (counts_out)
-            HIPCHK(hipMemcpyAsync(counts_out + (size_t)a * dim, dcnt.p, sizeof(uint32_t) * (size_t)rows * dim,
-                                  hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));   // (the host tables and the chunk's device buffers are reused by the next chunk)
-        ++h->kmer_chunks;
-    }
-    return CHB_OK;
-}
-
-int chb_kmer_profiles(chb_ctx *h, const unsigned char *seq, const int64_t *offsets, int64_t n, const int *ks, int nk,
-                      double *freq_out, uint32_t *counts_out)
-{
-    if (!h || !offsets || !freq_out) return fail(CHB_EINVAL, "null argument");
-    if (n < 0 || n >= (1LL << 31)) return fail(CHB_EINVAL, "bad contig count");
-    KmerMultiPlan plan;
-    std::vector<unsigned short> table;
-    const int dim = kmer_list_plan(ks, nk, &plan, &table);
-    if (dim <= 0) return dim;
-    if (n == 0) return CHB_OK;
-    { const int rc = kmer_check_sequences(seq, offsets, n); if (rc) return rc; }
-    HIPCHK(hipSetDevice(h->dev));
-    DevBuf<double> dfreq;
-    HIPCHK(dfreq.ensure((size_t)n * dim));
-    { const int rc = kmer_profiles_device(h, seq, offsets, n, plan, table, dfreq.p, dim, nullptr, nullptr, 0, counts_out); if (rc) return rc; }
-    HIPCHK(hipMemcpyAsync(freq_out, dfreq.p, sizeof(double) * (size_t)n * dim, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return CHB_OK;
-}
-
-int chb_set_samples_from_sequences(chb_ctx *h, const unsigned char *seq, const int64_t *offsets, int64_t n, const int *ks,
-                                   int nk, const double *extra, int64_t n_extra, int64_t S, const int64_t *extra_row,
-                                   double *X_out)
-{
-    // every check before anything is enqueued: a refused call leaves the resident samples as they were
-    if (!h || !offsets) return fail(CHB_EINVAL, "null argument");
-    if (n <= 0 || n >= (1LL << 31) - 64) return fail(CHB_EINVAL, "bad contig count");
-    KmerMultiPlan plan;
-    std::vector<unsigned short> table;
-    const int dim = kmer_list_plan(ks, nk, &plan, &table);
-    if (dim <= 0) return dim;
-    { const int rc = kmer_check_sequences(seq, offsets, n); if (rc) return rc; }
-    if (S < 0) return fail(CHB_EINVAL, "bad number of extra columns");
-    if (S > (1 << 20) - dim) return fail(CHB_EUNSUPPORTED, "N or D too large");
-    if (S > 0 && !extra) return fail(CHB_EINVAL, "extra is null");
-    if (S == 0 && extra) return fail(CHB_EINVAL, "extra given without columns");
-    if (S > 0) {
-        if (n_extra <= 0) return fail(CHB_EINVAL, "extra has no rows");
-        if (!extra_row && n_extra != n) return fail(CHB_EINVAL, "extra needs one row per contig when there is no extra_row");
-        if (extra_row)
-            for (int64_t i = 0; i < n; ++i)
-                if (extra_row[i] < 0 || extra_row[i] >= n_extra) return fail(CHB_EINVAL, "extra_row out of range");
-    }
-    const int64_t D = dim + S;
-    HIPCHK(hipSetDevice(h->dev));
-    DevBuf<double> mat, dextra;
-    HIPCHK(mat.ensure((size_t)n * D));
-    if (S > 0) {
-        HIPCHK(dextra.ensure((size_t)n_extra * S));
-        HIPCHK(hipMemcpyAsync(dextra.p, extra, sizeof(double) * (size_t)n_extra * S, hipMemcpyHostToDevice, h->stream));
-    }
-    { const int rc = kmer_profiles_device(h, seq, offsets, n, plan, table, mat.p, D, S > 0 ? dextra.p : nullptr, extra_row, (int)S, nullptr); if (rc) return rc; }
-    if (X_out) {
-        HIPCHK(hipMemcpyAsync(X_out, mat.p, sizeof(double) * (size_t)n * D, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
-    // from here on the matrix is a device matrix like any other: chb_set_samples_device's own routine (padded resident
-    // copy, shadow rows, an open stepwise fit ended; it returns with the stream drained, before `mat` is freed)
-    return set_samples_common(h, mat.p, n, D, true);
 }
 
 int chb_profile_enable(chb_ctx *h, int on)

@@ -9,7 +9,8 @@ mkdir -p _obj_var/$name
 extra=""; [ "$unit" = topm_kernels ] && extra="-ffp-contract=off"
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function $extra $flags -c $unit.hip -o _obj_var/$name/$unit.o
 objs=""
-for u in topm_kernels prefilter_kernels qp_kernels aux_kernels kmer_kernels chb_api; do
+for f in *.hip; do   # (every unit of the library, as the Makefile's wildcard finds them)
+  u=${f%.hip}
   if [ $u = $unit ]; then objs="$objs _obj_var/$name/$u.o"; else objs="$objs _obj/$u.o"; fi
 done
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../libchbin_var_$name.so $objs
